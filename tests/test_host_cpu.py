@@ -357,6 +357,42 @@ def test_bench_contract_on_cpu():
         assert r.returncode != 0 and "{" not in r.stdout, r.stdout[-500:]
 
 
+def test_bench_dump_outputs_on_cpu(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, a large array replaced by the same seeded sample on every run, at most
+    64 MB in all; --steps below 1 is refused"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        spec.loader.exec_module(bench)
+        assert bench.parse().dump_outputs is None
+        sys.argv = ["bench.py", "--steps", "3", "--dump-outputs", str(tmp_path / "a")]
+        args = bench.parse()
+        assert (args.steps, args.dump_outputs) == (3, str(tmp_path / "a"))
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+    big = torch.randn(bench.DUMP_MAX_ELEMS + 12345, generator=torch.Generator().manual_seed(3))
+    arrays = {"losses": torch.arange(5, dtype=torch.float64), "image": torch.rand(2, 36, 48, 12), "weights": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["image.npy", "losses.npy", "weights.npy"]
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    np.testing.assert_array_equal(got["losses"], np.arange(5))
+    np.testing.assert_array_equal(got["image"], arrays["image"].numpy())
+    w = got["weights"]
+    assert w.shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.isin(w, big.numpy()).all()                 # a sample of the elements, in index order
+    np.testing.assert_array_equal(w, np.load(str(tmp_path / "b" / "weights.npy")))
+
+
 def test_no_wide_buffer_store_with_register_soffset(tmp_path):
     """Enforced invariant: gfx950 takes a data register that a VALU instruction overwrites right
     after a > 8-byte `buffer_store` when the store's soffset is an SGPR - the ISA manual and the compiler's hazard
