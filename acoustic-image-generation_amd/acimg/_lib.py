@@ -40,6 +40,14 @@ class SequenceDims(C.Structure):
         "video_width", "video_depth", "audio_image_steps", "audio_data_steps", "video_steps", "audio_data_values")]
 
 
+class BoxSequenceDims(C.Structure):
+    """Mirror of AcimgBoxSequenceDims (include/acimg.h)."""
+
+    _fields_ = [(n, C.c_int64) for n in (
+        "mics", "samples", "video_height", "video_width", "video_depth", "box_rows", "audio_data_steps", "video_steps",
+        "audio_data_values")]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_long
@@ -147,9 +155,13 @@ PROTOTYPES = {
     "acimg_filtfilt_workspace": (_SZ, [_I, _I]),
     "acimg_find_logen": (_I, [_P, _P, _P, _L, _P]),
     "acimg_mask_iou": (_I, [_P, _P, _I, _I, _P, _P]),
+    "acimg_box_iou": (_I, [_P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "acimg_box_iou_workspace": (_SZ, [_I]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),
+    "acimg_box_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(BoxSequenceDims), _P, _SZ, _P, _SZ, _P, _SZ, _P,
+                                                _SZ]),
     "acimg_crc32c": (C.c_uint32, [_P, _SZ, C.c_uint32]),
 }
 

@@ -10,7 +10,12 @@ audio [n,12])), `.num_samples`, `.total_batches` (:117,214,973-976).
   device (`acimg_filtfilt` = `butter_lowpass_filter`, :558-575; `acimg_mfcc_frontend` = `_build_spectrograms_function`,
   :796-876, with `_normalize_mfcc`, :696-703), the per-frame maps of :634-703 on the host, unbatch to frames and batch
   (:99-104).  The tf.data machinery around it (parallel map, prefetch, shuffle buffer) is host plumbing the reference
-  leaves to TensorFlow: here a plain Python generator (SURVEY §2 #16 keeps that pipeline out of scope)."""
+  leaves to TensorFlow: here a plain Python generator (SURVEY §2 #16 keeps that pipeline out of scope).
+* `BoxRecordLoader`: the box-annotated Flickr-SoundNet records of dataloader/frames.py (`ActionsDataLoader(...,
+  embedding=1, nr_frames=1, sample_length=1, shuffle=False)`, written by convert_data2.py:200-307): 8-tuples (acoustic
+  zeros [n,36,48,12], mfcc [n,12], video [n,224,298,3], xmin, xmax, ymin, ymax, typescene [n,3] int32) that
+  showimages_bb.py:86-93 indexes.  Records through `acimg_box_sequence_example_decode`; the MFCC of the whole clip is
+  `box_mfcc` on the host (the [1, L] reading of `_build_spectrograms_function`)."""
 import numpy as np
 import torch
 
@@ -128,3 +133,96 @@ class TFRecordDataLoader(object):
                     pend = [rest] if have else []
         if have:
             yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(6))
+
+
+def box_mfcc(audio):
+    """float64 NumPy restatement of dataloader/frames.py `_build_spectrograms_function` (:659-688, with `createfilters`
+    and `get_feats`) + `_normalize_mfcc` (:559-566) on the [rows, L] array the function evidently means: ONE
+    un-windowed rfft over the whole clip, power of the first L // 2 bins, a mel bank built for fft_len = L // 2, the
+    1e-3 floor, log, DCT, * mfnorm, * lifter, NaN / inf -> 0, float32; then per row (x - min) / max in float32.
+    audio: int32 [rows, L] -> float32 [rows, 12].  (On the [1, 1, L] array the TF pipeline actually hands it the
+    function degenerates to an audio-independent vector; DESIGN §8 records why that is not reproduced.)"""
+    from .frontend import FILTER_NUM, HI_FREQ, LIFTER_NUM, LO_FREQ, MFCC_NUM, createfilters
+    x = np.asarray(audio)
+    if x.ndim != 2 or x.shape[1] < 4:
+        raise ValueError("box_mfcc wants [rows, L >= 4] audio, got %s" % (x.shape,))
+    length = x.shape[1]
+    fft_len = length // 2
+    power = np.abs(np.fft.rfft(x, length, axis=1))[:, :-1] ** 2
+    power = power.reshape(x.shape[0], fft_len)
+    dct_base = np.zeros((FILTER_NUM, MFCC_NUM))
+    for m in range(MFCC_NUM):
+        dct_base[:, m] = np.cos((m + 1) * np.pi / FILTER_NUM * (np.arange(FILTER_NUM) + 0.5))
+    lifter = 1 + (LIFTER_NUM / 2) * np.sin(np.pi * (1 + np.arange(MFCC_NUM)) / LIFTER_NUM)
+    mel = power.dot(createfilters(fft_len, FILTER_NUM, LO_FREQ, HI_FREQ, 2 * HI_FREQ))
+    mel[mel < 0.001] = 0.001
+    c = np.log(mel).dot(dct_base)
+    c *= np.sqrt(2.0 / FILTER_NUM)
+    c *= lifter
+    c[~np.isfinite(c)] = 0
+    c = c.astype(np.float32)
+    c = c - c.min(axis=1, keepdims=True)
+    return c / c.max(axis=1, keepdims=True)
+
+
+class BoxRecordLoader(object):
+    """`ActionsDataLoader(txt_file, 'testing', batch_size, ..., embedding=1, nr_frames=1, sample_length=1,
+    shuffle=False)` of dataloader/frames.py with modalities [1, 2] (audio data + video; no acoustic image in these
+    records, so the acoustic slot holds zeros as :316 builds them).  `files`: a list of TFRecord paths or the path of a
+    text file listing them.  Everything runs on the host (the MFCC is one clip-length rfft per record, loader work like
+    the per-frame maps of `TFRecordDataLoader`); tensors are returned on the host."""
+
+    def __init__(self, files, batch_size, compression_verify=True):
+        if isinstance(files, str):
+            with open(files) as f:
+                files = [ln.strip() for ln in f if ln.strip()]
+        self.files = list(files)
+        self.batch_size = int(batch_size)
+        self.verify = bool(compression_verify)
+        self.data = self
+        self._num_samples = None
+
+    @property
+    def num_samples(self):
+        """frames in the data set, counted from the decoded records (one frame per record in convert_data2.py files)"""
+        if self._num_samples is None:
+            from . import tfio
+            self._num_samples = sum(int(tfio.decode_box_sequence_example_native(r)["dims"].video_steps)
+                                    for p in self.files for r in tfio.read_tfrecord_native(p, verify=False) if len(r))
+        return self._num_samples
+
+    @property
+    def total_batches(self):
+        return -(-self.num_samples // self.batch_size)
+
+    def _record(self, rec):
+        from . import tfio
+        d = tfio.decode_box_sequence_example_native(rec)
+        boxes, vi, sa = d["boxes"], d["video_images"], d["audio_samples"]
+        n = vi.shape[0]
+        if not (boxes.shape[0] == n and sa.shape[0] == n and n > 0):
+            raise ValueError("record with %d video frames, %d box rows, %d audio rows" % (n, boxes.shape[0], sa.shape[0]))
+        mfcc = box_mfcc(sa)
+        # video: float, channel order reversed, 1/255 (`_normalize_images_rescaled`, :640-646)
+        v = vi[..., ::-1].astype(np.float32) * np.float32(1.0 / 255.0)
+        out = [np.zeros((n, 36, 48, 12), np.float32), mfcc, np.ascontiguousarray(v)]
+        out += [np.ascontiguousarray(boxes[:, k]) for k in range(4)] + [d["typescene"]]
+        return tuple(torch.from_numpy(a) for a in out)
+
+    def __iter__(self):
+        from . import tfio
+        pend, have = [], 0
+        for path in self.files:
+            for rec in tfio.read_tfrecord_native(path, verify=self.verify):
+                if len(rec) == 0:
+                    continue
+                pend.append(self._record(rec))
+                have += pend[-1][0].shape[0]
+                while have >= self.batch_size:
+                    cat = [torch.cat([p_[k] for p_ in pend], 0) for k in range(8)]
+                    yield tuple(c[:self.batch_size] for c in cat)
+                    rest = tuple(c[self.batch_size:] for c in cat)
+                    have = rest[0].shape[0]
+                    pend = [rest] if have else []
+        if have:
+            yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(8))

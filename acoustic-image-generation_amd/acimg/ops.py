@@ -844,6 +844,14 @@ def mask_iou(plan, map_a, map_b, N, P, iou):
     plan.add("mask_iou", _L().acimg_mask_iou, map_a, map_b, int(N), int(P), iou)
 
 
+def box_iou(plan, logen, boxes, N, iou, counts=None, mask_out=None):
+    """consensus bounding-box IoU (showimages_bb.py:286-320): logen [N,36*48] float32, boxes [N,4,3] int32 -> iou [N];
+    counts [N,2] int32 half-units and mask_out [N,224,298] uint8 only when given"""
+    plan.ws.require(_L().acimg_box_iou_workspace(int(N)))
+    plan.add("box_iou", _L().acimg_box_iou, logen, boxes, int(N), iou, counts, mask_out, _WsPtr(plan.ws),
+             _WsBytes(plan.ws))
+
+
 def adam_lr_t(lr, step, beta1=0.9, beta2=0.999):
     """TF-1 Adam effective step size for 1-based step t."""
     return lr * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step)

@@ -474,3 +474,25 @@ def decode_sequence_example_native(record):
         sa = sa.reshape(-1, dims.samples)
     return dict(audio_images=ai, audio_samples=sa, video_images=vi, action=int(dims.classes),
                 location=int(dims.location), dims=dims)
+
+
+def decode_box_sequence_example_native(record):
+    """One serialized box-annotated SequenceExample -> what `_parse_sequence` of dataloader/frames.py:246-341 returns:
+    dict(boxes int32 [rows,4,3] (xmin, xmax, ymin, ymax rows), typescene int32 [rows,3], audio_samples int32
+    [-1, samples], video_images uint8 [steps,H,W,D]) via acimg_box_sequence_example_decode."""
+    lib = _lib.load()
+    rec = np.frombuffer(record, dtype=np.uint8)
+    dims = _lib.BoxSequenceDims()
+    _lib.check(lib.acimg_box_sequence_example_decode(rec.ctypes.data, rec.size, ctypes.byref(dims), None, 0, None, 0,
+                                                     None, 0, None, 0), "box_sequence_example_decode")
+    boxes = np.empty((dims.box_rows, 4, 3), np.int32)
+    scene = np.empty((dims.box_rows, 3), np.int32)
+    sa = np.empty(dims.audio_data_values, np.int32)
+    vi = np.empty((dims.video_steps, dims.video_height, dims.video_width, dims.video_depth), np.uint8)
+
+    def ptr(a):
+        return a.ctypes.data if a.size else None
+    _lib.check(lib.acimg_box_sequence_example_decode(rec.ctypes.data, rec.size, ctypes.byref(dims), ptr(boxes),
+                                                     boxes.size, ptr(scene), scene.size, ptr(sa), sa.size, ptr(vi),
+                                                     vi.size), "box_sequence_example_decode")
+    return dict(boxes=boxes, typescene=scene, audio_samples=sa.reshape(-1, dims.samples), video_images=vi, dims=dims)

@@ -581,6 +581,17 @@ class Trainer(object):
             res["mse%d" % i] = sum(ch[3 * i:3 * i + 3]) / per
         return res
 
+    def generate(self, batch, eps=None):
+        """the generator output of the inference-mode forward (is_training = 0, BN moving statistics; the plan of
+        `eval_step`, whose loss part runs and is ignored) for `batch` = (acoustic, mfcc [n,12], video [n,224,298,3],
+        ...); the acoustic slot may hold zeros.  Returns the graph's [n,36,48,12] device buffer for that batch size
+        (partial batches included): it is overwritten by the next call with the same n."""
+        g = self._graph_for(int(batch[1].reshape(-1, 12).shape[0]))
+        self.flush_pipeline()
+        self._feed(g, batch, eps)
+        g.plan_eval.run()
+        return g.modelac.output
+
     # ------------------------------------------------------------------------------------------------
     # reference protocol: loops, checkpoints
     # ------------------------------------------------------------------------------------------------

@@ -336,4 +336,134 @@ int acimg_sequence_example_decode(const uint8_t* rec, size_t len, AcimgSequenceD
     return ACIMG_OK;
 }
 
+// dataloader/frames.py:246-341 (box-annotated records of convert_data2.py:200-307): sequence features xmin, xmax, ymin,
+// ymax, typescene (one raw-int32 bytes entry per step, tf.reshape [-1, 3]), audio/data (int32, reshape [-1, samples]),
+// video/image (uint8, reshape [-1, H, W, D]); context audio_data/{mics,samples}, video/{height,width,depth}.
+int acimg_box_sequence_example_decode(const uint8_t* rec, size_t len, AcimgBoxSequenceDims* dims, int32_t* boxes,
+                                      size_t box_cap, int32_t* typescene, size_t typescene_cap, int32_t* audio,
+                                      size_t audio_cap, uint8_t* video, size_t video_cap) {
+    if (!rec || !dims) return fail(ACIMG_EINVAL, "box_sequence_example_decode: null argument");
+    memset(dims, 0, sizeof(*dims));
+    static const char* const names[7] = {"xmin", "xmax", "ymin", "ymax", "typescene", "audio/data", "video/image"};
+    Span lists[7];
+    for (int i = 0; i < 7; ++i) lists[i] = Span{nullptr, 0};
+    const uint8_t* p = rec;
+    const uint8_t* end = rec + len;
+    Field f;
+    bool ok = true;
+    while (next_field(p, end, f, ok)) {
+        if (f.wt != 2 || (f.num != 1 && f.num != 2)) continue;
+        const uint8_t* q = f.sub.p;
+        const uint8_t* qe = q + f.sub.n;
+        Field e;
+        while (next_field(q, qe, e, ok)) {
+            if (e.num != 1 || e.wt != 2) continue;
+            Span key, val;
+            if (!map_entry(e.sub, key, val)) { ok = false; break; }
+            if (f.num == 1) {
+                int64_t v;
+                if (!feature_int64(val, v, ok)) continue;
+                if (key_is(key, "audio_data/mics")) dims->mics = v;
+                else if (key_is(key, "audio_data/samples")) dims->samples = v;
+                else if (key_is(key, "video/height")) dims->video_height = v;
+                else if (key_is(key, "video/width")) dims->video_width = v;
+                else if (key_is(key, "video/depth")) dims->video_depth = v;
+            } else {
+                for (int i = 0; i < 7; ++i)
+                    if (key_is(key, names[i])) lists[i] = val;
+            }
+        }
+    }
+    if (!ok) return fail(ACIMG_EINVAL, "box_sequence_example_decode: malformed protobuf");
+    // FixedLenFeature context: present and a sane positive size before any product is formed
+    {
+        const int64_t* dimv[5] = {&dims->mics, &dims->samples, &dims->video_height, &dims->video_width, &dims->video_depth};
+        static const char* const dn[5] = {"audio_data/mics", "audio_data/samples", "video/height", "video/width",
+                                          "video/depth"};
+        for (int i = 0; i < 5; ++i)
+            if (*dimv[i] < 1 || *dimv[i] > (i == 1 ? (int64_t)1 << 24 : 65536))
+                return fail(ACIMG_EINVAL, "box_sequence_example_decode: context '%s' = %lld is missing or out of range",
+                            dn[i], (long long)*dimv[i]);
+    }
+    for (int i = 0; i < 7; ++i)
+        if (!lists[i].p) return fail(ACIMG_EINVAL, "box_sequence_example_decode: no '%s' feature list", names[i]);
+    const int64_t frame_bytes = dims->video_height * dims->video_width * dims->video_depth;
+    // pass 0 validates and counts, pass 1 copies (only when every size is known to fit)
+    int64_t values[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int li = 0; li < 7; ++li) {
+            const uint8_t* q = lists[li].p;
+            const uint8_t* qe = q + lists[li].n;
+            Field st;
+            int64_t step = 0, got = 0;
+            while (next_field(q, qe, st, ok)) {
+                if (st.num != 1 || st.wt != 2) continue;
+                Span raw;
+                if (!feature_bytes(st.sub, raw))
+                    return fail(ACIMG_EINVAL, "box_sequence_example_decode: '%s' step %lld holds no bytes", names[li],
+                                (long long)step);
+                if (li < 6) {                                                // int32 lists
+                    if (raw.n % 4)
+                        return fail(ACIMG_EINVAL, "box_sequence_example_decode: '%s' step of %zu bytes is not int32",
+                                    names[li], raw.n);
+                    if (got + (int64_t)(raw.n / 4) > ((int64_t)1 << 31))
+                        return fail(ACIMG_EINVAL, "box_sequence_example_decode: '%s' too long", names[li]);
+                    if (pass == 1) {
+                        const int64_t nv = (int64_t)(raw.n / 4);
+                        if (li < 4 && boxes) {                               // row r = v / 3 -> boxes[r][li][v % 3]
+                            for (int64_t v = 0; v < nv; ++v)
+                                memcpy(boxes + ((got + v) / 3 * 4 + li) * 3 + (got + v) % 3, raw.p + v * 4, 4);
+                        } else if (li == 4 && typescene) {
+                            memcpy(typescene + got, raw.p, raw.n);
+                        } else if (li == 5 && audio) {
+                            memcpy(audio + got, raw.p, raw.n);
+                        }
+                    }
+                    got += (int64_t)(raw.n / 4);
+                } else {                                                     // video/image
+                    if ((int64_t)raw.n != frame_bytes)
+                        return fail(ACIMG_EINVAL, "box_sequence_example_decode: video/image step of %zu bytes, "
+                                    "context says %lld", raw.n, (long long)frame_bytes);
+                    if (step >= (int64_t)1 << 20)
+                        return fail(ACIMG_EINVAL, "box_sequence_example_decode: too many video steps");
+                    if (pass == 1 && video) memcpy(video + step * frame_bytes, raw.p, raw.n);
+                    got += frame_bytes;
+                }
+                ++step;
+            }
+            if (!ok) return fail(ACIMG_EINVAL, "box_sequence_example_decode: malformed '%s' feature list", names[li]);
+            if (pass == 0) {
+                values[li] = got;
+                if (li == 5) dims->audio_data_steps = step;
+                if (li == 6) dims->video_steps = step;
+            }
+        }
+        if (pass == 0) {
+            for (int li = 0; li < 5; ++li) {
+                if (values[li] % 3)
+                    return fail(ACIMG_EINVAL, "box_sequence_example_decode: '%s' holds %lld values, not [-1, 3]",
+                                names[li], (long long)values[li]);
+                if (values[li] != values[0])
+                    return fail(ACIMG_EINVAL, "box_sequence_example_decode: '%s' holds %lld values, 'xmin' %lld",
+                                names[li], (long long)values[li], (long long)values[0]);
+            }
+            if (values[5] % dims->samples)
+                return fail(ACIMG_EINVAL, "box_sequence_example_decode: audio/data holds %lld values, samples = %lld",
+                            (long long)values[5], (long long)dims->samples);
+            dims->box_rows = values[0] / 3;
+            dims->audio_data_values = values[5];
+            if (boxes && (size_t)(dims->box_rows * 12) > box_cap)
+                return fail(ACIMG_EWORKSPACE, "box_sequence_example_decode: boxes buffer too small");
+            if (typescene && (size_t)(dims->box_rows * 3) > typescene_cap)
+                return fail(ACIMG_EWORKSPACE, "box_sequence_example_decode: typescene buffer too small");
+            if (audio && (size_t)values[5] > audio_cap)
+                return fail(ACIMG_EWORKSPACE, "box_sequence_example_decode: audio buffer too small");
+            if (video && (size_t)(dims->video_steps * frame_bytes) > video_cap)
+                return fail(ACIMG_EWORKSPACE, "box_sequence_example_decode: video buffer too small");
+            if (!boxes && !typescene && !audio && !video) break;            // sizes-only query
+        }
+    }
+    return ACIMG_OK;
+}
+
 }  // extern "C"

@@ -574,6 +574,20 @@ int acimg_find_logen(const float* mfcc_img, const double* idct /*12x24*/, float*
  * iou[n] = |m_a & m_b| / |m_a | m_b|.  map_a, map_b: [N][P] float32 (acimg_find_logen outputs). */
 int acimg_mask_iou(const float* map_a, const float* map_b, int N, int P, float* iou, void* stream);
 
+/* Consensus bounding-box IoU of the Flickr-SoundNet evaluation (showimages_bb.py:286-320), per sample n < N:
+ *   m2   = map > mean(map)        (the fp64 mean of acimg_mask_iou, so both metrics threshold alike)
+ *   m2   = cv2.resize(m2 * 1.0, (298, 224)) > 0.5   (INTER_LINEAR: half-pixel mapping, float32 weights clamped at the
+ *          borders, applied in float64 without fused multiply-adds; the strict > 0.5 is decided exactly)
+ *   mtot = min(1, sum over annotators k < 3 with xmax[k] != 0 of 0.5 * filled closed rectangle, clipped to the frame)
+ *   iou  = sum(m2 * mtot) / sum((m2 | mtot > 0) + mtot - (mtot > 0));  0 / 0 = NaN as in the reference.
+ * logen: [N][36*48] float32 (acimg_find_logen outputs); boxes: [N][4][3] int32 = xmin[3], xmax[3], ymin[3], ymax[3]
+ * (dataloader/frames.py:290-297); iou: [N].  Optional (NULL = not written): counts [N][2] int32 = numerator and
+ * denominator in half-units (exact integers; iou = counts[0] / counts[1]); mask_out [N][224][298] uint8 = the resized
+ * mask m2 (0 / 1).  ws: acimg_box_iou_workspace(N) bytes.  Stream-ordered, deterministic, no atomics. */
+int acimg_box_iou(const float* logen, const int32_t* boxes, int N, float* iou, int32_t* counts, uint8_t* mask_out,
+                  void* ws, size_t ws_bytes, void* stream);
+size_t acimg_box_iou_workspace(int N);
+
 /* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
@@ -600,6 +614,23 @@ typedef struct AcimgSequenceDims {
 int acimg_sequence_example_decode(const uint8_t* rec, size_t len, AcimgSequenceDims* dims, float* audio_images,
                                   size_t audio_images_cap, int32_t* audio_samples, size_t audio_samples_cap,
                                   uint8_t* video, size_t video_cap);
+
+/* What `_parse_sequence` of the box-annotated loader (dataloader/frames.py:246-341, records written by
+ * convert_data2.py:200-307) extracts from one serialized SequenceExample: no 'classes' / 'location' context. */
+typedef struct AcimgBoxSequenceDims {
+    int64_t mics, samples;                            /* context 'audio_data/{mics,samples}' */
+    int64_t video_height, video_width, video_depth;   /* context 'video/{height,width,depth}' */
+    int64_t box_rows;                                 /* rows of tf.reshape(decode_raw(xmin), [-1, 3]) (all five alike) */
+    int64_t audio_data_steps, video_steps;            /* feature-list lengths */
+    int64_t audio_data_values;                        /* int32 values over all 'audio/data' steps */
+} AcimgBoxSequenceDims;
+/* Decode one record: context scalars + list lengths into *dims; when given (NULL = sizes only; capacities in
+ * ELEMENTS): boxes int32 [box_rows][4][3] = xmin, xmax, ymin, ymax rows (the layout acimg_box_iou reads), typescene
+ * int32 [box_rows][3], audio int32 [audio_data_values] (tf.reshape [-1, samples]), video uint8 [steps][H][W][D].
+ * The five box features and 'audio/data', 'video/image' and their context dimensions are required. */
+int acimg_box_sequence_example_decode(const uint8_t* rec, size_t len, AcimgBoxSequenceDims* dims, int32_t* boxes,
+                                      size_t box_cap, int32_t* typescene, size_t typescene_cap, int32_t* audio,
+                                      size_t audio_cap, uint8_t* video, size_t video_cap);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side helper (no GPU): CRC-32C (Castagnoli) of a byte range, continuing from `crc` (0 to start) — the

@@ -1,0 +1,267 @@
+"""Localisation evaluation, host side: the native decoder of box-annotated records (acimg_box_sequence_example_decode),
+the `BoxRecordLoader` tuples and its whole-clip MFCC (pinned by tests/golden/box_golden.npz), the NumPy restatement of
+the box metric on hand-computed cases, and `python -m acimg.localize`'s flags and output files."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+for p in (ROOT, os.path.join(ROOT, "acoustic-image-generation_amd"), HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from acimg import _lib, localize, tfio  # noqa: E402
+from acimg.data import BoxRecordLoader, box_mfcc  # noqa: E402
+from acimg.evaluate import THRESHOLDS, accuracy_curve, area_under_curve, mean_iou  # noqa: E402
+import localize_ref as ref  # noqa: E402
+
+GOLDEN = os.path.join(HERE, "golden", "box_golden.npz")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+def box_record(boxes, scene, audio, video, drop=None, override=None):
+    """one SequenceExample in the layout convert_data2.py:264-305 writes"""
+    ctx = {"audio_data/mics": np.array([1]), "audio_data/samples": np.array([audio.shape[-1]]),
+           "video/height": np.array([video.shape[-3]]), "video/width": np.array([video.shape[-2]]),
+           "video/depth": np.array([video.shape[-1]])}
+    b = np.asarray(boxes, np.int32).reshape(-1, 4, 3)
+    fl = {"xmin": [r[0].tobytes() for r in b], "xmax": [r[1].tobytes() for r in b],
+          "ymin": [r[2].tobytes() for r in b], "ymax": [r[3].tobytes() for r in b],
+          "typescene": [np.asarray(s, np.int32).tobytes() for s in np.asarray(scene).reshape(-1, 3)],
+          "audio/data": [np.asarray(audio, np.int32).reshape(-1).tobytes()],
+          "video/image": [f.tobytes() for f in np.asarray(video, np.uint8).reshape(-1, *video.shape[-3:])]}
+    for k, v in (override or {}).items():
+        (ctx if k in ctx else fl)[k] = v
+    for k in drop or ():
+        ctx.pop(k, None)
+        fl.pop(k, None)
+    return tfio.build_sequence_example(ctx, fl)
+
+
+def sample(rng, length=12288, h=224, w=298):
+    boxes = rng.randint(-20, 320, size=(4, 3)).astype(np.int32)
+    scene = rng.randint(0, 2, size=3).astype(np.int32)
+    audio = (rng.randn(1, length) * 900).astype(np.int32)
+    video = rng.randint(0, 256, size=(1, h, w, 3)).astype(np.uint8)
+    return boxes, scene, audio, video
+
+
+# ---- decoder ---------------------------------------------------------------------------------------------------------
+def test_box_decoder_round_trip(lib, tmp_path):
+    rng = np.random.RandomState(1)
+    recs = [sample(rng, length=L) for L in (12288, 7001)]
+    path = str(tmp_path / "boxes.tfrecord")
+    tfio.write_tfrecord(path, [box_record(*r) for r in recs], compression="GZIP")
+    got = tfio.read_tfrecord_native(path)
+    assert len(got) == 2
+    for rec, (boxes, scene, audio, video) in zip(got, recs):
+        d = tfio.decode_box_sequence_example_native(rec)
+        assert d["dims"].box_rows == 1 and d["dims"].video_steps == 1 and d["dims"].mics == 1
+        assert np.array_equal(d["boxes"][0], boxes)
+        assert np.array_equal(d["typescene"][0], scene)
+        assert np.array_equal(d["audio_samples"], audio) and d["audio_samples"].dtype == np.int32
+        assert np.array_equal(d["video_images"], video)
+
+
+def test_box_decoder_refuses_malformed_records(lib):
+    rng = np.random.RandomState(2)
+    boxes, scene, audio, video = sample(rng, length=512, h=8, w=10)
+    good = box_record(boxes, scene, audio, video)
+    assert tfio.decode_box_sequence_example_native(good)["boxes"].shape == (1, 4, 3)
+    bad = {
+        "truncated": good[:len(good) - 9],
+        "wrong type": box_record(boxes, scene, audio, video, override={"xmin": [np.array([1, 2, 3])]}),
+        "missing list": box_record(boxes, scene, audio, video, drop=["ymax"]),
+        "missing context": box_record(boxes, scene, audio, video, drop=["video/width"]),
+        "not [-1,3]": box_record(boxes, scene, audio, video, override={"xmax": [np.arange(4, dtype=np.int32).tobytes()]}),
+        "frame size": box_record(boxes, scene, audio, video, override={"video/image": [b"\0" * 17]}),
+        "negative dim": box_record(boxes, scene, audio, video, override={"video/height": np.array([-1])}),
+    }
+    for what, rec in bad.items():
+        r = np.frombuffer(rec, np.uint8)
+        dims = _lib.BoxSequenceDims()
+        rc = lib.acimg_box_sequence_example_decode(r.ctypes.data, r.size, dims, None, 0, None, 0, None, 0, None, 0)
+        assert rc < 0, what
+        assert "box_sequence_example_decode" in _lib.last_error(), what
+    # a buffer that is too small is refused with ACIMG_EWORKSPACE, not overrun
+    r = np.frombuffer(good, np.uint8)
+    dims = _lib.BoxSequenceDims()
+    small = np.zeros(11, np.int32)
+    rc = lib.acimg_box_sequence_example_decode(r.ctypes.data, r.size, dims, small.ctypes.data, small.size, None, 0,
+                                               None, 0, None, 0)
+    assert rc == -2 and not small.any()
+    # the existing decoder still refuses these records (no classes / location): unchanged behaviour
+    rc = lib.acimg_sequence_example_decode(r.ctypes.data, r.size, _lib.SequenceDims(), None, 0, None, 0, None, 0)
+    assert rc == -1
+
+
+# ---- loader ----------------------------------------------------------------------------------------------------------
+def test_box_mfcc_matches_the_reference_golden():
+    z = np.load(GOLDEN)
+    for i in range(3):
+        g = z["mfcc%d" % i].astype(np.float32)
+        g = g - g.min(axis=1, keepdims=True)
+        g = g / g.max(axis=1, keepdims=True)
+        got = box_mfcc(z["clip%d" % i])
+        assert got.dtype == np.float32 and got.shape == (1, 12)
+        assert np.abs(got - g).max() <= 2e-6, i
+    # the [1, 1, L] call of the TF pipeline: the same vector whatever the clip, not what the loader feeds
+    d = [z["degenerate%d" % i].ravel() for i in range(3)]
+    assert np.array_equal(d[0], d[1]) and np.array_equal(d[0], d[2]) and np.abs(d[0]).max() < 1e-12
+
+
+def test_box_loader_tuples(lib, tmp_path):
+    z = np.load(GOLDEN)
+    rng = np.random.RandomState(3)
+    recs = []
+    for i in range(3):
+        boxes, scene, _, video = sample(rng)
+        recs.append((boxes, scene, z["clip%d" % i], video))
+    files = [str(tmp_path / "a.tfrecord"), str(tmp_path / "b.tfrecord")]
+    tfio.write_tfrecord(files[0], [box_record(*r) for r in recs[:2]], compression="GZIP")
+    tfio.write_tfrecord(files[1], [box_record(*recs[2])], compression="GZIP")
+    listing = str(tmp_path / "test.txt")
+    with open(listing, "w") as f:
+        f.write("\n".join(files) + "\n")
+    loader = BoxRecordLoader(listing, batch_size=2)
+    assert loader.num_samples == 3 and loader.total_batches == 2
+    batches = list(loader.data)
+    assert [b[0].shape[0] for b in batches] == [2, 1]
+    cat = [np.concatenate([b[k].numpy() for b in batches]) for k in range(8)]
+    # a NumPy decode of the same files (pure-Python protobuf parser)
+    rows = []
+    for path in files:
+        for rec in tfio.read_tfrecord(path):
+            ctx, fl = tfio.parse_sequence_example(rec)
+            v = np.frombuffer(fl["video/image"][0][0], np.uint8).reshape(224, 298, 3)
+            a = np.frombuffer(fl["audio/data"][0][0], np.int32).reshape(-1, int(ctx["audio_data/samples"][0]))
+            bx = [np.frombuffer(fl[k][0][0], np.int32).reshape(-1, 3) for k in ("xmin", "xmax", "ymin", "ymax",
+                                                                                  "typescene")]
+            rows.append((v, a, bx))
+    assert cat[0].shape == (3, 36, 48, 12) and not cat[0].any() and cat[0].dtype == np.float32
+    for n, (v, a, bx) in enumerate(rows):
+        assert np.array_equal(cat[2][n], v[..., ::-1].astype(np.float32) * np.float32(1.0 / 255.0))
+        assert cat[2].dtype == np.float32 and cat[2].max() <= 1.0
+        for k in range(5):
+            assert np.array_equal(cat[3 + k][n], bx[k][0]) and cat[3 + k].dtype == np.int32
+        g = z["mfcc%d" % n].astype(np.float32)
+        g = (g - g.min()) / (g - g.min()).max()
+        assert np.abs(cat[1][n] - g.ravel()).max() <= 2e-6
+        assert np.array_equal(cat[1][n], box_mfcc(a)[0])
+
+
+# ---- the metric, hand-computed ---------------------------------------------------------------------------------------
+NOBOX = np.zeros((4, 3), np.int32)
+FULL = np.ones((224, 298), bool)
+EMPTY = np.zeros((224, 298), bool)
+
+
+def boxes_of(*rects):
+    b = np.zeros((4, 3), np.int32)
+    for k, (x0, x1, y0, y1) in enumerate(rects):
+        b[:, k] = (x0, x1, y0, y1)
+    return b
+
+
+def test_metric_box_over_the_whole_frame():
+    energy = np.zeros((36, 48), np.float32)
+    energy[:, :24] = 1.0                      # left half of the map above the mean
+    num, den, iou, m2 = ref.box_iou(energy, boxes_of((0, 297, 0, 223)))
+    # source column 23 reaches output columns 146..151; f < 0.5 (kept) up to dx = 148: columns 0..148 = half the frame
+    assert m2[:, :149].all() and not m2[:, 149:].any()
+    assert (num, den) == (149 * 224, 298 * 224)
+    assert iou == 0.5 and accuracy_curve([iou])[5] == 0.0    # IoU == tau is a miss
+
+
+def test_metric_overlapping_annotators_cap_and_half_weights():
+    b = boxes_of((0, 99, 0, 99), (50, 149, 0, 99), (50, 99, 0, 99))
+    mtot = ref.consensus(b)
+    assert mtot[0, 0] == 0.5 and mtot[0, 75] == 1.0 and mtot[0, 120] == 0.5 and mtot[100, 0] == 0.0
+    num, den, iou = ref.score(FULL, b)
+    # numerator 0.5*5000 + 1*5000 (1.5 capped) + 0.5*5000; denominator 66752 - 0.5 per half-weight pixel (10000)
+    assert (num, den) == (2 * 10000, 2 * (66752 - 5000))
+    assert iou == 10000 / 61752.0
+    num, den, iou = ref.score(EMPTY, b)
+    assert (num, den, iou) == (0, 2 * (15000 - 5000), 0.0)
+
+
+def test_metric_skips_xmax_zero_clips_and_orders_corners():
+    assert ref.score(FULL, boxes_of((10, 0, 5, 50)))[:2] == (0, 2 * 66752)         # xmax == 0: no annotator
+    off = boxes_of((200, 320, 150, 260))                                          # runs off the frame: clipped
+    assert ref.consensus(off).sum() == 0.5 * 98 * 74
+    assert ref.score(EMPTY, off)[:2] == (0, 98 * 74)
+    assert ref.score(FULL, off)[:2] == (98 * 74, 2 * 66752 - 98 * 74)
+    rev = boxes_of((100, 50, 80, 20))                                             # reversed corners
+    assert np.array_equal(ref.consensus(rev), ref.consensus(boxes_of((50, 100, 20, 80))))
+    assert ref.consensus(rev).sum() == 0.5 * 51 * 61
+
+
+def test_metric_empty_mask_and_no_box_is_nan():
+    num, den, iou = ref.score(EMPTY, NOBOX)
+    assert (num, den) == (0, 0) and np.isnan(iou)
+    assert not accuracy_curve([iou]).any()                                        # a miss at every tau
+    assert mean_iou([0.25, iou, 0.75]) == (0.5, 1)
+
+
+def test_metric_tie_column_74():
+    energy = np.zeros((36, 48), np.float32)
+    energy[:, :12] = 1.0                      # mask edge between source columns 11 | 12
+    m2 = ref.resize_mask(ref.energy_mask(energy))
+    sx, _, wx0, wx1 = ref.linear_coefs(48, 298)
+    assert sx[74] == 11 and wx0[74] == 0.5 and wx1[74] == 0.5
+    # horizontal value 0.5 on every row; vertically 0.5 * (wy0 + wy1), > 0.5 only where the float32 row weights
+    # round to a sum above 1 (two rows), never where they sum to exactly 1
+    _, _, wy0, wy1 = ref.linear_coefs(36, 224)
+    above = wy0.astype(np.float64) + wy1.astype(np.float64) > 1.0
+    assert above.sum() == 2
+    assert np.array_equal(m2[:, 74], above)
+    assert m2[:, :74].all() and not m2[:, 75:].any()
+    # the border rows read one source row twice in OpenCV (weights not clamped): those weights sum to exactly 1, so
+    # the clamped reading above decides the same way
+    f = ((np.arange(224) + 0.5) * (36 / 224.0) - 0.5).astype(np.float32)
+    fr = (f - np.floor(f).astype(np.float32)).astype(np.float32)
+    border = (f < 0) | (np.floor(f) >= 35)
+    assert (((np.float32(1) - fr).astype(np.float64) + fr.astype(np.float64))[border] == 1.0).all()
+
+
+# ---- python -m acimg.localize ----------------------------------------------------------------------------------------
+def test_localize_flags_and_output_files(tmp_path):
+    args = localize.parse_args(["--model", "UNet", "--train_file", "/data/lists/test.txt", "--init_checkpoint",
+                                str(tmp_path / "run" / "epoch_12.ckpt"), "--batch_size", "4", "--num_skip_conn", "2",
+                                "--ae", "1", "--threshold", "0.35", "--datatype", "flickr"])
+    assert (args.batch_size, args.num_skip_conn, args.ae, args.threshold) == (4, 2, 1, 0.35)
+    assert localize.is_box_metric(args)
+    d = localize.output_dir(args)
+    assert d == str(tmp_path / "run" / "UNet_test_AcousticFramesJet2_12")
+    args.datatype = "outdoor"
+    assert not localize.is_box_metric(args)
+    assert localize.output_dir(args) == str(tmp_path / "run" / "UNet_test_Acoustictry_12")
+    with pytest.raises(SystemExit):
+        localize.parse_args(["--train_file", "x.txt"])             # --init_checkpoint is required
+    ious = [0.05, 0.5, 0.62, float("nan"), 0.95, 0.3]
+    res = localize.write_outputs(d, ious, threshold=0.35)
+    names = sorted(os.listdir(d))
+    want = ["intersection_%s_accuracy.txt" % t for t in
+            ("0.0", "0.1", "0.2", "0.3", "0.35", "0.4", "0.5", "0.6", "0.7", "0.8", "0.9", "1.0")]
+    assert names == sorted(want + [localize.RESULT_FILE])
+    acc = accuracy_curve(ious)
+    for t, a in zip(THRESHOLDS, acc):
+        with open(localize.accuracy_file(d, t)) as f:
+            txt = f.read()
+        assert txt == "iou {:6f}".format(a) and float(txt.split(" ")[1]) == round(a, 6)
+    with open(localize.accuracy_file(d, 0.35)) as f:
+        assert f.read() == "iou {:6f}".format(3 / 6.0)
+    with open(os.path.join(d, localize.RESULT_FILE)) as f:
+        js = json.load(f)
+    assert js == json.loads(json.dumps(res))
+    assert js["iou"][3] is None and js["nan_count"] == 1 and js["num_samples"] == 6
+    assert js["accuracy"] == list(acc) and js["auc"] == area_under_curve(acc)
+    assert abs(js["mean_iou"] - np.mean([0.05, 0.5, 0.62, 0.95, 0.3])) < 1e-15
