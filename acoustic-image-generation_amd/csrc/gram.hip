@@ -54,7 +54,7 @@ struct GramParams {
     const char* X;       // split-format planes (hi at X, lo at X + lo_off)
     unsigned x_bytes;    // extent for the buffer resource
     unsigned lo_off;
-    int nblk16;          // 16-pixel blocks = ceil(rows / 16)
+    int rows;            // pixels; the pad rows of the last 16-pixel block are unspecified (include/acimg.h): read as zeros
     int C;
     int nb;              // BC-channel blocks per side
     int S;               // pixel ranges
@@ -140,8 +140,10 @@ __global__ __launch_bounds__(512, 2) void gram_partial_kernel(const GramParams p
 #pragma unroll
         for (int j = 0; j < PWN; ++j) {
             if (j >= PWD && diag) break;
+            // lane l of a 1 KiB request carries pixel row l >> 2 of its brick (16 rows of 64 bytes), on either plane
             const int p16 = pb0 + KPB * t + pc_pb[j];
-            const unsigned goff = (t < p.steps && p16 < p.nblk16) ? pc_goff[j] + (unsigned)p16 * cpb * 1024u : OOB;
+            const unsigned goff = (t < p.steps && 16 * p16 + (lane >> 2) < p.rows) ? pc_goff[j] + (unsigned)p16 * cpb * 1024u
+                                                                                    : OOB;
             char* dst = st + pc_dst[j];
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)dst, 16, goff, 0, 0, 0);
         }
@@ -374,7 +376,7 @@ using namespace acimg;
 extern "C" {
 
 size_t acimg_gram_stats_workspace(long rows, int C) {
-    if (rows <= 0 || C < 64 || (C != 64 && C % 128)) return 0;
+    if (rows <= 0 || C < 64 || (C != 64 && (C % 128 || C > 512))) return 0;     // exactly the shapes acimg_gram_stats takes
     return gram_plan(rows, C).bytes;
 }
 
@@ -395,7 +397,7 @@ int acimg_gram_stats(const void* x_planes, size_t x_lo_off, long rows, int C, co
     p.X = static_cast<const char*>(x_planes);
     p.x_bytes = (unsigned)(x_lo_off + plane);
     p.lo_off = (unsigned)x_lo_off;
-    p.nblk16 = g.nblk16;
+    p.rows = (int)rows;
     p.C = C;
     p.nb = g.nb;
     p.S = g.S;

@@ -194,7 +194,12 @@ int acimg_conv2d_dgrad_bf16(const AcimgConvDesc* d, const float* gy, int ldgy, c
  * ((row >> 4) * C / 32 + (c >> 5)) * 1024, inside it 16 rows (row & 15) of 64 bytes and the 16-byte group (c >> 3) & 3 of
  * a row at group ((c >> 3) ^ -(row >> 2)) & 3 - exactly the image the kernels keep in LDS, so an LDS-DMA request of the
  * K loop is one contiguous KiB (eight whole cache lines) instead of sixteen 64-byte pieces of sixteen rows.
- *   acimg_bn_relu_split:         planes = relu?(x*scale+shift)            (BN of a bottleneck conv, resnet50.py:109-121)
+ * When rows % 16 != 0 the last row of bricks has PAD ROWS (rows .. 16 ceil(rows / 16) - 1).  Their contents, and those of
+ * any gap between the end of the hi plane and lo_off, are unspecified: buffers are shared between layers of different
+ * shapes, so they may hold anything, NaN included.  No consumer lets them reach a result (convolution outputs,
+ * statistics, fused tails, shortcuts read back from planes, acimg_gram_stats), and no producer writes outside
+ * [0, plane_bytes) and [lo_off, lo_off + plane_bytes), plane_bytes = acimg_split_plane_bytes(rows, C).
+ *   acimg_bn_relu_split:        planes = relu?(x*scale+shift)            (BN of a bottleneck conv, resnet50.py:109-121)
  *   acimg_bn_add_relu_split:     planes (+ optional fp32) = relu(a*sa+ta + shortcut); shortcut = b32*sb+tb
  *                                (projection) or the previous unit's planes (identity / subsample)   (resnet50.py:104-123)
  *   acimg_bn_relu_maxpool_split: planes = maxpool3x3/s2(relu(x*scale+shift))                        (resnet50.py:207-208) */

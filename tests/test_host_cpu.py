@@ -114,6 +114,10 @@ def test_gram_stats_host_side(lib):
     assert lib.acimg_gram_stats_workspace(134400, 128) > 16 * 2 ** 20          # ~256 pixel ranges x 64 KiB + V + sums
     assert lib.acimg_gram_stats_workspace(134400, 64) > 0 and lib.acimg_gram_stats_workspace(8512, 512) > 0
     assert lib.acimg_gram_stats_workspace(1000, 96) == 0 and lib.acimg_gram_stats_workspace(0, 128) == 0
+    # the query agrees with the validator: C > 512 is refused by acimg_gram_stats, so no workspace (vision.py falls back to
+    # the statistics pass on a 0 here instead of failing at run time)
+    for cc in (640, 1024, 2048):
+        assert lib.acimg_gram_stats_workspace(8512, cc) == 0, cc
     buf = (C.c_float * 64)()
     big = (C.c_char * 4096)()
     a = C.addressof(big) + (-C.addressof(big)) % 16

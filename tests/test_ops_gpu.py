@@ -292,17 +292,40 @@ def plane_bytes(rows, Cc):
     return -(-rows // 16) * 16 * Cc * 2
 
 
-def unsplit(planes, lo_off, rows, Cc):
-    """two fp16 planes in LDS-tile order (uint8 buffer) -> float64 [rows, C] (undoing the 2^-2 scale): brick (row >> 4,
+def brick_index(rows, Cc):
+    """fp16 element index inside a split-format plane of every element of a [rows, C] tensor, row-major: brick (row >> 4,
     c >> 5) of 1 KiB, inside it row & 15 at 64 bytes and 16-byte group (c >> 3) & 3 at group ((c >> 3) ^ -(row >> 2)) & 3"""
     r = torch.arange(rows).view(-1, 1)
     c = torch.arange(Cc).view(1, -1)
     off = ((r >> 4) * (Cc // 32) + (c >> 5)) * 1024 + (r & 15) * 64 + ((((c >> 3) ^ (-(r >> 2))) & 3) << 4) + (c & 7) * 2
-    idx = (off // 2).reshape(-1).to(planes.device)
+    return (off // 2).reshape(-1)
+
+
+def unsplit(planes, lo_off, rows, Cc):
+    """two fp16 planes in LDS-tile order (uint8 buffer) -> float64 [rows, C] (undoing the 2^-2 scale)"""
+    idx = brick_index(rows, Cc).to(planes.device)
     n = plane_bytes(rows, Cc)
     hi = planes[:n].view(torch.float16)[idx].double()
     lo = planes[lo_off: lo_off + n].view(torch.float16)[idx].double()
     return ((hi + lo) * 4.0).reshape(rows, Cc).cpu()
+
+
+# what the bytes of split planes outside the valid rows' elements may hold (include/acimg.h: unspecified): fp16 NaN, and a
+# large finite value (0x7b7b = 6.2e4 per half, 2.5e5 after the x4 scale) that a ReLU or a max cannot hide; (fill byte, gap
+# between the hi plane's end and lo_off)
+POISONS = ((0xFF, 0), (0x7B, 4096))
+
+
+def repack(planes, lo_off, rows, Cc, fill, gap=0, slack=4096):
+    """a copy of split-format planes that keeps only the valid rows' elements: every other byte - the pad rows of the last
+    brick row, a `gap`-byte hole between the planes, `slack` bytes after the lo plane - holds `fill`.  -> (buffer, lo_off)"""
+    n = plane_bytes(rows, Cc)
+    lo2 = n + gap
+    out = torch.full((lo2 + n + slack,), fill, dtype=torch.uint8, device=planes.device)
+    idx = brick_index(rows, Cc).to(planes.device)
+    for src, dst in ((0, 0), (lo_off, lo2)):
+        out[dst:dst + n].view(torch.float16)[idx] = planes[src:src + n].view(torch.float16)[idx]
+    return out, lo2
 
 
 @pytest.mark.parametrize("tail", [False, True])
@@ -1405,13 +1428,16 @@ def test_batch_norm_affine_applied_while_staging(device, case):
 
 
 @pytest.mark.parametrize("case", [(134400, 64, 256), (34048, 256, 1024), (20011, 128, 512), (8512, 512, 2048), (37, 64, 100),
-                                  (4099, 128, 136), (50, 256, 256)])
+                                  (4099, 128, 136), (50, 256, 256), (4111, 128, 256), (15, 512, 136), (4111, 512, 512)])
 def test_gram_statistics_match_fp64(device, case):
     """acimg_gram_stats (round 4, csrc/gram.hip): the batch-norm statistics of a 1x1 conv's output from the column sums and
     the Gram matrix of its INPUT (split planes in brick order), finalised into scale / shift and the moving averages -
     against fp64 statistics of y = x w over the values the planes actually hold, against acimg_bn_finalize fed with those
     fp64 sums (the same finalisation arithmetic), and against the statistics pass it replaces; row counts that are not
-    multiples of 16 / 32, one row, K not a multiple of 16; deterministic (two runs, the same bits)"""
+    multiples of 16 / 32, one row, K not a multiple of 16; deterministic (two runs, the same bits).  The planes are
+    poisoned outside the valid rows (pad rows of the last brick row, a gap before lo_off, slack after the lo plane) with
+    fp16 NaN and with a large finite pattern: the pad rows are unspecified (include/acimg.h), and a consumer that sums
+    them gives NaN or statistics that are off by orders of magnitude"""
     from acimg import ops
 
     rows, Cc, K = case
@@ -1428,19 +1454,6 @@ def test_gram_statistics_match_fp64(device, case):
     ops.bn_relu_split(plan, x.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device), 1, xp, lo, rows, Cc)
     need = ops.gram_stats_workspace(rows, Cc)
     assert need > 0
-    outs = []
-    for rep in range(2):
-        ws = torch.full((need,), 0xff if rep else 0, dtype=torch.uint8, device=device)      # no dependence on its contents
-        sc = torch.full((K,), float("nan"), device=device)
-        sh = torch.full((K,), float("nan"), device=device)
-        mm, mv = mm0.to(device), mv0.to(device)
-        ops.gram_stats(plan, xp, lo, rows, Cc, w.to(device), ldw, K, gamma.to(device), beta.to(device), mm, mv, sc, sh, ws,
-                       decay=0.997, eps=1e-5)
-        torch.cuda.synchronize()
-        outs.append((sc.cpu(), sh.cpu(), mm.cpu(), mv.cpu()))
-    for a, b in zip(outs[0], outs[1]):
-        assert torch.equal(a, b)
-    sc, sh, mm, mv = outs[0]
     # fp64 reference on the values the planes hold (hi + lo: x to 2^-22)
     xv = unsplit(xp, lo, rows, Cc).double().cpu()
     y = xv @ w[:, :K].double()
@@ -1449,33 +1462,52 @@ def test_gram_statistics_match_fp64(device, case):
     inv = 1.0 / torch.sqrt(var.float() + 1e-5).double()
     sc_ref = gamma.double() * inv
     sh_ref = beta.double() - mean.float().double() * sc_ref
-    # statistics: mean to 1e-6 of the output's scale, variance to 2e-6 relative
-    mean_got = (beta.double() - sh.double()) / sc.double()
-    var_got = (gamma.double() / sc.double()) ** 2 - 1e-5
     scale_y = float(y.abs().max()) if rows > 1 else 1.0
-    assert float((mean_got - mean).abs().max()) <= 2e-6 * scale_y, float((mean_got - mean).abs().max())
-    if rows > 1:
-        assert float(((var_got - var).abs() / var.clamp_min(1e-12)).max()) <= 4e-6, float(((var_got - var).abs() / var).max())
-    close(sc, sc_ref, tol=3e-6, what="gram scale %s" % (case,))
-    close(sh, sh_ref, tol=3e-6, what="gram shift %s" % (case,))
     unb = var * (rows / (rows - 1.0)) if rows > 1 else var
-    close(mm, 0.997 * mm0.double() + 0.003 * mean, tol=2e-6, what="gram moving mean")
-    close(mv, 0.997 * mv0.double() + 0.003 * unb, tol=2e-6, what="gram moving variance")
-    # the statistics pass this replaces (same planes, split weights), finalised by acimg_bn_finalize
-    if K % 128 == 0 and rows >= 128 * 200:
-        d = ops.conv_desc(1, 1, rows, Cc, K, 1, 1, 1, "SAME")
-        wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
-        ops.conv2d_split3_prepare(plan, d, w[:, :K].reshape(1, 1, Cc, K).contiguous().to(device), wsplit)
-        tws = torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8, device=device)
-        srows = ops.conv2d_fwd_split3p_stats_rows(d)
-        st = torch.zeros(srows, 2, K, device=device)
-        ops.conv2d_fwd_split3p_stats(plan, d, xp, lo, wsplit, st, tail_ws=tws)
-        sc2, sh2 = torch.zeros(K, device=device), torch.zeros(K, device=device)
-        mm2, mv2 = mm0.to(device), mv0.to(device)
-        ops.bn_finalize(plan, st, srows, K, K, rows, gamma.to(device), beta.to(device), mm2, mv2, sc2, sh2, 0.997, 1e-5, True)
-        torch.cuda.synchronize()
-        close(sc, sc2.cpu(), tol=3e-6, what="gram scale vs statistics pass")
-        close(sh, sh2.cpu(), tol=3e-6, what="gram shift vs statistics pass")
+    for fill, gap in POISONS:
+        xq, loq = repack(xp, lo, rows, Cc, fill, gap)
+        what = "%s poison 0x%02x gap %d" % (case, fill, gap)
+        outs = []
+        for rep in range(2):
+            ws = torch.full((need,), 0xff if rep else 0, dtype=torch.uint8, device=device)      # no dependence on its contents
+            sc = torch.full((K,), float("nan"), device=device)
+            sh = torch.full((K,), float("nan"), device=device)
+            mm, mv = mm0.to(device), mv0.to(device)
+            ops.gram_stats(plan, xq, loq, rows, Cc, w.to(device), ldw, K, gamma.to(device), beta.to(device), mm, mv, sc, sh,
+                           ws, decay=0.997, eps=1e-5)
+            torch.cuda.synchronize()
+            outs.append((sc.cpu(), sh.cpu(), mm.cpu(), mv.cpu()))
+        for a, b in zip(outs[0], outs[1]):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), what      # the same bits, NaN included
+        sc, sh, mm, mv = outs[0]
+        # statistics: mean to 1e-6 of the output's scale, variance to 2e-6 relative
+        mean_got = (beta.double() - sh.double()) / sc.double()
+        var_got = (gamma.double() / sc.double()) ** 2 - 1e-5
+        err_mean = float((mean_got - mean).abs().max())
+        assert err_mean <= 2e-6 * scale_y, (what, err_mean)
+        if rows > 1:
+            err_var = float(((var_got - var).abs() / var.clamp_min(1e-12)).max())
+            assert err_var <= 4e-6, (what, err_var)
+        close(sc, sc_ref, tol=3e-6, what="gram scale " + what)
+        close(sh, sh_ref, tol=3e-6, what="gram shift " + what)
+        close(mm, 0.997 * mm0.double() + 0.003 * mean, tol=2e-6, what="gram moving mean " + what)
+        close(mv, 0.997 * mv0.double() + 0.003 * unb, tol=2e-6, what="gram moving variance " + what)
+        # the statistics pass this replaces (same poisoned planes, split weights), finalised by acimg_bn_finalize
+        if K % 128 == 0 and rows >= 128 * 200:
+            d = ops.conv_desc(1, 1, rows, Cc, K, 1, 1, 1, "SAME")
+            wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
+            ops.conv2d_split3_prepare(plan, d, w[:, :K].reshape(1, 1, Cc, K).contiguous().to(device), wsplit)
+            tws = torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8, device=device)
+            srows = ops.conv2d_fwd_split3p_stats_rows(d)
+            st = torch.zeros(srows, 2, K, device=device)
+            ops.conv2d_fwd_split3p_stats(plan, d, xq, loq, wsplit, st, tail_ws=tws)
+            sc2, sh2 = torch.zeros(K, device=device), torch.zeros(K, device=device)
+            mm2, mv2 = mm0.to(device), mv0.to(device)
+            ops.bn_finalize(plan, st, srows, K, K, rows, gamma.to(device), beta.to(device), mm2, mv2, sc2, sh2, 0.997, 1e-5,
+                            True)
+            torch.cuda.synchronize()
+            close(sc, sc2.cpu(), tol=3e-6, what="gram scale vs statistics pass " + what)
+            close(sh, sh2.cpu(), tol=3e-6, what="gram shift vs statistics pass " + what)
 
 
 @pytest.mark.parametrize("case", [(3, 14, 19, 64, 128), (2, 28, 38, 32, 160), (1, 56, 75, 32, 128), (5, 9, 79, 32, 128),
