@@ -26,19 +26,25 @@ The two documented 8-GPU commands (the driver runs the weak one; the >= 6x targe
         bench.py --gpus 8 --steps K --warmup W --scaling strong --global-batch 256  # strong: the same 256 images at every N
 At N > 1 (or `--dp-force` under torch.distributed.run at N = 1) the line verifies itself: `config.rccl_ranks`,
 `config.dp` = lanes obtained beside RCCL (min over ranks), the measured exchange time per step (events around the
-collectives, max over ranks), the same loop with the collectives muted, `exchange_hidden`, and the fallback taken if
-fewer than three streams run side by side (one-stream step, bucketed exchange overlapped with backward).
+collectives, max over ranks), the fallback taken if fewer than three streams run side by side (one-stream step, bucketed
+exchange overlapped with backward), and with --full the same loop with the collectives muted and `exchange_hidden`.
 
-One JSON line on rank 0.  `roofline` is for the dominant kernel (the 128x128-tile implicit-GEMM
+One JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, --warmup steps, the --steps
+timed steps, --dump-outputs, the line.  --full adds, after all of that, the parts below that take runs of their own;
+the headline is measured the same way with or without it.
+
+`roofline` is for the dominant kernel (the 128x128-tile implicit-GEMM
 forward conv that runs the ResNet trunk (LDS-DMA staged, XCD-aware tile order): split-fp16 "f16x3" MFMA by default, exact-f32 MFMA with
 --precision f32): ALGORITHMIC FLOPs (2*M*N*K per conv) of its launches divided by their
 HIP-event-measured duration, against the dense MFMA peak of the dtype the matrix cores run in.  One stream: the events
-of the timed region.  Pipelined: an event pair on a lane also brackets the wait behind the other lanes' kernels, so the
-kernel is timed in three one-stream steps right after the timed region (rocprofv3 --kernel-trace serialises kernels
-across streams, so its per-kernel average is the kernel alone on the chip too, and agrees); the timed region's event
-figure is reported beside it (`timed_region_event_*`).  The f16x3 kernel issues 3 MFMA FLOPs per algorithmic FLOP (`hw_flop_factor`).  `cpu_baseline` times the CPU oracle
-(PyTorch restatement of the reference's TF-1 graph; TF-1 itself is unavailable offline) on a bounded
-sample on this box's host cores.
+of the timed region.  Pipelined (--full only, null otherwise): an event pair on a lane also brackets the wait behind the
+other lanes' kernels, so the kernel is timed in three one-stream steps right after the timed region (rocprofv3
+--kernel-trace serialises kernels across streams, so its per-kernel average is the kernel alone on the chip too, and
+agrees); the timed region's event figure is reported beside it (`timed_region_event_*`).  The f16x3 kernel issues 3 MFMA
+FLOPs per algorithmic FLOP (`hw_flop_factor`).  --full also adds `cpu_baseline`, the CPU oracle (PyTorch restatement of
+the reference's TF-1 graph; TF-1 itself is unavailable offline) timed on a bounded sample on the host cores this process
+may use, and `secondary` / `secondary2`, configs[1] and configs[2] timed after the headline; `--workload classifier`
+carries its roofline with --full only (three more steps).
 """
 import argparse
 import json
@@ -104,9 +110,16 @@ def parse():
                     help="HIP priority of the pipeline's extra streams (0 normal, -1 high): experiment")
     ap.add_argument("--no-side-lane", action="store_true",
                     help="record the plans without the second HIP stream for weight gradients / projection shortcuts")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the configs[1] / "
+                         "configs[2] side measurements, the dominant kernel timed alone in one-stream steps after a "
+                         "pipelined timed region, the classifier's trunk-kernel roofline, and at N > 1 the step with the "
+                         "collectives muted (exchange_hidden).  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the configs[1] (UNet RGB VAE) and configs[2] (2-skip, batch 64) side measurements")
+                    help="with --full: skip the configs[1] (UNet RGB VAE) and configs[2] (2-skip, batch 64) side "
+                         "measurements")
     ap.add_argument("--cpu-batch", type=int, default=32, help="BASELINE.md §3: the CPU leg runs the GPU leg's batch")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed CPU steps (BASELINE.md §3: >= 10) after --cpu-warmup")
     ap.add_argument("--cpu-warmup", type=int, default=3, help="BASELINE.md §3: >= 3")
@@ -167,7 +180,7 @@ def cpu_baseline(args):
     """CPU oracle train step: the SAME step as the GPU leg — same generator variant (--num-skip), same
     batch (32) — on a BOUNDED sample: --cpu-warmup (3) warm-up steps, then up to --cpu-steps (10) timed steps (about
     6 s each on the GPU box's 16-core share: ~75 s), stopping early once --cpu-budget seconds (default 150) of timed
-    work are spent (at least one timed step), so the default bench.py run stays within a few minutes.  `cores` = the
+    work are spent (at least one timed step), so a bench.py --full run stays within a few minutes.  `cores` = the
     thread count actually set with torch.set_num_threads (affinity mask capped by the cgroup CPU quota).  Progress
     goes to stderr."""
     from oracle import trainer as otr
@@ -467,7 +480,7 @@ def other_workload(args):
     if args.workload in VAE_ACT_ELEMS:
         roof = vae_roofline(args.workload, B, dt / args.steps * 1e3,
                             "unet_rgb" if (args.workload == "unet_rgb" and args.unet_precision == "bf16" and B == 32) else None)
-    else:
+    elif args.full:
         # configs[4]: the dominant kernel is the trunk's (inference-mode forward of the frozen encoder): HIP events around
         # its launches in 3 more steps (one stream: the plan has no second lane here)
         probe_idx, flops, alg_bytes, kernel_name = cls_probe
@@ -653,31 +666,34 @@ def main():
     dp_report = None
     if dp_on:
         # what the exchange costs and whether the schedule hides it: (a) device time between the events that bracket the
-        # collectives of the timed region, per step, max over ranks; (b) the SAME timed loop once more with the collectives
-        # muted (weights diverge between ranks from here on: nothing after this point is a result) - `exchange_hidden` =
-        # the step with the exchange took at most 2 % longer than the step without it
-        tr.comm.muted = True
-        for _ in range(min(args.warmup, 3)):
-            one_step()
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            one_step()
-        barrier()
-        dt_mute = time.perf_counter() - t1
-        if pipelined:
-            tr.flush_pipeline()
-            torch.cuda.synchronize()
+        # collectives of the timed region, per step, max over ranks; (b) --full: the SAME timed loop once more with the
+        # collectives muted (weights diverge between ranks from here on: nothing after this point is a result) -
+        # `exchange_hidden` = the step with the exchange took at most 2 % longer than the step without it
+        dt_mute = 0.0
+        if args.full:
+            tr.comm.muted = True
+            for _ in range(min(args.warmup, 3)):
+                one_step()
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                one_step()
+            barrier()
+            dt_mute = time.perf_counter() - t1
+            if pipelined:
+                tr.flush_pipeline()
+                torch.cuda.synchronize()
         t = torch.tensor([ex_ms, dt_mute], device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ex_ms, dt_mute = float(t[0]), float(t[1])
         dp_report = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(),
                      "lanes_min_over_ranks": lanes_min, "fallback": dp_fallback,
-                     "collectives_per_step": n_coll / max(args.steps, 1),
-                     "exchange_ms_per_step": ex_ms, "no_exchange_ms_per_step": dt_mute / args.steps * 1e3}
+                     "collectives_per_step": n_coll / max(args.steps, 1), "exchange_ms_per_step": ex_ms,
+                     "no_exchange_ms_per_step": dt_mute / args.steps * 1e3 if args.full else None,
+                     "exchange_hidden": None}
     seq_events = []
-    if pipelined and events:
+    if pipelined and events and args.full:
         # kernel quality without a second lane on the chip: a few one-stream steps after the timed region
         for _ in range(3):
             tr.train_step(sync=False, probe=(probe_idx, seq_events))
@@ -686,13 +702,15 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    if dp_report is not None:
+    if dp_report is not None and args.full:
         dp_report["exchange_hidden"] = bool(dt / args.steps * 1e3 <= 1.02 * dp_report["no_exchange_ms_per_step"])
 
     roof = None
     prof = load_traffic_profile(kernel_name) if f16 else None
     prof_ok = bool(prof and prof["kernel_bytes_per_launch"] and B == 32 and not strong)
-    if events:
+    # one stream: the events of the timed region are the kernel's figure; pipelined: the figure needs the one-stream
+    # steps above (--full), and without them the line carries no roofline
+    if events and (seq_events or not pipelined):
         ms = sum(e0.elapsed_time(e1) for _, e0, e1 in events)
         fl = sum(flops[i] for i, _, _ in events)
         achieved = fl / (ms * 1e-3) / 1e12
@@ -791,9 +809,9 @@ def main():
             roof["traffic_ratio"] = roof["traffic"] / roof["alg_bytes"]
             roof["hbm_GBps"] = roof["traffic"] / (roof["avg_launch_ms"] * 1e-3) / 1e9
             roof["hbm_frac"] = roof["hbm_GBps"] * 1e9 / 8.0e12
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # BASELINE configs[1] (the RGB U-Net VAE at batch 32) timed next to the north-star path, for reference
             for key, fn in (("secondary", secondary_unet_rgb), ("secondary2", secondary_configs2)):
                 try:

@@ -397,6 +397,26 @@ def test_bench_dump_outputs_on_cpu(tmp_path):
     np.testing.assert_array_equal(w, np.load(str(tmp_path / "b" / "weights.npy")))
 
 
+def test_bench_extras_are_opt_in_on_cpu():
+    """bench.py --full: off by default (a plain run measures the headline only); the CPU baseline and side
+    measurements it gates keep their own switches"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+        spec.loader.exec_module(bench)
+        args = bench.parse()
+        assert not args.full and not args.no_cpu_baseline and not args.no_secondary
+        sys.argv = ["bench.py", "--full", "--no-cpu-baseline"]
+        args = bench.parse()
+        assert args.full and args.no_cpu_baseline and not args.no_secondary
+    finally:
+        sys.argv = argv
+
+
 def test_no_wide_buffer_store_with_register_soffset(tmp_path):
     """Enforced invariant: gfx950 takes a data register that a VALU instruction overwrites right
     after a > 8-byte `buffer_store` when the store's soffset is an SGPR - the ISA manual and the compiler's hazard
