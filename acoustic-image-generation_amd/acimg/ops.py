@@ -132,15 +132,21 @@ def _resolve(a):
 class PrepareJobs(object):
     """Kernels whose split images one acimg_conv2d_split3_prepare_multi launch rebuilds: (descriptor, fp32 kernel,
     image buffer, mode 0 forward / 1 data gradient).  The ctypes tables are built when the plan is finalised, so
-    jobs may still be added after the launch has been recorded."""
+    jobs may still be added after the launch has been recorded - but not after that: a later job would never run and its
+    consumer would read a stale image, so `add` refuses it."""
 
     def __init__(self):
         self.jobs = []
+        self._built = False
 
     def add(self, d, w, out, mode):
+        if self._built:
+            raise RuntimeError("PrepareJobs.add: the job tables were already built (a plan holding this launch was finalised "
+                               "or run); record every job before that")
         self.jobs.append((d, w, out, int(mode)))
 
     def build(self):
+        self._built = True
         n = len(self.jobs)
         assert n <= 16, "conv2d_split3_prepare_multi takes at most 16 jobs (%d)" % n
         self._d = (C.POINTER(ConvDesc) * n)(*[C.pointer(j[0]) for j in self.jobs])

@@ -1778,9 +1778,12 @@ static bool few16_channels(int cin, int nout, long pixels) {
     return (cin == 4 || cin == 8 || cin == 16) && nout >= 4 && nout <= 32 && (nout & 3) == 0 && !(cin != 8 && nout > 16) &&
            pixels >= 65536 && g_cfg.wgrad_halo;
 }
+// (ldx a multiple of 4: the kernel stages x in float4 pieces - and the predicate is what acimg_conv2d_stats_rows and
+// acimg_conv2d_affine_input_ok answer from, so it must not promise this form to a descriptor the entry point refuses)
 static bool few16_fwd_shape(const AcimgConvDesc* d) {
     return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->OH == d->H && d->OW == d->W &&
-           few16_channels(d->C, d->K, (long)d->N * d->OH * d->OW) && d->act == ACIMG_ACT_NONE && d->ldx >= d->C;
+           few16_channels(d->C, d->K, (long)d->N * d->OH * d->OW) && d->act == ACIMG_ACT_NONE && d->ldx >= d->C &&
+           (d->ldx & 3) == 0;
 }
 // the data gradient of a 3x3 conv is a 3x3 / stride-1 conv of gy (K channels, padded to 4) into C channels: of gy itself
 // (stride 1) or of its zero-inserted view (stride 2: the view is formed while the tile is staged, no copy)

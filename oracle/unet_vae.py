@@ -165,7 +165,9 @@ def forward(p, x, eps, model="UNet", training=True, relu_masks=None, bf16_operan
     relu_masks {layer name: 0/1 tensor}: the ReLU on/off pattern of the implementation under test, so that both
     sides differentiate the SAME piecewise-linear function (of the ~10^7 pre-activations of a batch a few hundred
     sit within fp32 rounding of zero; fp32 and fp64 evaluations of this very oracle differ by 1e-3..1e-2 in the
-    gradients for that reason alone).  Forward values are unaffected beyond that rounding."""
+    gradients for that reason alone).  Forward values are unaffected beyond that rounding.
+    out["masks"] holds this evaluation's OWN sign pattern (t > 0) of every ReLU, masked or not: one masked run gives
+    both the parity and the census of places where the supplied pattern disagrees with the oracle's."""
     cfg = CONFIGS[model]
     sc = cfg["scope"]
     new_stats = OrderedDict()
@@ -174,6 +176,7 @@ def forward(p, x, eps, model="UNet", training=True, relu_masks=None, bf16_operan
 
     def relu(name, t):
         if relu_masks is not None and name in relu_masks:
+            masks_out[name] = (t.detach() > 0)
             return t * relu_masks[name].to(t.dtype)
         y = torch.relu(t)
         masks_out[name] = (y > 0)
@@ -226,13 +229,36 @@ def forward(p, x, eps, model="UNet", training=True, relu_masks=None, bf16_operan
     return dict(output=out, mean=mean, variance=var, z=z, acts=acts, masks=masks_out), new_stats
 
 
-def losses(p, x, fw, model="UNet"):
-    """trainer/trainer.py:58-75"""
+class _KLGradAt(torch.autograd.Function):
+    """kl[n] = 0.5 * mean_j(mu^2 + sg^2 - log(1e-8 + sg^2) - 1) at (mu, sg), differentiated at (mu_at, sg_at)"""
+
+    @staticmethod
+    def forward(ctx, mu, sg, mu_at, sg_at):
+        ctx.save_for_backward(mu_at, sg_at)
+        return 0.5 * (mu * mu + sg * sg - torch.log(1e-8 + sg * sg) - 1).mean(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        mu, sg = ctx.saved_tensors
+        g = g[:, None] / mu.shape[1]
+        return g * mu, g * (sg - sg / (1e-8 + sg * sg)), None, None
+
+
+def losses(p, x, fw, model="UNet", kl_grad_at=None):
+    """trainer/trainer.py:58-75.
+    kl_grad_at (mu, sg): the latent statistics of the implementation under test, at which the KL term is DIFFERENTIATED
+    (its value stays this evaluation's own).  The KL gradient sg / (1e-8 + sg^2) peaks at |sg| = 1e-4, where it is larger
+    than the reconstruction's share of the head gradient by ~100x and as ill-conditioned as sg itself: a variance output
+    that is a near-cancelling sum of 32256 terms moves by ~1e-2 relative between an fp32 and an fp64 evaluation, and so
+    does its gradient.  Like `relu_masks`, this makes both sides differentiate at the same point."""
     cfg = CONFIGS[model]
     mse = tfsem.mse_loss(x, fw["output"])
     hub = tfsem.huber_loss(x, fw["output"])
     mu, sg = fw["mean"], fw["variance"]
-    kl = 0.5 * (mu * mu + sg * sg - torch.log(1e-8 + sg * sg) - 1).mean(1)
+    if kl_grad_at is None:
+        kl = 0.5 * (mu * mu + sg * sg - torch.log(1e-8 + sg * sg) - 1).mean(1)
+    else:
+        kl = _KLGradAt.apply(mu, sg, *(t.detach().to(mu.dtype).reshape(mu.shape) for t in kl_grad_at))
     latent = kl.mean(0) / 1000000
     reg = sum(tfsem.l2_regularizer(w, cfg["wd"]) for n, w in p.items() if regularized(n))
     return dict(loss=latent + mse + hub + reg, mse=mse, huber=hub, latent=latent, reg=reg)
@@ -252,10 +278,10 @@ class Oracle(object):
         self.v = OrderedDict((k, torch.zeros_like(v)) for k, v in self.params.items() if trainable(k))
         self.step = 0
 
-    def train_step(self, x, eps, apply=True, relu_masks=None):
+    def train_step(self, x, eps, apply=True, relu_masks=None, kl_grad_at=None):
         p = OrderedDict((k, v.clone().requires_grad_(trainable(k))) for k, v in self.params.items())
         fw, stats = forward(p, x.to(self.dtype), eps.to(self.dtype), self.model, True, relu_masks, self.bf16_operands)
-        ls = losses(p, x.to(self.dtype), fw, self.model)
+        ls = losses(p, x.to(self.dtype), fw, self.model, kl_grad_at)
         names = [k for k in p if trainable(k)]
         grads = torch.autograd.grad(ls["loss"], [p[k] for k in names])
         g = OrderedDict(zip(names, grads))

@@ -132,6 +132,58 @@ def test_gram_stats_host_side(lib):
     assert rc == -1 and "workspace too small" in _lib.last_error()
 
 
+def test_few_channel_forward_needs_a_float4_pixel_stride(lib):
+    """The few-channel MFMA forward stages x in float4 pieces at pixel * ldx.  The entry point and the input-affine query
+    already refused a descriptor whose ldx is not a multiple of 4 (8 channels, ldx 9); the statistics-row count (and the
+    forward workspace query) answered for the few-channel form all the same.  Now all of them agree; the refusal happens
+    before any launch (fake aligned pointers, no GPU here)."""
+    import ctypes as C
+
+    from acimg import _lib, ops
+
+    ok = ops.conv_desc(2, 224, 298, 8, 8, 3, 3, 1, "SAME", ldx=8)
+    odd = ops.conv_desc(2, 224, 298, 8, 8, 3, 3, 1, "SAME", ldx=9)
+    assert ops.conv2d_stats_rows(ok) == 512                   # one row per workgroup of the few-channel kernel
+    assert ops.conv2d_stats_rows(odd) == -(-2 * 224 * 298 // 256)
+    assert ops.conv2d_affine_input_ok(ok, 0) and not ops.conv2d_affine_input_ok(odd, 0)
+    big = (C.c_char * 4096)()
+    a = C.addressof(big) + (-C.addressof(big)) % 16
+    rc = lib.acimg_conv2d_fwd(C.byref(odd), a, a, None, a, None, None, 0, a, a, 4096, None, None)
+    assert rc == -1 and "multiples of 4" in _lib.last_error()
+
+
+def test_prepare_jobs_refuse_a_job_after_the_tables_are_built(lib):
+    """ops.PrepareJobs: the job tables of the one prepare_multi launch are built when a plan holding it is finalised; a job
+    added after that would never run (its data-gradient conv would read a stale weight image), so it is refused.  The
+    U-Net VAE adds its data-gradient jobs while the backward is recorded: finalising the forward plan first trips it."""
+    from acimg import ops
+    from acimg.session import Session
+    from acimg.unet_vae import UNet
+
+    d = ops.conv_desc(2, 12, 16, 64, 64, 3, 3, 1, "SAME")
+    w = torch.zeros(3, 3, 64, 64)
+    img = torch.zeros(int(ops.conv2d_split3_weight_bytes(d)), dtype=torch.uint8)
+    jobs = ops.PrepareJobs()
+    plan = ops.Plan(torch.device("cpu"))
+    ops.conv2d_split3_prepare_multi(plan, jobs)
+    jobs.add(d, w, img, 0)                       # recorded after the launch, before the plan is finalised: fine
+    plan.finalize()
+    assert len(jobs.jobs) == 1
+    with pytest.raises(RuntimeError, match="already built"):
+        jobs.add(d, w, img, 1)
+    plan.finalize()                              # a second finalisation rebuilds the same tables
+    assert len(jobs.jobs) == 1
+
+    sess = Session(torch.device("cpu"))
+    m = UNet()
+    N = 16
+    m._build_model(sess.zeros(N, 224, 298, 3), session=sess)
+    sess.finalize()
+    m.plan_fwd.finalize()                        # e.g. a forward-only run before the backward is recorded
+    with pytest.raises(RuntimeError, match="already built"):
+        m.record_backward(sess.new_plan(), sess.zeros(N, 224, 298, 4), 1e-6)
+
+
 def _build(num_skip, ae, batch=2):
     from acimg.flags import FLAGS
     from acimg.session import Session

@@ -588,3 +588,97 @@ def test_bf16_operand_mode_of_the_unet_oracle():
     assert torch.allclose(gb, gr.sum((0, 2, 3)), rtol=0, atol=1e-12)
     # the rounding is in the gradients too: an un-rounded gy gives a different data gradient
     assert not torch.allclose(gx.permute(0, 3, 1, 2), F.conv_transpose2d(gy.permute(0, 3, 1, 2), wr, padding=1), rtol=0, atol=1e-6)
+
+
+def test_unet_vae_masked_oracle_reports_its_own_relu_pattern():
+    """oracle/unet_vae.py forward(relu_masks=...): a masked run also reports its OWN sign pattern (one run gives the parity
+    and the census of the GPU tests).  Fed a free run's pattern it reproduces that run exactly; fed a pattern with a few
+    places flipped it still reports what it computed, so the census finds exactly those places."""
+    from oracle import unet_vae as ouv
+
+    params = ouv.init_params("UNet", seed=7, dtype=torch.float64, bias_std=0.05, bn_jitter=0.1)
+    x, eps = ouv.synthetic_batch("UNet", 1, seed=11, dtype=torch.float64)
+    orc = ouv.Oracle("UNet", learning_rate=1e-3, dtype=torch.float64, params=params)
+    free = orc.train_step(x, eps, apply=False)
+    masks = {k: v.clone() for k, v in free["fw"]["masks"].items()}
+    assert len(masks) == 22 + 2                  # every conv-BN-ReLU layer, the dense layer and conv2d
+    masked = orc.train_step(x, eps, apply=False, relu_masks=masks)
+    assert set(masked["fw"]["masks"]) == set(masks)
+    for k, v in masks.items():
+        assert torch.equal(masked["fw"]["masks"][k], v), k
+    for k in ("output", "mean", "variance"):
+        assert torch.equal(masked["fw"][k], free["fw"][k]), k
+    assert masked["losses"] == free["losses"]
+    for k, g in free["grads"].items():
+        assert torch.equal(masked["grads"][k], g), k
+    for k, v in free["new_stats"].items():
+        assert torch.equal(masked["new_stats"][k], v), k
+    # the first layer's pre-activations do not depend on any mask: flipping 5 of its places is seen as 5 flips there
+    first = "layer1/conv_1"
+    bad = dict(masks)
+    bad[first] = masks[first].clone().reshape(-1)
+    bad[first][[3, 1000, 20000, 300000, 500000]] ^= True
+    bad[first] = bad[first].reshape(masks[first].shape)
+    own = orc.train_step(x, eps, apply=False, relu_masks=bad)["fw"]["masks"]
+    assert torch.equal(own[first], masks[first])
+    assert int((own[first] != bad[first]).sum()) == 5
+
+
+def test_unet_vae_oracle_kl_gradient_point():
+    """oracle/unet_vae.py losses(kl_grad_at=(mu, sg)): the KL term keeps its own value and is differentiated at the given
+    latent statistics - at the oracle's own ones that is the plain step, exactly; at others only the gradients move, by
+    what d/dmu = mu / Z and d/dsg = (sg - sg / (1e-8 + sg^2)) / Z at the new point give."""
+    from oracle import unet_vae as ouv
+
+    params = ouv.init_params("UNet", seed=7, dtype=torch.float64, bias_std=0.05, bn_jitter=0.1)
+    x, eps = ouv.synthetic_batch("UNet", 2, seed=11, dtype=torch.float64)
+    orc = ouv.Oracle("UNet", learning_rate=1e-3, dtype=torch.float64, params=params)
+    plain = orc.train_step(x, eps, apply=False)
+    masks = dict(plain["fw"]["masks"])
+    mu, sg = plain["fw"]["mean"].detach(), plain["fw"]["variance"].detach()
+
+    def gscale(r):
+        return max(float(g.abs().max()) for g in r["grads"].values())
+    same = orc.train_step(x, eps, apply=False, relu_masks=masks, kl_grad_at=(mu, sg))
+    assert same["losses"] == plain["losses"]
+    for k, g in plain["grads"].items():      # (the KL gradient is summed in another order: rounding of fp64 only)
+        assert float((same["grads"][k] - g).abs().max()) <= 1e-12 * float(g.abs().max()) + 1e-15 * gscale(plain), k
+    mu2, sg2 = mu * 1.5, sg + 0.25
+    moved = orc.train_step(x, eps, apply=False, relu_masks=masks, kl_grad_at=(mu2, sg2))
+    assert moved["losses"] == plain["losses"]
+    Z, N = mu.shape[1], mu.shape[0]
+    w = 1.0 / (1e6 * N * Z)
+    d_mu = w * (mu2 - mu)
+    d_sg = w * ((sg2 - sg2 / (1e-8 + sg2 * sg2)) - (sg - sg / (1e-8 + sg * sg)))
+    # the heads' bias gradients are the column sums of d loss / d (mean | variance)
+    assert torch.allclose(moved["grads"]["UNet/mean/bias"] - plain["grads"]["UNet/mean/bias"], d_mu.sum(0), rtol=1e-9, atol=1e-20)
+    assert torch.allclose(moved["grads"]["UNet/variance/bias"] - plain["grads"]["UNet/variance/bias"], d_sg.sum(0), rtol=1e-9,
+                          atol=1e-20)
+
+
+def test_unet_vae_batch_16_selects_the_benched_kernels():
+    """bench.py times UNet at batch 32; tests/test_unet_vae_gpu.py::test_unet_vae_train_step_at_the_benched_selection checks
+    that selection against the fp64 oracle at batch 16, where the host plan is the same: the call sequence, the layers whose
+    batch norm is applied while the consumer stages its tiles, the split / bf16 layers and the layers that take an input
+    affine.  The size rules behind them (acimg/unet_vae.py `_use_split`, csrc/igemm.hip's 65536-pixel forms) decide this."""
+    from acimg import ops
+    from acimg.session import Session
+    from acimg.trainer_vae import TrainerVAE
+    from acimg.unet_vae import UNet
+
+    def selection(precision, N):
+        tr = TrainerVAE(UNet(precision=precision), session=Session(torch.device("cpu")))
+        g = tr._build_functions(batch_size=N)
+        m = tr.model
+        return dict(calls=[c[0] for c in g.plan_train.calls],
+                    deferred=[n for n, L in m.layers.items() if L.deferred],
+                    split=[n for n, L in m.layers.items() if m._use_split(L.d)],
+                    affine_ok=[n for n, L in m.layers.items() if ops.conv2d_affine_input_ok(L.d, m._prec(L.d))])
+
+    for precision in ("split", "bf16"):
+        s16, s32 = selection(precision, 16), selection(precision, 32)
+        for k in s16:
+            assert s16[k] == s32[k], ("UNet(precision=%r) selects differently at batch 16 and at the benched batch 32 (%s): a "
+                                      "size threshold moved, so the batch of test_unet_vae_train_step_at_the_benched_selection "
+                                      "must move with it" % (precision, k))
+        assert len(s16["deferred"]) == 8 and len(s16["split"]) == 11, s16

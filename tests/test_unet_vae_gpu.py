@@ -20,26 +20,57 @@ def rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
-@pytest.mark.parametrize("model,precision", [("UNet", "split"), ("UNetSound", "split"), ("UNetSound", "f32")])
-def test_unet_vae_train_step(model, precision):
+def _hip_masks(m):
+    """the ReLU on/off pattern of the HIP run, keyed like the oracle's ReLUs"""
+    masks = {name: (L.relu_output() > 0).cpu() for name, L in m.layers.items()}
+    masks["dense"] = (m.dns1 > 0).cpu()
+    masks["conv2d"] = (m.c2d.t > 0).cpu()
+    return masks
+
+
+def _oracle_step(orc, x, eps, masks, kl_grad_at=None):
+    """one oracle train step on the HIP run's ReLU pattern, kept lean: what the tests compare, with the graph and the
+    intermediate activations released (an fp64 step at batch 16 holds several GB while it runs).  `flips` of `total`:
+    pre-activations of the oracle's own evaluation that lie on the other side of zero from the HIP run's"""
+    r = orc.train_step(x, eps, apply=False, relu_masks=masks, kl_grad_at=kl_grad_at)
+    own = r["fw"]["masks"]
+    assert set(own) == set(masks) and all(own[k].shape == masks[k].shape for k in masks)
+    out = dict(output=r["fw"]["output"].detach(), mean=r["fw"]["mean"].detach(), variance=r["fw"]["variance"].detach(),
+               losses=r["losses"], grads={k: v.detach() for k, v in r["grads"].items()},
+               new_stats={k: v.detach() for k, v in r["new_stats"].items()},
+               flips=sum(int((own[k] != masks[k]).sum()) for k in masks), total=sum(v.numel() for v in masks.values()))
+    del r, own
+    return out
+
+
+def _build_step(model, precision, N):
+    """trainer at batch N, same parameters on both sides (biases / gamma / beta randomised so those paths carry signal)"""
     from acimg.session import Session
     from acimg.trainer_vae import TrainerVAE
     from acimg import unet_vae
     from oracle import unet_vae as ouv
-    from oracle import tfsem
 
-    dev = torch.device("cuda:0")
-    N = 2
-    cls = getattr(unet_vae, model)
-    sess = Session(dev)
-    tr = TrainerVAE(cls(precision=precision), learning_rate=1e-3, session=sess)
-    g = tr._build_functions(batch_size=N)
-    # same parameters on both sides; biases / gamma / beta randomised so those paths carry signal
+    sess = Session(torch.device("cuda:0"))
+    tr = TrainerVAE(getattr(unet_vae, model)(precision=precision), learning_rate=1e-3, session=sess)
+    tr._build_functions(batch_size=N)
     params = ouv.init_params(model, seed=7, dtype=torch.float64, bias_std=0.05, bn_jitter=0.1)
     tr.model.initialize(state={k: v.float() for k, v in params.items()})
     x, eps = ouv.synthetic_batch(model, N, seed=11, dtype=torch.float64)
-    orc = ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float64, params=params)
+    return tr, sess, params, x, eps
 
+
+def _step_against_fp64(model, tr, sess, params, x, eps, flips_ok, kl_at_hip=False):
+    """one step of the fp32-class product against the fp64 oracle: outputs, loss terms, every gradient, the moving
+    statistics and one TF-1 Adam update; flips_ok(flips, total) judges the ReLU census.
+    kl_at_hip: the oracle differentiates the KL term at the HIP run's latent statistics (oracle/unet_vae.py `losses`).  At
+    batch 16 one of the 2048 variance outputs is 3.1e-4, next to the peak of the KL gradient sg / (1e-8 + sg^2) at 1e-4, and
+    that one value, a near-cancelling sum of 32256 terms, moves the variance head's gradient and the encoder's behind it by
+    up to 8e-3 between fp32 and fp64 evaluations of the oracle itself (4.8e-5 once both differentiate at the same point)."""
+    from oracle import unet_vae as ouv
+    from oracle import tfsem
+
+    dev = torch.device("cuda:0")
+    orc = ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float64, params=params)
     r = tr.train_step(x.float().to(dev), eps.float().to(dev), apply=False)
     torch.cuda.synchronize()
     m = tr.model
@@ -47,21 +78,14 @@ def test_unet_vae_train_step(model, precision):
     # The oracle differentiates the same piecewise-linear function: ReLU on/off patterns are taken from the HIP run
     # (5 flips out of ~2e7 pre-activations move this model's gradients by up to 1e-2 — fp32 vs fp64 runs of the
     # oracle itself show it); forward values are compared independently of that below.
-    masks = {}
-    for name, L in m.layers.items():
-        masks[name] = (L.relu_output() > 0).cpu()
-    masks["dense"] = (m.dns1 > 0).cpu()
-    masks["conv2d"] = (m.c2d.t > 0).cpu()
-    free = orc.train_step(x, eps, apply=False)
-    flips = sum(int((free["fw"]["masks"][k] != masks[k].reshape(free["fw"]["masks"][k].shape)).sum()) for k in masks)
-    print("%s: ReLU pattern differs from the fp64 oracle's in %d of %d places" %
-          (model, flips, sum(v.numel() for v in masks.values())))
-    assert flips < 200
-    ref = orc.train_step(x, eps, apply=False, relu_masks={k: v.reshape(free["fw"]["masks"][k].shape)
-                                                          for k, v in masks.items()})
+    ref = _oracle_step(orc, x, eps, _hip_masks(m), (m.mean.cpu(), m.variance.cpu()) if kl_at_hip else None)
+    flips, total = ref["flips"], ref["total"]
+    print("%s: ReLU pattern differs from the fp64 oracle's in %d of %d places (rate %.2e)" %
+          (model, flips, total, flips / total))
+    assert flips_ok(flips, total), (flips, total)
     # forward
-    assert rel(m.output[..., :cout], ref["fw"]["output"]) < 1e-4, "output"
-    assert rel(m.mean, ref["fw"]["mean"]) < 1e-4 and rel(m.variance, ref["fw"]["variance"]) < 1e-4
+    assert rel(m.output[..., :cout], ref["output"]) < 1e-4, "output"
+    assert rel(m.mean, ref["mean"]) < 1e-4 and rel(m.variance, ref["variance"]) < 1e-4
     for k in ("mse", "huber", "latent", "reg", "loss"):
         assert abs(r[k] - ref["losses"][k]) <= 1e-4 * abs(ref["losses"][k]) + 1e-9, (k, r[k], ref["losses"][k])
     # gradients (the regulariser's gradient included)
@@ -95,6 +119,43 @@ def test_unet_vae_train_step(model, precision):
         p0 = before[name].double()
         want, _, _ = tfsem.adam_tf1(p0, g2[name].double(), torch.zeros_like(p0), torch.zeros_like(p0), 1, 1e-3)
         assert float((after[name].double() - want).abs().max()) < 2e-6, name
+
+
+@pytest.mark.parametrize("model,precision", [("UNet", "split"), ("UNetSound", "split"), ("UNetSound", "f32")])
+def test_unet_vae_train_step(model, precision):
+    tr, sess, params, x, eps = _build_step(model, precision, 2)
+    _step_against_fp64(model, tr, sess, params, x, eps, lambda flips, total: flips < 200)
+
+
+# the layers the benched batch (32) runs with batch norm + ReLU applied while the consumer stages its tiles; batch 16 has the
+# same selection (tests/test_oracle_cpu.py pins it)
+DEFERRED_AT_THE_BENCHED_SELECTION = ["layer1/conv_1", "layer1/pool_2", "layer2/conv_1", "layer2/pool_2", "layer3/conv_1",
+                                     "layer7/conv_1", "layer8/conv_1", "layer9/conv_1"]
+
+
+def _peak_rss_gb():
+    import resource
+
+    return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2.0 ** 20
+
+
+@pytest.mark.parametrize("precision", ["split", "bf16"])
+def test_unet_vae_train_step_at_the_benched_selection(precision):
+    """BASELINE configs[1] as bench.py times it: batch 16 picks the same kernels for every layer as batch 32 (few-channel
+    MFMA and halo forms from 65536 output pixels, split / bf16 layers from 16384, the eight deferred batch norms), which
+    batches 2 and 6 of the tests above do not.  The whole step against the fp64 oracle: `split` to the batch-2 bounds (the
+    ReLU census as a rate; the KL term differentiated at the HIP run's latent statistics, see `_step_against_fp64`), `bf16`
+    to the batch-6 rule (3x the fp32 oracle's own spread)."""
+    N = 16
+    tr, sess, params, x, eps = _build_step("UNet", precision, N)
+    m = tr.model
+    assert sorted(n for n, L in m.layers.items() if L.deferred) == DEFERRED_AT_THE_BENCHED_SELECTION
+    assert sum(1 for L in m.layers.values() if m._use_split(L.d)) == 11
+    if precision == "split":
+        _step_against_fp64("UNet", tr, sess, params, x, eps, lambda flips, total: flips <= 1e-5 * total, kl_at_hip=True)
+    else:
+        _bf16_step_against_fp64(tr, sess, params, x, eps, fp32_class_check=False)
+    print("peak RSS of this process: %.2f GB" % _peak_rss_gb())
 
 
 def test_unet_vae_batch32_properties():
@@ -193,41 +254,35 @@ def test_unet_vae_bf16_train_step():
     (test_bf16_operand_convs: 2e-5 against fp64 convolutions of the rounded operands), and the whole step is held to
     the oracle's own fp32-vs-fp64 spread: every error of the product against the fp64 oracle must stay within 3x the
     error of the fp32 oracle against the fp64 oracle (same ReLU pattern on all three)."""
-    from acimg.session import Session
-    from acimg.trainer_vae import TrainerVAE
-    from acimg import unet_vae
-    from oracle import unet_vae as ouv
-
-    dev = torch.device("cuda:0")
     N = 6                  # 6 x 56 x 49 >= 16384 pixels: layers 2, 3, 7 and 8 run on the bf16 kernels (7 convs)
-    model = "UNet"
-    sess = Session(dev)
-    tr = TrainerVAE(unet_vae.UNet(precision="bf16"), learning_rate=1e-3, session=sess)
-    tr._build_functions(batch_size=N)
-    params = ouv.init_params(model, seed=7, dtype=torch.float64, bias_std=0.05, bn_jitter=0.1)
-    tr.model.initialize(state={k: v.float() for k, v in params.items()})
-    x, eps = ouv.synthetic_batch(model, N, seed=11, dtype=torch.float64)
-    orc = ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float64, params=params, bf16_operands=True)
-    orc32 = ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float32, params=params, bf16_operands=True)
-    r = tr.train_step(x.float().to(dev), eps.float().to(dev), apply=False)
-    torch.cuda.synchronize()
+    tr, sess, params, x, eps = _build_step("UNet", "bf16", N)
     m = tr.model
     nsplit = sum(1 for L in m.layers.values() if m._use_split(L.d))
     assert nsplit >= 7, nsplit                       # the bf16 kernels really carry the model's large convs
-    masks = {name: (L.relu_output() > 0).cpu() for name, L in m.layers.items()}
-    masks["dense"] = (m.dns1 > 0).cpu()
-    masks["conv2d"] = (m.c2d.t > 0).cpu()
-    free = orc.train_step(x, eps, apply=False)
-    shaped = {k: v.reshape(free["fw"]["masks"][k].shape) for k, v in masks.items()}
-    flips = sum(int((free["fw"]["masks"][k] != shaped[k]).sum()) for k in masks)
-    total = sum(v.numel() for v in masks.values())
+    _bf16_step_against_fp64(tr, sess, params, x, eps, fp32_class_check=True)
+
+
+def _bf16_step_against_fp64(tr, sess, params, x, eps, fp32_class_check):
+    """one precision="bf16" step against the fp64 same-rounding oracle, every error within 3x the fp32 oracle's own spread
+    (test_unet_vae_bf16_train_step); fp32_class_check: and the output is NOT the fp32-class result"""
+    from oracle import unet_vae as ouv
+
+    dev = torch.device("cuda:0")
+    model = "UNet"
+    r = tr.train_step(x.float().to(dev), eps.float().to(dev), apply=False)
+    torch.cuda.synchronize()
+    m = tr.model
+    masks = _hip_masks(m)
+    ref = _oracle_step(ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float64, params=params, bf16_operands=True), x, eps,
+                       masks)
+    flips, total = ref["flips"], ref["total"]
     print("bf16 UNet: ReLU pattern differs from the same-rounding oracle's in %d of %d places" % (flips, total))
     assert flips < 1e-3 * total
-    ref = orc.train_step(x, eps, apply=False, relu_masks=shaped)
-    ref32 = orc32.train_step(x, eps, apply=False, relu_masks=shaped)
+    ref32 = _oracle_step(ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float32, params=params, bf16_operands=True), x,
+                         eps, masks)
     out = m.output[..., :m.COUT]
-    e_max, f_max = rel(out, ref["fw"]["output"]), rel(ref32["fw"]["output"], ref["fw"]["output"])
-    e_l2, f_l2 = l2rel(out, ref["fw"]["output"]), l2rel(ref32["fw"]["output"], ref["fw"]["output"])
+    e_max, f_max = rel(out, ref["output"]), rel(ref32["output"], ref["output"])
+    e_l2, f_l2 = l2rel(out, ref["output"]), l2rel(ref32["output"], ref["output"])
     print("bf16 UNet output: max err %.2e (fp32 oracle: %.2e), L2 err %.2e (fp32 oracle: %.2e)" % (e_max, f_max, e_l2, f_l2))
     assert e_l2 < 3 * f_l2 + 1e-5 and e_max < 3 * f_max + 1e-4
     assert e_l2 < 2e-3
@@ -250,9 +305,11 @@ def test_unet_vae_bf16_train_step():
     st = sess.store.state_dict()
     for name, v in ref["new_stats"].items():
         assert l2rel(st[name], v) < 3 * l2rel(ref32["new_stats"][name], v) + 1e-4, name
-    # it is bf16 arithmetic: the fp32-class oracle is NOT matched to 1e-3
-    free32 = ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float64, params=params).train_step(x, eps, apply=False)
-    assert rel(out, free32["fw"]["output"]) > 1e-3
+    if fp32_class_check:
+        # it is bf16 arithmetic: the fp32-class oracle is NOT matched to 1e-3
+        del ref, ref32
+        free32 = ouv.Oracle(model, learning_rate=1e-3, dtype=torch.float64, params=params).train_step(x, eps, apply=False)
+        assert rel(out, free32["fw"]["output"]) > 1e-3
 
 
 def test_deferred_batch_norm_equals_the_materialised_one():
