@@ -157,6 +157,9 @@ PROTOTYPES = {
     "acimg_mask_iou": (_I, [_P, _P, _I, _I, _P, _P]),
     "acimg_box_iou": (_I, [_P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
     "acimg_box_iou_workspace": (_SZ, [_I]),
+    "acimg_knn_topk": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "acimg_knn_topk_workspace": (_SZ, [_I, _I, _I, _I]),
+    "acimg_knn_vote": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

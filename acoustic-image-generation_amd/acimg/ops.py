@@ -858,6 +858,21 @@ def box_iou(plan, logen, boxes, N, iou, counts=None, mask_out=None):
              _WsBytes(plan.ws))
 
 
+def knn_topk(plan, query, ldq, Q, gallery, ldg, G, D, K, dist2, idx):
+    """exact K nearest gallery rows per query row (retrieve.py:53-57, knn.py:102-104): fp64 [Q,ldq] / [G,ldg] ->
+    dist2 float64 [Q,K], idx int32 [Q,K] ascending by (dist2, index); -1 / +inf past G"""
+    plan.ws.require(_L().acimg_knn_topk_workspace(int(Q), int(G), int(D), int(K)))
+    plan.add("knn_topk", _L().acimg_knn_topk, query, int(ldq), int(Q), gallery, int(ldg), int(G), int(D), int(K), dist2,
+             idx, _WsPtr(plan.ws), _WsBytes(plan.ws))
+
+
+def knn_vote(plan, idx, ldidx, Q, K, gallery_labels, query_labels, num_classes, pred=None, first_hit=None):
+    """majority label of the first K neighbours (smallest class on a tie) and the 1-based rank of the first neighbour
+    with the query's label (0: none)"""
+    plan.add("knn_vote", _L().acimg_knn_vote, idx, int(ldidx), int(Q), int(K), gallery_labels, query_labels,
+             int(num_classes), pred, first_hit)
+
+
 def adam_lr_t(lr, step, beta1=0.9, beta2=0.999):
     """TF-1 Adam effective step size for 1-based step t."""
     return lr * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step)

@@ -592,6 +592,18 @@ class Trainer(object):
         g.plan_eval.run()
         return g.modelac.output
 
+    def features(self, batch, eps=None):
+        """the latent of the same inference-mode forward as `generate`: the code the decoder's dense layer consumes,
+        `zbuf[:, :150]` = mean + std * eps (extract_features_unetraces.py:124-125), or the min-max normalised code
+        itself when the generator is a plain auto-encoder (--ae 1).  Returns a [n,150] float32 device view of the
+        graph's buffer for that batch size: it is overwritten by the next call with the same n."""
+        from .unet_acresnet import Z
+        g = self._graph_for(int(batch[1].reshape(-1, 12).shape[0]))
+        self.flush_pipeline()
+        self._feed(g, batch, eps)
+        g.plan_eval.run()
+        return g.modelac.zbuf[:, :Z]
+
     # ------------------------------------------------------------------------------------------------
     # reference protocol: loops, checkpoints
     # ------------------------------------------------------------------------------------------------

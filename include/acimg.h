@@ -593,6 +593,30 @@ int acimg_box_iou(const float* logen, const int32_t* boxes, int N, float* iou, i
                   void* ws, size_t ws_bytes, void* stream);
 size_t acimg_box_iou_workspace(int N);
 
+/* Exact K nearest gallery rows of every query row, fp64 (what retrieve.py:53-57 computes with scipy cdist + argsort per
+ * anchor, and knn.py:102-104 with KNeighborsClassifier(n_neighbors=15).kneighbors):
+ *   dist2[q][j] = sum_d (query[q][d] - gallery[g][d])^2, summed in fp64 in direct-difference form (not the
+ *                 |a|^2 - 2ab + |b|^2 expansion, which cancels and would reorder near neighbours), idx[q][j] = g;
+ *   order: ascending by the pair (dist2, gallery index), i.e. ties go to the LOWER index; slots j >= G hold idx -1 and
+ *   dist2 +inf.
+ * query [Q][ldq], gallery [G][ldg] row-major; dist2 / idx [Q][K].  1 <= K <= 64, ld >= D >= 1, G >= 1 (else
+ * ACIMG_EINVAL); Q == 0 is a no-op.  ws: acimg_knn_topk_workspace(Q, G, D, K) bytes (a host-only query; 0 = none
+ * needed, short = ACIMG_EWORKSPACE).  Stream-ordered, no atomics: bit-identical from run to run.  Finite inputs. */
+int acimg_knn_topk(const double* query, int ldq, int Q, const double* gallery, int ldg, int G, int D, int K,
+                   double* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream);
+size_t acimg_knn_topk_workspace(int Q, int G, int D, int K);
+
+/* The two numbers the latent-space evaluation reports from neighbour lists idx [Q][ldidx] (acimg_knn_topk output):
+ *   pred[q]      = the most frequent gallery_labels[idx[q][j]] over j < K; on a tie the SMALLEST class
+ *                  (KNeighborsClassifier.predict with uniform weights, knn.py:104: labels 3, 1, 3, 1 -> 1);
+ *   first_hit[q] = 1-based rank of the first neighbour j < K whose label equals query_labels[q], 0 if none
+ *                  (retrieve.py:60-82: a rank-r hit is 1 <= first_hit <= r).
+ * idx entries -1 are skipped; labels outside [0, num_classes) never count (callers validate the ranges, and every
+ * idx >= 0 must index gallery_labels).  1 <= K <= 64, ldidx >= K, 1 <= num_classes <= 64.  pred / first_hit: NULL =
+ * not written; query_labels may be NULL when first_hit is. */
+int acimg_knn_vote(const int32_t* idx, int ldidx, int Q, int K, const int32_t* gallery_labels,
+                   const int32_t* query_labels, int num_classes, int32_t* pred, int32_t* first_hit, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
