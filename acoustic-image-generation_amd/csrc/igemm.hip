@@ -1474,11 +1474,15 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
 }
 
 // column sums; workspace: parts*ncols floats
-static int launch_colsum(const float* G, long rows, int ncols, int ld, float* out, void* ws,
-                         size_t ws_bytes, hipStream_t st) {
+static int colsum_parts(long rows) {
     int parts = (int)((rows + 255) / 256);
     if (parts > 256) parts = 256;
     if (parts < 1) parts = 1;
+    return parts;
+}
+static int launch_colsum(const float* G, long rows, int ncols, int ld, float* out, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+    const int parts = colsum_parts(rows);
     const long rpb = (rows + parts - 1) / parts;
     const size_t need = (size_t)parts * ncols * sizeof(float);
     if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "colsum: workspace %zu < %zu", ws_bytes, need);
@@ -2547,6 +2551,10 @@ int acimg_deconv_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, 
     p.OH = d->H; p.OW = d->W; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = 0; p.pad_l = 0;
     p.M = d->N * d->H * d->W; p.KK = d->R * d->S * ca;
     p.G = x; p.ldg = d->ldx; p.Ngemm = d->C; p.Nld = d->C; p.ldo = d->ldw;
+    if (db) {       // refuse before dw is written: an unsplit weight gradient takes no workspace, the column sum always does
+        const size_t need = (size_t)colsum_parts((long)d->N * d->OH * d->OW) * d->K * sizeof(float);
+        if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "deconv_wgrad: workspace %zu < %zu (bias gradient)", ws_bytes, need);
+    }
     rc = launch_wgrad(p, dw, nullptr, ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
     // the transposed conv adds its bias at EVERY output pixel (gaps included): plain column sum of gy

@@ -68,7 +68,8 @@ typedef struct AcimgConvDesc {
 /* Forward: y = act(conv(x', w) + bias), x' = relu(x*in_scale[c] + in_shift[c]) when in_scale
  * is given (deferred batch-norm of the producer, zero padding applied AFTER the affine), else x.
  * stats (optional, [grid_m][2][ldw] floats, grid_m = acimg_conv2d_stats_rows(d)) receives per
- * row-block partial sums / sums of squares of the raw conv output for batch-norm statistics.
+ * row-block partial sums / sums of squares of conv + bias BEFORE the activation for batch-norm statistics (the
+ * few-channel direct kernel with an activation sums the stored, activated y instead; batch-norm layers use ACT_NONE).
  * The row count belongs to THIS descriptor, `act` included (the few-channel 3x3 / stride-1 layers from 65536
  * pixels on run on an MFMA kernel that leaves one row per workgroup - 512 - when act is ACIMG_ACT_NONE, and on
  * the direct kernel with one row per 256 pixels otherwise): size the buffer from the descriptor that is launched.

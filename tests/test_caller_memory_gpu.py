@@ -1,0 +1,983 @@
+"""The caller owns every buffer (include/acimg.h): each entry point that takes a workspace is run through the raw C ABI
+with EXACTLY the bytes its host-side query reports, poisoned with 0xFF (NaN), and with every output inside a guard arena
+(tests/guard_arena.py) pre-filled with a sentinel.  An under-reporting query, a kernel that writes past its slabs or its
+output extents, and a kernel that relies on scratch being zero all show up here; they do not behind `ops.Plan`, whose
+workspace is the maximum over a test's ops, sits in allocator slack and is usually zero on a fresh process.
+
+Per case (`run_case`):
+  reference run  workspace 4 x query + 1 MiB, zeroed; plain output tensors; compared with the fp64 reference of the op at
+                 the tolerance the existing test of that path uses (named next to each case);
+  guarded run    workspace = the query, 0xFF (zero only where the header demands it: the first 4 KiB of the split3p
+                 workspace, the loss scratch); rc == 0; documented elements bit-identical to the reference run; every other
+                 byte of every output region still the sentinel; all guard bands intact; tickets / zero-on-exit words zero;
+  short runs     ws_bytes = query - 16 (the last 16 bytes are canary), then ws = NULL: a negative code with every output
+                 untouched, or rc == 0 with the reference run's result, bit for bit.  Only a case that declares a fallback
+                 kernel (another summation order: the skinny forward, the loss sums' float atomics) may differ in bits; it
+                 must then pass the reference run's own fp64 check.  Zero-on-exit words are zero after these calls too.
+No case may fault: everything the library can reach lies inside memory the test owns."""
+import ctypes as C
+from collections import OrderedDict
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from guard_arena import CANARY, GuardArena
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 2e-5            # tests/test_ops_gpu.py: exact-f32 MFMA paths against fp64
+STATS_TOL = 2e-4       # ... and its batch-norm partial sums (fp32 sums of many signed terms)
+SENT = 0x7B            # 0x7B7B7B7B = 1.3e36 as a float, 2071690107 as an int: finite, never a result
+WS_FILL = 0xFF         # NaN in every float format
+
+
+def _lib():
+    from acimg import _lib as m
+    return m, m.load()
+
+
+def close(got, ref, tol=RTOL, what=""):
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    err = (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-12)
+    print("%s: rel err %.3e (tol %.1e)" % (what, err, tol))
+    assert np.isfinite(err) and err <= tol, "%s: rel err %.3e > %.1e" % (what, err, tol)
+
+
+def f32(g, *shape, scale=1.0):
+    return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).float()
+
+
+def tf_conv_ref(x, w, stride, pads, bias=None):
+    xt = F.pad(x.permute(0, 3, 1, 2), (pads[2], pads[3], pads[0], pads[1]))
+    return F.conv2d(xt, w.permute(3, 2, 0, 1), bias, stride=stride).permute(0, 2, 3, 1)
+
+
+def geom(H, W, R, S, stride, padding):
+    def same(size, k, s):
+        out = -(-size // s)
+        tot = max((out - 1) * s + k - size, 0)
+        return out, tot // 2, tot - tot // 2
+    if padding == "SAME":
+        OH, pt, pb = same(H, R, stride)
+        OW, pl, pr = same(W, S, stride)
+        return OH, OW, (pt, pb, pl, pr)
+    return (H - R) // stride + 1, (W - S) // stride + 1, (0, 0, 0, 0)
+
+
+def up4(v):
+    return (v + 3) & ~3
+
+
+def last_lt(shape, n):
+    """mask of the documented elements of a [..., ld] buffer: the first n of every row"""
+    return (torch.arange(shape[-1]) < n).expand(*shape)
+
+
+def first_lt(shape, n):
+    m = torch.zeros(*shape, dtype=torch.bool)
+    m[:n] = True
+    return m
+
+
+class Out(object):
+    """an output buffer: dtype, full shape of the memory handed over (pads included), mask of the documented elements
+    (None: all), init = a sentinel byte, or a tensor for in/out buffers the caller must initialise (accumulators)"""
+
+    def __init__(self, dtype, shape, mask=None, init=SENT):
+        self.dtype, self.shape, self.mask, self.init = dtype, tuple(int(s) for s in shape), mask, init
+        self.nbytes = int(np.prod(self.shape)) * torch.empty((), dtype=dtype).element_size() if self.shape else 0
+
+    def paint(self, u8):
+        if isinstance(self.init, torch.Tensor):
+            u8.copy_(self.init.contiguous().view(-1).view(torch.uint8).to(u8.device))
+        else:
+            u8.fill_(self.init)
+
+    def typed(self, u8):
+        return u8.cpu().view(self.dtype).view(*self.shape)
+
+
+class Case(object):
+    """calls: [fn(ws_ptr, ws_bytes, ptr, tickets_ptr) -> rc], run in order (state carried through the workspace:
+    triplet fwd + bwd); verify(outs): the fp64 check; zero_head: leading workspace bytes the header wants zero before
+    the first call; zero_exit: leading bytes (ticket words) it promises to leave zero after every call; short_code: the
+    code a short workspace must be refused with (None: any negative code, or a legal fallback), null_code: the same for
+    ws = NULL where the entry point names that another way; fallback: the entry point documents another kernel (another
+    summation order) for a short or missing workspace - only then may a short run that returns 0 differ in bits from the
+    reference run, and it must pass the fp64 check instead"""
+
+    def __init__(self, query, outs, calls, verify, tickets=False, zero_head=0, zero_exit=0, short_code=None, null_code=None,
+                 fallback=False, keep=None):
+        self.query, self.outs, self.verify = int(query), outs, verify
+        self.calls = calls if isinstance(calls, (list, tuple)) else [calls]
+        self.tickets, self.zero_head, self.zero_exit, self.keep = tickets, int(zero_head), int(zero_exit), keep
+        self.short_code, self.null_code = short_code, short_code if null_code is None else null_code
+        self.fallback = fallback
+
+
+def _bits(t):
+    return t.contiguous().view(-1).view(torch.uint8)
+
+
+def run_case(device, case, what):
+    from acimg import ops
+    m, L = _lib()
+    st = ops.current_stream_handle(device)
+    q = case.query
+    tbytes = 4 * ops.TICKET_WORDS
+
+    def launch(ws_ptr, ws_bytes, ptr, tick, arena=None, stage=""):
+        """every call of the case; one synchronize + arena check per call; stops at the first refusal"""
+        for i, fn in enumerate(case.calls):
+            rc = fn(ws_ptr, ws_bytes, ptr, tick)
+            torch.cuda.synchronize()
+            if arena is not None:
+                arena.check("%s, %s, call %d" % (what, stage, i))
+            if rc != 0:
+                return rc
+        return 0
+
+    # ---- reference run: roomy, zeroed workspace; plain tensors ---------------------------------------------------------
+    ws = torch.zeros(4 * q + (1 << 20), dtype=torch.uint8, device=device)
+    bufs = OrderedDict((n, torch.empty(max(o.nbytes, 16), dtype=torch.uint8, device=device)) for n, o in case.outs.items())
+    for n, o in case.outs.items():
+        o.paint(bufs[n][:o.nbytes])
+    tick = torch.zeros(ops.TICKET_WORDS, dtype=torch.int32, device=device) if case.tickets else None
+    rc = launch(ws.data_ptr(), ws.numel(), {n: b.data_ptr() for n, b in bufs.items()}, tick.data_ptr() if case.tickets else None)
+    assert rc == 0, "%s: reference run rc=%d: %s" % (what, rc, m.last_error())
+    ref = OrderedDict((n, o.typed(bufs[n][:o.nbytes])) for n, o in case.outs.items())
+    case.verify(ref)
+    if case.tickets:
+        assert int(tick.abs().max()) == 0, "%s: reference run left tickets non-zero" % what
+    del ws, bufs
+
+    # ---- guarded run: exactly the queried bytes, poisoned; outputs between guard bands ---------------------------------
+    sizes = [q] + [o.nbytes for o in case.outs.values()] + ([tbytes] if case.tickets else [])
+    arena = GuardArena.for_sizes(device, sizes)
+    wsr = arena.region(q, name="workspace")
+    regs = OrderedDict((n, arena.region(o.nbytes, name=n)) for n, o in case.outs.items())
+    tr = arena.region(tbytes, fill=0, name="tickets") if case.tickets else None
+    ptr = {n: r.ptr for n, r in regs.items()}
+
+    def paint(short=False):
+        wsr.fill(WS_FILL)
+        if case.zero_head:
+            wsr.u8[:case.zero_head].zero_()
+        if short:
+            wsr.u8[q - 16:].fill_(CANARY)
+        for n, o in case.outs.items():
+            o.paint(regs[n].u8)
+        if tr is not None:
+            tr.fill(0)
+
+    def outputs():
+        return OrderedDict((n, o.typed(regs[n].u8)) for n, o in case.outs.items())
+
+    def untouched(got, stage, everything):
+        """sentinel bytes: outside the documented elements, or (a refused call) everywhere"""
+        for n, o in case.outs.items():
+            if isinstance(o.init, torch.Tensor):
+                if everything:
+                    assert torch.equal(_bits(got[n]), _bits(o.init)), "%s, %s: %s changed by a refused call" % (what, stage, n)
+                continue
+            if everything or o.mask is not None:
+                sel = got[n] if everything else got[n][~o.mask]
+                bad = _bits(sel).ne(o.init)
+                assert not bool(bad.any()), "%s, %s: output %r written outside its documented extent (%d bytes)" % (
+                    what, stage, n, int(bad.sum()))
+
+    def same_as_reference(got, stage):
+        for n, o in case.outs.items():
+            a = got[n] if o.mask is None else got[n][o.mask]
+            b = ref[n] if o.mask is None else ref[n][o.mask]
+            if not torch.equal(_bits(a), _bits(b)):
+                return False, n
+        return True, None
+
+    paint()
+    rc = launch(wsr.ptr, q, ptr, tr.ptr if tr is not None else None, arena, "guarded run")
+    assert rc == 0, "%s: guarded run (ws = the query, %d bytes) rc=%d: %s" % (what, q, rc, m.last_error())
+    got = outputs()
+    ok, n = same_as_reference(got, "guarded run")
+    assert ok, "%s: output %r differs between a zeroed roomy workspace and a poisoned exact one" % (what, n)
+    untouched(got, "guarded run", False)
+    if tr is not None:
+        assert not bool(tr.u8.any()), "%s: tickets left non-zero" % what
+    if case.zero_exit:
+        assert not bool(wsr.u8[:case.zero_exit].any()), "%s: zero-on-exit words of the workspace left non-zero" % what
+
+    # ---- short runs: query - 16 bytes, then no workspace at all -------------------------------------------------------
+    if q > 0:
+        assert q >= 16, "%s: a query of %d bytes leaves no 16 bytes to cut" % (what, q)
+        for stage, p, nb in (("short run (query - 16)", wsr.ptr, q - 16), ("NULL workspace", None, 0)):
+            paint(short=True)
+            rc = launch(p, nb, ptr, tr.ptr if tr is not None else None, arena, stage)
+            assert bool((wsr.u8[q - 16:] == CANARY).all()), "%s, %s: the 16 bytes past ws_bytes were written" % (what, stage)
+            got = outputs()
+            if rc < 0:
+                print("%s, %s: refused rc=%d (%s)" % (what, stage, rc, m.last_error()))
+                want = case.short_code if p is not None else case.null_code
+                if want is not None:
+                    assert rc == want, (what, stage, rc, want)
+                untouched(got, stage, True)
+            else:
+                assert rc == 0 and case.short_code is None, (what, stage, rc)
+                ok, n = same_as_reference(got, stage)
+                assert ok or case.fallback, "%s, %s: rc == 0 but output %r differs from the reference run" % (what, stage, n)
+                if not ok:       # a declared fallback kernel (for the loss sums the float atomics the header documents for a
+                    # call without scratch): the reference run's own fp64 check at the op's existing tolerance
+                    print("%s, %s: fallback path, %r not bit-identical; fp64 check" % (what, stage, n))
+                    case.verify(got)
+                untouched(got, stage, False)
+            if tr is not None:
+                assert not bool(tr.u8.any()), "%s, %s: tickets left non-zero" % (what, stage)
+            if case.zero_exit and p is not None:        # "left zero by every call": accepted or refused
+                assert not bool(wsr.u8[:min(case.zero_exit, nb)].any()), "%s, %s: zero-on-exit words left non-zero" % (what, stage)
+    return ref
+
+
+# =====================================================================================================================
+# convolution family
+# =====================================================================================================================
+def conv_inputs(case, seed, wscale=0.1):
+    N, H, W, Cc, K, R, S, stride, padding = case
+    g = torch.Generator().manual_seed(seed)
+    OH, OW, pads = geom(H, W, R, S, stride, padding)
+    x, w, b = f32(g, N, H, W, Cc), f32(g, R, S, Cc, K, scale=wscale), f32(g, K)
+    gy, res, mask = f32(g, N, OH, OW, K), f32(g, N, H, W, Cc), f32(g, N, H, W, Cc)
+    return g, OH, OW, pads, x, w, b, gy, res, mask
+
+
+def padded(t, ld, fill=float("nan")):
+    """[..., C] -> fp32 [..., ld]; the pad columns are never read: NaN there would show"""
+    out = torch.full((*t.shape[:-1], ld), fill, dtype=torch.float32)
+    out[..., : t.shape[-1]] = t
+    return out
+
+
+# (shape, act, stats, branch, tolerance of y; the existing test of that path)
+FWD_CASES = OrderedDict([
+    # split-K (64x64 tiles, 9 K ranges): test_splitk_handoff_equals_reduce_launch, 1e-5
+    ("splitk_reduce_launch", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), 1, False, "splitk", 1e-5)),
+    ("splitk_handoff", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), 1, False, "splitk+tickets", 1e-5)),
+    # split-K + statistics (the small pass over y afterwards): test_conv2d_fwd_affine_stats_slice's path
+    ("splitk_stats", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), 0, True, "splitk+tickets", 1e-5)),
+    # 8 K steps per tap... kiters = 2 < 8: never split, query 0 (test_conv2d_fwd CONV_CASES[3])
+    ("unsplit_query0", ((2, 13, 10, 64, 32, 1, 1, 1, "SAME"), 1, True, "unsplit", RTOL)),
+    # K = 12 <= 16: the 256x16 tile, split 6 ways (CONV_CASES[5])
+    ("tile_256x16", ((2, 14, 19, 64, 12, 3, 4, 1, "VALID"), 1, False, "256x16", RTOL)),
+    # the VAE heads' dense layer on the skinny kernels: test_skinny_dense_gradients, 2e-6
+    ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), 0, False, "skinny", 2e-6)),
+    # few-channel MFMA (act NONE, >= 65536 pixels), one statistics row per workgroup: test_few_channel_mfma_conv_matches_fp64
+    ("few_channel_mfma", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), 0, True, "few16", 2e-6)),
+    # the direct kernel (ReLU keeps it off the MFMA form) and its stride-2 form: test_few_channel_direct_conv
+    ("direct_relu", ((2, 200, 180, 8, 8, 3, 3, 1, "SAME"), 1, True, "direct", RTOL)),
+    ("direct_stride2", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), 0, True, "direct", RTOL)),
+])
+
+
+def fwd_case(device, name, configure=None):
+    from acimg import ops
+    m, L = _lib()
+    shape, act, with_stats, branch, tol = FWD_CASES[name]
+    N, H, W, Cc, K, R, S, stride, padding = shape
+    g, OH, OW, pads, x, w, b, _, _, _ = conv_inputs(shape, 11 + sum(v for v in shape if isinstance(v, int)),
+                                                    wscale=0.05 if branch == "skinny" else (2.0 / (R * S * Cc)) ** 0.5)
+    ldy = K + 4
+    d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldy=ldy, act=act)
+    til = ops.conv2d_fwd_tiling(d)
+    q = int(L.acimg_conv2d_fwd_workspace(C.byref(d)))
+    if branch.startswith("splitk"):
+        assert til[2] > 1 and q > 0
+    elif branch == "unsplit":
+        assert til[2] == 1 and q == 0
+    elif branch == "256x16":
+        assert til[:2] == (256, 16) and til[2] > 1
+    elif branch == "few16":
+        assert ops.conv2d_stats_rows(d) == 512 and ops.conv2d_affine_input_ok(d, 0)
+    elif branch == "direct":
+        assert ops.conv2d_stats_rows(d) == -(-N * OH * OW // 256) and not ops.conv2d_affine_input_ok(d, 0)
+    raw = tf_conv_ref(x.double(), w.double(), stride, pads, b.double())
+    yref = torch.relu(raw) if act else raw
+    xd, wd, bd = x.to(device), w.to(device), b.to(device)
+    rows = ops.conv2d_stats_rows(d)
+    outs = OrderedDict(y=Out(torch.float32, (N, OH, OW, ldy), last_lt((N, OH, OW, ldy), K)))
+    if with_stats:
+        outs["stats"] = Out(torch.float32, (rows + 3, 2, d.ldw), first_lt((rows + 3, 2, d.ldw), rows))
+
+    def call(ws, nb, p, tick):
+        return L.acimg_conv2d_fwd(C.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), p["y"], None, None, 0,
+                                  p.get("stats"), ws, nb, tick if branch.endswith("tickets") else None,
+                                  ops.current_stream_handle(device))
+
+    def verify(o):
+        close(o["y"][..., :K], yref, tol=tol, what="conv2d_fwd %s" % name)
+        if with_stats:
+            # the implicit-GEMM epilogue sums conv + bias BEFORE the activation; the few-channel direct kernel with an
+            # activation leaves its statistics to a pass over the stored (activated) tensor (include/acimg.h; the same
+            # thing with ACIMG_ACT_NONE, which every batch-norm layer uses)
+            flat = (yref if act and branch == "direct" else raw).reshape(-1, K)
+            close(o["stats"][:rows, 0, :K].sum(0), flat.sum(0), tol=STATS_TOL, what="conv2d_fwd %s stats sum" % name)
+            close(o["stats"][:rows, 1, :K].sum(0), (flat * flat).sum(0), tol=STATS_TOL, what="conv2d_fwd %s stats sumsq" % name)
+    # skinny: without its full workspace the dense layer runs as a split-K implicit GEMM (another summation order)
+    return Case(q, outs, call, verify, tickets=branch.endswith("tickets"), fallback=branch == "skinny", keep=(xd, wd, bd, d))
+
+
+@pytest.mark.parametrize("name", list(FWD_CASES))
+def test_conv2d_fwd_caller_memory(device, name):
+    run_case(device, fwd_case(device, name), "conv2d_fwd[%s]" % name)
+
+
+# (shape, residual, mask, tickets, branch, tolerance; the existing test of that path)
+DGRAD_CASES = OrderedDict([
+    # stride-1 split-K, both combine forms: test_splitk_handoff_equals_reduce_launch / test_conv2d_dgrad_wgrad
+    ("s1_splitk_reduce_launch", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), True, True, False, RTOL)),
+    ("s1_splitk_handoff", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), True, True, True, RTOL)),
+    # stride == R == S, no padding: patch scatter (query 0 at this size)
+    ("patch_scatter", ((2, 36, 48, 16, 32, 3, 3, 3, "SAME"), True, True, True, RTOL)),
+    # stride 2, >= 16 channels written: the sub-pixel form (combined weights + its own split-K slabs)
+    ("subpixel_3x3_same", ((1, 16, 20, 64, 64, 3, 3, 2, "SAME"), True, True, True, RTOL)),
+    ("subpixel_2x3_valid", ((2, 12, 15, 32, 32, 2, 3, 2, "VALID"), True, True, False, RTOL)),
+    # stride 2, 8 channels written: zero-inserted copy of gy in the workspace, then the stride-1 form behind it
+    ("dilated_3x3_same", ((2, 17, 23, 8, 8, 3, 3, 2, "SAME"), True, True, True, RTOL)),
+    ("dilated_3x2_valid", ((2, 15, 18, 8, 16, 3, 2, 2, "VALID"), True, True, False, RTOL)),
+    # >= 65536 pixels: the few-channel MFMA form reads the zero-inserted view itself (no mask): test_few_channel_direct_conv, 3e-5
+    ("few_channel_stride2", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), True, False, False, 3e-5)),
+    # ... and with a ReLU mask neither MFMA nor direct form applies: dilated copy, then the implicit GEMM (exact f32)
+    ("dilated_then_igemm_65536", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), True, True, True, 3e-5)),
+    # 112x149 8 -> 32: the 16-row instance of the halo kernel (test_few_channel_mfma_conv_matches_fp64 (3,147,161,8,32), 3e-5)
+    ("halo16_narrow", ((4, 112, 149, 8, 32, 3, 3, 1, "SAME"), True, True, False, 3e-5)),
+    # not 3x3, <= 16 gy channels, >= 65536 pixels, no mask: the direct kernel (3e-5 as its stride-2 cases)
+    ("direct", ((2, 200, 190, 8, 16, 2, 3, 1, "VALID"), True, False, False, 3e-5)),
+    ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), True, True, False, 2e-6)),
+])
+
+
+def dgrad_case(device, name):
+    from acimg import ops
+    m, L = _lib()
+    shape, with_res, with_mask, tickets, tol = DGRAD_CASES[name]
+    N, H, W, Cc, K, R, S, stride, padding = shape
+    small = name in ("halo16_narrow", "few_channel_stride2", "dilated_then_igemm_65536")
+    g, OH, OW, pads, x, w, b, gy, res, mask = conv_inputs(shape, 5 + sum(v for v in shape if isinstance(v, int)),
+                                                          wscale=0.05 if name == "skinny" else 0.1)
+    if small:
+        gy, res = gy * 1e-3, res * 1e-3          # gradients of the size the bf16x3 forms were made for (fp16 would lose them)
+    lddx, ldgy = Cc + 4, K + 4
+    d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldw=K)
+    q = int(L.acimg_conv2d_dgrad_workspace(C.byref(d)))
+    xr = x.double().requires_grad_(True)
+    y = tf_conv_ref(xr, w.double(), stride, pads)
+    (gx,) = torch.autograd.grad(y, (xr,), gy.double())
+    ref = gx + (res.double() if with_res else 0)
+    if with_mask:
+        ref = ref * (mask > 0).double()
+    gyd, wd = padded(gy, ldgy).to(device), w.to(device)
+    resd, maskd = padded(res, Cc + 8).to(device), padded(mask, Cc + 4).to(device)
+    outs = OrderedDict(dx=Out(torch.float32, (N, H, W, lddx), last_lt((N, H, W, lddx), Cc)))
+
+    def call(ws, nb, p, tick):
+        return L.acimg_conv2d_dgrad(C.byref(d), gyd.data_ptr(), ldgy, wd.data_ptr(), p["dx"], lddx,
+                                    resd.data_ptr() if with_res else None, Cc + 8, maskd.data_ptr() if with_mask else None,
+                                    Cc + 4, ws, nb, tick if tickets else None, ops.current_stream_handle(device))
+
+    def verify(o):
+        close(o["dx"][..., :Cc], ref, tol=tol, what="conv2d_dgrad %s" % name)
+    return Case(q, outs, call, verify, tickets=tickets, keep=(gyd, wd, resd, maskd, d))
+
+
+@pytest.mark.parametrize("name", list(DGRAD_CASES))
+def test_conv2d_dgrad_caller_memory(device, name):
+    run_case(device, dgrad_case(device, name), "conv2d_dgrad[%s]" % name)
+
+
+# (shape, entry, tolerance; the existing test of that path)
+WGRAD_CASES = OrderedDict([
+    # 128 columns: 128-column tiles, 18 slabs (test_conv2d_dgrad_wgrad (2,18,24,256,128), RTOL; split3: 3e-5 as
+    # test_wgrad_split3_geometries)
+    ("cols128_f32", ((2, 18, 24, 256, 128, 3, 3, 1, "SAME"), "f32", RTOL)),
+    ("cols128_split3", ((2, 18, 24, 256, 128, 3, 3, 1, "SAME"), "split3", 3e-5)),
+    # 133 (padded 136) and 144 columns: 64-column tiles
+    ("cols133_f32", ((8, 12, 16, 128, 133, 3, 3, 1, "SAME"), "f32", RTOL)),
+    ("cols144_f32", ((8, 12, 16, 128, 144, 3, 3, 1, "SAME"), "f32", RTOL)),
+    ("cols144_split3", ((8, 12, 16, 128, 144, 3, 3, 1, "SAME"), "split3", 3e-5)),
+    # few channels through the fp32 entry onto the halo-16 kernel, 512 slabs: test_few_channel_wgrad_on_the_halo16_kernel, 2e-5
+    ("few_channel_halo", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), "f32", 2e-5)),
+    # 32 -> 32 at 112x149 on the halo-16 kernel, 256 slabs ("one slab per CU"): test_wgrad_halo16_matches_fp64, 4e-5 / 2e-5
+    ("halo16_split3", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "split3", 4e-5)),
+    ("halo16_bf16", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "bf16", 2e-5)),
+    # ... with the producer's batch norm applied on load: test_batch_norm_affine_applied_while_staging, 2e-5 against the same
+    # entry on the materialised tensor
+    ("halo16_affine_split3", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "affine1", 2e-5)),
+    ("few_channel_affine", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), "affine0", 2e-5)),
+    ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), "f32", 2e-6)),
+])
+
+
+def wgrad_case(device, name):
+    from acimg import ops
+    m, L = _lib()
+    shape, entry, tol = WGRAD_CASES[name]
+    N, H, W, Cc, K, R, S, stride, padding = shape
+    g, OH, OW, pads, x, w, b, gy, _, _ = conv_inputs(shape, 3 + sum(v for v in shape if isinstance(v, int)))
+    if name != "skinny":
+        gy = gy * 1e-2
+    kp = up4(K)
+    ldw, ldgy = kp + 4, kp + 4
+    d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldw=ldw)
+    q = int(L.acimg_conv2d_wgrad_workspace(C.byref(d)))
+    affine = entry.startswith("affine")
+    prec = int(entry[-1]) if affine else 0
+    if affine:
+        assert ops.conv2d_affine_input_ok(d, prec)
+        scale, shift = (torch.rand(Cc, generator=g) + 0.5).float(), f32(g, Cc, scale=0.5)
+        scd, shd = scale.to(device), shift.to(device)
+    rnd_ = (lambda t: t.to(torch.bfloat16).double()) if entry == "bf16" else (lambda t: t.double())   # bf16: fp64 of the ROUNDED operands
+    xd = x.to(device)
+    gyd = padded(gy, ldgy, 0.0).to(device)           # columns K .. kp are operands (zero); beyond kp never read
+    gyd[..., kp:] = float("nan")
+    st = ops.current_stream_handle(device)
+    if affine:
+        # the reference of the existing test: the SAME entry family on the materialised tensor (roomy zeroed workspace)
+        xmat = torch.relu(xd * scd + shd)
+        rws = torch.zeros(4 * q + (1 << 20), dtype=torch.uint8, device=device)
+        rdw = torch.zeros(R, S, Cc, ldw, device=device)
+        rdb = torch.zeros(ldw, device=device)
+        fn = L.acimg_conv2d_wgrad_split3 if prec == 1 else L.acimg_conv2d_wgrad
+        m.check(fn(C.byref(d), xmat.data_ptr(), gyd.data_ptr(), ldgy, rdw.data_ptr(), rdb.data_ptr(), rws.data_ptr(),
+                   rws.numel(), st), "reference wgrad")
+        torch.cuda.synchronize()
+        gw, gb = rdw[..., :K].cpu().double(), rdb[:K].cpu().double()
+        del rws, xmat
+        # ... and, independent of the library, fp64 of the same product at the tolerance of the non-affine case on the same
+        # kernel (halo16_split3: 4e-5, few_channel_halo: 2e-5)
+        wz = torch.zeros(R, S, Cc, K, dtype=torch.float64, requires_grad=True)
+        yr = tf_conv_ref(torch.relu(x.double() * scale.double() + shift.double()), wz, stride, pads)
+        (gw64,) = torch.autograd.grad(yr, (wz,), gy.double())
+        gb64, tol64 = gy.double().sum((0, 1, 2)), 4e-5 if prec == 1 else 2e-5
+    else:
+        wz = torch.zeros(R, S, Cc, K, dtype=torch.float64, requires_grad=True)
+        yr = tf_conv_ref(rnd_(x), wz, stride, pads)
+        (gw,) = torch.autograd.grad(yr, (wz,), rnd_(gy))
+        gb = rnd_(gy).sum((0, 1, 2))
+    # columns [K, kp) are the zero padding of the GEMM (written, zero); [kp, ldw) is outside the layer: untouched
+    outs = OrderedDict(dw=Out(torch.float32, (R, S, Cc, ldw), last_lt((R, S, Cc, ldw), kp)),
+                       db=Out(torch.float32, (ldw,), last_lt((ldw,), kp)))
+
+    def call(ws, nb, p, tick):
+        if affine:
+            return L.acimg_conv2d_wgrad_affine(C.byref(d), prec, xd.data_ptr(), scd.data_ptr(), shd.data_ptr(), 1, gyd.data_ptr(),
+                                               ldgy, p["dw"], p["db"], ws, nb, st)
+        fn = {"f32": L.acimg_conv2d_wgrad, "split3": L.acimg_conv2d_wgrad_split3, "bf16": L.acimg_conv2d_wgrad_bf16}[entry]
+        return fn(C.byref(d), xd.data_ptr(), gyd.data_ptr(), ldgy, p["dw"], p["db"], ws, nb, st)
+
+    def verify(o):
+        close(o["dw"][..., :K], gw, tol=tol, what="conv2d_wgrad %s" % name)
+        close(o["db"][:K], gb, tol=tol, what="conv2d_wgrad %s bias gradient" % name)
+        if affine:
+            close(o["dw"][..., :K], gw64, tol=tol64, what="conv2d_wgrad %s against fp64" % name)
+            close(o["db"][:K], gb64, tol=tol64, what="conv2d_wgrad %s bias gradient against fp64" % name)
+        assert float(o["dw"][..., K:kp].abs().max() if kp > K else 0.0) == 0.0
+    return Case(q, outs, call, verify, keep=(xd, gyd, d))
+
+
+@pytest.mark.parametrize("name", list(WGRAD_CASES))
+def test_conv2d_wgrad_caller_memory(device, name):
+    run_case(device, wgrad_case(device, name), "conv2d_wgrad[%s]" % name)
+
+
+# (shape, tolerances fwd / dgrad / wgrad; test_deconv: RTOL, test_deconv_dgrad_few_channels_direct: 2e-6 / 3e-5 / 2e-5)
+DECONV_CASES = OrderedDict([
+    ("scatter_gap_fill", ((2, 12, 16, 128, 128, 2, 2, 3), RTOL, RTOL, RTOL)),       # kernel < stride: gaps receive the bias
+    ("subpixel", ((2, 7, 9, 64, 32, 2, 3, 2), RTOL, RTOL, RTOL)),                   # kernel > stride, >= 16 outputs
+    ("dilated", ((2, 6, 8, 32, 8, 3, 3, 2), RTOL, RTOL, RTOL)),                     # kernel > stride, 8 outputs: zero-inserted x
+    ("pointwise_patch2", ((5, 112, 149, 32, 8, 2, 2, 2), 2e-6, 3e-5, 2e-5)),        # patch2_32x8 kernels, one slab per workgroup
+    ("direct_dgrad", ((2, 190, 180, 8, 8, 2, 2, 2), RTOL, 3e-5, RTOL)),             # <= 16 gy channels, >= 65536 pixels, no mask
+])
+
+
+def deconv_cases(device, name):
+    from acimg import ops
+    m, L = _lib()
+    shape, tol_f, tol_d, tol_w = DECONV_CASES[name]
+    N, H, W, Cc, K, R, S, s = shape
+    g = torch.Generator().manual_seed(77 + N + Cc)
+    x, w, b = f32(g, N, H, W, Cc), f32(g, R, S, K, Cc, scale=0.1), f32(g, K)
+    xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    y = F.conv_transpose2d(xr.permute(0, 3, 1, 2), wr.permute(3, 2, 0, 1), b.double(), stride=s,
+                           output_padding=(max(s - R, 0), max(s - S, 0))).permute(0, 2, 3, 1)
+    ldy = 2 * K
+    d = ops.deconv_desc(N, H, W, Cc, K, R, S, s, ldy=ldy)
+    OH, OW = d.OH, d.OW
+    assert tuple(y.shape[1:3]) == (OH, OW)
+    gy = f32(g, N, OH, OW, K)
+    gxr, gwr = torch.autograd.grad(y, (xr, wr), gy.double())
+    mask = f32(g, N, H, W, Cc)
+    with_mask = name != "direct_dgrad"
+    q = int(L.acimg_deconv_workspace(C.byref(d)))
+    xd, wd, bd, gyd, maskd = x.to(device), w.to(device), b.to(device), padded(gy, ldy).to(device), mask.to(device)
+    st = ops.current_stream_handle(device)
+    keep = (xd, wd, bd, gyd, maskd, d)
+    fwd = Case(q, OrderedDict(y=Out(torch.float32, (N, OH, OW, ldy), last_lt((N, OH, OW, ldy), K))),
+               lambda ws, nb, p, tick: L.acimg_deconv_fwd(C.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), p["y"], ws, nb, tick, st),
+               lambda o: close(o["y"][..., :K], y.detach(), tol=tol_f, what="deconv_fwd %s" % name), tickets=True, keep=keep)
+    dref = gxr * (mask > 0).double() if with_mask else gxr
+    dgr = Case(q, OrderedDict(dx=Out(torch.float32, (N, H, W, Cc))),
+               lambda ws, nb, p, tick: L.acimg_deconv_dgrad(C.byref(d), gyd.data_ptr(), ldy, wd.data_ptr(), p["dx"],
+                                                            maskd.data_ptr() if with_mask else None, Cc, ws, nb, tick, st),
+               lambda o: close(o["dx"], dref, tol=tol_d, what="deconv_dgrad %s" % name), tickets=True, keep=keep)
+
+    def verify_w(o):
+        close(o["dw"], gwr, tol=tol_w, what="deconv_wgrad %s" % name)
+        close(o["db"], gy.double().sum((0, 1, 2)), tol=tol_w, what="deconv_wgrad %s bias gradient" % name)
+    wgr = Case(q, OrderedDict(dw=Out(torch.float32, (R, S, K, Cc)), db=Out(torch.float32, (K,))),
+               lambda ws, nb, p, tick: L.acimg_deconv_wgrad(C.byref(d), xd.data_ptr(), gyd.data_ptr(), ldy, p["dw"], p["db"], ws, nb, st),
+               verify_w, keep=keep)
+    return fwd, dgr, wgr
+
+
+@pytest.mark.parametrize("name", list(DECONV_CASES))
+def test_deconv_caller_memory(device, name):
+    fwd, dgr, wgr = deconv_cases(device, name)
+    run_case(device, fwd, "deconv_fwd[%s]" % name)
+    run_case(device, dgr, "deconv_dgrad[%s]" % name)
+    run_case(device, wgr, "deconv_wgrad[%s]" % name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# non-default tuning: the sizing functions move with acimg_configure
+# ---------------------------------------------------------------------------------------------------------------------
+def test_queries_follow_the_tuning_record(device):
+    """one forward / data-gradient shape and one weight-gradient shape under a tuning record that changes their split
+    counts (split-K towards 96 workgroups instead of 768: 4 K ranges over 24 tiles instead of 9; 64 pixels per slab
+    instead of 128: 19 slabs instead of 12): the queries must move with the launches"""
+    from acimg import ops
+    m, L = _lib()
+    dflt = (int(L.acimg_conv2d_fwd_workspace(C.byref(ops.conv_desc(4, 12, 16, 128, 128, 3, 3, 1, "SAME")))),
+            ops.conv2d_fwd_tiling(ops.conv_desc(4, 12, 16, 128, 128, 3, 3, 1, "SAME"))[2],
+            int(L.acimg_conv2d_wgrad_workspace(C.byref(ops.conv_desc(8, 12, 16, 128, 144, 3, 3, 1, "SAME", ldw=148)))))
+    try:
+        m.configure(splitk_target=96, wgrad_minpix=64)
+        d = ops.conv_desc(4, 12, 16, 128, 128, 3, 3, 1, "SAME")
+        assert 1 < ops.conv2d_fwd_tiling(d)[2] < dflt[1] and int(L.acimg_conv2d_fwd_workspace(C.byref(d))) < dflt[0]
+        assert int(L.acimg_conv2d_wgrad_workspace(C.byref(ops.conv_desc(8, 12, 16, 128, 144, 3, 3, 1, "SAME", ldw=148)))) > dflt[2]
+        run_case(device, fwd_case(device, "splitk_handoff"), "conv2d_fwd[splitk_handoff, tuned]")
+        run_case(device, dgrad_case(device, "s1_splitk_handoff"), "conv2d_dgrad[s1_splitk_handoff, tuned]")
+        run_case(device, wgrad_case(device, "cols144_f32"), "conv2d_wgrad[cols144_f32, tuned]")
+        run_case(device, wgrad_case(device, "cols144_split3"), "conv2d_wgrad[cols144_split3, tuned]")
+    finally:
+        m.configure()
+
+
+# =====================================================================================================================
+# pre-split planes: split3p / split1p / stats / tail / tail_proj with the tail-split workspace; gram_stats
+# =====================================================================================================================
+def plane_bytes(rows, Cc):
+    return -(-rows // 16) * 16 * Cc * 2
+
+
+def brick_index(rows, Cc):
+    r = torch.arange(rows).view(-1, 1)
+    c = torch.arange(Cc).view(1, -1)
+    off = ((r >> 4) * (Cc // 32) + (c >> 5)) * 1024 + (r & 15) * 64 + ((((c >> 3) ^ (-(r >> 2))) & 3) << 4) + (c & 7) * 2
+    return (off // 2).reshape(-1)
+
+
+def unsplit(planes, lo_off, rows, Cc):
+    idx = brick_index(rows, Cc).to(planes.device)
+    n = plane_bytes(rows, Cc)
+    hi = planes[:n].view(torch.float16)[idx].double()
+    lo = planes[lo_off: lo_off + n].view(torch.float16)[idx].double()
+    return ((hi + lo) * 4.0).reshape(rows, Cc).cpu()
+
+
+def make_planes(device, x2d):
+    """split-format planes of a [rows, C] tensor through the library's own producer"""
+    from acimg import ops
+    m, L = _lib()
+    rows, Cc = x2d.shape
+    lo = plane_bytes(rows, Cc)
+    planes = torch.zeros(2 * lo, dtype=torch.uint8, device=device)
+    xd, one, zero = x2d.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device)
+    m.check(L.acimg_bn_relu_split(xd.data_ptr(), one.data_ptr(), zero.data_ptr(), 1, planes.data_ptr(), lo, rows, Cc,
+                                  ops.current_stream_handle(device)), "bn_relu_split")
+    torch.cuda.synchronize()
+    return planes, lo
+
+
+PRESPLIT_SHAPES = OrderedDict([("3x3_128_128", (8, 56, 75, 128, 128, 3, 3)), ("1x1_256_1024", (32, 28, 38, 256, 1024, 1, 1))])
+# acimg_conv2d_fwd_split3_tiling under the default tuning record: (BM, BN, kernel: 0 one tile per workgroup, 1 persistent,
+# 2 ring).  No query exposes whether the tail split engages for a shape: that it needs the workspace at all shows only in
+# the poisoned / short runs below.
+PRESPLIT_TILING = {"3x3_128_128": (128, 128, 0), "1x1_256_1024": (128, 128, 1)}
+
+
+@pytest.mark.parametrize("entry", ["split3p", "split1p", "stats", "tail", "tail_proj"])
+@pytest.mark.parametrize("shape", list(PRESPLIT_SHAPES))
+def test_presplit_conv_caller_memory(device, shape, entry):
+    """acimg_conv2d_fwd_split3p and its siblings with the DEDICATED tail-split workspace: first 4 KiB zero before and after,
+    the rest poisoned.  Tolerances: 2e-6 against fp64 (test_presplit_activation_path, test_two_pass_conv3_equals_conv_then_
+    bn_pass), 2e-4 statistics sums; split1p (operands keep 11 bits) against fp64 of the hi planes' values at the 2e-6 of
+    test_fp16_operand_storage_conv"""
+    from acimg import ops
+    m, L = _lib()
+    N, H, W, Cc, K, R, S = PRESPLIT_SHAPES[shape]
+    g = torch.Generator().manual_seed(3 + Cc + K)
+    x = torch.rand(N, H, W, Cc, generator=g)
+    w = torch.randn(R, S, Cc, K, generator=g) * (2.0 / (R * S * Cc)) ** 0.5
+    d = ops.conv_desc(N, H, W, Cc, K, R, S, 1, "SAME")
+    rows = N * H * W
+    st = ops.current_stream_handle(device)
+    xp, lo_x = make_planes(device, x.reshape(rows, Cc))
+    wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
+    m.check(L.acimg_conv2d_split3_prepare(C.byref(d), w.to(device).data_ptr(), wsplit.data_ptr(), st), "prepare")
+    torch.cuda.synchronize()
+    q = ops.conv2d_fwd_split3p_workspace(d)
+    til = tuple(ops.conv2d_fwd_split3_tiling(d))
+    print("%s %s: tiling %s, workspace %d" % (entry, shape, til, q))
+    assert til == PRESPLIT_TILING[shape], (shape, til)
+    assert q >= 4096 + til[0] * til[1] * 4, q        # the ticket page and at least one fp32 tile to meet in
+    xv = unsplit(xp, lo_x, rows, Cc).reshape(N, H, W, Cc)
+    pads = (R // 2, R // 2, S // 2, S // 2)
+    if entry == "split1p":
+        n = plane_bytes(rows, Cc)
+        idx = brick_index(rows, Cc)
+        xv = (xp[:n].cpu().view(torch.float16)[idx].double() * 4.0).reshape(N, H, W, Cc)
+        wv = (w * 1024.0).half().double() / 1024.0           # include/acimg.h: weights x 2^10 in fp16
+    else:
+        wv = w.double()
+    ref = tf_conv_ref(xv, wv, 1, pads)
+    flat = ref.reshape(rows, K)
+    srows = ops.conv2d_fwd_split3p_stats_rows(d) if entry != "split1p" else ops.conv2d_fwd_split3_stats_rows(d)
+    stats_out = Out(torch.float32, (srows + 3, 2, K), first_lt((srows + 3, 2, K), srows))
+
+    def check_stats(o):
+        close(o["stats"][:srows, 0].sum(0), flat.sum(0), tol=STATS_TOL, what="%s %s stats sum" % (entry, shape))
+        close(o["stats"][:srows, 1].sum(0), (flat * flat).sum(0), tol=STATS_TOL, what="%s %s stats sumsq" % (entry, shape))
+
+    if entry in ("split3p", "split1p"):
+        fn = L.acimg_conv2d_fwd_split3p if entry == "split3p" else L.acimg_conv2d_fwd_split1p
+        outs = OrderedDict(y=Out(torch.float32, (rows, K)), stats=stats_out)
+
+        def call(ws, nb, p, tick):
+            return fn(C.byref(d), xp.data_ptr(), lo_x, wsplit.data_ptr(), p["y"], p["stats"], ws, nb, st)
+
+        def verify(o):
+            close(o["y"], flat, tol=2e-6, what="%s %s" % (entry, shape))
+            check_stats(o)
+    elif entry == "stats":
+        outs = OrderedDict(stats=stats_out)
+
+        def call(ws, nb, p, tick):
+            return L.acimg_conv2d_fwd_split3p_stats(C.byref(d), xp.data_ptr(), lo_x, wsplit.data_ptr(), p["stats"], ws, nb, st)
+        verify = check_stats
+    else:
+        short = torch.rand(N, H, W, K, generator=g) * 2.0
+        scale, shift = torch.rand(K, generator=g) + 0.5, torch.rand(K, generator=g) - 0.7
+        sb, tb = torch.rand(K, generator=g) + 0.5, torch.rand(K, generator=g) - 0.5
+        scd, shd, sbd, tbd = (t.to(device) for t in (scale, shift, sb, tb))
+        lo_y = plane_bytes(rows, K)
+        assert rows % 16 == 0                                # no pad rows: every byte of both planes is documented
+        outs = OrderedDict(planes=Out(torch.uint8, (2 * lo_y,)))
+        if entry == "tail":
+            sp, _ = make_planes(device, short.reshape(rows, K))
+            shortcut = unsplit(sp, lo_y, rows, K)
+
+            def call(ws, nb, p, tick):
+                return L.acimg_conv2d_fwd_split3p_tail(C.byref(d), xp.data_ptr(), lo_x, wsplit.data_ptr(), scd.data_ptr(),
+                                                       shd.data_ptr(), sp.data_ptr(), lo_y, p["planes"], lo_y, ws, nb, st)
+        else:
+            sc32 = (short - 1.0).to(device)
+            shortcut = (short.double() - 1.0).reshape(rows, K) * sb.double() + tb.double()
+
+            def call(ws, nb, p, tick):
+                return L.acimg_conv2d_fwd_split3p_tail_proj(C.byref(d), xp.data_ptr(), lo_x, wsplit.data_ptr(), scd.data_ptr(),
+                                                            shd.data_ptr(), sc32.data_ptr(), sbd.data_ptr(), tbd.data_ptr(),
+                                                            p["planes"], lo_y, ws, nb, st)
+        r64 = torch.relu(flat * scale.double() + shift.double() + shortcut)
+
+        def verify(o):
+            close(unsplit(o["planes"], lo_y, rows, K), r64, tol=2e-6, what="%s %s" % (entry, shape))
+    run_case(device, Case(q, outs, call, verify, zero_head=4096, zero_exit=4096), "%s[%s]" % (entry, shape))
+
+
+@pytest.mark.parametrize("shape", [(20011, 128, 512), (37, 64, 100)])
+def test_gram_stats_caller_memory(device, shape):
+    """acimg_gram_stats: scale / shift at 3e-6, moving averages at 2e-6 (test_gram_statistics_match_fp64); a short
+    workspace is refused (tests/test_host_cpu.py::test_gram_stats_host_side: ACIMG_EINVAL)"""
+    m, L = _lib()
+    from acimg import ops
+    rows, Cc, K = shape
+    g = torch.Generator().manual_seed(11 + rows % 97 + Cc)
+    x = torch.relu(torch.randn(rows, Cc, generator=g) + 0.3) * (0.5 + torch.rand(Cc, generator=g))
+    ldw = up4(K)
+    w = torch.zeros(Cc, ldw)
+    w[:, :K] = torch.randn(Cc, K, generator=g) * (2.6 / Cc) ** 0.5
+    gamma, beta = torch.rand(K, generator=g) + 0.5, torch.rand(K, generator=g) - 0.5
+    mm0, mv0 = torch.randn(K, generator=g) * 0.1, torch.rand(K, generator=g) + 0.5
+    xp, lo = make_planes(device, x)
+    xv = unsplit(xp, lo, rows, Cc).double()
+    y = xv @ w[:, :K].double()
+    mean = y.mean(0)
+    var = (y * y).mean(0) - mean * mean
+    sc_ref = gamma.double() / torch.sqrt(var.float() + 1e-5).double()
+    sh_ref = beta.double() - mean.float().double() * sc_ref
+    unb = var * (rows / (rows - 1.0))
+    wd, gd, bd = w.to(device), gamma.to(device), beta.to(device)
+    q = int(L.acimg_gram_stats_workspace(rows, Cc))
+    assert q > 0
+    st = ops.current_stream_handle(device)
+    outs = OrderedDict(scale=Out(torch.float32, (K + 4,), first_lt((K + 4,), K)), shift=Out(torch.float32, (K + 4,), first_lt((K + 4,), K)),
+                       mm=Out(torch.float32, (K,), init=mm0), mv=Out(torch.float32, (K,), init=mv0))
+
+    def call(ws, nb, p, tick):
+        return L.acimg_gram_stats(xp.data_ptr(), lo, rows, Cc, wd.data_ptr(), ldw, K, gd.data_ptr(), bd.data_ptr(), p["mm"],
+                                  p["mv"], 0.997, 1e-5, p["scale"], p["shift"], ws, nb, st)
+
+    def verify(o):
+        close(o["scale"][:K], sc_ref, tol=3e-6, what="gram scale %s" % (shape,))
+        close(o["shift"][:K], sh_ref, tol=3e-6, what="gram shift %s" % (shape,))
+        close(o["mm"], 0.997 * mm0.double() + 0.003 * mean, tol=2e-6, what="gram moving mean %s" % (shape,))
+        close(o["mv"], 0.997 * mv0.double() + 0.003 * unb, tol=2e-6, what="gram moving variance %s" % (shape,))
+    run_case(device, Case(q, outs, call, verify, short_code=-1), "gram_stats[%s]" % (shape,))
+
+
+# =====================================================================================================================
+# the other workspace takers, one multi-chunk shape each
+# =====================================================================================================================
+def test_minmax_caller_memory(device):
+    """acimg_minmax_fwd / _bwd, 1728 pixels x 133 channels (32 chunks per sample), the output a slice at column 4 of a
+    wider buffer: forward RTOL, mm exact, backward 1e-4 (test_minmax_float)"""
+    m, L = _lib()
+    from acimg import ops
+    N, P, Cn, ldx, ldo, off = 2, 1728, 133, 136, 148, 4
+    g = torch.Generator().manual_seed(P + Cn)
+    x = f32(g, N, P, Cn).double().requires_grad_(True)
+    a = x - x.amin(dim=(1, 2), keepdim=True)
+    o = a / a.amax(dim=(1, 2), keepdim=True)
+    go = f32(g, N, P, Cn).double()
+    o.backward(go)
+    q = int(L.acimg_minmax_workspace(N, P, Cn))
+    assert q == N * 32 * 2 * 4
+    st = ops.current_stream_handle(device)
+    xd = padded(x.detach(), ldx).to(device)
+    cols = torch.arange(ldo)
+    omask = ((cols >= off) & (cols < off + Cn)).expand(N, P, ldo)
+    outs = OrderedDict(out=Out(torch.float32, (N, P, ldo), omask), mm=Out(torch.float32, (N + 2, 4), first_lt((N + 2, 4), N)))
+
+    def fwd(ws, nb, p, tick):
+        return L.acimg_minmax_fwd(xd.data_ptr(), ldx, p["out"] + 4 * off, ldo, p["mm"], N, P, Cn, ws, nb, st)
+
+    def verify(o_):
+        close(o_["out"][..., off:off + Cn], o.detach(), what="minmax fwd")
+        xm = x.detach()
+        ref_mm = torch.stack([xm.amin((1, 2)), xm.amax((1, 2)), torch.ones(N, dtype=torch.float64), torch.ones(N, dtype=torch.float64)], 1)
+        assert torch.equal(o_["mm"][:N].double(), ref_mm)
+    ref = run_case(device, Case(q, outs, fwd, verify, short_code=-2), "minmax_fwd")
+    mmd = ref["mm"][:N].contiguous().to(device)
+    god = torch.full((N, P, ldo), float("nan"))
+    god[..., off:off + Cn] = go.float()
+    god = god.to(device)
+    outs = OrderedDict(gx=Out(torch.float32, (N, P, ldx), last_lt((N, P, ldx), Cn)))
+
+    def bwd(ws, nb, p, tick):
+        return L.acimg_minmax_bwd(xd.data_ptr(), ldx, god.data_ptr() + 4 * off, ldo, mmd.data_ptr(), p["gx"], ldx, N, P, Cn, 0, 0,
+                                  ws, nb, st)
+    run_case(device, Case(q, outs, bwd, lambda o_: close(o_["gx"][..., :Cn], x.grad, tol=1e-4, what="minmax bwd"), short_code=-2),
+             "minmax_bwd")
+
+
+def test_bn_bwd_caller_memory(device):
+    """acimg_bn_bwd at 2 x 224 x 298 rows x 32 channels (256 partial blocks): gx RTOL, dgamma / dbeta 1e-4
+    (test_bn_bwd_float); short = ACIMG_EWORKSPACE (test_bn_bwd_workspace_refused)"""
+    m, L = _lib()
+    from acimg import ops
+    rows, Cn, ld = 133504, 32, 36
+    g = torch.Generator().manual_seed(rows + Cn)
+    x = (f32(g, rows, Cn) * 1.5 + f32(g, Cn)).double()
+    mean = x.mean(0).float().double()
+    invstd = (1.0 / torch.sqrt(x.var(0, unbiased=False) + 1e-5)).float().double()
+    gamma, beta = (f32(g, Cn).abs() + 0.5).double(), f32(g, Cn).double()
+    scale = (gamma * invstd).float().double()
+    shift = (beta - mean * scale).float().double()
+    pre = x * scale + shift
+    gy = f32(g, rows, Cn).double()
+    gy[pre.abs() < 1e-4] = 0.0
+    gm = gy * (pre > 0)
+    xhat = (x - mean) * invstd
+    dbeta, dgamma = gm.sum(0), (gm * xhat).sum(0)
+    gx = gamma * invstd * (gm - dbeta / rows - xhat * (dgamma / rows))
+    q = int(L.acimg_bn_bwd_workspace(rows, Cn))
+    st = ops.current_stream_handle(device)
+    xd, gyd = padded(x, ld).to(device), padded(gy, ld).to(device)
+    pv = [t.float().to(device) for t in (scale, shift, mean, invstd, gamma)]
+    outs = OrderedDict(gx=Out(torch.float32, (rows, ld), last_lt((rows, ld), Cn)), dgamma=Out(torch.float32, (Cn + 4,), first_lt((Cn + 4,), Cn)),
+                       dbeta=Out(torch.float32, (Cn + 4,), first_lt((Cn + 4,), Cn)))
+
+    def call(ws, nb, p, tick):
+        return L.acimg_bn_bwd(xd.data_ptr(), ld, gyd.data_ptr(), ld, *[t.data_ptr() for t in pv], rows, Cn, p["gx"], ld,
+                              p["dgamma"], p["dbeta"], ws, nb, st)
+
+    def verify(o):
+        close(o["gx"][:, :Cn], gx, what="bn_bwd gx")
+        close(o["dbeta"][:Cn], dbeta, tol=1e-4, what="bn_bwd dbeta")
+        close(o["dgamma"][:Cn], dgamma, tol=1e-4, what="bn_bwd dgamma")
+    run_case(device, Case(q, outs, call, verify, short_code=-2), "bn_bwd")
+
+
+@pytest.mark.parametrize("hard", [0, 1])
+def test_triplet_caller_memory(device, hard):
+    """acimg_triplet_loss_fwd + _bwd, B = 300 (several row blocks): the forward leaves the backward's state in the workspace,
+    so it is poisoned before the forward only and both calls are guarded.  Tolerances of test_triplet_random: loss and
+    fraction 1e-4, counts, gradients 1e-3"""
+    m, L = _lib()
+    from acimg import ops
+    from oracle import triplet as ot
+    B, D, ld = 300, 64, 68
+    g = torch.Generator().manual_seed(100 + B)
+    e0, e1 = f32(g, B, D, scale=0.05).double(), f32(g, B, D, scale=0.05).double()
+    labels, scenario = torch.randint(0, 5, (B,), generator=g), torch.randint(0, 3, (B,), generator=g)
+    a, b = e0.clone().requires_grad_(True), e1.clone().requires_grad_(True)
+    loss, frac, npos, nvalid = (ot.mix_data_hard if hard else ot.mix_all)(a, b, labels, scenario, 0.2)
+    ga, gb = torch.autograd.grad(loss, [a, b])
+    q = ops.triplet_loss_workspace(B)
+    st = ops.current_stream_handle(device)
+    ad, bd = padded(e0, ld).to(device), padded(e1, ld).to(device)
+    lab, sc = labels.int().to(device), scenario.int().to(device)
+    outs = OrderedDict(out=Out(torch.float32, (8,), first_lt((8,), 4)), g0=Out(torch.float32, (B, ld), last_lt((B, ld), D)),
+                       g1=Out(torch.float32, (B, ld), last_lt((B, ld), D)))
+
+    def fwd(ws, nb, p, tick):
+        return L.acimg_triplet_loss_fwd(ad.data_ptr(), ld, bd.data_ptr(), ld, lab.data_ptr(), sc.data_ptr(), B, D, 0.2, hard, ws, nb,
+                                        p["out"], st)
+
+    def bwd(ws, nb, p, tick):
+        return L.acimg_triplet_loss_bwd(ad.data_ptr(), ld, bd.data_ptr(), ld, B, D, 0.5, ws, nb, p["g0"], ld, p["g1"], ld, 0, st)
+
+    def rel(x, y):
+        return float((x.double() - y).abs().max() / y.abs().max().clamp_min(1e-30))
+
+    def verify(o):
+        out = o["out"]
+        assert float(out[3]) == float(nvalid)
+        assert abs(float(out[2]) - float(npos)) <= max(2.0, 2e-5 * float(npos))
+        assert abs(float(out[0]) - float(loss)) <= 1e-4 * abs(float(loss)) + 1e-7
+        assert abs(float(out[1]) - float(frac)) <= 1e-4 * float(frac) + 1e-7
+        assert rel(o["g0"][:, :D], 0.5 * ga) < 1e-3 and rel(o["g1"][:, :D], 0.5 * gb) < 1e-3
+    run_case(device, Case(q, outs, [fwd, bwd], verify), "triplet[hard=%d]" % hard)
+
+
+def test_filtfilt_caller_memory(device):
+    """acimg_filtfilt, 150 rows (more than one workgroup) of 1024 float32 samples: bit-identical to SciPy
+    (test_lowpass_filtfilt_matches_reference_golden)"""
+    m, L = _lib()
+    from acimg import ops
+    from acimg.frontend import butter_lowpass, lfilter_zi
+    from scipy import signal
+    rows, n = 150, 1024
+    rng = np.random.RandomState(9)
+    x = (rng.randn(rows, n) * 500).astype(np.float32)
+    b, a = butter_lowpass(125, 10)
+    want = torch.from_numpy(np.float32(signal.filtfilt(b, a, x)))
+    ba = torch.tensor(np.concatenate([b, a]), dtype=torch.float64, device=device)
+    zi = torch.tensor(lfilter_zi(b, a), dtype=torch.float64, device=device)
+    xd = torch.from_numpy(x).to(device)
+    q = int(L.acimg_filtfilt_workspace(rows, n))
+    st = ops.current_stream_handle(device)
+    outs = OrderedDict(out=Out(torch.float32, (rows + 1, n), first_lt((rows + 1, n), rows)))
+    run_case(device, Case(q, outs, lambda ws, nb, p, tick: L.acimg_filtfilt(xd.data_ptr(), 0, rows, n, ba.data_ptr(), zi.data_ptr(),
+                                                                           p["out"], ws, nb, st),
+                          lambda o: np.testing.assert_array_equal(o["out"][:rows].numpy(), want.numpy()), short_code=-2), "filtfilt")
+
+
+def test_box_iou_caller_memory(device):
+    """acimg_box_iou, 64 samples, all optional outputs: counts and mask exact, IoU to 1e-7 (tests/test_localize_gpu.py); a
+    short workspace is ACIMG_EWORKSPACE, a NULL one a null argument (ACIMG_EINVAL), as tests/test_host_cpu.py pins them"""
+    m, L = _lib()
+    from acimg import ops
+    import localize_ref as lref
+    from test_localize_gpu import random_boxes
+    N = 64
+    rng = np.random.RandomState(N)
+    logen = (rng.rand(N, 36, 48) * rng.rand(N, 1, 1) * 3).astype(np.float32)
+    boxes = random_boxes(rng, N)
+    lg = torch.from_numpy(logen.reshape(N, 36 * 48)).to(device)
+    bx = torch.from_numpy(np.ascontiguousarray(boxes, np.int32).reshape(N, 4, 3)).to(device)
+    q = int(L.acimg_box_iou_workspace(N))
+    st = ops.current_stream_handle(device)
+    outs = OrderedDict(iou=Out(torch.float32, (N + 4,), first_lt((N + 4,), N)), counts=Out(torch.int32, (N + 2, 2), first_lt((N + 2, 2), N)),
+                       mask=Out(torch.uint8, (N * 224 * 298 + 64,), first_lt((N * 224 * 298 + 64,), N * 224 * 298)))
+
+    def verify(o):
+        iou, counts = o["iou"].numpy(), o["counts"].numpy()
+        mask = o["mask"][:N * 224 * 298].view(N, 224, 298).numpy()
+        for n in range(N):
+            num, den, want, m2 = lref.box_iou(logen[n], boxes[n])
+            assert (counts[n, 0], counts[n, 1]) == (num, den), n
+            assert np.array_equal(mask[n], m2.astype(np.uint8)), n
+            if den == 0:
+                assert np.isnan(iou[n]) and np.isnan(want), n
+            else:
+                assert abs(float(iou[n]) - want) <= 1e-7 * max(abs(want), 1e-30), (n, iou[n], want)
+    run_case(device, Case(q, outs, lambda ws, nb, p, tick: L.acimg_box_iou(lg.data_ptr(), bx.data_ptr(), N, p["iou"], p["counts"], p["mask"],
+                                                                          ws, nb, st), verify, short_code=-2, null_code=-1), "box_iou")
+
+
+@pytest.mark.parametrize("Q,G,D,K", [(63, 50000, 12, 30), (63, 61, 150, 64)])
+def test_knn_topk_caller_memory(device, Q, G, D, K):
+    """acimg_knn_topk on integer-valued features (exact: tests/test_retrieval_gpu.py), the gallery cut into slabs that meet
+    in the workspace, and a small gallery (K > G: -1 / +inf slots); include/acimg.h: short = ACIMG_EWORKSPACE"""
+    m, L = _lib()
+    from acimg import ops
+    import retrieval_ref as rref
+    from test_retrieval_gpu import int_features
+    rng = np.random.RandomState(Q * 7 + G + D + K)
+    qf, gf = int_features(rng, Q, G, D)
+    want_d, want_i = rref.kneighbors(qf, gf, K)
+    qd, gd = padded(torch.from_numpy(qf), D + 3).double().to(device), padded(torch.from_numpy(gf), D + 5).double().to(device)
+    qd[:, :D], gd[:, :D] = torch.from_numpy(qf).to(device), torch.from_numpy(gf).to(device)
+    q = int(L.acimg_knn_topk_workspace(Q, G, D, K))
+    st = ops.current_stream_handle(device)
+    outs = OrderedDict(dist2=Out(torch.float64, (Q + 1, K), first_lt((Q + 1, K), Q)), idx=Out(torch.int32, (Q + 1, K), first_lt((Q + 1, K), Q)))
+
+    def verify(o):
+        assert np.array_equal(o["idx"][:Q].numpy(), want_i)
+        assert np.array_equal(o["dist2"][:Q].numpy(), want_d)
+    run_case(device, Case(q, outs, lambda ws, nb, p, tick: L.acimg_knn_topk(qd.data_ptr(), D + 3, Q, gd.data_ptr(), D + 5, G, D, K, p["dist2"],
+                                                                           p["idx"], ws, nb, st), verify, short_code=-2),
+             "knn_topk[%d,%d,%d,%d]" % (Q, G, D, K))
+
+
+def test_loss_scratch_caller_memory(device):
+    """acimg_recon_loss / acimg_sumsq with the dedicated scratch (zeroed once, as the header demands; its ticket back at
+    zero after every call): 327 683 elements reach the workgroup cap.  RTOL (test_recon_loss_float, test_sumsq).  Without the
+    scratch the header documents float atomics: the NULL run is compared at that tolerance instead of bit for bit."""
+    m, L = _lib()
+    from acimg import ops
+    count = 327683
+    g = torch.Generator().manual_seed(3)
+    yh = torch.sigmoid(f32(g, count).double()).float().double()
+    tgt = (torch.rand(count, generator=g, dtype=torch.float64) * 4 - 1.5).float().double()
+    e = yh - tgt
+    qq = e.abs().clamp(max=1.0)
+    sums_ref = torch.stack([(e * e).sum(), (0.5 * qq * qq + (e.abs() - qq)).sum()])
+    gl_ref = (0.75 * 2 * e + 1.5 * e.clamp(-1.0, 1.0)) / count * yh * (1 - yh)
+    yhd, tgd = yh.float().to(device), tgt.float().to(device)
+    q = int(L.acimg_loss_scratch_bytes())
+    st = ops.current_stream_handle(device)
+    zeros = torch.zeros(4)
+
+    def verify_recon(o):
+        close(o["sums"][:2], sums_ref, what="recon sums")
+        close(o["g_logit"][:count], gl_ref, what="g_logit")
+    run_case(device, Case(q, OrderedDict(g_logit=Out(torch.float32, (count + 5,), first_lt((count + 5,), count)),
+                                         sums=Out(torch.float32, (4,), init=zeros)),
+                          lambda ws, nb, p, tick: L.acimg_recon_loss(yhd.data_ptr(), tgd.data_ptr(), p["g_logit"], p["sums"], count, 0.75, 1.5,
+                                                                     ws, nb, st),
+                          verify_recon, zero_head=q, zero_exit=16, fallback=True), "recon_loss")
+    run_case(device, Case(q, OrderedDict(out=Out(torch.float32, (4,), init=zeros)),
+                          lambda ws, nb, p, tick: L.acimg_sumsq(tgd.data_ptr(), count, p["out"], ws, nb, st),
+                          lambda o: close(o["out"][:1], (tgt * tgt).sum().view(1), what="sumsq"), zero_head=q, zero_exit=16, fallback=True), "sumsq")

@@ -611,3 +611,138 @@ def test_joint_oracle_tables_reduce_to_the_12x16_feature_map():
             assert float(joint.regulariser(model, p)) > 0
         else:
             assert not net.new_stats and joint.regulariser(model, p) == 0.0
+
+
+def test_wrappers_require_at_least_the_queried_workspace(lib):
+    """Every ops.* wrapper that sizes the plan's workspace (`plan.ws.require`) must ask for at least what the C query of the
+    entry point it actually calls reports - over the case table of tests/test_caller_memory_gpu.py, recorded into a non-eager
+    Plan(None) (no GPU, nothing runs).  A wrapper that required another entry point's query (or none) would hand the kernel a
+    short buffer that only a guarded run notices."""
+    import ctypes as C
+
+    from acimg import ops
+    from test_caller_memory_gpu import DECONV_CASES, DGRAD_CASES, FWD_CASES, WGRAD_CASES
+
+    t = torch.zeros(1)
+
+    def need(record, side=False):
+        plan = ops.Plan(None)
+        record(plan)
+        assert len(plan.calls) >= 1
+        return (plan.side_ws if side else plan.ws).need
+
+    checked = 0
+    # every shape of the three tables with the leading dimensions its GPU case uses (fwd: ldy = K + 4; dgrad: ldw = K;
+    # wgrad: ldw = up4(K) + 4) and with the defaults: each wrapper against its query on every one of them
+    descs = [ops.conv_desc(*c[0], ldy=c[0][4] + 4, act=c[1]) for c in FWD_CASES.values()]
+    descs += [ops.conv_desc(*c[0], ldw=c[0][4]) for c in DGRAD_CASES.values()]
+    descs += [ops.conv_desc(*c[0], ldw=((c[0][4] + 3) & ~3) + 4) for c in WGRAD_CASES.values()]
+    descs += [ops.conv_desc(*shape) for shape in sorted(set(c[0] for c in list(FWD_CASES.values()) + list(DGRAD_CASES.values()) +
+                                                           list(WGRAD_CASES.values())), key=str)]
+    for d in descs:
+        shape = (d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.stride, d.ldy, d.ldw)
+        ref = C.byref(d)
+        assert need(lambda p: ops.conv2d_fwd(p, d, t, t, t, t)) >= lib.acimg_conv2d_fwd_workspace(ref), shape
+        assert need(lambda p: ops.conv2d_dgrad(p, d, t, d.ldy, t, t)) >= lib.acimg_conv2d_dgrad_workspace(ref), shape
+        wq = lib.acimg_conv2d_wgrad_workspace(ref)
+        for side in (False, True):
+            assert need(lambda p: ops.conv2d_wgrad(p, d, t, t, d.ldy, t, t, side=side), side) >= wq, shape
+            assert need(lambda p: ops.conv2d_wgrad_split3(p, d, t, t, d.ldy, t, t, side=side), side) >= wq, shape
+            assert need(lambda p: ops.conv2d_wgrad_split3(p, d, t, t, d.ldy, t, t, bf16=True, side=side), side) >= wq, shape
+        assert need(lambda p: ops.conv2d_wgrad_affine(p, d, 0, t, t, t, t, d.ldy, t, t)) >= wq, shape
+        checked += 1
+    for shape, _, _, _ in DECONV_CASES.values():
+        d = ops.deconv_desc(*shape, ldy=2 * shape[4])
+        dq = lib.acimg_deconv_workspace(C.byref(d))
+        assert dq > 0
+        assert need(lambda p: ops.deconv_fwd(p, d, t, t, t, t)) >= dq, shape
+        assert need(lambda p: ops.deconv_dgrad(p, d, t, d.ldy, t, t)) >= dq, shape
+        for side in (False, True):
+            assert need(lambda p: ops.deconv_wgrad(p, d, t, t, d.ldy, t, t, side=side), side) >= dq, shape
+        checked += 1
+    assert checked >= 15
+    N, P, Cn = 2, 1728, 133
+    assert need(lambda p: ops.minmax_fwd(p, t, 136, t, 148, t, N, P, Cn)) >= lib.acimg_minmax_workspace(N, P, Cn) > 256
+    assert need(lambda p: ops.minmax_bwd(p, t, 136, t, 148, t, t, 136, N, P, Cn)) >= lib.acimg_minmax_workspace(N, P, Cn)
+    assert need(lambda p: ops.bn_bwd(p, t, 36, t, 36, t, t, t, t, t, 133504, 32, t, 36, t, t)) >= lib.acimg_bn_bwd_workspace(133504, 32) > 256
+    assert need(lambda p: ops.box_iou(p, t, t, 64, t)) >= lib.acimg_box_iou_workspace(64) > 256
+    assert need(lambda p: ops.knn_topk(p, t, 12, 63, t, 12, 50000, 12, 30, t, t)) >= lib.acimg_knn_topk_workspace(63, 50000, 12, 30) > 256
+    assert need(lambda p: ops.filtfilt(p, t, 150, 1024, t, t, t)) >= lib.acimg_filtfilt_workspace(150, 1024) > 256
+    # the dedicated buffers are sized by the callers from these queries: positive, and the wrappers pass the buffer's own size
+    assert ops.triplet_loss_workspace(300) == lib.acimg_triplet_loss_workspace(300) > 0
+    assert ops.gram_stats_workspace(20011, 128) == lib.acimg_gram_stats_workspace(20011, 128) > 0
+    d = ops.conv_desc(8, 56, 75, 128, 128, 3, 3)
+    assert ops.conv2d_fwd_split3p_workspace(d) == lib.acimg_conv2d_fwd_split3p_workspace(C.byref(d)) >= 4096 + 65536
+    assert lib.acimg_loss_scratch_bytes() >= 16 + 2 * 4
+
+
+def test_short_or_missing_workspace_is_refused_before_any_launch(lib):
+    """Where include/acimg.h (or the entry point's own error text) promises a refusal, a workspace 16 bytes short of the query
+    and a NULL workspace return the negative code BEFORE any launch: there is no GPU here, fake aligned pointers stand for
+    the tensors, and a launch attempted first would come back as ACIMG_ELAUNCH instead.  Pattern of
+    test_gram_stats_host_side."""
+    import ctypes as C
+
+    from acimg import _lib, ops
+
+    big = (C.c_char * 8192)()
+    a = C.addressof(big) + (-C.addressof(big)) % 256
+    EW = -2
+
+    def both(call, q, code=EW, text="workspace", null_code=None):
+        assert q > 16
+        rc = call(a, q - 16)
+        assert rc == code and text in _lib.last_error(), (rc, _lib.last_error())
+        for ws, nb in ((None, 0), (None, q)):
+            rc = call(ws, nb)
+            assert rc == (code if null_code is None else null_code), (rc, _lib.last_error())
+
+    # acimg_knn_topk: "short = ACIMG_EWORKSPACE"
+    q = lib.acimg_knn_topk_workspace(63, 50000, 12, 30)
+    both(lambda ws, nb: lib.acimg_knn_topk(a, 12, 63, a, 12, 50000, 12, 30, a, a, ws, nb, None), q)
+    q = lib.acimg_minmax_workspace(2, 1728, 133)
+    both(lambda ws, nb: lib.acimg_minmax_fwd(a, 136, a, 148, a, 2, 1728, 133, ws, nb, None), q)
+    both(lambda ws, nb: lib.acimg_minmax_bwd(a, 136, a, 148, a, a, 136, 2, 1728, 133, 0, 0, ws, nb, None), q)
+    q = lib.acimg_bn_bwd_workspace(133504, 32)
+    both(lambda ws, nb: lib.acimg_bn_bwd(a, 32, a, 32, a, a, a, a, a, 133504, 32, a, 32, a, a, ws, nb, None), q)
+    q = lib.acimg_filtfilt_workspace(150, 1024)
+    both(lambda ws, nb: lib.acimg_filtfilt(a, 0, 150, 1024, a, a, a, ws, nb, None), q)
+    q = lib.acimg_box_iou_workspace(64)
+    both(lambda ws, nb: lib.acimg_box_iou(a, a, 64, a, None, None, ws, nb, None), q, null_code=-1)      # NULL: "null argument"
+    q = lib.acimg_triplet_loss_workspace(300)
+    both(lambda ws, nb: lib.acimg_triplet_loss_fwd(a, 64, a, 64, a, a, 300, 64, 0.2, 0, ws, nb, a, None), q, code=-1)
+    both(lambda ws, nb: lib.acimg_triplet_loss_bwd(a, 64, a, 64, 300, 64, 1.0, ws, nb, a, 64, a, 64, 0, None), q, code=-1)
+    # the loss scratch is optional (NULL = float atomics); a SHORT one is refused
+    q = lib.acimg_loss_scratch_bytes()
+    assert lib.acimg_recon_loss(a, a, a, a, 1000, 1.0, 1.0, a, q - 16, None) == EW and "scratch" in _lib.last_error()
+    assert lib.acimg_sumsq(a, 1000, a, a, q - 16, None) == EW and "scratch" in _lib.last_error()
+    # split-K implicit GEMM (forward, stride-1 data gradient), slab weight gradients: the slabs live in the workspace
+    d = ops.conv_desc(4, 12, 16, 128, 128, 3, 3, 1, "SAME")
+    q = lib.acimg_conv2d_fwd_workspace(C.byref(d))
+    both(lambda ws, nb: lib.acimg_conv2d_fwd(C.byref(d), a, a, a, a, None, None, 0, None, ws, nb, None, None), q)
+    # (the data-gradient query covers both K orders the launch may pick - ldgy decides - so "short" here is a page)
+    for ws, nb in ((a, 4096), (None, 0)):
+        assert lib.acimg_conv2d_dgrad(C.byref(d), a, 128, a, a, 128, None, 0, None, 0, ws, nb, None, None) == EW
+        assert "workspace" in _lib.last_error()
+    q = lib.acimg_conv2d_wgrad_workspace(C.byref(d))
+    for fn in (lib.acimg_conv2d_wgrad, lib.acimg_conv2d_wgrad_split3, lib.acimg_conv2d_wgrad_bf16):
+        for ws, nb in ((a, 4096), (None, 0)):
+            assert fn(C.byref(d), a, a, 128, a, a, ws, nb, None) == EW and "workspace" in _lib.last_error()
+    # the zero-inserted copy of the strided data gradient / of the transposed conv's input
+    d2 = ops.conv_desc(2, 17, 23, 8, 8, 3, 3, 2, "SAME")
+    for ws, nb in ((a, 4096), (None, 0)):
+        assert lib.acimg_conv2d_dgrad(C.byref(d2), a, 8, a, a, 8, None, 0, None, 0, ws, nb, None, None) == EW
+        assert "dilated" in _lib.last_error()
+    d3 = ops.deconv_desc(2, 6, 8, 32, 8, 3, 3, 2)
+    for ws, nb in ((a, 4096), (None, 0)):
+        assert lib.acimg_deconv_fwd(C.byref(d3), a, a, a, a, ws, nb, None, None) == EW and "dilated" in _lib.last_error()
+    # the input affine of a weight gradient needs the halo form, which needs its slabs
+    d4 = ops.conv_desc(4, 112, 149, 32, 32, 3, 3, 1, "SAME")
+    assert lib.acimg_conv2d_wgrad_affine(C.byref(d4), 1, a, a, a, 1, a, 32, a, a, a, 4096, None) == EW
+    assert "halo form" in _lib.last_error()
+    # a small transposed conv: the weight gradient is unsplit (no slabs), but the bias gradient's column sum needs its
+    # partials - refused up front, not after dw has been written
+    for d5 in (d3, ops.deconv_desc(2, 7, 9, 64, 32, 2, 3, 2)):
+        for ws, nb in ((a, 16), (None, 0)):
+            assert lib.acimg_deconv_wgrad(C.byref(d5), a, a, 2 * d5.K, a, a, ws, nb, None) == EW
+            assert "bias gradient" in _lib.last_error()
