@@ -16,13 +16,11 @@ import torch
 
 from . import ops
 from .ops import ACT_NONE, ACT_RELU
+from .model import Act, Model, load_state_file
 from .params import Var, up4
-from .session import get_default_session
-from .unet_acresnet import Act
-from .vision import load_state_file
 
 
-class DualCamHybridModel(object):
+class DualCamHybridModel(Model):
 
     def __init__(self, input_shape=None, num_classes=10, num_frames=12, embedding=True):
         self.scope = 'DualCamNet'
@@ -63,9 +61,7 @@ class DualCamHybridModel(object):
         return sd
 
     def init_model(self, session, checkpoint_file):
-        state = self._to_internal(load_state_file(checkpoint_file))
-        store = (session or self.session).store
-        return store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
+        return self._load_scope(self._to_internal(load_state_file(checkpoint_file)), session)
 
     def initialize(self, seed=1241, state=None):
         """truncated normal sigma=0.01 weights, zero biases (models/base.py:9-10)"""
@@ -79,24 +75,13 @@ class DualCamHybridModel(object):
                     state[name] = torch.zeros(v.tf_shape)
                 else:
                     state[name] = (torch.randn(*v.tf_shape, generator=g, dtype=torch.float64).clamp(-2, 2) * 0.01).float()
-        self.session.store.load_state(self._to_internal(state), strict=False,
-                                      only=lambda n: n.startswith(self.scope + "/"))
-
-    def _P(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.p(self.scope + "/" + name))
-
-    def _G(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.g(self.scope + "/" + name))
+        self._load_scope(self._to_internal(state))
 
     # ---- graph ------------------------------------------------------------------------------------------------
     def _build_model(self, acoustic_images, session=None):
         """acoustic_images: device buffer [clips*12, 36, 48, 12] (trainer_reconstructed_class.py:44 reshapes the
         generator output to [-1, 12, 36, 48, 12]: consecutive frames form a clip)"""
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         NF = acoustic_images.shape[0]
         F_, H, W, C = self.num_frames, self.height, self.width, self.channels
         assert NF % F_ == 0 and tuple(acoustic_images.shape[1:]) == (H, W, C) and C % 4 == 0
@@ -132,7 +117,7 @@ class DualCamHybridModel(object):
         self.network = OrderedDict([("input", acoustic_images), ("is_training", None), ("keep_prob", None),
                                     (2, self.relu1.t), (4, self.relu2.t), (5, self.pool2.t), (7, self.relu3.t),
                                     (8, self.pool3), (10, self.relu4), (13, self.logits)])
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/")]
+        self.train_vars = self._scope_vars()
 
     def record_backward(self, plan, g_logits):
         """g_logits [clips*12, up4(classes)]: d loss / d per-frame logits (acimg_clip_softmax_ce)"""

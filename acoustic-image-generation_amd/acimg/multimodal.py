@@ -7,20 +7,19 @@ latent statistics; `record_backward(plan, g_ext)` consumes the gradient `UNetAcZ
 """
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import ops
+from .model import Model, xavier
 from .ops import ACT_NONE, ACT_RELU
 from .params import Var, up4
 from .session import get_default_session
-from .vision import load_state_file
 from .unet_vae import AssociatorAudio          # noqa: F401  (models/multimodal.py:139-285: the conv associator)
 
 Z = 150
 
 
-class _Associator(object):
+class _Associator(Model):
     SCOPE, DIN, WIDTHS = None, None, None
 
     def __init__(self, input_shape=None, num_frames=12, embedding=True):
@@ -45,35 +44,18 @@ class _Associator(object):
             store.add(Var("%s/%s/kernel" % (self.scope, name), (cin, cout), "dense", "train"))
             store.add(Var("%s/%s/bias" % (self.scope, name), (cout,), "vec", "train"))
 
-    def init_model(self, session, checkpoint_file):
-        state = load_state_file(checkpoint_file)
-        store = (session or self.session).store
-        return store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
     def initialize(self, seed=1243, state=None):
         if state is None:
             g = torch.Generator().manual_seed(seed)
             state = OrderedDict()
             for name, cin, cout, _, _ in self._names():
-                lim = np.sqrt(6.0 / (cin + cout))
-                state["%s/%s/kernel" % (self.scope, name)] = (
-                    (torch.rand(cin, cout, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
+                state["%s/%s/kernel" % (self.scope, name)] = xavier(g, (cin, cout), cin, cout)
                 state["%s/%s/bias" % (self.scope, name)] = torch.zeros(cout)
-        self.session.store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
-    def _P(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.p(self.scope + "/" + name))
-
-    def _G(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.g(self.scope + "/" + name))
+        self._load_scope(state)
 
     def _build_model(self, mean, std, session=None):
         """mean, std: the halves of ONE device buffer [N, 2*DIN] = [mean | std] (an encoder's fused head output)"""
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         src = mean._base if mean._base is not None else mean
         N = src.shape[0]
         assert src.shape == (N, 2 * self.DIN), "mean / std must be the halves of one [N, %d] buffer" % (2 * self.DIN)
@@ -101,7 +83,7 @@ class _Associator(object):
         self.plan_fwd = p
         self.mean, self.std = self.ext[:, :Z], self.ext[:, Z:]
         self.network = OrderedDict(input=mean, input2=std)
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/")]
+        self.train_vars = self._scope_vars()
 
     def record_backward(self, plan, g_ext):
         """g_ext [N, 300]: d loss / d [mean' | std'] (e.g. UNetAcZ.g_ext)"""
@@ -130,7 +112,7 @@ class AssociatorAudioAc(_Associator):
     SCOPE, DIN, WIDTHS = "AssociatorAudioAc", 256, [256, 256, 150]
 
 
-class _JointMLP(object):
+class _JointMLP(Model):
     """The joint-latent fusion MLPs (models/multimodal.py:287-465): tf.layers.dense acts on the LAST axis, so on
     [N, 12, 16, C] feature maps these are per-pixel MLPs = 1x1 convolutions.  concat(inputs) -> 3 x dense 512 (ReLU)
     -> one ReLU dense head per output modality.  The inputs must be the consecutive channel slices of ONE device
@@ -159,20 +141,14 @@ class _JointMLP(object):
             store.add(Var("%s/%s/kernel" % (self.scope, name), (cin, cout), "dense", "train"))
             store.add(Var("%s/%s/bias" % (self.scope, name), (cout,), "vec", "train"))
 
-    init_model = _Associator.init_model
-    _P = _Associator._P
-    _G = _Associator._G
-
     def initialize(self, seed=1249, state=None):
         if state is None:
             g = torch.Generator().manual_seed(seed)
             state = OrderedDict()
             for name, cin, cout, _ in self._names():
-                lim = np.sqrt(6.0 / (cin + cout))
-                state["%s/%s/kernel" % (self.scope, name)] = (
-                    (torch.rand(cin, cout, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
+                state["%s/%s/kernel" % (self.scope, name)] = xavier(g, (cin, cout), cin, cout)
                 state["%s/%s/bias" % (self.scope, name)] = torch.zeros(cout)
-        self.session.store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
+        self._load_scope(state)
 
     def _build_model(self, *inputs, **kw):
         sess = kw.get("session") or get_default_session()
@@ -215,7 +191,7 @@ class _JointMLP(object):
                 setattr(self, attr, y.view(*(lead + (up4(cout),)))[..., :cout])
         self.plan_fwd = p
         self.network = OrderedDict(("input%s" % ("" if i == 0 else str(i + 1)), t) for i, t in enumerate(inputs))
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/")]
+        self.train_vars = self._scope_vars()
 
     def record_backward(self, plan, g_heads, need_input_grad=True):
         """g_heads: {head attribute: (gradient tensor / Ptr, row stride)} for the heads that carry a loss"""

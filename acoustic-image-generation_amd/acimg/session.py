@@ -1,5 +1,8 @@
 """`Session`: what stands where the reference has a tf.Session — the device, its stream, the
-parameter store and the kernel workspace shared by every model built in it."""
+parameter store and the kernel workspace shared by every model built in it — and the plumbing every
+trainer shares: `Graph`, `scope_range`, `draw_noise`, `loss_dict`."""
+from collections import OrderedDict
+
 import torch
 
 from . import _lib, ops
@@ -28,6 +31,40 @@ class Session(object):
         if not self._finalized:
             self.store.finalize()
             self._finalized = True
+
+    def adam_step(self, lr, step, off=0, numel=None, grad_scale=1.0):
+        """ONE Adam launch (TF-1 form, 1-based `step`) over `numel` floats at `off` of the flat trainable buffer and its
+        gradient / moment twins, on the current stream; numel None: the whole buffer"""
+        st = self.store
+        o = 4 * off
+        rc = _lib.load().acimg_adam_step(st.flat["train"].data_ptr() + o, st.grad.data_ptr() + o,
+                                         st.adam_m.data_ptr() + o, st.adam_v.data_ptr() + o,
+                                         st.train_numel() if numel is None else numel, ops.adam_lr_t(lr, step),
+                                         0.9, 0.999, 1e-8, grad_scale, ops.current_stream_handle(self.device))
+        _lib.check(rc, "adam_step")
+
+
+class Graph(object):
+    """Buffers + plans of a trainer for one batch size (the reference's graph has a dynamic batch dimension)."""
+
+
+def scope_range(store, scope):
+    """(offset, numel) of a scope's variables in the flat trainable buffer: one contiguous run"""
+    rng = [(o, c) for n, o, c in store.train_ranges() if n.startswith(scope + "/")]
+    return rng[0][0], rng[-1][0] + rng[-1][1] - rng[0][0]
+
+
+def draw_noise(session, tensor, seed, offset):
+    """fill `tensor` with N(0,1) on the device, from Philox counter `offset` on (the reference's tf.random_normal)"""
+    rc = _lib.load().acimg_randn(tensor.data_ptr(), tensor.numel(), seed, offset,
+                                 ops.current_stream_handle(session.device))
+    _lib.check(rc, "randn")
+
+
+def loss_dict(losses):
+    """python floats of a trainer's loss buffer (blocks until the step that wrote it has run)"""
+    v = losses[:5].tolist()
+    return OrderedDict(mse=v[0], huber=v[1], latent=v[2], reg=v[3], loss=v[4])
 
 
 _default = None

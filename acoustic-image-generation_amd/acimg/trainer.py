@@ -23,15 +23,10 @@ import torch
 
 from . import _lib, dp, ops
 from .flags import FLAGS
-from .session import Session
+from .session import Graph, Session, draw_noise, loss_dict
 from .unet_acresnet import Z
 
 _FRAMES_PER_SECOND = 12
-
-
-class _Graph(object):
-    """Buffers + plans for one batch size (the reference's graph has a dynamic batch dimension)."""
-    pass
 
 
 class Trainer(object):
@@ -76,7 +71,7 @@ class Trainer(object):
     def _build_graph(self, N, modelimages, modelac):
         sess = self.session
         z = sess.zeros
-        g = _Graph()
+        g = Graph()
         g.N = N
         g.modelimages, g.modelac = modelimages, modelac
         g.acoustic = z(N, 36, 48, 12)
@@ -214,9 +209,7 @@ class Trainer(object):
             g.eps.copy_(eps.reshape(g.N, Z), non_blocking=True)
         else:
             self._noise_calls = getattr(self, "_noise_calls", 0) + 1
-            rc = _lib.load().acimg_randn(g.eps.data_ptr(), g.N * Z, self.noise_seed, self._noise_calls * 65536,
-                                         ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "randn")
+            draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
 
     def train_step(self, batch=None, eps=None, sync=True, probe=None):
         """One optimisation step (the body of the reference's hot loop, trainer/mfcctrainer.py:343-349).
@@ -238,7 +231,6 @@ class Trainer(object):
                 g.plan_train.run_probed(probe[0], probe[1])
         finally:
             self.hold_exchange = held
-        store = self.session.store
         scale = 1.0
         if self.comm is not None and self.comm.enabled:
             if whole:
@@ -247,12 +239,7 @@ class Trainer(object):
                 self.comm.wait()
             scale = self.comm.grad_scale
         self.global_step += 1
-        lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-        st = ops.current_stream_handle(self.session.device)
-        rc = _lib.load().acimg_adam_step(store.flat["train"].data_ptr(), store.grad.data_ptr(),
-                                         store.adam_m.data_ptr(), store.adam_v.data_ptr(),
-                                         store.train_numel(), lr_t, 0.9, 0.999, 1e-8, scale, st)
-        _lib.check(rc, "adam_step")
+        self.session.adam_step(self.learning_rate, self.global_step, grad_scale=scale)
         if not sync:
             return g.losses
         return self._scalars(g)
@@ -381,12 +368,7 @@ class Trainer(object):
                     self.comm.allreduce_all()
                 scale = self.comm.grad_scale
             self.global_step += 1
-            lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-            rc = _lib.load().acimg_adam_step(store.flat["train"].data_ptr(), store.grad.data_ptr(),
-                                             store.adam_m.data_ptr(), store.adam_v.data_ptr(),
-                                             store.train_numel(), lr_t, 0.9, 0.999, 1e-8, scale,
-                                             ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "adam_step")
+            self.session.adam_step(self.learning_rate, self.global_step, grad_scale=scale)
             if acc is None and item.get("tag") is not None:
                 # a private copy of this batch's losses (the graph's buffer is rewritten by the next batch)
                 pipe["finished"].append((item["tag"], g.losses[:5].clone()))
@@ -478,8 +460,7 @@ class Trainer(object):
     def _lane_b_scalars(self, losses):
         """python floats of a loss tensor produced on lane B (read behind that lane, not behind the trunk in flight)"""
         with torch.cuda.stream(self._pipe["sb"]):
-            v = losses[:5].tolist()
-        return OrderedDict(mse=v[0], huber=v[1], latent=v[2], reg=v[3], loss=v[4])
+            return loss_dict(losses)
 
     def flush_pipeline(self):
         """finish the batches in flight (oldest first) and make the current stream wait for every lane; returns the
@@ -552,17 +533,11 @@ class Trainer(object):
             self.comm.allreduce_all()
             world = self.comm.world
         self.global_step += 1
-        lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-        rc = L.acimg_adam_step(store.flat["train"].data_ptr(), store.grad.data_ptr(), store.adam_m.data_ptr(),
-                               store.adam_v.data_ptr(), store.train_numel(), lr_t, 0.9, 0.999, 1e-8,
-                               1.0 / (len(shards) * world), st)
-        _lib.check(rc, "adam_step")
-        v = (tot / len(shards)).tolist()
-        return OrderedDict(mse=v[0], huber=v[1], latent=v[2], reg=v[3], loss=v[4])
+        self.session.adam_step(self.learning_rate, self.global_step, grad_scale=1.0 / (len(shards) * world))
+        return loss_dict(tot / len(shards))
 
     def _scalars(self, g):
-        v = g.losses[:5].tolist()
-        return OrderedDict(mse=v[0], huber=v[1], latent=v[2], reg=v[3], loss=v[4])
+        return loss_dict(g.losses)
 
     def eval_step(self, batch=None, eps=None):
         """forward in inference mode (BN moving statistics); returns mse + the four per-3-channel MSEs"""

@@ -11,16 +11,11 @@ One step = ONE recorded plan: associator forward -> decoder forward -> reconstru
 decoder data gradients down to d loss / d (mean, std) (KL term included) -> associator backward; then Adam over
 the associator's contiguous range of the flat parameter buffer.
 """
-from collections import OrderedDict
-
-from . import _lib, ops
-from .session import Session
+from . import ops
+from .model import flat_ptr, grad_ptr
+from .session import Graph, Session, draw_noise, loss_dict, scope_range
 
 _LATENT_W = 1e-6
-
-
-class _Graph(object):
-    pass
 
 
 class TrainerAssociator(object):
@@ -42,7 +37,7 @@ class TrainerAssociator(object):
         sess = self.session
         z = sess.zeros
         ma, md = self.modelassociator, self.modelac
-        g = _Graph()
+        g = Graph()
         g.N = N
         conv = bool(getattr(ma, "IMAGE_INPUT", False))
         g.acoustic = z(N, 36, 48, 12)
@@ -67,8 +62,7 @@ class TrainerAssociator(object):
         if conv:                                  # kernel regularisers of the conv associator: one pass each way
             roff, nreg = ma.reg_range()
             wd = ma.WD
-            wreg = ops.LazyPtr(lambda: st.flat["train"][roff:roff + nreg])
-            greg = ops.LazyPtr(lambda: st.grad[roff:roff + nreg])
+            wreg, greg = flat_ptr(st, "train", roff, nreg), grad_ptr(st, roff, nreg)
             ops.sumsq(p, wreg, nreg, ops.Ptr(g.sums, 2))
         ops.loss_finalize(p, g.sums, md.kl, N, count, _LATENT_W, 0.5 * wd, 1.0, 1.0, g.losses)
         md.record_backward(p, g.g_logit, _LATENT_W / N)
@@ -77,9 +71,7 @@ class TrainerAssociator(object):
             ops.axpy(p, wd, wreg, greg, nreg)
         g.plan_train = p
         sess.finalize()
-        rng = [(n, o, c) for n, o, c in sess.store.train_ranges() if n.startswith(ma.scope + "/")]
-        g.off = rng[0][1]
-        g.numel = rng[-1][1] + rng[-1][2] - g.off
+        g.off, g.numel = scope_range(st, ma.scope)
         self.primary = g
         return g
 
@@ -93,18 +85,9 @@ class TrainerAssociator(object):
             g.eps.copy_(eps.reshape(g.eps.shape), non_blocking=True)
         else:
             self._noise_calls = getattr(self, "_noise_calls", 0) + 1
-            rc = _lib.load().acimg_randn(g.eps.data_ptr(), g.eps.numel(), self.noise_seed, self._noise_calls * 65536,
-                                         ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "randn")
+            draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
         g.plan_train.run()
         if apply:
-            st = self.session.store
             self.global_step += 1
-            lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-            o = g.off * 4
-            rc = _lib.load().acimg_adam_step(st.flat["train"].data_ptr() + o, st.grad.data_ptr() + o,
-                                             st.adam_m.data_ptr() + o, st.adam_v.data_ptr() + o, g.numel, lr_t, 0.9,
-                                             0.999, 1e-8, 1.0, ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "adam_step")
-        v = g.losses[:5].tolist()
-        return OrderedDict(mse=v[0], huber=v[1], latent=v[2], reg=v[3], loss=v[4])
+            self.session.adam_step(self.learning_rate, self.global_step, g.off, g.numel)
+        return loss_dict(g.losses)

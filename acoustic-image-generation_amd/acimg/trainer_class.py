@@ -13,14 +13,10 @@ from collections import OrderedDict
 
 import torch
 
-from . import _lib, ops
+from . import ops
 from .params import up4
-from .session import Session
+from .session import Graph, Session, draw_noise, scope_range
 from .unet_acresnet import Z
-
-
-class _Graph(object):
-    pass
 
 
 class TrainerClass(object):
@@ -48,7 +44,7 @@ class TrainerClass(object):
             self.session = Session()
         sess = self.session
         z = sess.zeros
-        g = _Graph()
+        g = Graph()
         g.N, g.clips = N, N // self.nr_frames
         g.mfcc = z(N, 12)
         g.video = z(N, 224, 298, 3)
@@ -76,9 +72,7 @@ class TrainerClass(object):
         g.plan_train, g.plan_eval = p, e
         sess.finalize()
         # the DualCamNet variables are one contiguous run of the flat trainable buffer
-        rng = [(n, o, c) for n, o, c in sess.store.train_ranges() if n.startswith(m.scope + "/")]
-        g.off = rng[0][1]
-        g.numel = rng[-1][1] + rng[-1][2] - g.off
+        g.off, g.numel = scope_range(sess.store, m.scope)
         self.primary = g
         return g
 
@@ -94,9 +88,7 @@ class TrainerClass(object):
             g.eps.copy_(eps.reshape(g.N, Z), non_blocking=True)
         else:
             self._noise_calls = getattr(self, "_noise_calls", 0) + 1
-            rc = _lib.load().acimg_randn(g.eps.data_ptr(), g.N * Z, self.noise_seed, self._noise_calls * 65536,
-                                         ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "randn")
+            draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
 
     def train_step(self, batch=None, eps=None):
         """batch: (mfcc [N,12], video [N,224,298,3], labels [clips] or one-hot [clips, classes]); returns
@@ -104,14 +96,8 @@ class TrainerClass(object):
         g = self.primary
         self._feed(g, batch, eps)
         g.plan_train.run()
-        st = self.session.store
         self.global_step += 1
-        lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-        o, n = g.off * 4, g.numel
-        rc = _lib.load().acimg_adam_step(st.flat["train"].data_ptr() + o, st.grad.data_ptr() + o,
-                                         st.adam_m.data_ptr() + o, st.adam_v.data_ptr() + o, n, lr_t, 0.9, 0.999, 1e-8,
-                                         1.0, ops.current_stream_handle(self.session.device))
-        _lib.check(rc, "adam_step")
+        self.session.adam_step(self.learning_rate, self.global_step, g.off, g.numel)
         v = g.out[:2].tolist()
         return OrderedDict(loss=v[0], accuracy=v[1] / g.clips)
 

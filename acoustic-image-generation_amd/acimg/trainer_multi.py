@@ -19,14 +19,11 @@ reference's update_ops do.
 """
 from collections import OrderedDict
 
-from . import _lib, ops
-from .session import Session
+from . import ops
+from .model import flat_ptr
+from .session import Graph, Session, draw_noise, scope_range
 
 _LATENT_W = 1e-6
-
-
-class _Graph(object):
-    pass
 
 
 class TrainerMulti(object):
@@ -61,7 +58,7 @@ class TrainerMulti(object):
         sess = self.session
         z = sess.zeros
         mac, mau, mvi, ma = self.modelac, self.modelaudio, self.modelimages, self.modelassociator
-        g = _Graph()
+        g = Graph()
         g.N = N
         g.acoustic = z(N, mac.height, mac.width, mac.channels)
         g.mfcc = z(N, mau.height, mau.width, mau.channels)        # (the reference's name for the spectrogram input)
@@ -145,7 +142,7 @@ class TrainerMulti(object):
             for wd, roff, n in ranges:
                 buf = z(4)
                 ops.zero(p, buf)
-                ops.sumsq(p, ops.LazyPtr(lambda roff=roff, n=n: st.flat["train"][roff:roff + n]), n, buf)
+                ops.sumsq(p, flat_ptr(st, "train", roff, n), n, buf)
                 g.reg.append((wd, buf))
         g_heads = OrderedDict()
         for k, (m, _, attr) in g.mods.items():
@@ -171,9 +168,7 @@ class TrainerMulti(object):
         ma = trained
         g.plan_train = p
         sess.finalize()
-        rng = [(n, o, c) for n, o, c in st.train_ranges() if n.startswith(ma.scope + "/")]
-        g.off = rng[0][1]
-        g.numel = rng[-1][1] + rng[-1][2] - g.off
+        g.off, g.numel = scope_range(st, ma.scope)
         self.primary = g
         return g
 
@@ -196,19 +191,11 @@ class TrainerMulti(object):
         else:
             self._noise_calls = getattr(self, "_noise_calls", 0) + 1
             for i, t in enumerate(g.eps.values()):
-                rc = _lib.load().acimg_randn(t.data_ptr(), t.numel(), self.noise_seed, (self._noise_calls * 4 + i) << 24,
-                                             ops.current_stream_handle(self.session.device))
-                _lib.check(rc, "randn")
+                draw_noise(self.session, t, self.noise_seed, (self._noise_calls * 4 + i) << 24)
         g.plan_train.run()
         if apply:
-            st = self.session.store
             self.global_step += 1
-            lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-            o = g.off * 4
-            rc = _lib.load().acimg_adam_step(st.flat["train"].data_ptr() + o, st.grad.data_ptr() + o,
-                                             st.adam_m.data_ptr() + o, st.adam_v.data_ptr() + o, g.numel, lr_t, 0.9,
-                                             0.999, 1e-8, 1.0, ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "adam_step")
+            self.session.adam_step(self.learning_rate, self.global_step, g.off, g.numel)
         out = OrderedDict()
         mse = hub = lat = 0.0
         for k in g.mods:

@@ -10,14 +10,9 @@ One step = ONE recorded plan: zero sums -> forward (BN batch statistics, moving 
 reconstruction loss + its gradient -> L2 term (one pass over the contiguous regularised kernels) -> scalars
 -> backward -> L2 gradient (one axpy) ; then Adam (one launch over the flat parameter buffer).
 """
-from collections import OrderedDict
-
-from . import _lib, ops
-from .session import Session
-
-
-class _Graph(object):
-    pass
+from . import ops
+from .model import flat_ptr, grad_ptr
+from .session import Graph, Session, draw_noise, loss_dict
 
 
 class TrainerVAE(object):
@@ -39,7 +34,7 @@ class TrainerVAE(object):
         sess = self.session
         m = self.model
         z = sess.zeros
-        g = _Graph()
+        g = Graph()
         g.N = N
         H, W, Cin = m.height, m.width, m.channels
         g.images = z(N, H, W, Cin)
@@ -54,8 +49,7 @@ class TrainerVAE(object):
         ratio = float(padded) / float(count)
         st = sess.store
         off, n = m.reg_range()
-        wreg = ops.LazyPtr(lambda: st.flat["train"][off:off + n])
-        greg = ops.LazyPtr(lambda: st.grad[off:off + n])
+        wreg, greg = flat_ptr(st, "train", off, n), grad_ptr(st, off, n)
         latent_w = 1.0 / (1e6 * m.Z)       # kl[n] holds 0.5 * sum_j; the reference takes mean_j, then / 1e6
 
         p = sess.new_plan()
@@ -78,9 +72,7 @@ class TrainerVAE(object):
             g.eps.copy_(eps.reshape(g.N, -1), non_blocking=True)
         else:
             self._noise_calls = getattr(self, "_noise_calls", 0) + 1
-            rc = _lib.load().acimg_randn(g.eps.data_ptr(), g.eps.numel(), self.noise_seed, self._noise_calls * 65536,
-                                         ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "randn")
+            draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
 
     def train_step(self, batch=None, eps=None, sync=True, apply=True):
         """batch: images [N,H,W,C] (or None to reuse the resident input); returns {mse, huber, latent, reg, loss}"""
@@ -90,14 +82,8 @@ class TrainerVAE(object):
         self._noise(g, eps)
         g.plan_train.run()
         if apply:
-            store = self.session.store
             self.global_step += 1
-            lr_t = ops.adam_lr_t(self.learning_rate, self.global_step)
-            rc = _lib.load().acimg_adam_step(store.flat["train"].data_ptr(), store.grad.data_ptr(),
-                                             store.adam_m.data_ptr(), store.adam_v.data_ptr(), store.train_numel(),
-                                             lr_t, 0.9, 0.999, 1e-8, 1.0, ops.current_stream_handle(self.session.device))
-            _lib.check(rc, "adam_step")
+            self.session.adam_step(self.learning_rate, self.global_step)
         if not sync:
             return g.losses
-        v = g.losses[:5].tolist()
-        return OrderedDict(mse=v[0], huber=v[1], latent=v[2], reg=v[3], loss=v[4])
+        return loss_dict(g.losses)

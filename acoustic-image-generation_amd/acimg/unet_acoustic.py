@@ -11,20 +11,19 @@ encoder_type 'Ac'; with external statistics `record_backward` leaves d loss / d 
 """
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID
-from .params import FusedHeads, Var, up4
-from .session import get_default_session
-from .unet_acresnet import Act
-from .vision import load_state_file
+from .model import Act, ConvModel, xavier
+from .ops import ACT_RELU, ACT_SIGMOID
+from .params import FusedHeads, Var
 
 Z = 150
 
 
-class UNetAcNoConc(object):
+class UNetAcNoConc(ConvModel):
+    # ConvModel's defaults as they stand, unlike UNetAc: a weight gradient is split only where the forward is, every
+    # kernel is re-split by a launch of its own in front of its conv, and nothing runs on a side lane
     WD = 0.0                      # kernel_regularizer=None everywhere (unet_noconc.py:143,163,197)
     EXTERNAL_Z = False
 
@@ -35,7 +34,6 @@ class UNetAcNoConc(object):
         self.height, self.width, self.channels = input_shape or [36, 48, 12]
         self.Z = Z
         self.session = None
-        self._wsplit_bufs = {}
 
     # ---- variables ------------------------------------------------------------------------------------------
     def _conv_specs(self):
@@ -72,45 +70,25 @@ class UNetAcNoConc(object):
     def reg_range(self):
         return 0, 0
 
-    def init_model(self, session, checkpoint_file):
-        state = load_state_file(checkpoint_file)
-        store = (session or self.session).store
-        return store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
     def initialize(self, seed=1242, state=None):
         if state is None:
             g = torch.Generator().manual_seed(seed)
             state = OrderedDict()
-
-            def xav(shape, fin, fout):
-                lim = np.sqrt(6.0 / (fin + fout))
-                return ((torch.rand(*shape, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
-
             for name, (kh, kw, cin, cout) in self._conv_specs().items():
-                state["%s/%s/kernel" % (self.scope, name)] = xav((kh, kw, cin, cout), kh * kw * cin, kh * kw * cout)
+                state["%s/%s/kernel" % (self.scope, name)] = xavier(g, (kh, kw, cin, cout), kh * kw * cin, kh * kw * cout)
                 state["%s/%s/bias" % (self.scope, name)] = torch.zeros(cout)
             for h in ("mean", "std"):
-                state["%s/%s/kernel" % (self.scope, h)] = xav((12, 16, 133, Z), 12 * 16 * 133, 12 * 16 * Z)
+                state["%s/%s/kernel" % (self.scope, h)] = xavier(g, (12, 16, 133, Z), 12 * 16 * 133, 12 * 16 * Z)
                 state["%s/%s/bias" % (self.scope, h)] = torch.zeros(Z)
-            state[self.scope + "/dense/kernel"] = xav((Z, 2304), Z, 2304)
+            state[self.scope + "/dense/kernel"] = xavier(g, (Z, 2304), Z, 2304)
             state[self.scope + "/dense/bias"] = torch.zeros(2304)
-            state[self.scope + "/upsample_1/kernel"] = xav((2, 2, 128, 133), 4 * 133, 4 * 128)
+            state[self.scope + "/upsample_1/kernel"] = xavier(g, (2, 2, 128, 133), 4 * 133, 4 * 128)
             state[self.scope + "/upsample_1/bias"] = torch.zeros(128)
-        self.session.store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
-    def _P(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.p(self.scope + "/" + name))
-
-    def _G(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.g(self.scope + "/" + name))
+        self._load_scope(state)
 
     # ---- graph ------------------------------------------------------------------------------------------------
     def _alloc(self, acoustic_images, mean2=None, std2=None, session=None, eps=None):
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         N = acoustic_images.shape[0]
         H, W = self.height, self.width
         assert tuple(acoustic_images.shape[1:]) == (H, W, 12) and H % 3 == 0 and W % 3 == 0
@@ -152,36 +130,12 @@ class UNetAcNoConc(object):
         self._publish()
 
     def _publish(self):
-        sess, acoustic_images = self.session, self.images
+        acoustic_images = self.images
         self.mean = self.heads_out[:, :Z]
         self.std = self.sigma
         self.output = self.yhat.t
         self.network = OrderedDict(input=acoustic_images, is_training=None, keep_prob=None, features=self.conv2.t)
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/")]
-
-    def _desc(self, x, K, stride=1, y=None, act=ACT_NONE):
-        return ops.conv_desc(x.N, x.H, x.W, x.Cp if x.off == 0 and x.ld == x.Cp else x.C, K, 3, 3, stride, "SAME",
-                             ldx=x.ld, ldy=(y.ld if y is not None else up4(K)), ldw=up4(K), act=act)
-
-    def _use_split(self, d):
-        return (self.precision == "split" and d.stride == 1 and d.C % 32 == 0 and d.K % 32 == 0 and
-                d.N * d.OH * d.OW >= 16384)
-
-    def _wsplit(self, name, nbytes, kind):
-        key = (name, kind)
-        if key not in self._wsplit_bufs:
-            self._wsplit_bufs[key] = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.session.device)
-        return self._wsplit_bufs[key]
-
-    def _conv(self, plan, name, x, y, stride=1, act=ACT_RELU):
-        d = self._desc(x, y.C, stride, y, act)
-        self._descs[name] = (d, x, y)
-        if self._use_split(d):
-            ws = self._wsplit(name, ops.conv2d_split3_weight_bytes(d), "fwd")
-            ops.conv2d_split3_prepare(plan, d, self._P(name + "/kernel"), ws)
-            ops.conv2d_fwd_split3(plan, d, x.ptr, ws, y.ptr, bias=self._P(name + "/bias"))
-        else:
-            ops.conv2d_fwd(plan, d, x.ptr, self._P(name + "/kernel"), self._P(name + "/bias"), y.ptr)
+        self.train_vars = self._scope_vars()
 
     def _record_forward(self, plan):
         self._descs = {}
@@ -234,22 +188,10 @@ class UNetAcNoConc(object):
         z = self.session.zeros
         H, W, h, w = self.height, self.width, self.pool1.H, self.pool1.W
 
-        def gbuf(a):
-            return Act(z(a.N, a.H, a.W, up4(a.C)), a.N, a.H, a.W, a.C)
+        gbuf = self._gbuf
 
         def back(name, gy, dx=None, mask=None):
-            d, x, y = self._descs[name]
-            wg = ops.conv2d_wgrad_split3 if (self._use_split(d) and d.K % 64 == 0) else ops.conv2d_wgrad
-            wg(plan, d, x.ptr, gy.ptr, gy.ld, self._G(name + "/kernel"), self._G(name + "/bias"))
-            if dx is not None and self._use_split(d):
-                wt = self._wsplit(name, ops.conv2d_split3_dgrad_weight_bytes(d), "dgrad")
-                ops.conv2d_split3_prepare_dgrad(plan, d, self._P(name + "/kernel"), wt)
-                ops.conv2d_dgrad_split3(plan, d, gy.ptr, gy.ld, wt, dx.ptr, None, 0,
-                                        mask.ptr if mask is not None else None, mask.ld if mask is not None else 0,
-                                        lddx=dx.ld)
-            elif dx is not None:
-                ops.conv2d_dgrad(plan, d, gy.ptr, gy.ld, self._P(name + "/kernel"), dx.ptr, None, 0,
-                                 mask.ptr if mask is not None else None, mask.ld if mask is not None else 0, lddx=dx.ld)
+            self._conv_back(plan, name, gy, dx, mask)
 
         g_final = Act(g_logit, N, H, W, 12)
         g_conv5, g_c51, g_conv4, g_c41, g_up = (gbuf(self.conv5), gbuf(self.c51), gbuf(self.conv4), gbuf(self.c41),

@@ -13,53 +13,29 @@ concatenated [mean|std] weight; every backward kernel emits the PRE-activation g
 layer below (ReLU mask applied in the data-gradient epilogue from the saved activation), so no
 standalone ReLU / ReLU-grad / concat / slice pass touches HBM.
 """
-import os
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Ptr
-from .params import FusedHeads, Var, up4
-from .session import get_default_session
-from .vision import load_state_file
+from .model import Act, ConvModel, xavier
+from .ops import ACT_RELU, ACT_SIGMOID, Ptr
+from .params import FusedHeads, Var
 
 Z = 150
 
 
-class Act(object):
-    """An NHWC activation: logical channels C inside a buffer with pixel stride ld at channel offset."""
-
-    def __init__(self, t, N, H, W, C, ld=None, off=0):
-        self.t, self.N, self.H, self.W, self.C = t, N, H, W, C
-        self.ld = up4(C) if ld is None else ld
-        self.off = off
-
-    @property
-    def ptr(self):
-        return Ptr(self.t, self.off)
-
-    @property
-    def Cp(self):
-        return up4(self.C)
-
-    @property
-    def pixels(self):
-        return self.N * self.H * self.W
-
-
-class UNetAc(object):
+class UNetAc(ConvModel):
+    # the 12x16 layers run f32 forward (too few rows) but their weight gradients still take the bf16x3 kernel
+    WGRAD_SPLIT_NEEDS_ROWS = False
 
     def __init__(self, input_shape=None, num_frames=12, embedding=False, num_skip=1, precision="split", side_lane=True):
         """precision: "split" = the large convs on the split-MFMA kernels (fp32-class results), "f32" = every
         conv on the exact-f32 MFMA kernel"""
         assert precision in ("split", "f32")
         self.precision = precision
-        self.split_min_rows = 16384      # below this the f32 kernel (64x64 tiles + split-K) fills the chip better
         # backward: weight gradients on the plan's side lane (a second HIP stream), beside the data gradients
         self.side_lane = bool(side_lane)
-        self._wsplit_bufs = {}
         self.scope = 'UNetAcRes'
         self.num_frames = num_frames
         self.height = input_shape[0]
@@ -109,42 +85,29 @@ class UNetAc(object):
         for name in ("layer2/conv_2", "layer2/conv_1", "layer1/pool_2", "layer1/conv_2", "layer1/conv_1"):
             conv(name)
 
-    def init_model(self, session, checkpoint_file):
-        """Initialise every variable of the scope from a TF-named state (models/unet_acresnet.py:33-41)."""
-        state = load_state_file(checkpoint_file)
-        store = (session or self.session).store
-        return store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
     def initialize(self, seed=1239):
         """xavier_initializer() kernels (models/unet_acresnet.py:165,179,216), zero biases"""
         g = torch.Generator().manual_seed(seed)
         state = OrderedDict()
-
-        def xav(shape, fin, fout):
-            lim = np.sqrt(6.0 / (fin + fout))
-            return ((torch.rand(*shape, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
-
         for name, (kh, kw, cin, cout) in self._conv_specs().items():
-            state["%s/%s/kernel" % (self.scope, name)] = xav((kh, kw, cin, cout), kh * kw * cin, kh * kw * cout)
+            state["%s/%s/kernel" % (self.scope, name)] = xavier(g, (kh, kw, cin, cout), kh * kw * cin, kh * kw * cout)
             state["%s/%s/bias" % (self.scope, name)] = torch.zeros(cout)
         heads = ["mean"] + ([] if self.embedding else ["std"])
         for h in heads:
-            state["%s/%s/kernel" % (self.scope, h)] = xav((12, 16, 145, Z), 12 * 16 * 145, 12 * 16 * Z)
+            state["%s/%s/kernel" % (self.scope, h)] = xavier(g, (12, 16, 145, Z), 12 * 16 * 145, 12 * 16 * Z)
             state["%s/%s/bias" % (self.scope, h)] = torch.zeros(Z)
-        state[self.scope + "/dense/kernel"] = xav((Z, 2304), Z, 2304)
+        state[self.scope + "/dense/kernel"] = xavier(g, (Z, 2304), Z, 2304)
         state[self.scope + "/dense/bias"] = torch.zeros(2304)
-        state[self.scope + "/upsample_1/kernel"] = xav((2, 2, 128, 128), 4 * 128, 4 * 128)
+        state[self.scope + "/upsample_1/kernel"] = xavier(g, (2, 2, 128, 128), 4 * 128, 4 * 128)
         state[self.scope + "/upsample_1/bias"] = torch.zeros(128)
-        self.session.store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
+        self._load_scope(state)
 
     # ---- graph ------------------------------------------------------------------------------------------
     def _build_model(self, acoustic_images, resnetfeature, session=None, eps=None):
         """acoustic_images: device buffer [N,36,48,12] (the tiled MFCC map); resnetfeature: device buffer
         [N,12,16,12] (ResNet50Model.output); eps: device buffer [N,150] standing where the reference
         samples tf.random_normal (models/unet_acresnet.py:77)."""
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         N = acoustic_images.shape[0]
         assert tuple(acoustic_images.shape[1:]) == (self.height, self.width, self.channels)
         assert tuple(resnetfeature.shape) == (N, 12, 16, 12)
@@ -206,58 +169,14 @@ class UNetAc(object):
         self.output = self.yhat.t
         self.network = OrderedDict(input=acoustic_images, is_training=None, keep_prob=None,
                                    features=self.cat145[..., :145])
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/")]
-
-    # weight / grad pointers (resolved once the flat buffers exist)
-    def _P(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.p(self.scope + "/" + name))
-
-    def _G(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.g(self.scope + "/" + name))
-
-    def _desc(self, x, K, stride=1, y=None, act=ACT_NONE):
-        return ops.conv_desc(x.N, x.H, x.W, x.Cp if x.off == 0 and x.ld == x.Cp else x.C, K, 3, 3, stride, "SAME",
-                             ldx=x.ld, ldy=(y.ld if y is not None else up4(K)), ldw=up4(K), act=act)
-
-    def _use_split(self, d):
-        """big stride-1 convs of the generator run on the split-MFMA kernels (forward f16x3, data gradient
-        bf16x3); the 12x16 layers (48 row tiles: they need split-K) and the 12/133-channel layers stay f32"""
-        return (self.precision == "split" and d.stride == 1 and d.C % 32 == 0 and d.K % 32 == 0 and
-                d.N * d.OH * d.OW >= self.split_min_rows)
-
-    def _wsplit(self, name, nbytes, kind):
-        key = (name, kind)
-        if key not in self._wsplit_bufs:
-            self._wsplit_bufs[key] = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.session.device)
-        return self._wsplit_bufs[key]
-
-    def _prepare_job(self, plan, d, name, image, mode):
-        """the kernels change every step: ONE launch at the head of the forward plan re-splits them all (forward
-        images and, once the backward is recorded, the flipped / transposed data-gradient images)"""
-        if getattr(self, "_prep_jobs", None) is None:
-            # a plan other than the forward one (should not happen): fall back to a launch in place
-            (ops.conv2d_split3_prepare_dgrad if mode else ops.conv2d_split3_prepare)(plan, d, self._P(name + "/kernel"),
-                                                                                      image)
-            return
-        self._prep_jobs.add(d, self._P(name + "/kernel"), image, mode)
-
-    def _conv(self, plan, name, x, y, stride=1, act=ACT_RELU):
-        d = self._desc(x, y.C, stride, y, act)
-        self._descs[name] = (d, x, y)
-        if self._use_split(d):
-            # the kernel changes every step: re-split it right before use (one tiny launch)
-            ws = self._wsplit(name, ops.conv2d_split3_weight_bytes(d), "fwd")
-            self._prepare_job(plan, d, name, ws, 0)
-            ops.conv2d_fwd_split3(plan, d, x.ptr, ws, y.ptr, bias=self._P(name + "/bias"))
-        else:
-            ops.conv2d_fwd(plan, d, x.ptr, self._P(name + "/kernel"), self._P(name + "/bias"), y.ptr)
+        self.train_vars = self._scope_vars()
 
     def _record_forward(self, plan):
         N = self.N
         self._descs = {}
         h, w = self.pool1.H, self.pool1.W
+        # ONE launch at the head of the forward plan re-splits every kernel (the forward images and, once the backward is
+        # recorded, the flipped / transposed data-gradient images); without it (f32) `_prepare_job` launches in place
         self._prep_jobs = None
         if self.precision == "split":
             self._prep_jobs = ops.PrepareJobs()
@@ -310,34 +229,10 @@ class UNetAc(object):
         H, W, h, w = self.height, self.width, self.pool1.H, self.pool1.W
         ns = self.num_skip
 
-        def gbuf(a, full=False):
-            return Act(z(a.N, a.H, a.W, up4(a.C)), a.N, a.H, a.W, a.C)
+        gbuf = self._gbuf
 
         def back(name, gy, dx=None, mask=None, res=None):
-            """weight/bias gradient of conv `name`, and its data gradient into dx (if given)"""
-            d, x, y = self._descs[name]
-            wg = ops.conv2d_wgrad_split3 if (self.precision == "split" and d.K % 64 == 0) else ops.conv2d_wgrad
-            # the weight gradients run on the side lane (a second stream, in layer order) beside the chain of data
-            # gradients on the main stream: a weight gradient only needs its layer's gy (fork = the side lane waits
-            # for it), every gradient buffer is written once, before the fork that publishes it, and nothing on the
-            # main stream waits for a weight gradient until a consumer of the parameter gradients joins
-            beside = dx is not None and self.side_lane
-            if beside:
-                plan.fork()
-            wg(plan, d, x.ptr, gy.ptr, gy.ld, self._G(name + "/kernel"), self._G(name + "/bias"), side=beside)
-            if dx is not None and self._use_split(d):
-                wt = self._wsplit(name, ops.conv2d_split3_dgrad_weight_bytes(d), "dgrad")
-                self._prepare_job(plan, d, name, wt, 1)
-                ops.conv2d_dgrad_split3(plan, d, gy.ptr, gy.ld, wt, dx.ptr,
-                                        res.ptr if res is not None else None, res.ld if res is not None else 0,
-                                        mask.ptr if mask is not None else None, mask.ld if mask is not None else 0,
-                                        lddx=dx.ld)
-            elif dx is not None:
-                ops.conv2d_dgrad(plan, d, gy.ptr, gy.ld, self._P(name + "/kernel"), dx.ptr,
-                                 res.ptr if res is not None else None, res.ld if res is not None else 0,
-                                 mask.ptr if mask is not None else None, mask.ld if mask is not None else 0,
-                                 lddx=dx.ld)
-            on_ready(name)
+            self._conv_back(plan, name, gy, dx, mask, res, on_ready)
 
         g_final = Act(g_logit, N, H, W, 12)
         g_conv7, g_c71, g_conv6, g_c61 = gbuf(self.conv7), gbuf(self.c71), gbuf(self.conv6), gbuf(self.c61)

@@ -18,10 +18,9 @@ from collections import OrderedDict
 
 from . import ops
 from .ops import ACT_RELU, ACT_SIGMOID
+from .model import Act, ptr_ld
 from .params import up4
-from .session import get_default_session
 from .unet_acoustic import UNetAcNoConc
-from .unet_acresnet import Act
 from .unet_vae import UNetVAE
 
 HEAD = (12, 16)
@@ -98,9 +97,7 @@ class _SplitBN(UNetVAE):
 
     # ---- encoder --------------------------------------------------------------------------------------------
     def _build_network(self, images, session=None, eps=None, training=True):
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         N = images.shape[0]
         H, W = self.height, self.width
         assert tuple(images.shape[1:]) == (H, W, self.channels)
@@ -191,8 +188,7 @@ class _SplitBN(UNetVAE):
         self.mean, self.std = self.ext[:, :Zn], self.ext[:, Zn:]
         self.output = self.yhat.t
         self.network = OrderedDict(input=self.images, is_training=None, keep_prob=None, features=self.conv5.t)
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/") and
-                           not n.endswith(("moving_mean", "moving_variance"))]
+        self.train_vars = self._scope_vars(skip=("moving_mean", "moving_variance"))
 
     def record_backward(self, plan, g_logit, kl_weight):
         """g_logit: gradient w.r.t. the pre-sigmoid output [N,H,W,up4(cout)]; kl_weight: d loss / d kl[n].  Leaves
@@ -219,8 +215,7 @@ class _SplitBN(UNetVAE):
                              self._G("upsample_%s/bias" % name))
             g_src = gbuf(src)
             mask = src if src is self.c2d else None       # conv2d has a plain ReLU; BN layers mask inside bn_bwd
-            ops.deconv_dgrad(plan, d, g.ptr, g.ld, self._P("upsample_%s/kernel" % name), g_src.ptr,
-                             mask.ptr if mask is not None else None, mask.ld if mask is not None else 0)
+            ops.deconv_dgrad(plan, d, g.ptr, g.ld, self._P("upsample_%s/kernel" % name), g_src.ptr, *ptr_ld(mask))
             g = g_src
         g_dns = gbuf(self.dns)
         ops.conv2d_wgrad(plan, self.d_c2d, self.dns.ptr, g.ptr, g.ld, self._G("conv2d/kernel"), self._G("conv2d/bias"))

@@ -16,15 +16,12 @@ overlapping transposed convs use the zero-insertion forms of acimg_conv2d_dgrad 
 """
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import ops
+from .model import Act, ConvModel, ptr_ld, xavier
 from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID
 from .params import FusedHeads, Var, up4
-from .session import get_default_session
-from .unet_acresnet import Act
-from .vision import load_state_file
 
 BN_MOMENTUM, BN_EPS = 0.99, 1e-3   # tf.layers.batch_normalization defaults
 
@@ -43,7 +40,10 @@ class _CBR(object):
         return v
 
 
-class UNetVAE(object):
+class UNetVAE(ConvModel):
+    SPLIT_PRECISIONS = ("split", "bf16")     # bf16: the same layers, on the one-MFMA-per-product kernels
+    PREP_JOBS_CAP = 16                       # a prepare_multi launch takes 16 jobs; later layers re-split in place
+    _prep_fwd = _prep_bwd = None             # the two batched launches of `_begin_prepares` (None: every re-split in place)
     SCOPE = None
     CIN = None
     WD = None
@@ -73,18 +73,13 @@ class UNetVAE(object):
         self.height, self.width, self.channels = input_shape
         assert self.channels == self.CIN
         self.session = None
-        self._wsplit_bufs = {}
-
-    def _use_split(self, d):
-        return (self.precision in ("split", "bf16") and d.stride == 1 and d.C % 32 == 0 and d.K % 32 == 0 and
-                d.N * d.OH * d.OW >= 16384)
 
     def _begin_prepares(self, plan):
         """the kernels change every step: TWO launches at the head of the forward plan re-split them all (16 jobs each at most:
         the forward images, and - added while the backward is recorded - the flipped / transposed data-gradient images)
         instead of one ~5 us launch in front of every conv"""
         self._prep_fwd = self._prep_bwd = None
-        if self.precision in ("split", "bf16"):
+        if self.precision in self.SPLIT_PRECISIONS:
             self._prep_fwd, self._prep_bwd = ops.PrepareJobs(), ops.PrepareJobs()
             ops.conv2d_split3_prepare_multi(plan, self._prep_fwd)
             ops.conv2d_split3_prepare_multi(plan, self._prep_bwd)
@@ -100,12 +95,6 @@ class UNetVAE(object):
             return False
         d = ops.conv_desc(N, h, w, up4(cin), K, 3, 3, 1, "SAME", ldx=up4(cin), ldy=up4(K), ldw=up4(K), act=ACT_NONE)
         return ops.conv2d_affine_input_ok(d, self._prec(d))
-
-    def _wsplit(self, name, nbytes, kind):
-        key = (name, kind)
-        if key not in self._wsplit_bufs:
-            self._wsplit_bufs[key] = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.session.device)
-        return self._wsplit_bufs[key]
 
     # ---- variables --------------------------------------------------------------------------------------
     def _layer_table(self):
@@ -170,27 +159,16 @@ class UNetVAE(object):
         a, b = self._reg_range
         return a.offset, b.offset + b.numel - a.offset
 
-    def init_model(self, session, checkpoint_file):
-        """models/unet_architecture.py:31-44: restore every model variable of the scope from a TF-named state"""
-        state = load_state_file(checkpoint_file)
-        store = (session or self.session).store
-        return store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
     def initialize(self, seed=1240, state=None):
         """xavier_initializer() / Glorot-uniform kernels, zero biases, gamma 1, beta 0, moving mean 0 / variance 1"""
         if state is None:
             g = torch.Generator().manual_seed(seed)
             state = OrderedDict()
             s = self.scope
-
-            def xav(shape, fin, fout):
-                lim = np.sqrt(6.0 / (fin + fout))
-                return ((torch.rand(*shape, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
-
             for kind, name, bn, shape in self._layer_table():
                 if kind == "cbr":
                     kh, kw, cin, cout = shape
-                    state["%s/%s/kernel" % (s, name)] = xav(shape, kh * kw * cin, kh * kw * cout)
+                    state["%s/%s/kernel" % (s, name)] = xavier(g, shape, kh * kw * cin, kh * kw * cout)
                     state["%s/%s/bias" % (s, name)] = torch.zeros(cout)
                     state["%s/%s/gamma" % (s, bn)] = torch.ones(cout)
                     state["%s/%s/beta" % (s, bn)] = torch.zeros(cout)
@@ -199,37 +177,26 @@ class UNetVAE(object):
                 elif kind == "heads":
                     kh, kw, cin, cout = shape
                     for h in self.HEAD_NAMES:
-                        state["%s/%s/kernel" % (s, h)] = xav(shape, kh * kw * cin, kh * kw * cout)
+                        state["%s/%s/kernel" % (s, h)] = xavier(g, shape, kh * kw * cin, kh * kw * cout)
                         state["%s/%s/bias" % (s, h)] = torch.zeros(cout)
                 elif kind == "dense":
-                    state[s + "/dense/kernel"] = xav(shape, shape[0], shape[1])
+                    state[s + "/dense/kernel"] = xavier(g, shape, shape[0], shape[1])
                     state[s + "/dense/bias"] = torch.zeros(shape[1])
                 elif kind == "deconv":
                     kh, kw, cout, cin = shape
-                    state["%s/%s/kernel" % (s, name)] = xav(shape, kh * kw * cin, kh * kw * cout)
+                    state["%s/%s/kernel" % (s, name)] = xavier(g, shape, kh * kw * cin, kh * kw * cout)
                     state["%s/%s/bias" % (s, name)] = torch.zeros(cout)
                 else:
                     kh, kw, cin, cout = shape
-                    state["%s/%s/kernel" % (s, name)] = xav(shape, kh * kw * cin, kh * kw * cout)
+                    state["%s/%s/kernel" % (s, name)] = xavier(g, shape, kh * kw * cin, kh * kw * cout)
                     state["%s/%s/bias" % (s, name)] = torch.zeros(cout)
-        self.session.store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
-
-    # ---- pointers ---------------------------------------------------------------------------------------
-    def _P(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.p(self.scope + "/" + name))
-
-    def _G(self, name):
-        st = self.session.store
-        return ops.LazyPtr(lambda: st.g(self.scope + "/" + name))
+        self._load_scope(state)
 
     # ---- graph ------------------------------------------------------------------------------------------
     def _build_model(self, images, session=None, eps=None, training=True):
         """images: device buffer [N,H,W,cin]; eps: device buffer [N,Z] standing where the reference samples
         tf.random_normal (models/unet_architecture.py:66)."""
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         N = images.shape[0]
         assert tuple(images.shape[1:]) == (self.height, self.width, self.channels)
         self.N = N
@@ -268,8 +235,7 @@ class UNetVAE(object):
         self.std = self.variance            # trainer/trainer.py:61 reads `model.std`
         self.output = self.yhat.t
         self.network = OrderedDict(input=images, is_training=None, keep_prob=None, features=self.conv5.t)
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/") and
-                           not n.endswith(("moving_mean", "moving_variance"))]
+        self.train_vars = self._scope_vars(skip=("moving_mean", "moving_variance"))
 
     def _cbr(self, plan, name, bn, x, K, R, S, stride, padding, out, defer=False):
         """conv + bias -> raw (+ BN statistics) ; bn_finalize ; out = relu(raw*scale + shift).
@@ -280,8 +246,7 @@ class UNetVAE(object):
         L.name, L.bn, L.x, L.y = name, bn, x, out
         aff = getattr(x, "affine", None)
         in_scale, in_shift = aff if aff is not None else (None, None)
-        L.d = ops.conv_desc(x.N, x.H, x.W, x.Cp if x.off == 0 and x.ld == x.Cp else x.C, K, R, S, stride, padding,
-                            ldx=x.ld, ldy=up4(K), ldw=up4(K), act=ACT_NONE)
+        L.d = self._desc(x, K, stride, None, ACT_NONE, R, S, padding)
         assert (L.d.OH, L.d.OW) == (out.H, out.W), (name, L.d.OH, L.d.OW, out.H, out.W)
         L.raw = Act(z(x.N, out.H, out.W, up4(K)), x.N, out.H, out.W, K)
         kp = up4(K)
@@ -292,11 +257,7 @@ class UNetVAE(object):
             L.rows = ops.conv2d_fwd_split3_stats_rows(L.d)
             L.stats = z(L.rows, 2, kp)
             ws = self._wsplit(name, ops.conv2d_split3_weight_bytes(L.d), "fwd")
-            jobs = getattr(self, "_prep_fwd", None)
-            if jobs is not None and len(jobs.jobs) < 16:
-                jobs.add(L.d, self._P(name + "/kernel"), ws, 2 if self._bf16 else 0)
-            else:
-                ops.conv2d_split3_prepare(plan, L.d, self._P(name + "/kernel"), ws, bf16=self._bf16)
+            self._prepare_job(plan, L.d, name, ws, 2 if self._bf16 else 0, self._prep_fwd)
             ops.conv2d_fwd_split3(plan, L.d, x.ptr, ws, L.raw.ptr, in_scale=in_scale, in_shift=in_shift,
                                   in_relu=1 if aff is not None else 0, stats=L.stats if self.training else None,
                                   bias=self._P(name + "/bias"), bf16=self._bf16)
@@ -418,10 +379,6 @@ class UNetVAE(object):
         ops.conv2d_fwd(plan, self.d_final, net.ptr, self._P("final/kernel"), self._P("final/bias"), self.yhat.ptr)
 
     # ---- backward ---------------------------------------------------------------------------------------
-    def _gbuf(self, a):
-        z = self.session.zeros
-        return Act(z(a.N, a.H, a.W, up4(a.C)), a.N, a.H, a.W, a.C)
-
     def _cbr_back(self, plan, name, gy, dx, res=None):
         """gy: gradient w.r.t. the layer's ReLU output (overwritten with the pre-BN gradient);
         dx: where the gradient w.r.t. the layer's input goes (None for the first layer)"""
@@ -439,21 +396,8 @@ class UNetVAE(object):
                                     self._G(name + "/bias"), bf16=self._bf16)
         else:
             ops.conv2d_wgrad(plan, L.d, L.x.ptr, gy.ptr, gy.ld, self._G(name + "/kernel"), self._G(name + "/bias"))
-        if dx is not None and self._use_split(L.d):
-            wt = self._wsplit(name, ops.conv2d_split3_dgrad_weight_bytes(L.d), "dgrad")
-            jobs = getattr(self, "_prep_bwd", None)
-            if jobs is not None and len(jobs.jobs) < 16:
-                jobs.add(L.d, self._P(name + "/kernel"), wt, 1)
-            else:
-                ops.conv2d_split3_prepare_dgrad(plan, L.d, self._P(name + "/kernel"), wt)
-            ops.conv2d_dgrad_split3(plan, L.d, gy.ptr, gy.ld, wt, dx.ptr,
-                                    res.ptr if res is not None else None, res.ld if res is not None else 0,
-                                    None, 0, lddx=dx.ld, bf16=self._bf16)
-        elif dx is not None:
-            ops.conv2d_dgrad(plan, L.d, gy.ptr, gy.ld, self._P(name + "/kernel"), dx.ptr,
-                             res.ptr if res is not None else None, res.ld if res is not None else 0,
-                             None, 0, lddx=dx.ld)
-
+        if dx is not None:
+            self._dgrad(plan, L.d, name, gy, dx, None, res, self._prep_bwd, self._bf16)
 
     def record_backward(self, plan, g_logit, kl_weight):
         """g_logit: gradient w.r.t. the PRE-sigmoid output [N,H,W,up4(cout)] (from recon_loss);
@@ -489,8 +433,7 @@ class UNetVAE(object):
                              self._G("upsample_%s/bias" % name))
             g = gbuf(src)
             mask = src if src is self.c2d else None       # conv2d has a plain ReLU; BN layers mask inside bn_bwd
-            ops.deconv_dgrad(plan, d, g_up.ptr, g_up.ld, self._P("upsample_%s/kernel" % name), g.ptr,
-                             mask.ptr if mask is not None else None, mask.ld if mask is not None else 0)
+            ops.deconv_dgrad(plan, d, g_up.ptr, g_up.ld, self._P("upsample_%s/kernel" % name), g.ptr, *ptr_ld(mask))
         # conv2d 1 -> 128 (3x3, ReLU): g is already its pre-activation gradient
         g_dns = gbuf(self.dns)
         ops.conv2d_wgrad(plan, self.d_c2d, self.dns.ptr, g.ptr, g.ld, self._G("conv2d/kernel"), self._G("conv2d/bias"))
@@ -577,9 +520,7 @@ class AssociatorAudio(UNetVAE):
 
     def _build_model(self, inputs, session=None, training=True):
         """inputs: device buffer [N,193,257,1] (the STFT-magnitude spectrogram)"""
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         N = inputs.shape[0]
         assert tuple(inputs.shape[1:]) == (self.height, self.width, self.channels)
         self.N, self.training = N, training
@@ -605,8 +546,7 @@ class AssociatorAudio(UNetVAE):
         self.plan_fwd = p
         self.mean, self.std = self.ext[:, :Zn], self.ext[:, Zn:]
         self.network = OrderedDict(input=inputs, is_training=None, keep_prob=None, features=self.conv5.t)
-        self.train_vars = [n for n in sess.store.tf_names() if n.startswith(self.scope + "/") and
-                           not n.endswith(("moving_mean", "moving_variance"))]
+        self.train_vars = self._scope_vars(skip=("moving_mean", "moving_variance"))
 
     def record_backward(self, plan, g_ext):
         """g_ext [N, 300]: d loss / d [mean | std] (e.g. `UNetAcZ.g_ext`)"""

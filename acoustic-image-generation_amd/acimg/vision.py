@@ -17,15 +17,14 @@ statistics of round 4): BN + shortcut + ReLU + split then run in the conv's own 
 Activations live in a few reusable arenas (about 1.2 GB at batch 32), so consecutive layers hit the 256 MiB Infinity
 Cache instead of streaming 6.5 GB of distinct tensors.
 """
-import os
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import ops
+from .model import Model, flat_ptr, load_state_file  # noqa: F401  (load_state_file: imported from here by callers)
 from .params import Var, up4
-from .session import get_default_session
 
 BLOCKS = (("block1", 64, 3, 1), ("block2", 128, 4, 2), ("block3", 256, 6, 2), ("block4", 512, 3, 1))
 WEIGHT_DECAY = 5e-4   # resnet_arg_scope(weight_decay=5e-4), models/vision.py:54
@@ -34,7 +33,7 @@ BN_EPS = 1e-5
 PLANE_SLACK = 2 * 15 * 2048 * 2 + 512   # a split-format plane ends on a whole 16-pixel brick: <= 15 pixels more, twice
 
 
-class ResNet50Model(object):
+class ResNet50Model(Model):
 
     def __init__(self, input_shape=None, num_classes=None, precision="f16x3", stages=None, stage_cut=8, side_lane=True,
                  two_pass=True, two_pass_max_cin=256, gram=True):
@@ -152,14 +151,12 @@ class ResNet50Model(object):
             state[scope + "/BatchNorm/beta"] = torch.zeros(cout)
             state[scope + "/BatchNorm/moving_mean"] = torch.zeros(cout)
             state[scope + "/BatchNorm/moving_variance"] = torch.ones(cout)
-        self.session.store.load_state(state, strict=False, only=lambda n: n.startswith(self.scope + "/"))
+        self._load_scope(state)
 
     def _build_model(self, visual_images, session=None):
         """visual_images: device buffer [N,224,298,3] float32 (the feed target).  Records the forward
         plans (training / inference BN mode) and the conv_map backward plan."""
-        sess = session or get_default_session()
-        self.session = sess
-        self._register(sess.store)
+        sess = self._attach(session)
         N = visual_images.shape[0]
         assert tuple(visual_images.shape[1:]) == (self.height, self.width, self.channels)
         self.N = N
@@ -693,28 +690,13 @@ class ResNet50Model(object):
             self._trunk_ss_version = -1
             self._plan_reg = self.session.new_plan()
             ops.zero(self._plan_reg, self._trunk_ss)
-            ops.sumsq(self._plan_reg, ops.LazyPtr(lambda: st.flat["trunkw"]), st._sizes["trunkw"], self._trunk_ss)
+            ops.sumsq(self._plan_reg, flat_ptr(st, "trunkw"), st._sizes["trunkw"], self._trunk_ss)
         plan.add_hook(self._refresh_trunk_sumsq)
         ops.axpy(plan, 1.0, self._trunk_ss, accum, 1)
-        ops.sumsq(plan, ops.LazyPtr(lambda: st.p(self.scope + "/conv_map/weights")), 3 * 4 * 2048 * 12, accum)
+        ops.sumsq(plan, self._P("conv_map/weights"), 3 * 4 * 2048 * 12, accum)
 
     def _refresh_trunk_sumsq(self):
         st = self.session.store
         if self._trunk_ss_version != st.version:
             self._plan_reg.run()
             self._trunk_ss_version = st.version
-
-
-def load_state_file(f):
-    """{TF variable name: array}: a dict, a TensorFlow checkpoint prefix, an .npz, or a torch-saved dict (possibly
-    under 'model')."""
-    if isinstance(f, dict):
-        return f.get("model", f)
-    if os.path.exists(str(f) + ".index"):
-        # a TensorFlow Saver-V2 bundle prefix (the reference's own checkpoints: trainer/mfcctrainer.py:214-247)
-        from . import tfio
-        return tfio.read_checkpoint(str(f))
-    if str(f).endswith(".npz"):
-        return dict(np.load(f))
-    obj = torch.load(f, map_location="cpu", weights_only=False)
-    return obj.get("model", obj) if isinstance(obj, dict) else obj
