@@ -784,6 +784,50 @@ static void launch_cfg(const IgemmParams& p, bool nt, bool cal, dim3 grid, hipSt
     }
 }
 
+// 16-byte epilogue accesses: every operand the epilogue touches allows them
+static void epi_vec_flag(EpiParams& e) {
+    e.vec = aligned16(e.Y) && (e.ldy & 3) == 0 && (!e.bias || aligned16(e.bias)) &&
+            (!e.res || (aligned16(e.res) && (e.ldres & 3) == 0)) &&
+            (!e.mask || (aligned16(e.mask) && (e.ldmask & 3) == 0)) && (!e.scatter || (e.Ko & 3) == 0);
+}
+
+// ---- descriptor -> implicit-GEMM views: the geometry fields of IgemmParams; operands, row runs and epilogue extras are the
+// caller's ----
+// forward conv: rows = output pixels, K = (tap, input channel), columns = output channels
+static IgemmParams fwd_view(const AcimgConvDesc* d) {
+    IgemmParams p{};
+    p.H = d->H; p.W = d->W; p.C = d->C; p.lda = d->ldx;
+    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride;
+    p.pad_t = d->pad_t; p.pad_l = d->pad_l;
+    p.M = d->N * d->OH * d->OW;
+    p.Nld = d->ldw; p.Ngemm = d->K;
+    p.e.ldy = d->ldy; p.e.M = p.M; p.e.Nstore = d->K; p.e.act = d->act; p.e.stats_ld = d->ldw;
+    return p;
+}
+// data gradient of a stride-1 conv: a forward conv of gy (ca channels, pixel stride ldgy) with the flipped kernel,
+//   dx[h,w,c] = sum_{r',s',k} gy[h-(R-1-pt)+r', w-(S-1-pl)+s', k] * W[R-1-r'][S-1-s'][c][k]
+// (gy: [N][GH][GW] pixels of ca channels; dx: [N][H][W] pixels of `cols` channels; pad_t / pad_l: the conv's own padding)
+static IgemmParams flipped_view(int N, int GH, int GW, int ca, int ldgy, int H, int W, int R, int S, int pad_t, int pad_l,
+                                int cols) {
+    IgemmParams p{};
+    p.H = GH; p.W = GW; p.C = ca; p.lda = ldgy;
+    p.OH = H; p.OW = W; p.R = R; p.S = S; p.stride = 1;
+    p.pad_t = R - 1 - pad_t; p.pad_l = S - 1 - pad_l;
+    p.M = N * H * W;
+    p.Ngemm = cols;
+    p.e.M = p.M; p.e.Nstore = cols; p.e.act = ACIMG_ACT_NONE;
+    return p;
+}
+static IgemmParams flipped_view(const AcimgConvDesc* d, int ca, int ldgy) {
+    return flipped_view(d->N, d->OH, d->OW, ca, ldgy, d->H, d->W, d->R, d->S, d->pad_t, d->pad_l, d->C);
+}
+// the 16-bit MFMA kernels walk K as (tap, 32-channel chunk) in one pass
+static void split_ksteps(IgemmParams& p) {
+    p.ntaps = p.R * p.S;
+    p.kiters = p.ntaps * (p.C / 32);
+    p.splits = 1;
+}
+
 // tickets: ACIMG_TICKET_WORDS zeroed ints owned by the caller (or nullptr: split-K combines through a reduce launch)
 static int launch_igemm(IgemmParams p, bool nt, void* ws, size_t ws_bytes, void* tickets, hipStream_t st) {
     if (p.M <= 0 || p.Ngemm <= 0) return fail(ACIMG_EINVAL, "igemm: empty problem");
@@ -806,9 +850,7 @@ static int launch_igemm(IgemmParams p, bool nt, void* ws, size_t ws_bytes, void*
     p.a_bytes = (unsigned)a_bytes;
     p.b_bytes = (unsigned)b_bytes;
     EpiParams& e = p.e;
-    e.vec = aligned16(e.Y) && (e.ldy & 3) == 0 && (!e.bias || aligned16(e.bias)) &&
-            (!e.res || (aligned16(e.res) && (e.ldres & 3) == 0)) &&
-            (!e.mask || (aligned16(e.mask) && (e.ldmask & 3) == 0)) && (!e.scatter || (e.Ko & 3) == 0);
+    epi_vec_flag(e);
     TileCfg c = pick_cfg(p.M, p.Ngemm);
     p.splits = pick_splits(p.M, p.Ngemm, c, p.kiters);
     float* stats_after = nullptr;  // split-K + BN statistics: a small pass over y afterwards
@@ -882,13 +924,18 @@ static void wgrad_tile(int Ngemm, int& bmo, int& bn) {
 static int wgrad_split3_bn(int Ngemm) {      // column tile of the split-MFMA weight-gradient kernel
     return Ngemm > 64 ? 128 : (Ngemm > 32 ? 64 : 32);   // (64-column tiles for 144 columns: measured equal / slower)
 }
+// the part of wgrad_halo16_ok (below, with its kernel) that the sizing query knows: 3x3 taps of at most 64 channels into at
+// most 32 columns, from 65536 pixels on
+static bool wgrad_halo16_shape(long M, int KK, int Ngemm) { return Ngemm <= 32 && KK % 9 == 0 && KK <= 9 * 64 && M >= 65536; }
 static size_t wgrad_ws_bytes(int M, int KK, int Ngemm, int ldo) {
     // one sizing query serves acimg_conv2d_wgrad and acimg_conv2d_wgrad_split3 / _bf16: the larger of their slab counts
     int bmo, bn;
     wgrad_tile(Ngemm, bmo, bn);
     int s = std::max(pick_wgrad_splits(M, KK, Ngemm, bmo, bn), pick_wgrad_splits(M, KK, Ngemm, bmo, wgrad_split3_bn(Ngemm)));
     // the halo form of the 3x3 32- / 64-channel -> 32-column layers (wgrad_halo16_kernel) leaves one slab per CU
-    if (Ngemm <= 32 && KK % 9 == 0 && KK <= 9 * 64 && M >= 65536 && s < (KK <= 9 * 16 ? 512 : 256)) s = KK <= 9 * 16 ? 512 : 256;
+    if (wgrad_halo16_shape(M, KK, Ngemm) && s < (KK <= 9 * 16 ? 512 : 256)) s = KK <= 9 * 16 ? 512 : 256;
+    // (s + 1: one slab more than any launch below asks for - each needs splits x (KK + 1) rows, bias row included.  The guard-
+    // band tests of every workspace pass without it; it stays because callers size their buffers by this answer)
     return s > 1 ? (size_t)(s + 1) * ((size_t)KK + 1) * ldo * sizeof(float) : 0;
 }
 
@@ -1325,9 +1372,9 @@ __global__ __launch_bounds__(512, C == 16 ? 4 : 1) void wgrad_halo16_kernel(cons
 // 32 x 32 channel tile: 224x298 16->8 189 -> ~60 us against the exact-f32 halo kernel (round 4)
 static bool wgrad_halo16_ok(const WgradParams& p, bool split3) {
     const bool few = p.C < 32;
-    return (split3 || few) && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 &&
-           (p.C == 64 || (p.C <= 32 && p.C % 4 == 0)) && p.Ngemm <= 32 && p.Ngemm % 4 == 0 && p.Nld == p.Ngemm && p.OH == p.H &&
-           p.OW == p.W && p.ldo >= p.Ngemm && (long)p.M >= 65536 && g_cfg.wgrad_halo;
+    return wgrad_halo16_shape(p.M, p.KK, p.Ngemm) && (split3 || few) && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad_t == 1 &&
+           p.pad_l == 1 && (p.C == 64 || (p.C <= 32 && p.C % 4 == 0)) && p.Ngemm % 4 == 0 && p.Nld == p.Ngemm && p.OH == p.H &&
+           p.OW == p.W && p.ldo >= p.Ngemm && g_cfg.wgrad_halo;
 }
 
 static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t st,
@@ -1514,19 +1561,12 @@ static int check_desc(const AcimgConvDesc* d, const char* who, bool row_run = fa
 }
 static inline int up4(int v) { return (v + 3) & ~3; }
 
-}  // namespace acimg
-
-using namespace acimg;
-
-// ==========================================================================================
-// C ABI
-// ==========================================================================================
-extern "C" {
-
-// few-channel direct path: C <= 16 (wider pixels stop coalescing across lanes), K <= 32 and a multiple of 8
+// few-channel direct path: C <= 16 (wider pixels stop coalescing across lanes), K <= 32 and a multiple of 8.
+// direct_shape is what the sizing queries know (the few-channel MFMA form's shapes lie inside it); direct_ok adds the operands
+static bool direct_shape(int C, int K) { return C <= 16 && K <= 32; }
 static bool direct_ok(int C, int K, int ldy, int ldres, const float* y, const float* bias, const float* res,
                       bool affine, const float* mask) {
-    return !affine && !mask && C <= 16 && K <= 32 && ldy >= ((K + 3) & ~3) && (C & 3) == 0 && (ldy & 3) == 0 &&
+    return !affine && !mask && direct_shape(C, K) && ldy >= ((K + 3) & ~3) && (C & 3) == 0 && (ldy & 3) == 0 &&
            (!res || ((ldres & 3) == 0 && aligned16(res))) && aligned16(y) && (!bias || aligned16(bias));
 }
 static size_t direct_ws_bytes(int R, int S, int C, int K) { return ((size_t)R * S * C * K * sizeof(float) + 255) & ~(size_t)255; }
@@ -1550,7 +1590,6 @@ static int launch_direct(const DirectParams& q, void* ws, size_t ws_bytes, hipSt
     return check_launch("direct_conv");
 }
 
-extern "C++" {
 // ------------------------------------------------------------------------------------------
 // MFMA form of the FEW-CHANNEL 3x3 / stride-1 / SAME layers (8 or 16 channels in, up to 32 out: the full-resolution
 // layers of the RGB / spectrogram U-Nets; round 4).  The direct kernel above does these with packed fp32 FMAs at ~2x its
@@ -1821,9 +1860,7 @@ static int dispatch_few16(const FewParams& q, int N, int cin, int nout, void* ws
     if (cin == 8) return nout <= 16 ? launch_few16<TR, 8, 16, MODE>(q, N, ws, st) : launch_few16<TR, 8, 32, MODE>(q, N, ws, st);
     return launch_few16<TR, 16, 16, MODE>(q, N, ws, st);
 }
-}  // extern "C++"
 
-extern "C++" {
 // ------------------------------------------------------------------------------------------
 // 2x2 / stride-2 transposed conv with 32 input and 8 output channels (models/unet_architecture.py upsample_9 at 112x149 ->
 // 224x298; round 4): patches do not overlap, so per INPUT pixel it is one 32 x 32 product - y'[(tap, k)] = W[(tap, k)][c] x[c],
@@ -2041,7 +2078,6 @@ static int launch_patch2(const Patch2Params& q, hipStream_t st) {
     hipLaunchKernelGGL((patch2_32x8_kernel<TR, MODE>), dim3((unsigned)blocks), dim3(256), 0, st, q);
     return check_launch("patch2_32x8");
 }
-}  // extern "C++"
 
 static int fwd_kiters(const AcimgConvDesc* d) {
     const bool rowrun = d->S > 1 && d->ldx == d->C;
@@ -2055,49 +2091,6 @@ static int stats_block_rows(const AcimgConvDesc* d) {
     TileCfg c = pick_cfg(M, d->K);
     return pick_splits(M, d->K, c, fwd_kiters(d)) > 1 ? 256 : c.bm;
 }
-int acimg_conv2d_stats_rows(const AcimgConvDesc* d) {
-    if (few16_fwd_shape(d)) return FEW16_WGS;        // the few-channel MFMA kernel leaves one row per workgroup
-    return cdiv((long)d->N * d->OH * d->OW, stats_block_rows(d));
-}
-
-int acimg_conv2d_fwd_tiling(const AcimgConvDesc* d, int* out) {
-    if (!d || !out) return fail(ACIMG_EINVAL, "conv2d_fwd_tiling: null argument");
-    const int M = d->N * d->OH * d->OW;
-    TileCfg c = pick_cfg(M, d->K);
-    out[0] = c.bm;
-    out[1] = c.bn;
-    out[2] = pick_splits(M, d->K, c, fwd_kiters(d));
-    return ACIMG_OK;
-}
-
-int acimg_config_default(AcimgConfig* c) {
-    if (!c) return fail(ACIMG_EINVAL, "config_default: null");
-    *c = AcimgConfig{320, 768, 1, 128, 1, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0};
-    return ACIMG_OK;
-}
-
-int acimg_configure(const AcimgConfig* c) {
-    if (!c) return fail(ACIMG_EINVAL, "configure: null");
-    if (c->splitk_cut < 0 || c->splitk_target < 1 || c->wgrad_minpix < 1 || c->tail_s < 0)
-        return fail(ACIMG_EINVAL, "configure: negative / zero tuning value");
-    if (c->trunk_persistent < 0 || c->trunk_persistent > 2) return fail(ACIMG_EINVAL, "configure: trunk_persistent is 0, 1 or 2");
-    if (c->trunk_dma_pos < 0 || c->trunk_dma_pos > 1) return fail(ACIMG_EINVAL, "configure: trunk_dma_pos is 0 or 1");
-    if (c->trunk_stagger < 0 || c->trunk_stagger > 100) return fail(ACIMG_EINVAL, "configure: trunk_stagger is a percentage");
-    if (c->trunk_bk != 0 && c->trunk_bk != 32)
-        return fail(ACIMG_EINVAL, "configure: trunk_bk must be 0 or 32 (the 64-deep K step was measured slower and removed)");
-    if (c->trunk_ring < 0 || c->trunk_ring > 2) return fail(ACIMG_EINVAL, "configure: trunk_ring is 0, 1 or 2");
-    if (c->trunk_ring_bm != 0 && c->trunk_ring_bm != 128 && c->trunk_ring_bm != 256)
-        return fail(ACIMG_EINVAL, "configure: trunk_ring_bm must be 0 (per shape), 128 or 256");
-    if (c->trunk_halo < 0 || c->trunk_halo > 2) return fail(ACIMG_EINVAL, "configure: trunk_halo is 0, 1 or 2");
-    if (c->split3_tile_bm || c->split3_tile_bn) {
-        const int bm = c->split3_tile_bm, bn = c->split3_tile_bn;
-        if (!((bm == 128 && bn == 128) || (bm == 64 && bn == 128) || (bm == 128 && bn == 64)))
-            return fail(ACIMG_EINVAL, "configure: split3 tile %dx%d is not an instantiated tile", bm, bn);
-    }
-    g_cfg = *c;
-    return ACIMG_OK;
-}
-
 // a dense layer over at most 64 batch rows with a large weight matrix (csrc/skinny_kernel.hpp)
 static bool skinny_shape(const AcimgConvDesc* d) {
     return d->R == 1 && d->S == 1 && d->H == 1 && d->W == 1 && d->OH == 1 && d->OW == 1 && d->stride == 1 &&
@@ -2106,83 +2099,6 @@ static bool skinny_shape(const AcimgConvDesc* d) {
 }
 static size_t skinny_fwd_ws_bytes(const AcimgConvDesc* d) {
     return skinny_shape(d) ? (size_t)cdiv(d->C, SKINNY_KS) * d->N * d->K * 4 : 0;
-}
-
-size_t acimg_conv2d_fwd_workspace(const AcimgConvDesc* d) {
-    const size_t a = igemm_ws_bytes(d->N * d->OH * d->OW, d->K, fwd_kiters(d));
-    const size_t b = d->C <= 16 && d->K <= 32 ? direct_ws_bytes(d->R, d->S, d->C, (d->K + 7) & ~7) : 0;
-    const size_t c = skinny_fwd_ws_bytes(d);
-    const size_t f = few16_fwd_shape(d) ? few16_ws_bytes(d->C, d->K) : 0;
-    return std::max(std::max(a, f), std::max(b, c));
-}
-
-int acimg_conv2d_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
-                     float* y, const float* in_scale, const float* in_shift, int in_relu,
-                     float* stats, void* ws, size_t ws_bytes, void* tickets, void* stream) {
-    int rc = check_desc(d, "conv2d_fwd");
-    if (rc) return rc;
-    if (d->ldw < d->K) return fail(ACIMG_EINVAL, "conv2d_fwd: ldw < K");
-    if (skinny_shape(d) && !in_scale && !in_shift && !in_relu && !stats && ws && ws_bytes >= skinny_fwd_ws_bytes(d) && aligned16(x) &&
-        aligned16(w) && aligned16(y) && aligned16(ws) && (!bias || aligned16(bias)) && (d->ldw & 3) == 0 && (d->ldx & 3) == 0 &&
-        (d->ldy & 3) == 0) {
-        // the VAE heads' dense layer: weight rows read once in whole lines, K slabs combined in slab order
-        SkinnyParams q{};
-        q.W = w; q.X = x; q.out = y; q.bias = bias; q.act = d->act; q.part = static_cast<float*>(ws);
-        q.M = d->N; q.C = d->C; q.N = d->K; q.ldw = d->ldw; q.ldx = d->ldx; q.ldo = d->ldy;
-        q.slabs = cdiv(d->C, SKINNY_KS);
-        const dim3 grid(q.slabs, cdiv(d->K, 64));
-        const int mb = cdiv(d->N, 16);
-        if (mb == 1) hipLaunchKernelGGL(skinny_fwd_kernel<1>, grid, dim3(64), 0, (hipStream_t)stream, q);
-        else if (mb == 2) hipLaunchKernelGGL(skinny_fwd_kernel<2>, grid, dim3(64), 0, (hipStream_t)stream, q);
-        else if (mb == 3) hipLaunchKernelGGL(skinny_fwd_kernel<3>, grid, dim3(64), 0, (hipStream_t)stream, q);
-        else hipLaunchKernelGGL(skinny_fwd_kernel<4>, grid, dim3(64), 0, (hipStream_t)stream, q);
-        rc = check_launch("conv2d_fwd (skinny)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(skinny_fwd_reduce_kernel, dim3(cdiv(d->N * (d->K / 4), 256)), dim3(256), 0, (hipStream_t)stream, q);
-        return check_launch("conv2d_fwd (skinny reduce)");
-    }
-    if (few16_fwd_shape(d)) {
-        // acimg_conv2d_stats_rows(d) promised one statistics row per workgroup of this kernel: no silent fallback
-        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || !aligned16(x) || !aligned16(y) || (d->ldy & 3) ||
-            d->ldy < d->K || (bias && !aligned16(bias)) || (in_scale && (!aligned16(in_scale) || !aligned16(in_shift))))
-            return fail(ACIMG_EINVAL, "conv2d_fwd: few-channel MFMA shape with half an input affine or unaligned operands");
-        FewParams q{};
-        q.a_scale = in_scale; q.a_shift = in_shift; q.a_relu = in_relu;
-        q.X = x; q.H = d->H; q.W = d->W; q.ldx = d->ldx; q.Y = y; q.ldy = d->ldy; q.nout = d->K; q.bias = bias;
-        q.Hin = q.SH = d->H; q.Win = q.SW = d->W; q.dil = 1; q.pad_t = 1; q.pad_l = 1;
-        q.stats = stats; q.stats_ld = d->ldw;
-        q.w = w; q.ldw = d->ldw; q.wrows = d->C; q.cin = d->C; q.mode = 0;
-        return dispatch_few16<0>(q, d->N, d->C, d->K, ws, ws_bytes, (hipStream_t)stream);
-    }
-    if (direct_ok(d->C, d->K, d->ldy, 0, y, bias, nullptr, in_scale != nullptr, nullptr) &&
-        (long)d->N * d->OH * d->OW >= 65536) {
-        DirectParams q{};
-        q.x = x; q.ldx = d->ldx; q.H = d->H; q.W = d->W; q.C = d->C;
-        q.y = y; q.ldy = d->ldy; q.OH = d->OH; q.OW = d->OW; q.K = d->K;
-        q.R = d->R; q.S = d->S; q.stride = d->stride; q.pad_t = d->pad_t; q.pad_l = d->pad_l;
-        q.w = w; q.ldw = d->ldw; q.mode = 0; q.wrows = d->C; q.bias = bias; q.act = d->act;
-        q.M = (long)d->N * d->OH * d->OW;
-        const bool fuse_stats = stats && stats_block_rows(d) == 256 && d->act == ACIMG_ACT_NONE;
-        if (fuse_stats) { q.stats = stats; q.stats_ld = d->ldw; }
-        rc = launch_direct(q, ws, ws_bytes, (hipStream_t)stream);
-        if (!rc && stats && !fuse_stats) {   // batch-norm partials of y = conv + bias, in acimg_conv2d_stats_rows(d) row blocks
-            hipLaunchKernelGGL(partial_stats_kernel, dim3(acimg_conv2d_stats_rows(d)), dim3(256), 0, (hipStream_t)stream,
-                               y, d->ldy, (int)q.M, d->K, stats, d->ldw, stats_block_rows(d));
-            rc = check_launch("partial_stats");
-        }
-        return rc;
-    }
-    IgemmParams p{};
-    p.A = x; p.H = d->H; p.W = d->W; p.C = d->C; p.lda = d->ldx;
-    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride;
-    p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.M = d->N * d->OH * d->OW;
-    p.rowrun = (d->S > 1 && d->ldx == d->C) ? 1 : 0;
-    p.a_scale = in_scale; p.a_shift = in_shift; p.a_relu = in_relu;
-    p.B = w; p.ldb = d->ldw; p.Nld = d->ldw; p.Ngemm = d->K; p.tap_stride = 0; p.flip = 0;
-    p.e.Y = y; p.e.ldy = d->ldy; p.e.M = p.M; p.e.Nstore = d->K; p.e.bias = bias; p.e.act = d->act;
-    p.e.stats = stats; p.e.stats_ld = d->ldw;
-    return launch_igemm(p, false, ws, ws_bytes, tickets, (hipStream_t)stream);
 }
 
 // the sub-pixel form pays from 16 output channels on: with 8 (the full-resolution layers) its scatter writes 16-byte
@@ -2241,327 +2157,6 @@ static bool dgrad_halo16_narrow_shape(const AcimgConvDesc* d) {
            d->K == 32 && d->C <= 16 && (d->C & 3) == 0 && (long)d->N * d->H * d->W >= 65536 && g_cfg.wgrad_halo;
 }
 static constexpr size_t DGRAD_HALO16_NARROW_WS = 2 * 16 * 288 * 2;
-static int dgrad_halo16_narrow(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w, float* dx, int lddx,
-                               const float* residual, int ldres, const float* mask, int ldmask, void* ws, hipStream_t st);
-
-size_t acimg_conv2d_dgrad_workspace(const AcimgConvDesc* d) {
-    if (dgrad_halo16_narrow_shape(d)) return DGRAD_HALO16_NARROW_WS + 256;
-    if (dgrad_is_patch(d)) return igemm_ws_bytes(d->N * d->OH * d->OW, d->R * d->S * d->C, cdiv(up4(d->K), 32));
-    const int ca = up4(d->K);
-    if (subpixel_ok(d->stride, d->C, ca))   // sub-pixel form: combined weights + the GEMM's own split-K slabs
-        return subpixel_ws_bytes(d->N, d->H, d->W, -d->pad_t, -d->pad_l, d->R, d->S, ca, d->C);
-    if (d->stride > 1)   // zero-inserted copy of gy, then the stride-1 path
-        return dilated_bytes(d->N, d->OH, d->OW, ca, d->stride) +
-               igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * d->S * cdiv(ca, 32)) +
-               igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * cdiv(d->S * ca, 32)) +
-               (ca <= 16 && d->C <= 32 ? std::max(direct_ws_bytes(d->R, d->S, ca, (d->C + 7) & ~7), few16_ws_bytes(ca, d->C)) : 0);
-    // rowrun depends on ldgy, unknown here: per-tap kiters is the larger bound for splits
-    return igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * d->S * cdiv(ca, 32)) +
-           igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * cdiv(d->S * ca, 32)) +
-           (ca <= 16 && d->C <= 32 ? std::max(direct_ws_bytes(d->R, d->S, ca, (d->C + 7) & ~7), few16_ws_bytes(ca, d->C)) : 0);
-}
-
-int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w,
-                       float* dx, int lddx, const float* residual, int ldres, const float* mask,
-                       int ldmask, void* ws, size_t ws_bytes, void* tickets, void* stream) {
-    int rc = check_desc(d, "conv2d_dgrad");
-    if (rc) return rc;
-    const int ca = up4(d->K);
-    if (ca > ldgy || ca > d->ldw || (ldgy & 3)) return fail(ACIMG_EINVAL, "conv2d_dgrad: padded K=%d exceeds ldgy=%d/ldw=%d", ca, ldgy, d->ldw);
-    if (skinny_shape(d) && aligned16(gy) && aligned16(w) && (d->ldw & 3) == 0) {
-        // a dense layer over a few batch rows (the 28 416 -> 300 VAE heads): the weight matrix is read once, in rows
-        SkinnyParams q{};
-        q.W = w; q.G = gy; q.out = dx; q.res = residual; q.mask = mask;
-        q.M = d->N; q.C = d->C; q.N = ca;
-        q.ldw = d->ldw; q.ldg = ldgy; q.ldo = lddx > 0 ? lddx : d->ldx; q.ldres = ldres; q.ldmask = ldmask;
-        if (q.ldo < d->C) return fail(ACIMG_EINVAL, "conv2d_dgrad: lddx < C");
-        const dim3 grid(cdiv(cdiv(d->C, 16), 4));
-        const int mb = cdiv(d->N, 16);
-        if (mb == 1) hipLaunchKernelGGL(skinny_dgrad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, q);
-        else if (mb == 2) hipLaunchKernelGGL(skinny_dgrad_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, q);
-        else if (mb == 3) hipLaunchKernelGGL(skinny_dgrad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, q);
-        else hipLaunchKernelGGL(skinny_dgrad_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, q);
-        return check_launch("conv2d_dgrad (skinny)");
-    }
-    IgemmParams p{};
-    p.A = gy; p.C = ca; p.lda = ldgy;
-    p.B = w; p.ldb = d->ldw;
-    if (lddx <= 0) lddx = d->ldx;
-    if (lddx < d->C) return fail(ACIMG_EINVAL, "conv2d_dgrad: lddx < C");
-    p.e.Y = dx; p.e.ldy = lddx; p.e.res = residual; p.e.ldres = ldres; p.e.mask = mask; p.e.ldmask = ldmask;
-    p.e.act = ACIMG_ACT_NONE;
-    if (subpixel_ok(d->stride, d->C, ca) && !dgrad_is_patch(d))
-        // dx[2 oy - pad_t + r][2 ox - pad_l + s][c] += gy[oy][ox][k] w[r][s][c][k]: the sub-pixel form over gy's own grid
-        return launch_subpixel(gy, d->N, d->OH, d->OW, ca, ldgy, w, d->R, d->S, d->ldw, d->C, dx, lddx, d->H, d->W, -d->pad_t,
-                               -d->pad_l, nullptr, residual, ldres, mask, ldmask, ACIMG_ACT_NONE, ws, ws_bytes, tickets,
-                               (hipStream_t)stream, "conv2d_dgrad");
-    if (dgrad_halo16_narrow_shape(d) && aligned16(gy) && aligned16(dx) && (lddx & 3) == 0 && ws && aligned16(ws) &&
-        ws_bytes >= DGRAD_HALO16_NARROW_WS && (!residual || ((ldres & 3) == 0 && aligned16(residual))) &&
-        (!mask || ((ldmask & 3) == 0 && aligned16(mask))))
-        return dgrad_halo16_narrow(d, gy, ldgy, w, dx, lddx, residual, ldres, mask, ldmask, ws, (hipStream_t)stream);
-    if (few16_dgrad_shape(d) && !subpixel_ok(d->stride, d->C, ca) && !mask && aligned16(gy) && aligned16(dx) && (lddx & 3) == 0 &&
-        ws && aligned16(ws) && ws_bytes >= few16_ws_bytes(ca, d->C) && (!residual || ((ldres & 3) == 0 && aligned16(residual)))) {
-        // dx[h][w][c] = sum gy1[h - (2 - pad_t) + r'][w - (2 - pad_l) + s'][k] W[2 - r'][2 - s'][c][k], gy1 = gy (stride 1) or
-        // its zero-inserted view (stride 2), zero outside
-        FewParams q{};
-        q.X = gy; q.ldx = ldgy; q.SH = d->OH; q.SW = d->OW; q.dil = d->stride;
-        q.Hin = (d->OH - 1) * d->stride + 1; q.Win = (d->OW - 1) * d->stride + 1;
-        q.pad_t = 2 - d->pad_t; q.pad_l = 2 - d->pad_l;
-        q.H = d->H; q.W = d->W; q.Y = dx; q.ldy = lddx; q.nout = d->C;
-        q.res = residual; q.ldres = ldres;
-        q.w = w; q.ldw = d->ldw; q.wrows = d->C; q.cin = d->K; q.mode = 1;
-        return dispatch_few16<1>(q, d->N, ca, d->C, ws, ws_bytes, (hipStream_t)stream);
-    }
-    if (d->stride > 1 && !dgrad_is_patch(d)) {
-        // general stride: the strided conv is a subsampled stride-1 conv, so its data gradient is the stride-1
-        // data gradient of the zero-inserted gy
-        const size_t db = dilated_bytes(d->N, d->OH, d->OW, ca, d->stride);
-        if (ws_bytes < db || !ws) return fail(ACIMG_EWORKSPACE, "conv2d_dgrad: workspace too small for the dilated gradient");
-        const int OH1 = (d->OH - 1) * d->stride + 1, OW1 = (d->OW - 1) * d->stride + 1;
-        const long opix = (long)d->N * OH1 * OW1;
-        if (opix * ca >= (1L << 31)) return fail(ACIMG_EINVAL, "conv2d_dgrad: dilated gradient exceeds 2^31 elements");
-        hipLaunchKernelGGL(dilate2d_kernel, dim3(cdiv(opix * (ca / 4), 256)), dim3(256), 0, (hipStream_t)stream, gy, ldgy,
-                           static_cast<float*>(ws), opix, d->OH, d->OW, OH1, OW1, ca, d->stride);
-        rc = check_launch("dilate2d");
-        if (rc) return rc;
-        AcimgConvDesc d1 = *d;
-        d1.stride = 1; d1.OH = OH1; d1.OW = OW1;
-        return acimg_conv2d_dgrad(&d1, static_cast<const float*>(ws), ca, w, dx, lddx, residual, ldres, mask, ldmask,
-                                  static_cast<char*>(ws) + db, ws_bytes - db, tickets, stream);
-    }
-    if (d->stride == 1 && direct_ok(ca, d->C, lddx, ldres, dx, nullptr, residual, false, mask) &&
-        (long)d->N * d->H * d->W >= 65536) {
-        DirectParams q{};
-        q.x = gy; q.ldx = ldgy; q.H = d->OH; q.W = d->OW; q.C = ca;
-        q.y = dx; q.ldy = lddx; q.OH = d->H; q.OW = d->W; q.K = d->C;
-        q.R = d->R; q.S = d->S; q.stride = 1; q.pad_t = d->R - 1 - d->pad_t; q.pad_l = d->S - 1 - d->pad_l;
-        q.w = w; q.ldw = d->ldw; q.mode = 1; q.wrows = d->C; q.act = ACIMG_ACT_NONE;
-        q.res = residual; q.ldres = ldres;
-        q.M = (long)d->N * d->H * d->W;
-        return launch_direct(q, ws, ws_bytes, (hipStream_t)stream);
-    }
-    if (d->stride == 1) {
-        // dx[h,w,c] = sum_{r',s',k} gy[h-(R-1-pt)+r', w-(S-1-pl)+s', k] * W[R-1-r'][S-1-s'][c][k]
-        p.H = d->OH; p.W = d->OW; p.OH = d->H; p.OW = d->W;
-        p.R = d->R; p.S = d->S; p.stride = 1;
-        p.pad_t = d->R - 1 - d->pad_t; p.pad_l = d->S - 1 - d->pad_l;
-        p.M = d->N * d->H * d->W;
-        p.rowrun = (d->S > 1 && ldgy == ca) ? 1 : 0;
-        p.tap_stride = (long)d->C * d->ldw; p.flip = 1;
-        p.Ngemm = d->C;
-        p.e.M = p.M; p.e.Nstore = d->C;
-    } else {
-        // patch scatter: rows = output pixels, columns = (tap, c)
-        p.H = d->OH; p.W = d->OW; p.OH = d->OH; p.OW = d->OW;
-        p.R = 1; p.S = 1; p.stride = 1; p.pad_t = 0; p.pad_l = 0;
-        p.M = d->N * d->OH * d->OW;
-        p.rowrun = 0; p.tap_stride = 0; p.flip = 0;
-        p.Ngemm = d->R * d->S * d->C;
-        p.e.M = p.M; p.e.Nstore = p.Ngemm;
-        p.e.scatter = 1; p.e.Ko = d->C; p.e.Sq = d->S; p.e.sc = d->stride;
-        p.e.YH = d->H; p.e.YW = d->W; p.e.AH = d->OH; p.e.AW = d->OW;
-    }
-    return launch_igemm(p, true, ws, ws_bytes, tickets, (hipStream_t)stream);
-}
-
-size_t acimg_conv2d_wgrad_workspace(const AcimgConvDesc* d) {
-    return wgrad_ws_bytes(d->N * d->OH * d->OW, d->R * d->S * d->C, up4(d->K), d->ldw) + colsum_ws_bytes(up4(d->K));
-}
-
-int acimg_conv2d_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
-                       float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
-    int rc = check_desc(d, "conv2d_wgrad");
-    if (rc) return rc;
-    const int kp = up4(d->K);
-    if (kp > ldgy || kp > d->ldw) return fail(ACIMG_EINVAL, "conv2d_wgrad: padded K exceeds ldgy/ldw");
-    if (skinny_shape(d) && aligned16(x) && aligned16(gy) && aligned16(dw) && (!db || aligned16(db)) && (d->ldw & 3) == 0 &&
-        (ldgy & 3) == 0 && (d->ldx & 3) == 0) {
-        // the same dense layer's weight gradient: every weight row is written once, 256 contiguous bytes per wave
-        SkinnyParams q{};
-        q.X = x; q.G = gy; q.out = dw; q.db = db;
-        q.M = d->N; q.C = d->C; q.N = kp;
-        q.ldw = d->ldw; q.ldg = ldgy; q.ldx = d->ldx;
-        const int ngroups = cdiv(kp, 64);
-        const int tasks = cdiv(d->C, 64) * ngroups;
-        hipLaunchKernelGGL(skinny_wgrad_kernel, dim3(cdiv(tasks, 4)), dim3(256), 0, (hipStream_t)stream, q, ngroups);
-        return check_launch("conv2d_wgrad (skinny)");
-    }
-    WgradParams p{};
-    p.X = x; p.H = d->H; p.W = d->W; p.C = d->C; p.ldx = d->ldx;
-    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.M = d->N * d->OH * d->OW; p.KK = d->R * d->S * d->C;
-    p.G = gy; p.ldg = ldgy; p.Ngemm = kp; p.Nld = kp; p.ldo = d->ldw;
-    return launch_wgrad(p, dw, db, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t acimg_deconv_workspace(const AcimgConvDesc* d) {
-    size_t a = igemm_ws_bytes(d->N * d->H * d->W, d->R * d->S * d->K, cdiv(d->C, 32));
-    size_t b = igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * d->S * cdiv(up4(d->K), 32));
-    size_t c = wgrad_ws_bytes(d->N * d->H * d->W, d->R * d->S * up4(d->K), d->C, d->ldw) + colsum_ws_bytes(up4(d->K));
-    size_t m = a > b ? a : b;
-    m = m > c ? m : c;
-    if (patch2_shape(d)) {                      // weight gradient of the pointwise form: one 32 x ldw slab per workgroup
-        const size_t pw = (size_t)PATCH2_WGRAD_WGS * (32 * d->ldw + 8) * sizeof(float);
-        m = m > pw ? m : pw;
-    }
-    if (up4(d->K) <= 16 && d->C <= 32) {        // data gradient on the direct few-channel kernel
-        const size_t dd = direct_ws_bytes(d->R, d->S, up4(d->K), (d->C + 7) & ~7);
-        m = m > dd ? m : dd;
-    }
-    if ((d->R > d->stride || d->S > d->stride) && subpixel_ok(d->stride, d->K, d->C)) {   // forward in the sub-pixel form
-        const size_t sp = subpixel_ws_bytes(d->N, d->OH, d->OW, 0, 0, d->R, d->S, d->C, d->K);
-        return m > sp ? m : sp;
-    }
-    if (d->R > d->stride || d->S > d->stride)   // forward goes through a zero-inserted copy of x
-        m += dilated_bytes(d->N, d->H, d->W, d->C, d->stride) +
-             igemm_ws_bytes(d->N * d->OH * d->OW, d->K, d->R * d->S * cdiv(d->C, 32)) +
-             igemm_ws_bytes(d->N * d->OH * d->OW, d->K, d->R * cdiv(d->S * d->C, 32));
-    return m;
-}
-
-int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
-                     float* y, void* ws, size_t ws_bytes, void* tickets, void* stream) {
-    int rc = check_desc(d, "deconv_fwd");
-    if (rc) return rc;
-    if (d->ldw < d->C || (d->K & 3)) return fail(ACIMG_EINVAL, "deconv_fwd: ldw<C or K%%4");
-    if (d->R > d->stride || d->S > d->stride) {
-        // overlapping patches (tf conv2d_transpose VALID: OH = (H-1)*stride + R): y = stride-1 "full" correlation
-        // of the zero-inserted x with the flipped kernel = the data gradient of the stride-1 VALID conv
-        // [OH,OW,K] -> [(H-1)s+1, (W-1)s+1, C] whose HWIO kernel is this layer's [R][S][K][C]
-        if (d->OH != (d->H - 1) * d->stride + d->R || d->OW != (d->W - 1) * d->stride + d->S)
-            return fail(ACIMG_EINVAL, "deconv_fwd: kernel>stride needs OH=(H-1)*stride+R");
-        if (subpixel_ok(d->stride, d->K, d->C))
-            // y[2 h + r][2 w + s][k] += x[h][w][c] W[r][s][k][c]: the sub-pixel form over x's own grid (every output
-            // pixel belongs to exactly one parity class: written once, bias included)
-            return launch_subpixel(x, d->N, d->H, d->W, d->C, d->ldx, w, d->R, d->S, d->ldw, d->K, y, d->ldy, d->OH, d->OW, 0, 0,
-                                   bias, nullptr, 0, nullptr, 0, d->act, ws, ws_bytes, tickets, (hipStream_t)stream,
-                                   "deconv_fwd");
-        const size_t db = dilated_bytes(d->N, d->H, d->W, d->C, d->stride);
-        if (ws_bytes < db || !ws) return fail(ACIMG_EWORKSPACE, "deconv_fwd: workspace too small for the dilated input");
-        const int H1 = (d->H - 1) * d->stride + 1, W1 = (d->W - 1) * d->stride + 1;
-        const long opix = (long)d->N * H1 * W1;
-        hipLaunchKernelGGL(dilate2d_kernel, dim3(cdiv(opix * (d->C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, d->ldx,
-                           static_cast<float*>(ws), opix, d->H, d->W, H1, W1, d->C, d->stride);
-        rc = check_launch("dilate2d");
-        if (rc) return rc;
-        IgemmParams p{};
-        p.A = static_cast<const float*>(ws); p.C = d->C; p.lda = d->C;
-        p.B = w; p.ldb = d->ldw;
-        p.H = H1; p.W = W1; p.OH = d->OH; p.OW = d->OW;
-        p.R = d->R; p.S = d->S; p.stride = 1; p.pad_t = d->R - 1; p.pad_l = d->S - 1;
-        p.M = d->N * d->OH * d->OW;
-        p.rowrun = d->S > 1 ? 1 : 0;
-        p.tap_stride = (long)d->K * d->ldw; p.flip = 1;
-        p.Ngemm = d->K;
-        p.e.Y = y; p.e.ldy = d->ldy; p.e.M = p.M; p.e.Nstore = d->K; p.e.bias = bias; p.e.act = d->act;
-        return launch_igemm(p, true, static_cast<char*>(ws) + db, ws_bytes - db, tickets, (hipStream_t)stream);
-    }
-    if (d->OH != d->H * d->stride || d->OW != d->W * d->stride)
-        return fail(ACIMG_EINVAL, "deconv_fwd: kernel<=stride needs OH=H*stride");
-    if (patch2_shape(d) && aligned16(x) && aligned16(y) && aligned16(w) && (d->ldx & 3) == 0 && (d->ldy & 3) == 0 && (d->ldw & 3) == 0 &&
-        (!bias || aligned16(bias))) {
-        Patch2Params q{};
-        q.X = x; q.ldx = d->ldx; q.Y = y; q.ldy = d->ldy; q.w = w; q.ldw = d->ldw; q.bias = bias; q.act = d->act;
-        q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
-        return launch_patch2<SplitF16, 0>(q, (hipStream_t)stream);
-    }
-    IgemmParams p{};
-    p.A = x; p.H = d->H; p.W = d->W; p.C = d->C; p.lda = d->ldx; p.OH = d->H; p.OW = d->W;
-    p.R = 1; p.S = 1; p.stride = 1; p.M = d->N * d->H * d->W; p.rowrun = 0;
-    p.B = w; p.ldb = d->ldw; p.tap_stride = 0; p.flip = 0; p.Ngemm = d->R * d->S * d->K;
-    p.e.Y = y; p.e.ldy = d->ldy; p.e.M = p.M; p.e.Nstore = p.Ngemm; p.e.bias = bias; p.e.act = d->act;
-    p.e.scatter = 1; p.e.Ko = d->K; p.e.Sq = d->S; p.e.sc = d->stride;
-    p.e.YH = d->OH; p.e.YW = d->OW; p.e.AH = d->H; p.e.AW = d->W;
-    rc = launch_igemm(p, true, ws, ws_bytes, tickets, (hipStream_t)stream);
-    if (rc) return rc;
-    if (d->R < d->stride || d->S < d->stride) {
-        const long pixels = (long)d->N * d->OH * d->OW;
-        hipLaunchKernelGGL(deconv_gap_fill_kernel, dim3(cdiv(pixels * (d->K / 4), 256)), dim3(256), 0,
-                           (hipStream_t)stream, y, d->ldy, bias, pixels, d->OH, d->OW, d->K, d->R, d->S, d->stride);
-        rc = check_launch("deconv_gap_fill");
-    }
-    return rc;
-}
-
-int acimg_deconv_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w,
-                       float* dx, const float* mask, int ldmask, void* ws, size_t ws_bytes,
-                       void* tickets, void* stream) {
-    int rc = check_desc(d, "deconv_dgrad");
-    if (rc) return rc;
-    const int ca = up4(d->K);
-    if (ca > ldgy || (ldgy & 3) || ca != d->K) return fail(ACIMG_EINVAL, "deconv_dgrad: K must be a multiple of 4 and <= ldgy");
-    // dx[n,h,w,c] = sum_{r,s,k} gy[n, h*stride+r, w*stride+s, k] * W[r][s][k][c]  (a strided conv)
-    if (patch2_shape(d) && aligned16(gy) && aligned16(dx) && aligned16(w) && (d->ldx & 3) == 0 && (d->ldw & 3) == 0 &&
-        (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
-        Patch2Params q{};
-        q.X = gy; q.ldx = ldgy; q.Y = dx; q.ldy = d->ldx; q.w = w; q.ldw = d->ldw; q.mask = mask; q.ldmask = ldmask;
-        q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
-        return launch_patch2<SplitBF16, 1>(q, (hipStream_t)stream);
-    }
-    if (!mask && direct_ok(ca, d->C, d->ldx, 0, dx, nullptr, nullptr, false, nullptr) &&
-        (long)d->N * d->H * d->W >= 65536) {
-        // few channels: the direct kernel, the [kh][kw][out][in] kernel read as the HWIO kernel of that conv
-        DirectParams q{};
-        q.x = gy; q.ldx = ldgy; q.H = d->OH; q.W = d->OW; q.C = ca;
-        q.y = dx; q.ldy = d->ldx; q.OH = d->H; q.OW = d->W; q.K = d->C;
-        q.R = d->R; q.S = d->S; q.stride = d->stride; q.pad_t = 0; q.pad_l = 0;
-        q.w = w; q.ldw = d->ldw; q.mode = 0; q.wrows = d->K; q.act = ACIMG_ACT_NONE;
-        q.M = (long)d->N * d->H * d->W;
-        return launch_direct(q, ws, ws_bytes, (hipStream_t)stream);
-    }
-    IgemmParams p{};
-    p.A = gy; p.H = d->OH; p.W = d->OW; p.C = ca; p.lda = ldgy; p.OH = d->H; p.OW = d->W;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = 0; p.pad_l = 0;
-    p.M = d->N * d->H * d->W;
-    p.rowrun = (d->S > 1 && ldgy == ca) ? 1 : 0;
-    p.B = w; p.ldb = d->ldw; p.Nld = d->ldw; p.Ngemm = d->C;
-    p.e.Y = dx; p.e.ldy = d->ldx; p.e.M = p.M; p.e.Nstore = d->C; p.e.mask = mask; p.e.ldmask = ldmask;
-    return launch_igemm(p, false, ws, ws_bytes, tickets, (hipStream_t)stream);
-}
-
-int acimg_deconv_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
-                       float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
-    int rc = check_desc(d, "deconv_wgrad");
-    if (rc) return rc;
-    const int ca = up4(d->K);
-    if (ca > ldgy || (ldgy & 3) || ca != d->K) return fail(ACIMG_EINVAL, "deconv_wgrad: K must be a multiple of 4 and <= ldgy");
-    // dW[(r,s,k)][c] = sum_{n,h,w} gy[n,h*stride+r,w*stride+s,k] * x[n,h,w,c]
-    if (patch2_shape(d) && aligned16(dw) && (d->ldw & 3) == 0 && ws && aligned16(ws) &&
-        ws_bytes >= (size_t)PATCH2_WGRAD_WGS * (32 * d->ldw + 8) * sizeof(float) && (!db || aligned16(db))) {
-        Patch2WgradParams q{};
-        q.X = x; q.ldx = d->ldx; q.G = gy; q.ldg = ldgy; q.out = static_cast<float*>(ws); q.ldo = d->ldw;
-        q.db_part = db ? q.out + (size_t)PATCH2_WGRAD_WGS * 32 * d->ldw : nullptr;
-        q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
-        hipLaunchKernelGGL(patch2_wgrad_32x8_kernel, dim3(PATCH2_WGRAD_WGS), dim3(1024), 0, (hipStream_t)stream, q);
-        rc = check_launch("patch2_wgrad");
-        if (rc) return rc;
-        launch_slab_reduce_wide(q.out, PATCH2_WGRAD_WGS, 32L, 32, d->ldw, dw, nullptr, nullptr, (hipStream_t)stream);
-        rc = check_launch("patch2_wgrad reduce");
-        if (rc) return rc;
-        // the transposed conv adds its bias at every output pixel, and every output pixel belongs to exactly one patch: the
-        // bias gradient is the sum of all the gy values the kernel has just read
-        if (db) {
-            hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, q.db_part, PATCH2_WGRAD_WGS, 8, db);
-            rc = check_launch("patch2_wgrad bias");
-        }
-        return rc;
-    }
-    WgradParams p{};
-    p.X = gy; p.H = d->OH; p.W = d->OW; p.C = ca; p.ldx = ldgy;
-    p.OH = d->H; p.OW = d->W; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = 0; p.pad_l = 0;
-    p.M = d->N * d->H * d->W; p.KK = d->R * d->S * ca;
-    p.G = x; p.ldg = d->ldx; p.Ngemm = d->C; p.Nld = d->C; p.ldo = d->ldw;
-    if (db) {       // refuse before dw is written: an unsplit weight gradient takes no workspace, the column sum always does
-        const size_t need = (size_t)colsum_parts((long)d->N * d->OH * d->OW) * d->K * sizeof(float);
-        if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "deconv_wgrad: workspace %zu < %zu (bias gradient)", ws_bytes, need);
-    }
-    rc = launch_wgrad(p, dw, nullptr, ws, ws_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-    // the transposed conv adds its bias at EVERY output pixel (gaps included): plain column sum of gy
-    if (db) rc = launch_colsum(gy, (long)d->N * d->OH * d->OW, d->K, ldgy, db, ws, ws_bytes, (hipStream_t)stream);
-    return rc;
-}
-
 // ------------------------------------------------------------------------------------------
 // f16x3 (split fp16) forward convolution (frozen ResNet trunk)
 // ------------------------------------------------------------------------------------------
@@ -2579,7 +2174,6 @@ static Split3Cfg pick_split3(int M, int K, bool allow32 = false) {
     return {128, 128};
 }
 
-extern "C++" {
 // ------------------------------------------------------------------------------------------
 // HALO form of the FORWARD conv / DATA GRADIENT of the same 3x3 / stride-1 / SAME layers with 32 or 64 channels on either
 // side (round 4; configs[1]'s 112x149 and 56x74 stages).  As an implicit GEMM with a 32- or 64-column tile these layers
@@ -2814,7 +2408,6 @@ static int launch_conv_halo16(ConvHaloParams q, int N, hipStream_t st) {
     hipLaunchKernelGGL((conv_halo16_kernel<TR, TERMS, CIN, NOUT, MODE>), dim3(CONV_HALO16_WGS), dim3(512), lds, st, q);
     return check_launch("conv_halo16");
 }
-}  // extern "C++"
 
 static int dgrad_halo16_narrow(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w, float* dx, int lddx,
                                const float* residual, int ldres, const float* mask, int ldmask, void* ws, hipStream_t st) {
@@ -2829,80 +2422,70 @@ static int dgrad_halo16_narrow(const AcimgConvDesc* d, const float* gy, int ldgy
     return launch_conv_halo16<SplitBF16, 3, 32, 16, 1>(q, d->N, st);
 }
 
-int acimg_conv2d_fwd_split3_stats_rows(const AcimgConvDesc* d) {
-    const int M = d->N * d->OH * d->OW;
-    if (conv_halo16_fwd_shape(d)) return CONV_HALO16_WGS;      // the halo form leaves one row per workgroup
-    return cdiv(M, pick_split3(M, d->K).bm);
-}
-
-// Persistent kernel or one tile per workgroup for the pre-split (trunk) forward conv (tools/trunk_shapes.py,
-// profiles/r02/trunk_shapes_*.txt): walking a tile list wins 2-9 % wherever there is at least one full round of whole
-// 128x128 tiles (most on short-K multi-round layers); when every tile belongs to the split tail (fewer tiles than
-// resident workgroups) the one-tile kernel's leaner code is 3-7 % faster.
-static bool split3p_persistent(const Split3Cfg& c, long tiles) {
-    if (c.bm != 128 || c.bn != 128) return false;
-    return g_cfg.trunk_persistent == 2 || (g_cfg.trunk_persistent == 1 && tiles >= 512);
-}
+// ---- which kernel a pre-split (trunk) forward conv runs on: the ONE place that decides it.  fwd_presplit launches what
+// pick_trunk says; acimg_conv2d_fwd_split3p_stats_rows and acimg_conv2d_fwd_split3_tiling report it ----
+enum TrunkKind { TRUNK_ONE_TILE = 0, TRUNK_PERSISTENT = 1, TRUNK_RING = 2, TRUNK_HALO = 3 };   // = the tiling query's third word
+struct TrunkPick {
+    TrunkKind kind;
+    int bm, bn;          // row and column tile
+    int stats_rows;      // statistics partials the kernel leaves: one per row tile
+    bool big_out;        // the output exceeds a 32-bit buffer descriptor
+};
 
 // Halo kernel (igemm_split3h_kernel.hpp) for a pre-split trunk conv: 3x3 / stride 1 / SAME on 128x128 tiles, image rows
 // short enough for an 18-brick patch.  trunk_halo = 1 takes it where it was measured to pay, 2 wherever it applies.
 static constexpr int HALO_NB = 18;
-static bool halo_applies(const AcimgConvDesc* d, int terms) {
+static bool halo_applies(const AcimgConvDesc* d, int terms, const Split3Cfg& c) {
     if (terms != 3 || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->OH != d->H ||
         d->OW != d->W || d->C % 32)
         return false;
-    const int M = d->N * d->OH * d->OW;
-    const Split3Cfg c = pick_split3(M, d->K);
     if (c.bm != 128 || c.bn != 128) return false;
     return ((d->W + 16) >> 4) + 8 + (d->W >> 4) + 1 <= HALO_NB;
 }
-static bool halo_on(const AcimgConvDesc* d, int terms) {
+
+static TrunkPick pick_trunk(const AcimgConvDesc* d, int terms, bool two_pass) {
+    const int M = d->N * d->OH * d->OW;
+    const Split3Cfg c = pick_split3(M, d->K);
+    const bool t128 = c.bm == 128 && c.bn == 128;
+    // the persistent and the ring kernel address the output through a 32-bit buffer descriptor; a larger output (per-GPU
+    // batches around 512 on the first trunk units) falls back to the one-tile kernel's 64-bit pointer stores
+    TrunkPick t{TRUNK_ONE_TILE, c.bm, c.bn, 0, (long)M * d->ldy * 4 >= (1L << 31)};
+    // statistics-only / fused-tail passes: always the persistent kernel (whole tiles, then K ranges of the tail tiles);
+    // fwd_presplit refuses the shapes that kernel does not take
+    if (two_pass) t.kind = TRUNK_PERSISTENT;
     // trunk_halo = 1 ("where it was measured to pay") selects nothing yet: at batch 32 the halo form is at parity with the
     // per-tap kernels on the 56x75 / 28x38 layers and behind the ring kernel on 14x19; 2 = wherever it applies
-    return g_cfg.trunk_halo == 2 && halo_applies(d, terms);
-}
-
-// Ring kernel (igemm_split3r_kernel.hpp) for a pre-split trunk conv, and with how many tile rows: 0 = not on it.
-// Measured per shape at batch 32 and 30 (tools/trunk_shapes.py, profiles/r03/trunk_shapes_r03*.txt): in its steady state
-// the ring kernel's K loop is 8-14 % faster than the two-workgroups-per-CU kernels' (long-K layers whose tiles fill one
-// round of the 256 CUs), but with ONE workgroup per CU it pays more for tile quantisation (a 1.04-round layer leaves
-// 246 CUs idle for a round, where 512 slots leave a quarter of the chip) and for short-K tiles (the output tile's stores
-// and the deferred stage at every unit boundary).  trunk_ring = 1 therefore takes it where it won: layers of at most
-// ~1.2 rounds of 128x128 tiles over the CUs (the 14x19 stage) with at least 64 K steps, on 128-row tiles with the tail
-// cut into K ranges; trunk_ring = 2 forces it (experiments, tests).
-static int ring_rows(const AcimgConvDesc* d, int terms) {
-    if (!g_cfg.trunk_ring || terms != 3 || halo_on(d, terms)) return 0;
-    const int M = d->N * d->OH * d->OW;
-    if ((long)M * d->ldy * 4 >= (1L << 31)) return 0;      // 32-bit output descriptor (see fwd_presplit)
-    const Split3Cfg c = pick_split3(M, d->K);
-    if (c.bm != 128 || c.bn != 128) return 0;
-    const long t128 = (long)cdiv(M, 128) * cdiv(d->K, 128);
-    const int kiters = d->R * d->S * (d->C / 32);
-    if (g_cfg.trunk_ring == 1) return (t128 > 256 && t128 <= 300 && kiters >= 64) ? 128 : 0;
-    if (g_cfg.trunk_ring_bm) return g_cfg.trunk_ring_bm;
-    const long t256 = (long)cdiv(M, 256) * cdiv(d->K, 128);
-    return t256 >= 500 ? 256 : 128;
-}
-
-int acimg_conv2d_fwd_split3p_stats_rows(const AcimgConvDesc* d) {
-    const int M = d->N * d->OH * d->OW;
-    const int rr = ring_rows(d, 3);
-    return cdiv(M, rr ? rr : pick_split3(M, d->K).bm);
-}
-
-int acimg_conv2d_fwd_split3_tiling(const AcimgConvDesc* d, int* out) {
-    if (!d || !out) return fail(ACIMG_EINVAL, "conv2d_fwd_split3_tiling: null argument");
-    const int M = d->N * d->OH * d->OW;
-    Split3Cfg c = pick_split3(M, d->K);
-    out[0] = c.bm;
-    out[1] = c.bn;
-    out[2] = split3p_persistent(c, (long)cdiv(M, c.bm) * cdiv(d->K, c.bn)) ? 1 : 0;
-    if (const int rr = ring_rows(d, 3)) {      // the ring kernel: its row tile, flag 2
-        out[0] = rr;
-        out[2] = 2;
+    else if (g_cfg.trunk_halo == 2 && halo_applies(d, terms, c)) t.kind = TRUNK_HALO;
+    // Ring kernel (igemm_split3r_kernel.hpp) for a pre-split trunk conv, and with how many tile rows (ring_rows; 0 = not on it).
+    // Measured per shape at batch 32 and 30 (tools/trunk_shapes.py, profiles/r03/trunk_shapes_r03*.txt): in its steady state
+    // the ring kernel's K loop is 8-14 % faster than the two-workgroups-per-CU kernels' (long-K layers whose tiles fill one
+    // round of the 256 CUs), but with ONE workgroup per CU it pays more for tile quantisation (a 1.04-round layer leaves
+    // 246 CUs idle for a round, where 512 slots leave a quarter of the chip) and for short-K tiles (the output tile's stores
+    // and the deferred stage at every unit boundary).  trunk_ring = 1 therefore takes it where it won: layers of at most
+    // ~1.2 rounds of 128x128 tiles over the CUs (the 14x19 stage) with at least 64 K steps, on 128-row tiles with the tail
+    // cut into K ranges; trunk_ring = 2 forces it (experiments, tests).
+    int ring_rows = 0;
+    if (!two_pass && t.kind != TRUNK_HALO && !t.big_out && g_cfg.trunk_ring && terms == 3 && t128) {
+        const long t128s = (long)cdiv(M, 128) * cdiv(d->K, 128);
+        const int kiters = d->R * d->S * (d->C / 32);
+        const long t256 = (long)cdiv(M, 256) * cdiv(d->K, 128);
+        if (g_cfg.trunk_ring == 1) ring_rows = (t128s > 256 && t128s <= 300 && kiters >= 64) ? 128 : 0;
+        else if (g_cfg.trunk_ring_bm) ring_rows = g_cfg.trunk_ring_bm;
+        else ring_rows = t256 >= 500 ? 256 : 128;
     }
-    if (halo_on(d, 3)) out[2] = 3;             // the halo kernel (128x128)
-    return ACIMG_OK;
+    if (ring_rows) {
+        t.kind = TRUNK_RING;
+        t.bm = ring_rows;
+    }
+    // Persistent kernel or one tile per workgroup for the pre-split (trunk) forward conv (tools/trunk_shapes.py,
+    // profiles/r02/trunk_shapes_*.txt): walking a tile list wins 2-9 % wherever there is at least one full round of whole
+    // 128x128 tiles (most on short-K multi-round layers); when every tile belongs to the split tail (fewer tiles than
+    // resident workgroups) the one-tile kernel's leaner code is 3-7 % faster.
+    const long tiles = (long)cdiv(M, c.bm) * cdiv(d->K, c.bn);
+    if (t.kind == TRUNK_ONE_TILE && !t.big_out && t128 && (g_cfg.trunk_persistent == 2 || (g_cfg.trunk_persistent == 1 && tiles >= 512)))
+        t.kind = TRUNK_PERSISTENT;
+    t.stats_rows = cdiv(M, t.bm);
+    return t;
 }
 
 // Row-major planes [hi | lo][ldw][R*S*C], then (C % 32 == 0) the same weights once more in LDS-TILE ORDER: for every
@@ -2913,10 +2496,6 @@ static size_t split3_rowmajor_bytes(const AcimgConvDesc* d) { return (size_t)2 *
 static size_t split3_brick_bytes(const AcimgConvDesc* d) {
     return d->C % 32 ? 0 : (size_t)cdiv(d->ldw, 128) * (d->R * d->S * d->C / 32) * 2 * 8192;
 }
-size_t acimg_conv2d_split3_weight_bytes(const AcimgConvDesc* d) {
-    return split3_rowmajor_bytes(d) + split3_brick_bytes(d);
-}
-
 // one thread per 16-byte chunk of the tile-ordered image: brick (nt, q, plane), row, physical chunk
 __global__ void split3_brick_kernel(const char* __restrict__ planes, char* __restrict__ bricks, const int Nrows,
                                     const int Ktot, const long total) {
@@ -2931,6 +2510,807 @@ __global__ void split3_brick_kernel(const char* __restrict__ planes, char* __res
     if (n < Nrows)
         v = *reinterpret_cast<const uint4*>(planes + (((long)plane * Nrows + n) * Ktot + q * 32 + ((pch ^ swz(row)) << 3)) * 2);
     *reinterpret_cast<uint4*>(bricks + i * 16) = v;
+}
+
+template <typename TR, int TERMS = 3>
+static int launch_split3(IgemmParams& p, hipStream_t st) {
+    Split3Cfg c = pick_split3(p.M, p.Ngemm, true);
+    dim3 grid(cdiv(p.M, c.bm), cdiv(p.Ngemm, c.bn), 1);
+    if (c.bm == 128 && c.bn == 32)
+        hipLaunchKernelGGL((igemm_split3_kernel<128, 32, 4, 1, 256, TR, TERMS>), grid, dim3(256), 2 * (2 * 128 * 64 + 2 * 32 * 64), st, p);
+    else if (c.bm == 128 && c.bn == 128)
+        hipLaunchKernelGGL((igemm_split3_kernel<128, 128, 2, 4, 512, TR, TERMS>), grid, dim3(512), 65536, st, p);
+    else if (c.bm == 64 && c.bn == 128)
+        hipLaunchKernelGGL((igemm_split3_kernel<64, 128, 1, 4, 256, TR, TERMS>), grid, dim3(256), 2 * (2 * 64 * 64 + 2 * 128 * 64), st, p);
+    else if (c.bm == 128 && c.bn == 64)
+        hipLaunchKernelGGL((igemm_split3_kernel<128, 64, 2, 2, 256, TR, TERMS>), grid, dim3(256), 2 * (2 * 128 * 64 + 2 * 64 * 64), st, p);
+    else
+        return fail(ACIMG_EINVAL, "split3: unsupported tile %dx%d", c.bm, c.bn);
+    return check_launch("igemm_split3");
+}
+
+static int fwd_split_onthefly(const AcimgConvDesc* d, const float* x, const void* wsplit, const float* bias, float* y,
+                              const float* in_scale, const float* in_shift, int in_relu, float* stats, void* stream,
+                              bool bf16) {
+    int rc = check_desc(d, "conv2d_fwd_split3", true);
+    if (rc) return rc;
+    if (d->C % 32) return fail(ACIMG_EINVAL, "conv2d_fwd_split3: C=%d must be a multiple of 32", d->C);
+    if (d->ldw < d->K || !aligned16(x) || !aligned16(wsplit))
+        return fail(ACIMG_EINVAL, "conv2d_fwd_split3: ldw<K or unaligned operands");
+    if (conv_halo16_fwd_shape(d)) {
+        // (acimg_conv2d_fwd_split3_stats_rows already told the caller this shape leaves CONV_HALO16_WGS rows: no fallback)
+        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || !aligned16(y) || (d->ldy & 3) || (d->ldx & 3) ||
+            (bias && !aligned16(bias)) || (in_scale && (!aligned16(in_scale) || !aligned16(in_shift))))
+            return fail(ACIMG_EINVAL, "conv2d_fwd_split3: the halo form of this shape needs scale AND shift of an input affine, "
+                                      "16-byte aligned y / bias / affine and ldx, ldy multiples of 4");
+        ConvHaloParams q{};
+        q.a_scale = in_scale; q.a_shift = in_shift; q.a_relu = in_relu;
+        q.X = x; q.H = d->H; q.W = d->W; q.ldx = d->ldx; q.Wimg = static_cast<const char*>(wsplit);
+        q.w_lo_off = (unsigned)((size_t)d->ldw * d->R * d->S * d->C * 2);
+        q.Y = y; q.ldy = d->ldy; q.bias = bias; q.stats = stats; q.stats_ld = d->ldw;
+        hipStream_t st = (hipStream_t)stream;
+        if (bf16) return d->C == 64 ? launch_conv_halo16<SplitBF16, 1, 64, 32, 0>(q, d->N, st)
+                                    : launch_conv_halo16<SplitBF16, 1, 32, 32, 0>(q, d->N, st);
+        return d->C == 64 ? launch_conv_halo16<SplitF16, 3, 64, 32, 0>(q, d->N, st)
+                          : launch_conv_halo16<SplitF16, 3, 32, 32, 0>(q, d->N, st);
+    }
+    IgemmParams p = fwd_view(d);
+    split_ksteps(p);
+    p.A = x; p.a_scale = in_scale; p.a_shift = in_shift; p.a_relu = in_relu;
+    p.B = static_cast<const float*>(wsplit);
+    const long a_bytes = (((long)d->N * d->H * d->W - 1) * d->ldx + d->C) * 4;
+    const long b_bytes = (long)acimg_conv2d_split3_weight_bytes(d);
+    if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31)) return fail(ACIMG_EINVAL, "conv2d_fwd_split3: operand >= 2 GiB");
+    p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes;
+    p.e.Y = y; p.e.bias = bias; p.e.stats = stats;
+    epi_vec_flag(p.e);
+    if (bf16) return launch_split3<SplitBF16, 1>(p, (hipStream_t)stream);
+    return launch_split3<SplitF16>(p, (hipStream_t)stream);
+}
+
+/* data gradient on the bf16x3 path (stride-1 convs): a forward conv of gy with the flipped/transposed kernel */
+static int dgrad_split_onthefly(const AcimgConvDesc* d, const float* gy, int ldgy, const void* wsplit_t, float* dx,
+                                int lddx, const float* residual, int ldres, const float* mask, int ldmask,
+                                void* stream, int terms) {
+    int rc = check_desc(d, "conv2d_dgrad_split3");
+    if (rc) return rc;
+    if (d->stride != 1 || d->K % 32 || d->K > ldgy || (ldgy & 3))
+        return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: needs stride 1 and K %% 32 == 0 (K=%d)", d->K);
+    if (lddx <= 0) lddx = d->ldx;
+    if (conv_halo16_dgrad_shape(d) && aligned16(gy) && aligned16(wsplit_t) && aligned16(dx) && (lddx & 3) == 0 &&
+        (!residual || (aligned16(residual) && (ldres & 3) == 0)) && (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
+        // a forward SAME conv of gy (32 channels) with the flipped / transposed image: rows = the layer's input channels
+        ConvHaloParams q{};
+        q.X = gy; q.H = d->H; q.W = d->W; q.ldx = ldgy; q.Wimg = static_cast<const char*>(wsplit_t);
+        q.w_lo_off = (unsigned)((size_t)d->C * d->R * d->S * d->K * 2);
+        q.Y = dx; q.ldy = lddx; q.res = residual; q.ldres = ldres; q.mask = mask; q.ldmask = ldmask;
+        hipStream_t st = (hipStream_t)stream;
+        if (terms == 1) return d->C == 64 ? launch_conv_halo16<SplitBF16, 1, 32, 64, 1>(q, d->N, st)
+                                          : launch_conv_halo16<SplitBF16, 1, 32, 32, 1>(q, d->N, st);
+        return d->C == 64 ? launch_conv_halo16<SplitBF16, 3, 32, 64, 1>(q, d->N, st)
+                          : launch_conv_halo16<SplitBF16, 3, 32, 32, 1>(q, d->N, st);
+    }
+    IgemmParams p = flipped_view(d, d->K, ldgy);
+    split_ksteps(p);
+    p.A = gy; p.B = static_cast<const float*>(wsplit_t); p.Nld = d->C;
+    const long a_bytes = (((long)d->N * d->OH * d->OW - 1) * ldgy + d->K) * 4;
+    const long b_bytes = (long)acimg_conv2d_split3_dgrad_weight_bytes(d);
+    if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31)) return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: operand >= 2 GiB");
+    p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes;
+    EpiParams& e = p.e;
+    e.Y = dx; e.ldy = lddx; e.res = residual; e.ldres = ldres; e.mask = mask; e.ldmask = ldmask;
+    epi_vec_flag(e);
+    if (terms == 1) return launch_split3<SplitBF16, 1>(p, (hipStream_t)stream);
+    return launch_split3<SplitBF16>(p, (hipStream_t)stream);
+}
+
+// ---- tail split of the trunk kernel: which tiles to cut, and into how many K ranges ------------------------
+struct TailPlan { int whole, s, rem; };
+
+// One record per trunk kernel that is launched: what a launch and the occupancy question need to know about it, and what
+// was learnt about it in this process (both once per process).
+struct TrunkVariant {
+    const void* fn;
+    int threads;
+    size_t lds;                  // dynamic LDS bytes of a launch
+    int wgs_per_cu;              // resident workgroups per CU assumed when no device answers
+    bool lds_opt_in;             // its dynamic LDS exceeds 64 KiB: needs the opt-in once per process
+    TrunkVariant* slots_of;      // the sibling whose occupancy stands for this kernel's (nullptr: its own)
+    int slots;                   // resident workgroups on the device, 0 = not asked yet
+    bool opted_in;
+};
+// one-tile kernels: 2 stages x (hi, lo) x 64-byte rows; the epilogue restages the fp32 output tile there (+ 2 x WGM x BN
+// floats of statistics scratch behind it)
+static constexpr size_t tile_lds(size_t bm, size_t bn) { return std::max(2 * 2 * (bm + bn) * 64, bm * bn * 4) + 4 * 2 * bn * 4; }
+// (a 64-deep K step - whole 128-byte operand rows, one workgroup per CU - was measured slower on every trunk shape in
+//  round 2 and removed when the operands moved to LDS-tile order, which gives whole-line requests at two per CU)
+static constexpr size_t PERSISTENT_LDS = (size_t)2 * 4 * 128 * 64 + 4 * 2 * 128 * 4;    // 2 stages + statistics scratch
+static constexpr size_t ring_lds(size_t rows) { return 3 * 2 * (rows + 128) * 64 + 4 * 2 * 128 * 4; }
+static constexpr size_t HALO_LDS = (size_t)2 * (HALO_NB * 1024 + 64) + 2 * 2 * 128 * 64;
+#define ACIMG_KFN(...) reinterpret_cast<const void*>(__VA_ARGS__)
+static TrunkVariant TILE_128x128 = {ACIMG_KFN(igemm_split3d_kernel<128, 128, 2, 4, 512, 2, 2>), 512, tile_lds(128, 128), 2, false, nullptr};
+static TrunkVariant TILE_64x128 = {ACIMG_KFN(igemm_split3d_kernel<64, 128, 1, 4, 256, 2, 2>), 256, tile_lds(64, 128), 3, false, nullptr};
+static TrunkVariant TILE_128x64 = {ACIMG_KFN(igemm_split3d_kernel<128, 64, 2, 2, 256, 2, 2>), 256, tile_lds(128, 64), 3, false, nullptr};
+static TrunkVariant TILE1_128x128 = {ACIMG_KFN(igemm_split3d_kernel<128, 128, 2, 4, 512, 2, 2, 1>), 512, tile_lds(128, 128), 2, false, &TILE_128x128};
+static TrunkVariant TILE1_64x128 = {ACIMG_KFN(igemm_split3d_kernel<64, 128, 1, 4, 256, 2, 2, 1>), 256, tile_lds(64, 128), 3, false, &TILE_64x128};
+static TrunkVariant TILE1_128x64 = {ACIMG_KFN(igemm_split3d_kernel<128, 64, 2, 2, 256, 2, 2, 1>), 256, tile_lds(128, 64), 3, false, &TILE_128x64};
+static TrunkVariant PERSISTENT = {ACIMG_KFN(igemm_split3dp_kernel<32, 0>), 512, PERSISTENT_LDS, 2, false, nullptr};
+static TrunkVariant PERSISTENT_SPREAD = {ACIMG_KFN(igemm_split3dp_kernel<32, 1>), 512, PERSISTENT_LDS, 2, false, &PERSISTENT};
+static TrunkVariant PERSISTENT1 = {ACIMG_KFN(igemm_split3dp_kernel<32, 0, 1>), 512, PERSISTENT_LDS, 2, false, &PERSISTENT};
+static TrunkVariant PASS_STATS = {ACIMG_KFN(igemm_split3dp_kernel<32, 0, 3, 1>), 512, PERSISTENT_LDS, 2, false, nullptr};
+static TrunkVariant PASS_TAIL = {ACIMG_KFN(igemm_split3dp_kernel<32, 0, 3, 2>), 512, PERSISTENT_LDS, 2, false, nullptr};
+static TrunkVariant PASS_TAIL_PROJ = {ACIMG_KFN(igemm_split3dp_kernel<32, 0, 3, 3>), 512, PERSISTENT_LDS, 2, false, nullptr};
+static TrunkVariant RING_256 = {ACIMG_KFN(igemm_split3r_kernel<4>), 512, ring_lds(256), 1, true, nullptr};
+static TrunkVariant RING_128 = {ACIMG_KFN(igemm_split3r_kernel<2>), 512, ring_lds(128), 1, true, nullptr};
+static TrunkVariant HALO = {ACIMG_KFN(igemm_split3h_kernel<HALO_NB>), 512, HALO_LDS, 2, true, nullptr};
+#undef ACIMG_KFN
+
+static void opt_in_lds(TrunkVariant& v) {
+    if (!v.lds_opt_in || v.opted_in) return;
+    (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
+    v.opted_in = true;
+}
+// workgroups of `v` the device holds at once (the occupancy question is only answered for a kernel that may use its LDS:
+// it is opted in first)
+static int resident_slots(TrunkVariant& v) {
+    opt_in_lds(v);
+    TrunkVariant& o = v.slots_of ? *v.slots_of : v;
+    if (!o.slots) {
+        int dev = 0, ncu = 0, per = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, o.fn, o.threads, v.lds) != hipSuccess || ncu <= 0 || per <= 0) {
+            (void)hipGetLastError();
+            ncu = 256;                    // MI355X; no device (CPU-side sizing queries): same answer
+            per = o.wgs_per_cu;
+        }
+        o.slots = ncu * per;
+    }
+    return o.slots;
+}
+// `units` and `cap` reach the kernels that walk a unit list (persistent, ring).  The one-tile and halo kernels take p alone:
+// the runtime reads as many argument pointers as the kernel's metadata declares, so the two spare ones are never touched.
+// The launch's status is left to the caller's check_launch (hipGetLastError), as after hipLaunchKernelGGL.
+static void launch_trunk(const TrunkVariant& v, int nwg, hipStream_t st, IgemmParams& p, int units = 0, int cap = 0) {
+    void* args[] = {&p, &units, &cap};
+    (void)hipLaunchKernel(v.fn, dim3(nwg), dim3(v.threads), args, v.lds, st);
+}
+static TailPlan pick_tail(int T, int P, int KI, int max_units) {
+    const int rem = T % P;
+    TailPlan best{T, 1, 0};
+    if (rem == 0 || !g_cfg.tail_split) return best;
+    if (g_cfg.tail_s) {   // experiments only: force the number of K ranges
+        const int s = g_cfg.tail_s;
+        if (s > 1 && KI / s >= 1 && (long)rem * s <= max_units) return TailPlan{T - rem, s, rem};
+        return best;
+    }
+    // cost in K steps of the last round: whole tiles = KI; s ranges = rounds(rem*s) * ceil(KI/s) + hand-off
+    double best_cost = KI;
+    static const int cand[] = {2, 3, 4, 6, 8, 12, 16};
+    for (int s : cand) {
+        if (KI / s < 2 || (long)rem * s > max_units) break;
+        // hand-off calibrated on the trunk shapes (tools/tune_dma.py): partial store + ticket + the last arriver's
+        // s x 64 KiB of sc1 loads cost about 8 + s K steps, so 1x1 layers with few K steps are left whole
+        const double cost = (double)cdiv((long)rem * s, P) * cdiv(KI, s) + 8.0 + 1.0 * s;
+        if (cost < 0.9 * best_cost) {
+            best_cost = cost;
+            best = TailPlan{T - rem, s, rem};
+        }
+    }
+    return best;
+}
+static constexpr int TS_MAX_UNITS = 1024;      // partial slots (64 KiB each for a 128x128 tile; a 256x128 tile takes two)
+static constexpr size_t TS_COUNTER_BYTES = 4096;
+static constexpr size_t TS_WS_BYTES = TS_COUNTER_BYTES + (size_t)TS_MAX_UNITS * 128 * 128 * sizeof(float);   // acimg_conv2d_fwd_split3p_workspace
+
+// Tail wiring of a trunk launch: with the caller's workspace (and a kernel that takes the split: `allow`) the tiles of the
+// last, partial round over `slots` workgroups are cut into K ranges; the ticket counters and partial slots are wired either
+// way.  Returns the number of work units: whole tiles + K ranges.
+static int wire_tail(IgemmParams& p, void* ws, size_t ws_bytes, int tiles, int slots, int max_units, bool allow) {
+    TailPlan t{tiles, 1, 0};
+    if (allow && ws && ws_bytes >= TS_WS_BYTES) t = pick_tail(tiles, slots, p.kiters, max_units);
+    p.ts_whole = t.whole; p.ts_s = t.s;
+    p.ts_counters = static_cast<int*>(ws);
+    p.ts_partial = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + TS_COUNTER_BYTES) : nullptr;
+    return t.whole + t.rem * t.s;
+}
+
+#if defined(ACIMG_STAMP) || defined(ACIMG_ABLATE)
+static float* g_stamp_buf = nullptr;      // diagnostic build only (tools/build_stamp.sh): never in libacimg.so
+static int g_stamp_nostore = 0;           // ablation: the persistent kernel's output stores go out of range (dropped)
+#endif
+
+// the two passes of a conv whose raw output never reaches memory (igemm_split3dp_kernel, EPI 1 / 2)
+struct Split3pTail {
+    int mode;                      // 1: statistics only; 2: relu(acc * scale + shift + shortcut) -> split planes;
+                                   // 3: the same with a projection shortcut (raw fp32 + its own scale / shift)
+    const float* scale;
+    const float* shift;
+    const void* sc_planes;         // mode 3: the fp32 [M][K] output of the shortcut conv
+    size_t sc_lo_off;
+    void* out_planes;
+    size_t out_lo_off;
+    const float* scale2;
+    const float* shift2;
+};
+
+static int fwd_presplit(const AcimgConvDesc* d, const void* x_planes, size_t x_lo_off, const void* wsplit, float* y,
+                        float* stats, void* ws, size_t ws_bytes, void* stream, const int terms,
+                        const Split3pTail* tail = nullptr) {
+    int rc = check_desc(d, "conv2d_fwd_split3p");
+    if (rc) return rc;
+    if (d->C % 32) return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: C=%d must be a multiple of 32", d->C);
+    if (d->ldw < d->K || !aligned16(x_planes) || !aligned16(wsplit) || !aligned16(y) || (d->ldy & 3) || d->ldx != d->C ||
+        (x_lo_off & 15))
+        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: ldw<K, ldx != C (split-format tensors are dense) or unaligned operands");
+    IgemmParams p = fwd_view(d);
+    split_ksteps(p);
+    p.A = static_cast<const float*>(x_planes); p.B = static_cast<const float*>(wsplit);
+    const long plane = (long)acimg_split_plane_bytes((long)d->N * d->H * d->W, d->C);
+    const long a_bytes = (long)x_lo_off + plane;
+    const long b_bytes = (long)acimg_conv2d_split3_weight_bytes(d);
+    if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || (long)x_lo_off < plane)
+        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: operand >= 2 GiB or overlapping planes");
+    p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes; p.a_lo_off = (unsigned)x_lo_off;
+    p.b_brick = (unsigned)split3_rowmajor_bytes(d);
+    EpiParams& e = p.e;
+    e.Y = y; e.stats = stats; e.vec = 1;
+    const TrunkPick t = pick_trunk(d, terms, tail != nullptr);
+    hipStream_t st = (hipStream_t)stream;
+    // XCD-aware rasterisation: the ~64 tiles resident on one XCD (32 of the ring kernel's, one workgroup per CU) form a
+    // (64/gn) x gn rectangle of the tile grid
+    p.ras_tiles_m = cdiv(p.M, t.bm);
+    p.ras_tiles_n = cdiv(d->K, t.bn);
+    p.ras_gn = std::min(p.ras_tiles_n, 8);
+    p.ras_gm = std::max(1, (t.kind == TRUNK_RING ? 32 : 64) / p.ras_gn);
+    const int T = p.ras_tiles_m * p.ras_tiles_n;
+    const bool t128 = t.bm == 128 && t.bn == 128;
+    if (tail) {
+        if (terms != 3 || !t128 || t.big_out || d->K % 128 || d->ldy != d->K || d->ldw != d->K)
+            return fail(ACIMG_EINVAL, "conv2d_fwd_split3p (two-pass): needs 128x128 tiles, K %% 128 == 0, dense output < 2 GiB");
+        TrunkVariant& v = tail->mode == 1 ? PASS_STATS : tail->mode == 2 ? PASS_TAIL : PASS_TAIL_PROJ;
+        const int slots = resident_slots(v);
+        const int units = wire_tail(p, ws, ws_bytes, T, slots, TS_MAX_UNITS, true);
+        const int nwg = std::min(units, slots);
+        const char* what = "conv2d_fwd_split3p_stats";
+        e.Y = nullptr;
+        if (tail->mode != 1) {
+            const long oplane = (long)acimg_split_plane_bytes((long)p.M, d->K);
+            if (!aligned16(tail->sc_planes) || !aligned16(tail->out_planes) || (tail->out_lo_off & 15) ||
+                (long)tail->out_lo_off < oplane || (long)tail->out_lo_off + oplane >= (1L << 31))
+                return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: unaligned / overlapping / >= 2 GiB split-format operands");
+            e.stats = nullptr;
+            e.f_scale = tail->scale; e.f_shift = tail->shift;
+            e.f_sc = static_cast<const char*>(tail->sc_planes);
+            e.f_out = static_cast<char*>(tail->out_planes); e.f_out_lo = (unsigned)tail->out_lo_off;
+            e.f_out_bytes = (unsigned)(tail->out_lo_off + oplane);
+            if (tail->mode == 3) {
+                e.f_scale2 = tail->scale2; e.f_shift2 = tail->shift2;
+                e.f_sc_lo = 0; e.f_sc_bytes = (unsigned)((long)p.M * d->K * 4);      // < 2 GiB: big_out was refused above
+                what = "conv2d_fwd_split3p_tail_proj";
+            } else {
+                if ((tail->sc_lo_off & 15) || (long)tail->sc_lo_off < oplane || (long)tail->sc_lo_off + oplane >= (1L << 31))
+                    return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: unaligned / overlapping / >= 2 GiB shortcut planes");
+                e.f_sc_lo = (unsigned)tail->sc_lo_off;
+                e.f_sc_bytes = (unsigned)(tail->sc_lo_off + oplane);
+                what = "conv2d_fwd_split3p_tail";
+            }
+        }
+        launch_trunk(v, nwg, st, p, units, nwg);
+        return check_launch(what);
+    }
+    if (t.kind == TRUNK_HALO) {
+        // one tile per workgroup, K walked as (channel chunk, tap) over one staged patch per chunk; tail tiles in K ranges
+        const int units = wire_tail(p, ws, ws_bytes, T, resident_slots(HALO), TS_MAX_UNITS, true);
+        launch_trunk(HALO, units, st, p);
+        return check_launch("conv2d_fwd_split3p (halo)");
+    }
+#if defined(ACIMG_STAMP) || defined(ACIMG_ABLATE)
+    p.slab = g_stamp_buf;
+    p.flip = g_stamp_nostore;
+#endif
+    if (t.kind == TRUNK_RING) {
+        // one workgroup per CU walks units blockIdx.x, blockIdx.x + P, ... (whole tiles, then K ranges of the tail tiles)
+        TrunkVariant& v = t.bm == 256 ? RING_256 : RING_128;
+        const int slots = resident_slots(v);
+        const int units = wire_tail(p, ws, ws_bytes, T, slots, TS_MAX_UNITS * 128 / t.bm, true);
+        const int nwg = std::min(units, slots);
+        p.splits = g_cfg.trunk_stagger > 0 ? 2 : 1;   // ring kernel: waves 4-7 do a step's scalar work before their first MFMA group
+        launch_trunk(v, nwg, st, p, units, nwg);
+        return check_launch("conv2d_fwd_split3p (ring)");
+    }
+    if (t.kind == TRUNK_PERSISTENT) {
+        TrunkVariant& v = terms == 1 ? PERSISTENT1 : g_cfg.trunk_dma_pos == 1 ? PERSISTENT_SPREAD : PERSISTENT;
+        const int slots = resident_slots(v);
+        const int units = wire_tail(p, ws, ws_bytes, T, slots, TS_MAX_UNITS, true);
+        p.splits = g_cfg.trunk_stagger > 0 ? g_cfg.trunk_stagger * (p.kiters * 2500 + 8000) / 100 : 1;
+        // a workgroup per resident slot walks units blockIdx.x, blockIdx.x + P, ...: whole tiles first (with the
+        // next tile's first operand stage and addresses prepared under the current tile's last K step and output
+        // stores), then the K ranges of the tail tiles
+        const int nwg = std::min(units, slots);
+        launch_trunk(v, nwg, st, p, units, nwg);
+        return check_launch("conv2d_fwd_split3p");
+    }
+    // one tile (or K range of a tail tile) per workgroup
+    TrunkVariant& v = t128 ? (terms == 1 ? TILE1_128x128 : TILE_128x128)
+                    : t.bm == 64 ? (terms == 1 ? TILE1_64x128 : TILE_64x128) : (terms == 1 ? TILE1_128x64 : TILE_128x64);
+    const int units = wire_tail(p, ws, ws_bytes, T, resident_slots(v), TS_MAX_UNITS, t128);
+    launch_trunk(v, units, st, p);
+    return check_launch("conv2d_fwd_split3p");
+}
+
+/* ---- tap-GEMM helpers (see the kernels above) ---- */
+static int tapconv_check(const AcimgConvDesc* d, const char* who) {
+    int rc = check_desc(d, who);
+    if (rc) return rc;
+    if (d->stride != 1 || d->pad_t || d->pad_l || d->OH != d->H - d->R + 1 || d->OW != d->W - d->S + 1)
+        return fail(ACIMG_EINVAL, "%s: stride-1 VALID convolutions only", who);
+    if (d->K > 64) return fail(ACIMG_EINVAL, "%s: K=%d > 64 (this form is for few output channels)", who, d->K);
+    return ACIMG_OK;
+}
+
+/* weight + bias gradient on the bf16x3 MFMA path (same contract as acimg_conv2d_wgrad) */
+static int wgrad_split_onthefly(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy, float* dw, float* db,
+                                void* ws, size_t ws_bytes, void* stream, int terms) {
+    int rc = check_desc(d, "conv2d_wgrad_split3");
+    if (rc) return rc;
+    const int kp = up4(d->K);
+    if (kp > ldgy || kp > d->ldw) return fail(ACIMG_EINVAL, "conv2d_wgrad_split3: padded K exceeds ldgy/ldw");
+    WgradParams p{};
+    p.X = x; p.H = d->H; p.W = d->W; p.C = d->C; p.ldx = d->ldx;
+    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
+    p.M = d->N * d->OH * d->OW; p.KK = d->R * d->S * d->C;
+    p.G = gy; p.ldg = ldgy; p.Ngemm = kp; p.Nld = kp; p.ldo = d->ldw;
+    return launch_wgrad(p, dw, db, ws, ws_bytes, (hipStream_t)stream, true, terms);
+}
+
+}  // namespace acimg
+
+using namespace acimg;
+
+// ==========================================================================================
+// C ABI
+// ==========================================================================================
+extern "C" {
+
+int acimg_conv2d_stats_rows(const AcimgConvDesc* d) {
+    if (few16_fwd_shape(d)) return FEW16_WGS;        // the few-channel MFMA kernel leaves one row per workgroup
+    return cdiv((long)d->N * d->OH * d->OW, stats_block_rows(d));
+}
+
+int acimg_conv2d_fwd_tiling(const AcimgConvDesc* d, int* out) {
+    if (!d || !out) return fail(ACIMG_EINVAL, "conv2d_fwd_tiling: null argument");
+    const int M = d->N * d->OH * d->OW;
+    TileCfg c = pick_cfg(M, d->K);
+    out[0] = c.bm;
+    out[1] = c.bn;
+    out[2] = pick_splits(M, d->K, c, fwd_kiters(d));
+    return ACIMG_OK;
+}
+
+int acimg_config_default(AcimgConfig* c) {
+    if (!c) return fail(ACIMG_EINVAL, "config_default: null");
+    *c = AcimgConfig{320, 768, 1, 128, 1, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0};
+    return ACIMG_OK;
+}
+
+int acimg_configure(const AcimgConfig* c) {
+    if (!c) return fail(ACIMG_EINVAL, "configure: null");
+    if (c->splitk_cut < 0 || c->splitk_target < 1 || c->wgrad_minpix < 1 || c->tail_s < 0)
+        return fail(ACIMG_EINVAL, "configure: negative / zero tuning value");
+    if (c->trunk_persistent < 0 || c->trunk_persistent > 2) return fail(ACIMG_EINVAL, "configure: trunk_persistent is 0, 1 or 2");
+    if (c->trunk_dma_pos < 0 || c->trunk_dma_pos > 1) return fail(ACIMG_EINVAL, "configure: trunk_dma_pos is 0 or 1");
+    if (c->trunk_stagger < 0 || c->trunk_stagger > 100) return fail(ACIMG_EINVAL, "configure: trunk_stagger is a percentage");
+    if (c->trunk_bk != 0 && c->trunk_bk != 32)
+        return fail(ACIMG_EINVAL, "configure: trunk_bk must be 0 or 32 (the 64-deep K step was measured slower and removed)");
+    if (c->trunk_ring < 0 || c->trunk_ring > 2) return fail(ACIMG_EINVAL, "configure: trunk_ring is 0, 1 or 2");
+    if (c->trunk_ring_bm != 0 && c->trunk_ring_bm != 128 && c->trunk_ring_bm != 256)
+        return fail(ACIMG_EINVAL, "configure: trunk_ring_bm must be 0 (per shape), 128 or 256");
+    if (c->trunk_halo < 0 || c->trunk_halo > 2) return fail(ACIMG_EINVAL, "configure: trunk_halo is 0, 1 or 2");
+    if (c->split3_tile_bm || c->split3_tile_bn) {
+        const int bm = c->split3_tile_bm, bn = c->split3_tile_bn;
+        if (!((bm == 128 && bn == 128) || (bm == 64 && bn == 128) || (bm == 128 && bn == 64)))
+            return fail(ACIMG_EINVAL, "configure: split3 tile %dx%d is not an instantiated tile", bm, bn);
+    }
+    g_cfg = *c;
+    return ACIMG_OK;
+}
+
+size_t acimg_conv2d_fwd_workspace(const AcimgConvDesc* d) {
+    const size_t a = igemm_ws_bytes(d->N * d->OH * d->OW, d->K, fwd_kiters(d));
+    const size_t b = direct_shape(d->C, d->K) ? direct_ws_bytes(d->R, d->S, d->C, (d->K + 7) & ~7) : 0;
+    const size_t c = skinny_fwd_ws_bytes(d);
+    const size_t f = few16_fwd_shape(d) ? few16_ws_bytes(d->C, d->K) : 0;
+    return std::max(std::max(a, f), std::max(b, c));
+}
+
+int acimg_conv2d_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
+                     float* y, const float* in_scale, const float* in_shift, int in_relu,
+                     float* stats, void* ws, size_t ws_bytes, void* tickets, void* stream) {
+    int rc = check_desc(d, "conv2d_fwd");
+    if (rc) return rc;
+    if (d->ldw < d->K) return fail(ACIMG_EINVAL, "conv2d_fwd: ldw < K");
+    if (skinny_shape(d) && !in_scale && !in_shift && !in_relu && !stats && ws && ws_bytes >= skinny_fwd_ws_bytes(d) && aligned16(x) &&
+        aligned16(w) && aligned16(y) && aligned16(ws) && (!bias || aligned16(bias)) && (d->ldw & 3) == 0 && (d->ldx & 3) == 0 &&
+        (d->ldy & 3) == 0) {
+        // the VAE heads' dense layer: weight rows read once in whole lines, K slabs combined in slab order
+        SkinnyParams q{};
+        q.W = w; q.X = x; q.out = y; q.bias = bias; q.act = d->act; q.part = static_cast<float*>(ws);
+        q.M = d->N; q.C = d->C; q.N = d->K; q.ldw = d->ldw; q.ldx = d->ldx; q.ldo = d->ldy;
+        q.slabs = cdiv(d->C, SKINNY_KS);
+        const dim3 grid(q.slabs, cdiv(d->K, 64));
+        const int mb = cdiv(d->N, 16);
+        if (mb == 1) hipLaunchKernelGGL(skinny_fwd_kernel<1>, grid, dim3(64), 0, (hipStream_t)stream, q);
+        else if (mb == 2) hipLaunchKernelGGL(skinny_fwd_kernel<2>, grid, dim3(64), 0, (hipStream_t)stream, q);
+        else if (mb == 3) hipLaunchKernelGGL(skinny_fwd_kernel<3>, grid, dim3(64), 0, (hipStream_t)stream, q);
+        else hipLaunchKernelGGL(skinny_fwd_kernel<4>, grid, dim3(64), 0, (hipStream_t)stream, q);
+        rc = check_launch("conv2d_fwd (skinny)");
+        if (rc) return rc;
+        hipLaunchKernelGGL(skinny_fwd_reduce_kernel, dim3(cdiv(d->N * (d->K / 4), 256)), dim3(256), 0, (hipStream_t)stream, q);
+        return check_launch("conv2d_fwd (skinny reduce)");
+    }
+    if (few16_fwd_shape(d)) {
+        // acimg_conv2d_stats_rows(d) promised one statistics row per workgroup of this kernel: no silent fallback
+        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || !aligned16(x) || !aligned16(y) || (d->ldy & 3) ||
+            d->ldy < d->K || (bias && !aligned16(bias)) || (in_scale && (!aligned16(in_scale) || !aligned16(in_shift))))
+            return fail(ACIMG_EINVAL, "conv2d_fwd: few-channel MFMA shape with half an input affine or unaligned operands");
+        FewParams q{};
+        q.a_scale = in_scale; q.a_shift = in_shift; q.a_relu = in_relu;
+        q.X = x; q.H = d->H; q.W = d->W; q.ldx = d->ldx; q.Y = y; q.ldy = d->ldy; q.nout = d->K; q.bias = bias;
+        q.Hin = q.SH = d->H; q.Win = q.SW = d->W; q.dil = 1; q.pad_t = 1; q.pad_l = 1;
+        q.stats = stats; q.stats_ld = d->ldw;
+        q.w = w; q.ldw = d->ldw; q.wrows = d->C; q.cin = d->C; q.mode = 0;
+        return dispatch_few16<0>(q, d->N, d->C, d->K, ws, ws_bytes, (hipStream_t)stream);
+    }
+    if (direct_ok(d->C, d->K, d->ldy, 0, y, bias, nullptr, in_scale != nullptr, nullptr) &&
+        (long)d->N * d->OH * d->OW >= 65536) {
+        DirectParams q{};
+        q.x = x; q.ldx = d->ldx; q.H = d->H; q.W = d->W; q.C = d->C;
+        q.y = y; q.ldy = d->ldy; q.OH = d->OH; q.OW = d->OW; q.K = d->K;
+        q.R = d->R; q.S = d->S; q.stride = d->stride; q.pad_t = d->pad_t; q.pad_l = d->pad_l;
+        q.w = w; q.ldw = d->ldw; q.mode = 0; q.wrows = d->C; q.bias = bias; q.act = d->act;
+        q.M = (long)d->N * d->OH * d->OW;
+        const bool fuse_stats = stats && stats_block_rows(d) == 256 && d->act == ACIMG_ACT_NONE;
+        if (fuse_stats) { q.stats = stats; q.stats_ld = d->ldw; }
+        rc = launch_direct(q, ws, ws_bytes, (hipStream_t)stream);
+        if (!rc && stats && !fuse_stats) {   // batch-norm partials of y = conv + bias, in acimg_conv2d_stats_rows(d) row blocks
+            hipLaunchKernelGGL(partial_stats_kernel, dim3(acimg_conv2d_stats_rows(d)), dim3(256), 0, (hipStream_t)stream,
+                               y, d->ldy, (int)q.M, d->K, stats, d->ldw, stats_block_rows(d));
+            rc = check_launch("partial_stats");
+        }
+        return rc;
+    }
+    IgemmParams p = fwd_view(d);
+    p.A = x; p.rowrun = (d->S > 1 && d->ldx == d->C) ? 1 : 0;
+    p.a_scale = in_scale; p.a_shift = in_shift; p.a_relu = in_relu;
+    p.B = w; p.ldb = d->ldw;
+    p.e.Y = y; p.e.bias = bias; p.e.stats = stats;
+    return launch_igemm(p, false, ws, ws_bytes, tickets, (hipStream_t)stream);
+}
+
+size_t acimg_conv2d_dgrad_workspace(const AcimgConvDesc* d) {
+    if (dgrad_halo16_narrow_shape(d)) return DGRAD_HALO16_NARROW_WS + 256;
+    if (dgrad_is_patch(d)) return igemm_ws_bytes(d->N * d->OH * d->OW, d->R * d->S * d->C, cdiv(up4(d->K), 32));
+    const int ca = up4(d->K);
+    if (subpixel_ok(d->stride, d->C, ca))   // sub-pixel form: combined weights + the GEMM's own split-K slabs
+        return subpixel_ws_bytes(d->N, d->H, d->W, -d->pad_t, -d->pad_l, d->R, d->S, ca, d->C);
+    if (d->stride > 1)   // zero-inserted copy of gy, then the stride-1 path
+        return dilated_bytes(d->N, d->OH, d->OW, ca, d->stride) +
+               igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * d->S * cdiv(ca, 32)) +
+               igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * cdiv(d->S * ca, 32)) +
+               (direct_shape(ca, d->C) ? std::max(direct_ws_bytes(d->R, d->S, ca, (d->C + 7) & ~7), few16_ws_bytes(ca, d->C)) : 0);
+    // rowrun depends on ldgy, unknown here: per-tap kiters is the larger bound for splits
+    return igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * d->S * cdiv(ca, 32)) +
+           igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * cdiv(d->S * ca, 32)) +
+           (direct_shape(ca, d->C) ? std::max(direct_ws_bytes(d->R, d->S, ca, (d->C + 7) & ~7), few16_ws_bytes(ca, d->C)) : 0);
+}
+
+int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w,
+                       float* dx, int lddx, const float* residual, int ldres, const float* mask,
+                       int ldmask, void* ws, size_t ws_bytes, void* tickets, void* stream) {
+    int rc = check_desc(d, "conv2d_dgrad");
+    if (rc) return rc;
+    const int ca = up4(d->K);
+    if (ca > ldgy || ca > d->ldw || (ldgy & 3)) return fail(ACIMG_EINVAL, "conv2d_dgrad: padded K=%d exceeds ldgy=%d/ldw=%d", ca, ldgy, d->ldw);
+    if (skinny_shape(d) && aligned16(gy) && aligned16(w) && (d->ldw & 3) == 0) {
+        // a dense layer over a few batch rows (the 28 416 -> 300 VAE heads): the weight matrix is read once, in rows
+        SkinnyParams q{};
+        q.W = w; q.G = gy; q.out = dx; q.res = residual; q.mask = mask;
+        q.M = d->N; q.C = d->C; q.N = ca;
+        q.ldw = d->ldw; q.ldg = ldgy; q.ldo = lddx > 0 ? lddx : d->ldx; q.ldres = ldres; q.ldmask = ldmask;
+        if (q.ldo < d->C) return fail(ACIMG_EINVAL, "conv2d_dgrad: lddx < C");
+        const dim3 grid(cdiv(cdiv(d->C, 16), 4));
+        const int mb = cdiv(d->N, 16);
+        if (mb == 1) hipLaunchKernelGGL(skinny_dgrad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, q);
+        else if (mb == 2) hipLaunchKernelGGL(skinny_dgrad_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, q);
+        else if (mb == 3) hipLaunchKernelGGL(skinny_dgrad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, q);
+        else hipLaunchKernelGGL(skinny_dgrad_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, q);
+        return check_launch("conv2d_dgrad (skinny)");
+    }
+    if (lddx <= 0) lddx = d->ldx;
+    if (lddx < d->C) return fail(ACIMG_EINVAL, "conv2d_dgrad: lddx < C");
+    if (subpixel_ok(d->stride, d->C, ca) && !dgrad_is_patch(d))
+        // dx[2 oy - pad_t + r][2 ox - pad_l + s][c] += gy[oy][ox][k] w[r][s][c][k]: the sub-pixel form over gy's own grid
+        return launch_subpixel(gy, d->N, d->OH, d->OW, ca, ldgy, w, d->R, d->S, d->ldw, d->C, dx, lddx, d->H, d->W, -d->pad_t,
+                               -d->pad_l, nullptr, residual, ldres, mask, ldmask, ACIMG_ACT_NONE, ws, ws_bytes, tickets,
+                               (hipStream_t)stream, "conv2d_dgrad");
+    if (dgrad_halo16_narrow_shape(d) && aligned16(gy) && aligned16(dx) && (lddx & 3) == 0 && ws && aligned16(ws) &&
+        ws_bytes >= DGRAD_HALO16_NARROW_WS && (!residual || ((ldres & 3) == 0 && aligned16(residual))) &&
+        (!mask || ((ldmask & 3) == 0 && aligned16(mask))))
+        return dgrad_halo16_narrow(d, gy, ldgy, w, dx, lddx, residual, ldres, mask, ldmask, ws, (hipStream_t)stream);
+    if (few16_dgrad_shape(d) && !subpixel_ok(d->stride, d->C, ca) && !mask && aligned16(gy) && aligned16(dx) && (lddx & 3) == 0 &&
+        ws && aligned16(ws) && ws_bytes >= few16_ws_bytes(ca, d->C) && (!residual || ((ldres & 3) == 0 && aligned16(residual)))) {
+        // dx[h][w][c] = sum gy1[h - (2 - pad_t) + r'][w - (2 - pad_l) + s'][k] W[2 - r'][2 - s'][c][k], gy1 = gy (stride 1) or
+        // its zero-inserted view (stride 2), zero outside
+        FewParams q{};
+        q.X = gy; q.ldx = ldgy; q.SH = d->OH; q.SW = d->OW; q.dil = d->stride;
+        q.Hin = (d->OH - 1) * d->stride + 1; q.Win = (d->OW - 1) * d->stride + 1;
+        q.pad_t = 2 - d->pad_t; q.pad_l = 2 - d->pad_l;
+        q.H = d->H; q.W = d->W; q.Y = dx; q.ldy = lddx; q.nout = d->C;
+        q.res = residual; q.ldres = ldres;
+        q.w = w; q.ldw = d->ldw; q.wrows = d->C; q.cin = d->K; q.mode = 1;
+        return dispatch_few16<1>(q, d->N, ca, d->C, ws, ws_bytes, (hipStream_t)stream);
+    }
+    if (d->stride > 1 && !dgrad_is_patch(d)) {
+        // general stride: the strided conv is a subsampled stride-1 conv, so its data gradient is the stride-1
+        // data gradient of the zero-inserted gy
+        const size_t db = dilated_bytes(d->N, d->OH, d->OW, ca, d->stride);
+        if (ws_bytes < db || !ws) return fail(ACIMG_EWORKSPACE, "conv2d_dgrad: workspace too small for the dilated gradient");
+        const int OH1 = (d->OH - 1) * d->stride + 1, OW1 = (d->OW - 1) * d->stride + 1;
+        const long opix = (long)d->N * OH1 * OW1;
+        if (opix * ca >= (1L << 31)) return fail(ACIMG_EINVAL, "conv2d_dgrad: dilated gradient exceeds 2^31 elements");
+        hipLaunchKernelGGL(dilate2d_kernel, dim3(cdiv(opix * (ca / 4), 256)), dim3(256), 0, (hipStream_t)stream, gy, ldgy,
+                           static_cast<float*>(ws), opix, d->OH, d->OW, OH1, OW1, ca, d->stride);
+        rc = check_launch("dilate2d");
+        if (rc) return rc;
+        AcimgConvDesc d1 = *d;
+        d1.stride = 1; d1.OH = OH1; d1.OW = OW1;
+        return acimg_conv2d_dgrad(&d1, static_cast<const float*>(ws), ca, w, dx, lddx, residual, ldres, mask, ldmask,
+                                  static_cast<char*>(ws) + db, ws_bytes - db, tickets, stream);
+    }
+    if (d->stride == 1 && direct_ok(ca, d->C, lddx, ldres, dx, nullptr, residual, false, mask) &&
+        (long)d->N * d->H * d->W >= 65536) {
+        DirectParams q{};
+        q.x = gy; q.ldx = ldgy; q.H = d->OH; q.W = d->OW; q.C = ca;
+        q.y = dx; q.ldy = lddx; q.OH = d->H; q.OW = d->W; q.K = d->C;
+        q.R = d->R; q.S = d->S; q.stride = 1; q.pad_t = d->R - 1 - d->pad_t; q.pad_l = d->S - 1 - d->pad_l;
+        q.w = w; q.ldw = d->ldw; q.mode = 1; q.wrows = d->C; q.act = ACIMG_ACT_NONE;
+        q.res = residual; q.ldres = ldres;
+        q.M = (long)d->N * d->H * d->W;
+        return launch_direct(q, ws, ws_bytes, (hipStream_t)stream);
+    }
+    IgemmParams p{};
+    if (d->stride == 1) {
+        p = flipped_view(d, ca, ldgy);
+        p.rowrun = (d->S > 1 && ldgy == ca) ? 1 : 0;
+        p.tap_stride = (long)d->C * d->ldw; p.flip = 1;
+    } else {
+        // patch scatter: rows = output pixels, columns = (tap, c)
+        p.H = d->OH; p.W = d->OW; p.C = ca; p.lda = ldgy; p.OH = d->OH; p.OW = d->OW;
+        p.R = 1; p.S = 1; p.stride = 1;
+        p.M = d->N * d->OH * d->OW;
+        p.Ngemm = d->R * d->S * d->C;
+        p.e.M = p.M; p.e.Nstore = p.Ngemm; p.e.act = ACIMG_ACT_NONE;
+        p.e.scatter = 1; p.e.Ko = d->C; p.e.Sq = d->S; p.e.sc = d->stride;
+        p.e.YH = d->H; p.e.YW = d->W; p.e.AH = d->OH; p.e.AW = d->OW;
+    }
+    p.A = gy; p.B = w; p.ldb = d->ldw;
+    p.e.Y = dx; p.e.ldy = lddx; p.e.res = residual; p.e.ldres = ldres; p.e.mask = mask; p.e.ldmask = ldmask;
+    return launch_igemm(p, true, ws, ws_bytes, tickets, (hipStream_t)stream);
+}
+
+size_t acimg_conv2d_wgrad_workspace(const AcimgConvDesc* d) {
+    return wgrad_ws_bytes(d->N * d->OH * d->OW, d->R * d->S * d->C, up4(d->K), d->ldw) + colsum_ws_bytes(up4(d->K));
+}
+
+int acimg_conv2d_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
+                       float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_desc(d, "conv2d_wgrad");
+    if (rc) return rc;
+    const int kp = up4(d->K);
+    if (kp > ldgy || kp > d->ldw) return fail(ACIMG_EINVAL, "conv2d_wgrad: padded K exceeds ldgy/ldw");
+    if (skinny_shape(d) && aligned16(x) && aligned16(gy) && aligned16(dw) && (!db || aligned16(db)) && (d->ldw & 3) == 0 &&
+        (ldgy & 3) == 0 && (d->ldx & 3) == 0) {
+        // the same dense layer's weight gradient: every weight row is written once, 256 contiguous bytes per wave
+        SkinnyParams q{};
+        q.X = x; q.G = gy; q.out = dw; q.db = db;
+        q.M = d->N; q.C = d->C; q.N = kp;
+        q.ldw = d->ldw; q.ldg = ldgy; q.ldx = d->ldx;
+        const int ngroups = cdiv(kp, 64);
+        const int tasks = cdiv(d->C, 64) * ngroups;
+        hipLaunchKernelGGL(skinny_wgrad_kernel, dim3(cdiv(tasks, 4)), dim3(256), 0, (hipStream_t)stream, q, ngroups);
+        return check_launch("conv2d_wgrad (skinny)");
+    }
+    WgradParams p{};
+    p.X = x; p.H = d->H; p.W = d->W; p.C = d->C; p.ldx = d->ldx;
+    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
+    p.M = d->N * d->OH * d->OW; p.KK = d->R * d->S * d->C;
+    p.G = gy; p.ldg = ldgy; p.Ngemm = kp; p.Nld = kp; p.ldo = d->ldw;
+    return launch_wgrad(p, dw, db, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t acimg_deconv_workspace(const AcimgConvDesc* d) {
+    size_t a = igemm_ws_bytes(d->N * d->H * d->W, d->R * d->S * d->K, cdiv(d->C, 32));
+    size_t b = igemm_ws_bytes(d->N * d->H * d->W, d->C, d->R * d->S * cdiv(up4(d->K), 32));
+    size_t c = wgrad_ws_bytes(d->N * d->H * d->W, d->R * d->S * up4(d->K), d->C, d->ldw) + colsum_ws_bytes(up4(d->K));
+    size_t m = a > b ? a : b;
+    m = m > c ? m : c;
+    if (patch2_shape(d)) {                      // weight gradient of the pointwise form: one 32 x ldw slab per workgroup
+        const size_t pw = (size_t)PATCH2_WGRAD_WGS * (32 * d->ldw + 8) * sizeof(float);
+        m = m > pw ? m : pw;
+    }
+    if (direct_shape(up4(d->K), d->C)) {        // data gradient on the direct few-channel kernel
+        const size_t dd = direct_ws_bytes(d->R, d->S, up4(d->K), (d->C + 7) & ~7);
+        m = m > dd ? m : dd;
+    }
+    if ((d->R > d->stride || d->S > d->stride) && subpixel_ok(d->stride, d->K, d->C)) {   // forward in the sub-pixel form
+        const size_t sp = subpixel_ws_bytes(d->N, d->OH, d->OW, 0, 0, d->R, d->S, d->C, d->K);
+        return m > sp ? m : sp;
+    }
+    if (d->R > d->stride || d->S > d->stride)   // forward goes through a zero-inserted copy of x
+        m += dilated_bytes(d->N, d->H, d->W, d->C, d->stride) +
+             igemm_ws_bytes(d->N * d->OH * d->OW, d->K, d->R * d->S * cdiv(d->C, 32)) +
+             igemm_ws_bytes(d->N * d->OH * d->OW, d->K, d->R * cdiv(d->S * d->C, 32));
+    return m;
+}
+
+int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
+                     float* y, void* ws, size_t ws_bytes, void* tickets, void* stream) {
+    int rc = check_desc(d, "deconv_fwd");
+    if (rc) return rc;
+    if (d->ldw < d->C || (d->K & 3)) return fail(ACIMG_EINVAL, "deconv_fwd: ldw<C or K%%4");
+    if (d->R > d->stride || d->S > d->stride) {
+        // overlapping patches (tf conv2d_transpose VALID: OH = (H-1)*stride + R): y = stride-1 "full" correlation
+        // of the zero-inserted x with the flipped kernel = the data gradient of the stride-1 VALID conv
+        // [OH,OW,K] -> [(H-1)s+1, (W-1)s+1, C] whose HWIO kernel is this layer's [R][S][K][C]
+        if (d->OH != (d->H - 1) * d->stride + d->R || d->OW != (d->W - 1) * d->stride + d->S)
+            return fail(ACIMG_EINVAL, "deconv_fwd: kernel>stride needs OH=(H-1)*stride+R");
+        if (subpixel_ok(d->stride, d->K, d->C))
+            // y[2 h + r][2 w + s][k] += x[h][w][c] W[r][s][k][c]: the sub-pixel form over x's own grid (every output
+            // pixel belongs to exactly one parity class: written once, bias included)
+            return launch_subpixel(x, d->N, d->H, d->W, d->C, d->ldx, w, d->R, d->S, d->ldw, d->K, y, d->ldy, d->OH, d->OW, 0, 0,
+                                   bias, nullptr, 0, nullptr, 0, d->act, ws, ws_bytes, tickets, (hipStream_t)stream,
+                                   "deconv_fwd");
+        const size_t db = dilated_bytes(d->N, d->H, d->W, d->C, d->stride);
+        if (ws_bytes < db || !ws) return fail(ACIMG_EWORKSPACE, "deconv_fwd: workspace too small for the dilated input");
+        const int H1 = (d->H - 1) * d->stride + 1, W1 = (d->W - 1) * d->stride + 1;
+        const long opix = (long)d->N * H1 * W1;
+        hipLaunchKernelGGL(dilate2d_kernel, dim3(cdiv(opix * (d->C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, d->ldx,
+                           static_cast<float*>(ws), opix, d->H, d->W, H1, W1, d->C, d->stride);
+        rc = check_launch("dilate2d");
+        if (rc) return rc;
+        IgemmParams p = flipped_view(d->N, H1, W1, d->C, d->C, d->OH, d->OW, d->R, d->S, 0, 0, d->K);
+        p.A = static_cast<const float*>(ws); p.B = w; p.ldb = d->ldw;
+        p.rowrun = d->S > 1 ? 1 : 0;
+        p.tap_stride = (long)d->K * d->ldw; p.flip = 1;
+        p.e.Y = y; p.e.ldy = d->ldy; p.e.bias = bias; p.e.act = d->act;
+        return launch_igemm(p, true, static_cast<char*>(ws) + db, ws_bytes - db, tickets, (hipStream_t)stream);
+    }
+    if (d->OH != d->H * d->stride || d->OW != d->W * d->stride)
+        return fail(ACIMG_EINVAL, "deconv_fwd: kernel<=stride needs OH=H*stride");
+    if (patch2_shape(d) && aligned16(x) && aligned16(y) && aligned16(w) && (d->ldx & 3) == 0 && (d->ldy & 3) == 0 && (d->ldw & 3) == 0 &&
+        (!bias || aligned16(bias))) {
+        Patch2Params q{};
+        q.X = x; q.ldx = d->ldx; q.Y = y; q.ldy = d->ldy; q.w = w; q.ldw = d->ldw; q.bias = bias; q.act = d->act;
+        q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
+        return launch_patch2<SplitF16, 0>(q, (hipStream_t)stream);
+    }
+    IgemmParams p{};
+    p.A = x; p.H = d->H; p.W = d->W; p.C = d->C; p.lda = d->ldx; p.OH = d->H; p.OW = d->W;
+    p.R = 1; p.S = 1; p.stride = 1; p.M = d->N * d->H * d->W; p.rowrun = 0;
+    p.B = w; p.ldb = d->ldw; p.tap_stride = 0; p.flip = 0; p.Ngemm = d->R * d->S * d->K;
+    p.e.Y = y; p.e.ldy = d->ldy; p.e.M = p.M; p.e.Nstore = p.Ngemm; p.e.bias = bias; p.e.act = d->act;
+    p.e.scatter = 1; p.e.Ko = d->K; p.e.Sq = d->S; p.e.sc = d->stride;
+    p.e.YH = d->OH; p.e.YW = d->OW; p.e.AH = d->H; p.e.AW = d->W;
+    rc = launch_igemm(p, true, ws, ws_bytes, tickets, (hipStream_t)stream);
+    if (rc) return rc;
+    if (d->R < d->stride || d->S < d->stride) {
+        const long pixels = (long)d->N * d->OH * d->OW;
+        hipLaunchKernelGGL(deconv_gap_fill_kernel, dim3(cdiv(pixels * (d->K / 4), 256)), dim3(256), 0,
+                           (hipStream_t)stream, y, d->ldy, bias, pixels, d->OH, d->OW, d->K, d->R, d->S, d->stride);
+        rc = check_launch("deconv_gap_fill");
+    }
+    return rc;
+}
+
+int acimg_deconv_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w,
+                       float* dx, const float* mask, int ldmask, void* ws, size_t ws_bytes,
+                       void* tickets, void* stream) {
+    int rc = check_desc(d, "deconv_dgrad");
+    if (rc) return rc;
+    const int ca = up4(d->K);
+    if (ca > ldgy || (ldgy & 3) || ca != d->K) return fail(ACIMG_EINVAL, "deconv_dgrad: K must be a multiple of 4 and <= ldgy");
+    // dx[n,h,w,c] = sum_{r,s,k} gy[n, h*stride+r, w*stride+s, k] * W[r][s][k][c]  (a strided conv)
+    if (patch2_shape(d) && aligned16(gy) && aligned16(dx) && aligned16(w) && (d->ldx & 3) == 0 && (d->ldw & 3) == 0 &&
+        (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
+        Patch2Params q{};
+        q.X = gy; q.ldx = ldgy; q.Y = dx; q.ldy = d->ldx; q.w = w; q.ldw = d->ldw; q.mask = mask; q.ldmask = ldmask;
+        q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
+        return launch_patch2<SplitBF16, 1>(q, (hipStream_t)stream);
+    }
+    if (!mask && direct_ok(ca, d->C, d->ldx, 0, dx, nullptr, nullptr, false, nullptr) &&
+        (long)d->N * d->H * d->W >= 65536) {
+        // few channels: the direct kernel, the [kh][kw][out][in] kernel read as the HWIO kernel of that conv
+        DirectParams q{};
+        q.x = gy; q.ldx = ldgy; q.H = d->OH; q.W = d->OW; q.C = ca;
+        q.y = dx; q.ldy = d->ldx; q.OH = d->H; q.OW = d->W; q.K = d->C;
+        q.R = d->R; q.S = d->S; q.stride = d->stride; q.pad_t = 0; q.pad_l = 0;
+        q.w = w; q.ldw = d->ldw; q.mode = 0; q.wrows = d->K; q.act = ACIMG_ACT_NONE;
+        q.M = (long)d->N * d->H * d->W;
+        return launch_direct(q, ws, ws_bytes, (hipStream_t)stream);
+    }
+    IgemmParams p{};
+    p.A = gy; p.H = d->OH; p.W = d->OW; p.C = ca; p.lda = ldgy; p.OH = d->H; p.OW = d->W;
+    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = 0; p.pad_l = 0;
+    p.M = d->N * d->H * d->W;
+    p.rowrun = (d->S > 1 && ldgy == ca) ? 1 : 0;
+    p.B = w; p.ldb = d->ldw; p.Nld = d->ldw; p.Ngemm = d->C;
+    p.e.Y = dx; p.e.ldy = d->ldx; p.e.M = p.M; p.e.Nstore = d->C; p.e.mask = mask; p.e.ldmask = ldmask;
+    return launch_igemm(p, false, ws, ws_bytes, tickets, (hipStream_t)stream);
+}
+
+int acimg_deconv_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
+                       float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_desc(d, "deconv_wgrad");
+    if (rc) return rc;
+    const int ca = up4(d->K);
+    if (ca > ldgy || (ldgy & 3) || ca != d->K) return fail(ACIMG_EINVAL, "deconv_wgrad: K must be a multiple of 4 and <= ldgy");
+    // dW[(r,s,k)][c] = sum_{n,h,w} gy[n,h*stride+r,w*stride+s,k] * x[n,h,w,c]
+    if (patch2_shape(d) && aligned16(dw) && (d->ldw & 3) == 0 && ws && aligned16(ws) &&
+        ws_bytes >= (size_t)PATCH2_WGRAD_WGS * (32 * d->ldw + 8) * sizeof(float) && (!db || aligned16(db))) {
+        Patch2WgradParams q{};
+        q.X = x; q.ldx = d->ldx; q.G = gy; q.ldg = ldgy; q.out = static_cast<float*>(ws); q.ldo = d->ldw;
+        q.db_part = db ? q.out + (size_t)PATCH2_WGRAD_WGS * 32 * d->ldw : nullptr;
+        q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
+        hipLaunchKernelGGL(patch2_wgrad_32x8_kernel, dim3(PATCH2_WGRAD_WGS), dim3(1024), 0, (hipStream_t)stream, q);
+        rc = check_launch("patch2_wgrad");
+        if (rc) return rc;
+        launch_slab_reduce_wide(q.out, PATCH2_WGRAD_WGS, 32L, 32, d->ldw, dw, nullptr, nullptr, (hipStream_t)stream);
+        rc = check_launch("patch2_wgrad reduce");
+        if (rc) return rc;
+        // the transposed conv adds its bias at every output pixel, and every output pixel belongs to exactly one patch: the
+        // bias gradient is the sum of all the gy values the kernel has just read
+        if (db) {
+            hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, q.db_part, PATCH2_WGRAD_WGS, 8, db);
+            rc = check_launch("patch2_wgrad bias");
+        }
+        return rc;
+    }
+    WgradParams p{};
+    p.X = gy; p.H = d->OH; p.W = d->OW; p.C = ca; p.ldx = ldgy;
+    p.OH = d->H; p.OW = d->W; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = 0; p.pad_l = 0;
+    p.M = d->N * d->H * d->W; p.KK = d->R * d->S * ca;
+    p.G = x; p.ldg = d->ldx; p.Ngemm = d->C; p.Nld = d->C; p.ldo = d->ldw;
+    if (db) {       // refuse before dw is written: an unsplit weight gradient takes no workspace, the column sum always does
+        const size_t need = (size_t)colsum_parts((long)d->N * d->OH * d->OW) * d->K * sizeof(float);
+        if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "deconv_wgrad: workspace %zu < %zu (bias gradient)", ws_bytes, need);
+    }
+    rc = launch_wgrad(p, dw, nullptr, ws, ws_bytes, (hipStream_t)stream);
+    if (rc) return rc;
+    // the transposed conv adds its bias at EVERY output pixel (gaps included): plain column sum of gy
+    if (db) rc = launch_colsum(gy, (long)d->N * d->OH * d->OW, d->K, ldgy, db, ws, ws_bytes, (hipStream_t)stream);
+    return rc;
+}
+
+int acimg_conv2d_fwd_split3_stats_rows(const AcimgConvDesc* d) {
+    const int M = d->N * d->OH * d->OW;
+    if (conv_halo16_fwd_shape(d)) return CONV_HALO16_WGS;      // the halo form leaves one row per workgroup
+    return cdiv(M, pick_split3(M, d->K).bm);
+}
+
+int acimg_conv2d_fwd_split3p_stats_rows(const AcimgConvDesc* d) { return pick_trunk(d, 3, false).stats_rows; }
+
+int acimg_conv2d_fwd_split3_tiling(const AcimgConvDesc* d, int* out) {
+    if (!d || !out) return fail(ACIMG_EINVAL, "conv2d_fwd_split3_tiling: null argument");
+    const TrunkPick t = pick_trunk(d, 3, false);
+    out[0] = t.bm;
+    out[1] = t.bn;
+    out[2] = t.kind;
+    return ACIMG_OK;
+}
+
+size_t acimg_conv2d_split3_weight_bytes(const AcimgConvDesc* d) {
+    return split3_rowmajor_bytes(d) + split3_brick_bytes(d);
 }
 
 int acimg_conv2d_split3_prepare(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream) {
@@ -3009,35 +3389,6 @@ int acimg_conv2d_split3_prepare_multi(int n, const AcimgConvDesc* const* descs, 
     return check_launch("split3_prepare_multi");
 }
 
-extern "C++" {
-template <typename TR, int TERMS = 3>
-static int launch_split3(IgemmParams& p, hipStream_t st) {
-    Split3Cfg c = pick_split3(p.M, p.Ngemm, true);
-    dim3 grid(cdiv(p.M, c.bm), cdiv(p.Ngemm, c.bn), 1);
-    if (c.bm == 128 && c.bn == 32)
-        hipLaunchKernelGGL((igemm_split3_kernel<128, 32, 4, 1, 256, TR, TERMS>), grid, dim3(256), 2 * (2 * 128 * 64 + 2 * 32 * 64), st, p);
-    else if (c.bm == 128 && c.bn == 128)
-        hipLaunchKernelGGL((igemm_split3_kernel<128, 128, 2, 4, 512, TR, TERMS>), grid, dim3(512), 65536, st, p);
-    else if (c.bm == 64 && c.bn == 128)
-        hipLaunchKernelGGL((igemm_split3_kernel<64, 128, 1, 4, 256, TR, TERMS>), grid, dim3(256), 2 * (2 * 64 * 64 + 2 * 128 * 64), st, p);
-    else if (c.bm == 128 && c.bn == 64)
-        hipLaunchKernelGGL((igemm_split3_kernel<128, 64, 2, 2, 256, TR, TERMS>), grid, dim3(256), 2 * (2 * 128 * 64 + 2 * 64 * 64), st, p);
-    else
-        return fail(ACIMG_EINVAL, "split3: unsupported tile %dx%d", c.bm, c.bn);
-    return check_launch("igemm_split3");
-}
-
-static void epi_vec_flag(EpiParams& e) {
-    e.vec = aligned16(e.Y) && (e.ldy & 3) == 0 && (!e.bias || aligned16(e.bias)) &&
-            (!e.res || (aligned16(e.res) && (e.ldres & 3) == 0)) &&
-            (!e.mask || (aligned16(e.mask) && (e.ldmask & 3) == 0)) && (!e.scatter || (e.Ko & 3) == 0);
-}
-}  // extern "C++"
-
-static int fwd_split_onthefly(const AcimgConvDesc* d, const float* x, const void* wsplit, const float* bias, float* y,
-                              const float* in_scale, const float* in_shift, int in_relu, float* stats, void* stream,
-                              bool bf16);
-
 int acimg_conv2d_fwd_split3(const AcimgConvDesc* d, const float* x, const void* wsplit, const float* bias,
                             float* y, const float* in_scale, const float* in_shift, int in_relu, float* stats,
                             void* stream) {
@@ -3052,58 +3403,6 @@ int acimg_conv2d_fwd_bf16(const AcimgConvDesc* d, const float* x, const void* ws
     return fwd_split_onthefly(d, x, wsplit, bias, y, in_scale, in_shift, in_relu, stats, stream, true);
 }
 
-static int fwd_split_onthefly(const AcimgConvDesc* d, const float* x, const void* wsplit, const float* bias, float* y,
-                              const float* in_scale, const float* in_shift, int in_relu, float* stats, void* stream,
-                              bool bf16) {
-    int rc = check_desc(d, "conv2d_fwd_split3", true);
-    if (rc) return rc;
-    if (d->C % 32) return fail(ACIMG_EINVAL, "conv2d_fwd_split3: C=%d must be a multiple of 32", d->C);
-    if (d->ldw < d->K || !aligned16(x) || !aligned16(wsplit))
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3: ldw<K or unaligned operands");
-    if (conv_halo16_fwd_shape(d)) {
-        // (acimg_conv2d_fwd_split3_stats_rows already told the caller this shape leaves CONV_HALO16_WGS rows: no fallback)
-        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || !aligned16(y) || (d->ldy & 3) || (d->ldx & 3) ||
-            (bias && !aligned16(bias)) || (in_scale && (!aligned16(in_scale) || !aligned16(in_shift))))
-            return fail(ACIMG_EINVAL, "conv2d_fwd_split3: the halo form of this shape needs scale AND shift of an input affine, "
-                                      "16-byte aligned y / bias / affine and ldx, ldy multiples of 4");
-        ConvHaloParams q{};
-        q.a_scale = in_scale; q.a_shift = in_shift; q.a_relu = in_relu;
-        q.X = x; q.H = d->H; q.W = d->W; q.ldx = d->ldx; q.Wimg = static_cast<const char*>(wsplit);
-        q.w_lo_off = (unsigned)((size_t)d->ldw * d->R * d->S * d->C * 2);
-        q.Y = y; q.ldy = d->ldy; q.bias = bias; q.stats = stats; q.stats_ld = d->ldw;
-        hipStream_t st = (hipStream_t)stream;
-        if (bf16) return d->C == 64 ? launch_conv_halo16<SplitBF16, 1, 64, 32, 0>(q, d->N, st)
-                                    : launch_conv_halo16<SplitBF16, 1, 32, 32, 0>(q, d->N, st);
-        return d->C == 64 ? launch_conv_halo16<SplitF16, 3, 64, 32, 0>(q, d->N, st)
-                          : launch_conv_halo16<SplitF16, 3, 32, 32, 0>(q, d->N, st);
-    }
-    IgemmParams p{};
-    p.A = x; p.H = d->H; p.W = d->W; p.C = d->C; p.lda = d->ldx;
-    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride;
-    p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.M = d->N * d->OH * d->OW;
-    p.a_scale = in_scale; p.a_shift = in_shift; p.a_relu = in_relu;
-    p.B = static_cast<const float*>(wsplit); p.Nld = d->ldw; p.Ngemm = d->K;
-    p.ntaps = d->R * d->S;
-    p.kiters = p.ntaps * (d->C / 32);
-    p.splits = 1;
-    const long a_bytes = (((long)d->N * d->H * d->W - 1) * d->ldx + d->C) * 4;
-    const long b_bytes = (long)acimg_conv2d_split3_weight_bytes(d);
-    if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31)) return fail(ACIMG_EINVAL, "conv2d_fwd_split3: operand >= 2 GiB");
-    p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes;
-    EpiParams& e = p.e;
-    e.Y = y; e.ldy = d->ldy; e.M = p.M; e.Nstore = d->K; e.act = d->act; e.bias = bias;
-    e.stats = stats; e.stats_ld = d->ldw;
-    epi_vec_flag(e);
-    if (bf16) return launch_split3<SplitBF16, 1>(p, (hipStream_t)stream);
-    return launch_split3<SplitF16>(p, (hipStream_t)stream);
-}
-
-/* data gradient on the bf16x3 path (stride-1 convs): a forward conv of gy with the flipped/transposed kernel */
-static int dgrad_split_onthefly(const AcimgConvDesc* d, const float* gy, int ldgy, const void* wsplit_t, float* dx,
-                                int lddx, const float* residual, int ldres, const float* mask, int ldmask,
-                                void* stream, int terms);
-
 int acimg_conv2d_dgrad_split3(const AcimgConvDesc* d, const float* gy, int ldgy, const void* wsplit_t, float* dx,
                               int lddx, const float* residual, int ldres, const float* mask, int ldmask,
                               void* stream) {
@@ -3117,307 +3416,21 @@ int acimg_conv2d_dgrad_bf16(const AcimgConvDesc* d, const float* gy, int ldgy, c
     return dgrad_split_onthefly(d, gy, ldgy, wsplit_t, dx, lddx, residual, ldres, mask, ldmask, stream, 1);
 }
 
-static int dgrad_split_onthefly(const AcimgConvDesc* d, const float* gy, int ldgy, const void* wsplit_t, float* dx,
-                                int lddx, const float* residual, int ldres, const float* mask, int ldmask,
-                                void* stream, int terms) {
-    int rc = check_desc(d, "conv2d_dgrad_split3");
-    if (rc) return rc;
-    if (d->stride != 1 || d->K % 32 || d->K > ldgy || (ldgy & 3))
-        return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: needs stride 1 and K %% 32 == 0 (K=%d)", d->K);
-    if (lddx <= 0) lddx = d->ldx;
-    if (conv_halo16_dgrad_shape(d) && aligned16(gy) && aligned16(wsplit_t) && aligned16(dx) && (lddx & 3) == 0 &&
-        (!residual || (aligned16(residual) && (ldres & 3) == 0)) && (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
-        // a forward SAME conv of gy (32 channels) with the flipped / transposed image: rows = the layer's input channels
-        ConvHaloParams q{};
-        q.X = gy; q.H = d->H; q.W = d->W; q.ldx = ldgy; q.Wimg = static_cast<const char*>(wsplit_t);
-        q.w_lo_off = (unsigned)((size_t)d->C * d->R * d->S * d->K * 2);
-        q.Y = dx; q.ldy = lddx; q.res = residual; q.ldres = ldres; q.mask = mask; q.ldmask = ldmask;
-        hipStream_t st = (hipStream_t)stream;
-        if (terms == 1) return d->C == 64 ? launch_conv_halo16<SplitBF16, 1, 32, 64, 1>(q, d->N, st)
-                                          : launch_conv_halo16<SplitBF16, 1, 32, 32, 1>(q, d->N, st);
-        return d->C == 64 ? launch_conv_halo16<SplitBF16, 3, 32, 64, 1>(q, d->N, st)
-                          : launch_conv_halo16<SplitBF16, 3, 32, 32, 1>(q, d->N, st);
-    }
-    IgemmParams p{};
-    p.A = gy; p.H = d->OH; p.W = d->OW; p.C = d->K; p.lda = ldgy;
-    p.OH = d->H; p.OW = d->W; p.R = d->R; p.S = d->S; p.stride = 1;
-    p.pad_t = d->R - 1 - d->pad_t; p.pad_l = d->S - 1 - d->pad_l;
-    p.M = d->N * d->H * d->W;
-    p.B = static_cast<const float*>(wsplit_t); p.Nld = d->C; p.Ngemm = d->C;
-    p.ntaps = d->R * d->S;
-    p.kiters = p.ntaps * (d->K / 32);
-    p.splits = 1;
-    const long a_bytes = (((long)d->N * d->OH * d->OW - 1) * ldgy + d->K) * 4;
-    const long b_bytes = (long)acimg_conv2d_split3_dgrad_weight_bytes(d);
-    if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31)) return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: operand >= 2 GiB");
-    p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes;
-    EpiParams& e = p.e;
-    e.Y = dx; e.ldy = lddx; e.M = p.M; e.Nstore = d->C; e.act = ACIMG_ACT_NONE;
-    e.res = residual; e.ldres = ldres; e.mask = mask; e.ldmask = ldmask;
-    epi_vec_flag(e);
-    if (terms == 1) return launch_split3<SplitBF16, 1>(p, (hipStream_t)stream);
-    return launch_split3<SplitBF16>(p, (hipStream_t)stream);
+size_t acimg_conv2d_fwd_split3p_workspace(const AcimgConvDesc* d) {
+    (void)d;
+    return TS_WS_BYTES;
 }
-
-// ---- tail split of the trunk kernel: which tiles to cut, and into how many K ranges ------------------------
-struct TailPlan { int whole, s, rem; };
-static int resident_slots(int which, const void* fn, int threads, size_t lds) {
-    static int cache[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (!cache[which]) {
-        int dev = 0, ncu = 0, per = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, threads, lds) != hipSuccess || ncu <= 0 || per <= 0) {
-            (void)hipGetLastError();
-            ncu = 256;                    // MI355X; no device (CPU-side sizing queries): same answer
-            per = which >= 7 ? 2 : which >= 4 ? 1 : (which == 0 || which == 3) ? 2 : 3;
-        }
-        cache[which] = ncu * per;
-    }
-    return cache[which];
-}
-static TailPlan pick_tail(int T, int P, int KI, int max_units) {
-    const int rem = T % P;
-    TailPlan best{T, 1, 0};
-    if (rem == 0 || !g_cfg.tail_split) return best;
-    if (g_cfg.tail_s) {   // experiments only: force the number of K ranges
-        const int s = g_cfg.tail_s;
-        if (s > 1 && KI / s >= 1 && (long)rem * s <= max_units) return TailPlan{T - rem, s, rem};
-        return best;
-    }
-    // cost in K steps of the last round: whole tiles = KI; s ranges = rounds(rem*s) * ceil(KI/s) + hand-off
-    double best_cost = KI;
-    static const int cand[] = {2, 3, 4, 6, 8, 12, 16};
-    for (int s : cand) {
-        if (KI / s < 2 || (long)rem * s > max_units) break;
-        // hand-off calibrated on the trunk shapes (tools/tune_dma.py): partial store + ticket + the last arriver's
-        // s x 64 KiB of sc1 loads cost about 8 + s K steps, so 1x1 layers with few K steps are left whole
-        const double cost = (double)cdiv((long)rem * s, P) * cdiv(KI, s) + 8.0 + 1.0 * s;
-        if (cost < 0.9 * best_cost) {
-            best_cost = cost;
-            best = TailPlan{T - rem, s, rem};
-        }
-    }
-    return best;
-}
-static constexpr int TS_MAX_UNITS = 1024;      // partial slots (64 KiB each for a 128x128 tile; a 256x128 tile takes two)
-static constexpr size_t TS_COUNTER_BYTES = 4096;
 
 #if defined(ACIMG_STAMP) || defined(ACIMG_ABLATE)
-static float* g_stamp_buf = nullptr;      // diagnostic build only (tools/build_stamp.sh): never in libacimg.so
-static int g_stamp_nostore = 0;           // ablation: the persistent kernel's output stores go out of range (dropped)
-extern "C" int acimg_debug_stamp_buffer(void* buf) {
+int acimg_debug_stamp_buffer(void* buf) {
     g_stamp_buf = static_cast<float*>(buf);
     return 0;
 }
-extern "C" int acimg_debug_no_output_stores(int on) {
+int acimg_debug_no_output_stores(int on) {
     g_stamp_nostore = on;
     return 0;
 }
 #endif
-
-size_t acimg_conv2d_fwd_split3p_workspace(const AcimgConvDesc* d) {
-    (void)d;
-    return TS_COUNTER_BYTES + (size_t)TS_MAX_UNITS * 128 * 128 * sizeof(float);
-}
-
-// the two passes of a conv whose raw output never reaches memory (igemm_split3dp_kernel, EPI 1 / 2)
-struct Split3pTail {
-    int mode;                      // 1: statistics only; 2: relu(acc * scale + shift + shortcut) -> split planes;
-                                   // 3: the same with a projection shortcut (raw fp32 + its own scale / shift)
-    const float* scale;
-    const float* shift;
-    const void* sc_planes;         // mode 3: the fp32 [M][K] output of the shortcut conv
-    size_t sc_lo_off;
-    void* out_planes;
-    size_t out_lo_off;
-    const float* scale2;
-    const float* shift2;
-};
-
-static int fwd_presplit(const AcimgConvDesc* d, const void* x_planes, size_t x_lo_off, const void* wsplit, float* y,
-                        float* stats, void* ws, size_t ws_bytes, void* stream, const int terms,
-                        const Split3pTail* tail = nullptr) {
-    int rc = check_desc(d, "conv2d_fwd_split3p");
-    if (rc) return rc;
-    if (d->C % 32) return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: C=%d must be a multiple of 32", d->C);
-    if (d->ldw < d->K || !aligned16(x_planes) || !aligned16(wsplit) || !aligned16(y) || (d->ldy & 3) || d->ldx != d->C ||
-        (x_lo_off & 15))
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: ldw<K, ldx != C (split-format tensors are dense) or unaligned operands");
-    IgemmParams p{};
-    p.A = static_cast<const float*>(x_planes); p.H = d->H; p.W = d->W; p.C = d->C; p.lda = d->ldx;
-    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride;
-    p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.M = d->N * d->OH * d->OW;
-    p.B = static_cast<const float*>(wsplit); p.Nld = d->ldw; p.Ngemm = d->K;
-    p.ntaps = d->R * d->S;
-    p.kiters = p.ntaps * (d->C / 32);
-    p.splits = 1;
-    const long plane = (long)acimg_split_plane_bytes((long)d->N * d->H * d->W, d->C);
-    const long a_bytes = (long)x_lo_off + plane;
-    const long b_bytes = (long)acimg_conv2d_split3_weight_bytes(d);
-    if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || (long)x_lo_off < plane)
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: operand >= 2 GiB or overlapping planes");
-    p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes; p.a_lo_off = (unsigned)x_lo_off;
-    p.b_brick = (unsigned)split3_rowmajor_bytes(d);
-    EpiParams& e = p.e;
-    e.Y = y; e.ldy = d->ldy; e.M = p.M; e.Nstore = d->K; e.act = d->act;
-    e.stats = stats; e.stats_ld = d->ldw; e.vec = 1;
-    Split3Cfg c = pick_split3(p.M, d->K);
-    hipStream_t st = (hipStream_t)stream;
-    // XCD-aware rasterisation: the ~64 tiles resident on one XCD form a (64/gn) x gn rectangle of the tile grid
-    p.ras_tiles_m = cdiv(p.M, c.bm);
-    p.ras_tiles_n = cdiv(d->K, c.bn);
-    p.ras_gn = std::min(p.ras_tiles_n, 8);
-    p.ras_gm = std::max(1, 64 / p.ras_gn);
-    // 2 stages x (hi, lo) x 64-byte rows; the epilogue restages the fp32 output tile there (+ 2 x WGM x BN floats
-    // of statistics scratch behind it)
-    const size_t lds_bytes = std::max((size_t)2 * 2 * (c.bm + c.bn) * 64, (size_t)c.bm * c.bn * 4) + 4 * 2 * c.bn * 4;
-    const int T = p.ras_tiles_m * p.ras_tiles_n;
-    const int which = (c.bm == 128 && c.bn == 128) ? 0 : (c.bm == 64 ? 1 : 2);
-    const void* fn = which == 0 ? (const void*)igemm_split3d_kernel<128, 128, 2, 4, 512, 2, 2>
-                   : which == 1 ? (const void*)igemm_split3d_kernel<64, 128, 1, 4, 256, 2, 2>
-                                : (const void*)igemm_split3d_kernel<128, 64, 2, 2, 256, 2, 2>;
-    // the persistent and the ring kernel address the output through a 32-bit buffer descriptor; a larger output (per-GPU
-    // batches around 512 on the first trunk units) falls back to the one-tile kernel's 64-bit pointer stores
-    const bool big_out = (long)p.M * d->ldy * 4 >= (1L << 31);
-    if (tail) {
-        // statistics-only / fused-tail passes: always the persistent kernel (whole tiles, then K ranges of the tail tiles)
-        if (terms != 3 || c.bm != 128 || c.bn != 128 || big_out || d->K % 128 || d->ldy != d->K || d->ldw != d->K)
-            return fail(ACIMG_EINVAL, "conv2d_fwd_split3p (two-pass): needs 128x128 tiles, K %% 128 == 0, dense output < 2 GiB");
-        const size_t lds_t = (size_t)2 * 4 * 128 * 64 + 4 * 2 * 128 * 4;
-        const void* ft = tail->mode == 1 ? (const void*)igemm_split3dp_kernel<32, 0, 3, 1>
-                       : tail->mode == 2 ? (const void*)igemm_split3dp_kernel<32, 0, 3, 2>
-                                         : (const void*)igemm_split3dp_kernel<32, 0, 3, 3>;
-        const int Pt = resident_slots(7 + tail->mode, ft, 512, lds_t);
-        TailPlan tt{T, 1, 0};
-        if (ws && ws_bytes >= acimg_conv2d_fwd_split3p_workspace(d)) tt = pick_tail(T, Pt, p.kiters, TS_MAX_UNITS);
-        p.ts_whole = tt.whole; p.ts_s = tt.s;
-        p.ts_counters = static_cast<int*>(ws);
-        p.ts_partial = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + TS_COUNTER_BYTES) : nullptr;
-        const int units = tt.whole + tt.rem * tt.s;
-        const int nwg = std::min(units, Pt);
-        if (tail->mode == 1) {
-            e.Y = nullptr;
-            hipLaunchKernelGGL((igemm_split3dp_kernel<32, 0, 3, 1>), dim3(nwg), dim3(512), lds_t, st, p, units, nwg);
-            return check_launch("conv2d_fwd_split3p_stats");
-        }
-        const long oplane = (long)acimg_split_plane_bytes((long)p.M, d->K);
-        if (!aligned16(tail->sc_planes) || !aligned16(tail->out_planes) || (tail->out_lo_off & 15) ||
-            (long)tail->out_lo_off < oplane || (long)tail->out_lo_off + oplane >= (1L << 31))
-            return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: unaligned / overlapping / >= 2 GiB split-format operands");
-        e.Y = nullptr; e.stats = nullptr;
-        e.f_scale = tail->scale; e.f_shift = tail->shift;
-        e.f_sc = static_cast<const char*>(tail->sc_planes);
-        e.f_out = static_cast<char*>(tail->out_planes); e.f_out_lo = (unsigned)tail->out_lo_off;
-        e.f_out_bytes = (unsigned)(tail->out_lo_off + oplane);
-        if (tail->mode == 3) {
-            e.f_scale2 = tail->scale2; e.f_shift2 = tail->shift2;
-            e.f_sc_lo = 0; e.f_sc_bytes = (unsigned)((long)p.M * d->K * 4);      // < 2 GiB: big_out was refused above
-            hipLaunchKernelGGL((igemm_split3dp_kernel<32, 0, 3, 3>), dim3(nwg), dim3(512), lds_t, st, p, units, nwg);
-            return check_launch("conv2d_fwd_split3p_tail_proj");
-        }
-        if ((tail->sc_lo_off & 15) || (long)tail->sc_lo_off < oplane || (long)tail->sc_lo_off + oplane >= (1L << 31))
-            return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: unaligned / overlapping / >= 2 GiB shortcut planes");
-        e.f_sc_lo = (unsigned)tail->sc_lo_off;
-        e.f_sc_bytes = (unsigned)(tail->sc_lo_off + oplane);
-        hipLaunchKernelGGL((igemm_split3dp_kernel<32, 0, 3, 2>), dim3(nwg), dim3(512), lds_t, st, p, units, nwg);
-        return check_launch("conv2d_fwd_split3p_tail");
-    }
-    if (halo_on(d, terms)) {
-        // one tile per workgroup, K walked as (channel chunk, tap) over one staged patch per chunk; tail tiles in K ranges
-        const size_t lds_h = (size_t)2 * (HALO_NB * 1024 + 64) + 2 * 2 * 128 * 64;
-        const void* fh = (const void*)igemm_split3h_kernel<HALO_NB>;
-        static bool attr_h = false;                  // > 64 KiB of dynamic LDS needs the opt-in once per process
-        if (!attr_h) {
-            (void)hipFuncSetAttribute(fh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-            attr_h = true;
-        }
-        const int Ph = resident_slots(7, fh, 512, lds_h);
-        TailPlan th{T, 1, 0};
-        if (ws && ws_bytes >= acimg_conv2d_fwd_split3p_workspace(d)) th = pick_tail(T, Ph, p.kiters, TS_MAX_UNITS);
-        p.ts_whole = th.whole; p.ts_s = th.s;
-        p.ts_counters = static_cast<int*>(ws);
-        p.ts_partial = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + TS_COUNTER_BYTES) : nullptr;
-        hipLaunchKernelGGL((igemm_split3h_kernel<HALO_NB>), dim3(th.whole + th.rem * th.s), dim3(512), lds_h, st, p);
-        return check_launch("conv2d_fwd_split3p (halo)");
-    }
-    if (const int rr = big_out ? 0 : ring_rows(d, terms)) {
-#if defined(ACIMG_STAMP) || defined(ACIMG_ABLATE)
-        p.slab = g_stamp_buf;
-        p.flip = g_stamp_nostore;
-#endif
-        // one workgroup per CU walks units blockIdx.x, blockIdx.x + P, ... (whole tiles, then K ranges of the tail tiles)
-        p.ras_tiles_m = cdiv(p.M, rr);
-        p.ras_gm = std::max(1, 32 / p.ras_gn);       // 32 resident tiles per XCD
-        const int Tr = p.ras_tiles_m * p.ras_tiles_n;
-        const size_t lds_r = (size_t)3 * 2 * (rr + 128) * 64 + 4 * 2 * 128 * 4;
-        const void* fr = rr == 256 ? (const void*)igemm_split3r_kernel<4> : (const void*)igemm_split3r_kernel<2>;
-        static bool attr[2] = {false, false};        // > 64 KiB of dynamic LDS needs the opt-in once per process
-        if (!attr[rr == 256]) {
-            (void)hipFuncSetAttribute(fr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-            attr[rr == 256] = true;
-        }
-        const int Pr = resident_slots(rr == 256 ? 5 : 6, fr, 512, lds_r);
-        TailPlan tr{Tr, 1, 0};
-        if (ws && ws_bytes >= acimg_conv2d_fwd_split3p_workspace(d))
-            tr = pick_tail(Tr, Pr, p.kiters, TS_MAX_UNITS * 128 / rr);
-        p.ts_whole = tr.whole; p.ts_s = tr.s;
-        p.ts_counters = static_cast<int*>(ws);
-        p.ts_partial = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + TS_COUNTER_BYTES) : nullptr;
-        const int units = tr.whole + tr.rem * tr.s;
-        const int nwg = std::min(units, Pr);
-        p.splits = g_cfg.trunk_stagger > 0 ? 2 : 1;   // ring kernel: waves 4-7 do a step's scalar work before their first MFMA group
-        if (rr == 256) hipLaunchKernelGGL((igemm_split3r_kernel<4>), dim3(nwg), dim3(512), lds_r, st, p, units, nwg);
-        else hipLaunchKernelGGL((igemm_split3r_kernel<2>), dim3(nwg), dim3(512), lds_r, st, p, units, nwg);
-        return check_launch("conv2d_fwd_split3p (ring)");
-    }
-    const bool persistent = !big_out && split3p_persistent(c, T);
-    // (a 64-deep K step - whole 128-byte operand rows, one workgroup per CU - was measured slower on every trunk shape in
-    //  round 2 and removed when the operands moved to LDS-tile order, which gives whole-line requests at two per CU)
-    const size_t lds_p = (size_t)2 * 4 * 128 * 64 + 4 * 2 * 128 * 4;    // 2 stages + statistics scratch
-    TailPlan tp{T, 1, 0};
-    const int P = !persistent ? resident_slots(which, fn, which == 0 ? 512 : 256, lds_bytes)
-                              : resident_slots(3, (const void*)igemm_split3dp_kernel<32, 0>, 512, lds_p);
-    if (ws && ws_bytes >= acimg_conv2d_fwd_split3p_workspace(d) && which == 0)
-        tp = pick_tail(T, P, p.kiters, TS_MAX_UNITS);
-    p.ts_whole = tp.whole; p.ts_s = tp.s;
-    p.ts_counters = static_cast<int*>(ws);
-    p.ts_partial = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + TS_COUNTER_BYTES) : nullptr;
-    const int n_units = tp.whole + tp.rem * tp.s;
-    const dim3 grid(n_units);
-#if defined(ACIMG_STAMP) || defined(ACIMG_ABLATE)
-    p.slab = g_stamp_buf;
-    p.flip = g_stamp_nostore;
-#endif
-    if (persistent) {
-        p.splits = g_cfg.trunk_stagger > 0 ? g_cfg.trunk_stagger * (p.kiters * 2500 + 8000) / 100 : 1;
-        // a workgroup per resident slot walks units blockIdx.x, blockIdx.x + P, ...: whole tiles first (with the
-        // next tile's first operand stage and addresses prepared under the current tile's last K step and output
-        // stores), then the K ranges of the tail tiles
-        const int nwg = std::min(n_units, P);
-        if (terms == 1) {
-            hipLaunchKernelGGL((igemm_split3dp_kernel<32, 0, 1>), dim3(nwg), dim3(512), lds_p, st, p, n_units, nwg);
-        } else if (g_cfg.trunk_dma_pos == 1) {
-            hipLaunchKernelGGL((igemm_split3dp_kernel<32, 1>), dim3(nwg), dim3(512), lds_p, st, p, n_units, nwg);
-        } else {
-            hipLaunchKernelGGL((igemm_split3dp_kernel<32, 0>), dim3(nwg), dim3(512), lds_p, st, p, n_units, nwg);
-        }
-    } else if (terms == 1) {
-        if (which == 0)
-            hipLaunchKernelGGL((igemm_split3d_kernel<128, 128, 2, 4, 512, 2, 2, 1>), grid, dim3(512), lds_bytes, st, p);
-        else if (which == 1)
-            hipLaunchKernelGGL((igemm_split3d_kernel<64, 128, 1, 4, 256, 2, 2, 1>), grid, dim3(256), lds_bytes, st, p);
-        else
-            hipLaunchKernelGGL((igemm_split3d_kernel<128, 64, 2, 2, 256, 2, 2, 1>), grid, dim3(256), lds_bytes, st, p);
-    } else if (which == 0)
-        hipLaunchKernelGGL((igemm_split3d_kernel<128, 128, 2, 4, 512, 2, 2>), grid, dim3(512), lds_bytes, st, p);
-    else if (which == 1)
-        hipLaunchKernelGGL((igemm_split3d_kernel<64, 128, 1, 4, 256, 2, 2>), grid, dim3(256), lds_bytes, st, p);
-    else
-        hipLaunchKernelGGL((igemm_split3d_kernel<128, 64, 2, 2, 256, 2, 2>), grid, dim3(256), lds_bytes, st, p);
-    return check_launch("conv2d_fwd_split3p");
-}
 
 int acimg_conv2d_fwd_split3p(const AcimgConvDesc* d, const void* x_planes, size_t x_lo_off, const void* wsplit,
                              float* y, float* stats, void* ws, size_t ws_bytes, void* stream) {
@@ -3454,16 +3467,6 @@ int acimg_conv2d_fwd_split3p_tail_proj(const AcimgConvDesc* d, const void* x_pla
         return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail_proj: null / unaligned scale, shift, shortcut or output");
     const Split3pTail t{3, scale, shift, sc32, 0, out_planes, out_lo_off, sc_scale, sc_shift};
     return fwd_presplit(d, x_planes, x_lo_off, wsplit, nullptr, nullptr, ws, ws_bytes, stream, 3, &t);
-}
-
-/* ---- tap-GEMM helpers (see the kernels above) ---- */
-static int tapconv_check(const AcimgConvDesc* d, const char* who) {
-    int rc = check_desc(d, who);
-    if (rc) return rc;
-    if (d->stride != 1 || d->pad_t || d->pad_l || d->OH != d->H - d->R + 1 || d->OW != d->W - d->S + 1)
-        return fail(ACIMG_EINVAL, "%s: stride-1 VALID convolutions only", who);
-    if (d->K > 64) return fail(ACIMG_EINVAL, "%s: K=%d > 64 (this form is for few output channels)", who, d->K);
-    return ACIMG_OK;
 }
 
 int acimg_tapconv_stats_rows(const AcimgConvDesc* d) { return cdiv(d->N * d->OH * d->OW, TG_PPB); }
@@ -3512,10 +3515,6 @@ int acimg_tapconv_scatter(const AcimgConvDesc* d, const float* gy, int ldgy, flo
     return check_launch("tapconv_scatter");
 }
 
-/* weight + bias gradient on the bf16x3 MFMA path (same contract as acimg_conv2d_wgrad) */
-static int wgrad_split_onthefly(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy, float* dw, float* db,
-                                void* ws, size_t ws_bytes, void* stream, int terms);
-
 int acimg_conv2d_wgrad_split3(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
                               float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
     return wgrad_split_onthefly(d, x, gy, ldgy, dw, db, ws, ws_bytes, stream, 3);
@@ -3525,20 +3524,6 @@ int acimg_conv2d_wgrad_split3(const AcimgConvDesc* d, const float* x, const floa
 int acimg_conv2d_wgrad_bf16(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
                             float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
     return wgrad_split_onthefly(d, x, gy, ldgy, dw, db, ws, ws_bytes, stream, 1);
-}
-
-static int wgrad_split_onthefly(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy, float* dw, float* db,
-                                void* ws, size_t ws_bytes, void* stream, int terms) {
-    int rc = check_desc(d, "conv2d_wgrad_split3");
-    if (rc) return rc;
-    const int kp = up4(d->K);
-    if (kp > ldgy || kp > d->ldw) return fail(ACIMG_EINVAL, "conv2d_wgrad_split3: padded K exceeds ldgy/ldw");
-    WgradParams p{};
-    p.X = x; p.H = d->H; p.W = d->W; p.C = d->C; p.ldx = d->ldx;
-    p.OH = d->OH; p.OW = d->OW; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.M = d->N * d->OH * d->OW; p.KK = d->R * d->S * d->C;
-    p.G = gy; p.ldg = ldgy; p.Ngemm = kp; p.Nld = kp; p.ldo = d->ldw;
-    return launch_wgrad(p, dw, db, ws, ws_bytes, (hipStream_t)stream, true, terms);
 }
 
 /* precision of a conv layer's entry points: 0 = acimg_conv2d_fwd / _wgrad (fp32-class), 1 = _split3, 2 = _bf16 */
