@@ -13,6 +13,7 @@
 // is permuted identically for A and B (lane group g owns k = 4g..4g+3), which leaves the sum
 // unchanged.  Global->register prefetch of tile t+1 overlaps the MFMAs of tile t.
 #include "wgrad_split3_kernel.hpp"
+#include "wgrad_tap_kernel.hpp"
 #include "igemm_split3d_kernel.hpp"
 #include "igemm_split3dp_kernel.hpp"
 #include "igemm_split3r_kernel.hpp"
@@ -927,6 +928,9 @@ static int wgrad_split3_bn(int Ngemm) {      // column tile of the split-MFMA we
 // the part of wgrad_halo16_ok (below, with its kernel) that the sizing query knows: 3x3 taps of at most 64 channels into at
 // most 32 columns, from 65536 pixels on
 static bool wgrad_halo16_shape(long M, int KK, int Ngemm) { return Ngemm <= 32 && KK % 9 == 0 && KK <= 9 * 64 && M >= 65536; }
+// the part of wgrad_tap_ok (below) that depends on the shape alone: 3x3 taps of at least 64 channels into more than 32 columns
+// (wgrad_tap_kernel; it asks for no more slabs than pick_wgrad_splits grants, so the sizing query does not look at it)
+static bool wgrad_tap_shape(int KK, int Ngemm) { return KK % 9 == 0 && KK >= 9 * 64 && Ngemm > 32; }
 static size_t wgrad_ws_bytes(int M, int KK, int Ngemm, int ldo) {
     // one sizing query serves acimg_conv2d_wgrad and acimg_conv2d_wgrad_split3 / _bf16: the larger of their slab counts
     int bmo, bn;
@@ -1377,6 +1381,17 @@ static bool wgrad_halo16_ok(const WgradParams& p, bool split3) {
            p.OW == p.W && p.ldo >= p.Ngemm && g_cfg.wgrad_halo;
 }
 
+// the tap-sharing form of the bf16x3 weight gradient (wgrad_tap_kernel.hpp): 3x3 / stride 1 / SAME, image rows of 32 or 48
+// pixels (a multiple of 16 keeps a fragment's two 8-pixel groups in one row; 16-pixel rows are the latency-bound 12x16 layers,
+// left on the per-tap kernel), no input affine.  Measured per shape at batch 32 (profiles/wgrad_tap/, tools/op_report.py, per-tap
+// kernel -> this form): 36x48 256->128 181.3-183.8 -> 122.3 us, 128->128 110.6-112.6 -> 74.2, 128->64 80.8-81.3 -> 50.1, 64->64
+// 35.1-35.5 -> 33.4: all four beat the per-tap kernel by more than its spread over three reports, so all four ship here
+static bool wgrad_tap_ok(const WgradParams& p) {
+    return wgrad_tap_shape(p.KK, p.Ngemm) && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 &&
+           p.OH == p.H && p.OW == p.W && p.W % 16 == 0 && p.W >= 32 && p.W <= WT_MAXW && p.KK == 9 * p.C && p.Nld == p.Ngemm &&
+           p.Ngemm % 4 == 0 && p.ldo >= p.Ngemm && p.M % (p.H * p.W) == 0 && !p.a_scale && g_cfg.wgrad_halo;
+}
+
 static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t st,
                         bool split3 = false, int terms = 3) {
     if ((p.C & 3) || (p.ldx & 3) || (p.ldg & 3) || (p.ldo & 3))
@@ -1475,6 +1490,50 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         return check_launch("wgrad_reduce");
     }
     if (split3) bn = wgrad_split3_bn(p.Ngemm);
+    if (split3 && terms == 3 && wgrad_tap_ok(p)) {
+        WgradTapParams q{};
+        q.X = p.X; q.H = p.H; q.W = p.W; q.C = p.C; q.ldx = p.ldx; q.G = p.G; q.ldg = p.ldg;
+        q.Ngemm = p.Ngemm; q.Nld = p.Nld; q.KK = p.KK; q.ldo = p.ldo;
+        q.tiles_y = cdiv(p.H, WT_TH);
+        q.tiles = (long)(p.M / (p.H * p.W)) * q.tiles_y;
+        // pixel splits: what the generic path is granted for this shape (the workspace is sized for it), one tile each at least
+        int ns = pick_wgrad_splits(p.M, p.KK, p.Ngemm, bmo, bn);
+        if (ns > q.tiles) ns = (int)q.tiles;
+        float* db_slab = nullptr;
+        if (ns > 1) {
+            const size_t need = (size_t)ns * ((size_t)p.KK + 1) * p.ldo * sizeof(float);
+            if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "wgrad: workspace %zu < %zu", ws_bytes, need);
+            q.out = static_cast<float*>(ws);
+            db_slab = q.out + (size_t)ns * p.KK * p.ldo;
+            q.db_out = db ? db_slab : nullptr;
+        } else {
+            q.out = dw;
+            q.db_out = db;
+        }
+        const size_t lds = wgrad_tap_lds(p.W);
+        static bool attr_set = false;
+        if (!attr_set) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tap_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wgrad_tap_lds(WT_MAXW));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tap_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wgrad_tap_lds(WT_MAXW));
+            attr_set = true;
+        }
+        const dim3 grid(cdiv(p.C, WT_CB), cdiv(p.Ngemm, bn), ns);
+        if (bn == 128) hipLaunchKernelGGL((wgrad_tap_kernel<128>), grid, dim3(512), lds, st, q);
+        else hipLaunchKernelGGL((wgrad_tap_kernel<64>), grid, dim3(512), lds, st, q);
+        int rc = check_launch("wgrad_tap");
+        if (rc || ns == 1) return rc;
+        if (ns > 32) {
+            launch_slab_reduce_wide(q.out, ns, (long)p.KK, p.Ngemm, p.ldo, dw, db ? db_slab : nullptr, db, st);
+        } else {
+            const long total = (long)p.KK * p.Ngemm;
+            const int nb1 = (int)cdiv(total, 256), nb2 = db ? cdiv(p.Ngemm, 256) : 0;
+            hipLaunchKernelGGL(slab_reduce_kernel, dim3(nb1 + nb2), dim3(256), 0, st, q.out, ns, (long)p.KK, p.Ngemm, p.ldo, dw, nb1,
+                               db_slab, db);
+        }
+        return check_launch("wgrad_reduce");
+    }
     p.splits = pick_wgrad_splits(p.M, p.KK, p.Ngemm, bmo, bn);
     int rps = cdiv(p.M, p.splits);
     rps = ((rps + 31) / 32) * 32;

@@ -3,7 +3,8 @@ process in interleaved rounds; variants are builds of the library (tools/build_r
 
     python tools/wgrad_shapes.py [rounds] name=[lib:<path>][,field:val ...] ...
 
-Checks every variant against the first one (max |d| / max |ref|)."""
+Checks every variant against the first one (max |d| / max |ref|).  The two forms of the 36x48 3x3 weight gradients (tap-sharing
+wgrad_tap_kernel against the per-tap wgrad_split3_kernel) side by side:  python tools/wgrad_shapes.py 7 tap= pertap=wgrad_halo:0"""
 import os
 import sys
 
