@@ -133,7 +133,9 @@ size_t acimg_conv2d_fwd_workspace(const AcimgConvDesc* d);
  * ah*wh + ah*wl + al*wh on the fp16 matrix cores with fp32 accumulation (~2^-22 relative per product:
  * fp32-class results, same 1e-3 parity bar) at 3/16 of the exact-f32 MFMA cost.  Exact power-of-two
  * scaling (weights x2^10, activations x2^-2, accumulators x2^-8) keeps everything in fp16's range for
- * |w| < 63 and |x| < 2.6e5.  Needs C % 32 == 0.  `wsplit` (caller-owned,
+ * |w| < 63 and |x| < 2.6e5.  Below |x| = 0.5 the lo half of an activation is an fp16 subnormal: the split has an absolute floor
+ * of 2^-23 per activation (2^-35 per weight, below |w| ~ 1.2e-4), so an activation near 2^-8 keeps about 14 bits.
+ * Needs C % 32 == 0.  `wsplit` (caller-owned,
  * acimg_conv2d_split3_weight_bytes(d) bytes) is filled by acimg_conv2d_split3_prepare from the HWIO fp32
  * kernel: [hi|lo][ldw][R*S*C] fp16, followed - for the pre-split entry points acimg_conv2d_fwd_split3p / _split1p - by
  * the same weights in LDS-tile order (per 128 output channels and 32-deep K step the two 8 KiB plane images
