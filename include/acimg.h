@@ -73,6 +73,13 @@ typedef struct AcimgConvDesc {
  * The row count belongs to THIS descriptor, `act` included (the few-channel 3x3 / stride-1 layers from 65536
  * pixels on run on an MFMA kernel that leaves one row per workgroup - 512 - when act is ACIMG_ACT_NONE, and on
  * the direct kernel with one row per 256 pixels otherwise): size the buffer from the descriptor that is launched.
+ * ARITHMETIC: exact fp32 products (fp32 matrix cores / packed FMAs) EXCEPT, from 65536 output pixels on (wgrad_halo = 1, the
+ * default), the few-channel layers: 3x3 / stride 1 / SAME, C = 4, 8 or 16 and K % 4 == 0, K <= 32 (<= 16 unless C = 8), ACT_NONE - the
+ * layers above with 512 statistics rows - run f16x3 as acimg_conv2d_fwd_split3 below does (in_scale / in_shift applied in
+ * fp32 BEFORE the 2^-2 scale and the split).  Its operand range (|w| < 63, |x'| < 2.6e5) and its floors (2^-23 absolute per
+ * activation below |x'| = 0.5, 2^-35 per weight below |w| ~ 1.2e-4) apply to these shapes; outside that range the output
+ * is not finite.  Per element |y - exact| <= ~2^-19 sum |x'| |w| + 2^-22 sum |w| + 2^-34 sum |x'|
+ * (tests/split_format_ref.py: bound_f16x3, held per element by tests/test_operand_range_gpu.py).
  * Replaces: tf.layers.conv2d   models/unet_acresnet.py:159-168,173-182,82,89-94
  *           slim layers.conv2d / resnet_utils.conv2d_same   models/resnet50.py:109-121,205-209 */
 int acimg_conv2d_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
@@ -282,6 +289,11 @@ int acimg_bn_relu_maxpool_split(const float* x, const float* scale, const float*
  * stride == R == S with zero padding (non-overlapping patches, layer1/pool_2: scatter form), and any other
  * stride (the strided "pool" convs of models/unet_architecture.py:168-176, models/unet_sound.py:162-170) via a
  * zero-inserted copy of gy in the workspace followed by the stride-1 form.
+ * ARITHMETIC: exact fp32 products EXCEPT, from 65536 input pixels (N H W) on (wgrad_halo = 1), the 3x3 layers with few
+ * channels, which run bf16x3 (both operands split into bf16 hi / lo in fp32's exponent range: no scaling, no operand range,
+ * no floor while gy stays fp32-normal; per product up to 2^-15 of |gy w|, acimg_conv2d_dgrad_split3 above): stride 1 or 2
+ * without a mask, up4(K) = 8 or 16 gy channels into C % 4 == 0, C <= 32 (<= 16 unless up4(K) = 8; stride 2: C = 4, 8 or 12, read
+ * from the zero-inserted VIEW of gy, no copy), and stride 1 / SAME with K = 32 into C <= 16 (mask and residual allowed).
  * Replaces: the Conv2DBackpropInput ops tf.gradients emits for the calls above
  *           (trainer/mfcctrainer.py:72-79). */
 int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w,
@@ -290,6 +302,9 @@ int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const 
 size_t acimg_conv2d_dgrad_workspace(const AcimgConvDesc* d);
 
 /* Weight + bias gradient: dw[R][S][C][ldw] = sum_pixels x (*) gy, db[k] = sum gy (db optional).
+ * ARITHMETIC: exact fp32 products EXCEPT, from 65536 pixels on (wgrad_halo = 1), the 3x3 / stride 1 / SAME layers with
+ * C < 32 (a multiple of 4) and K <= 32, which run bf16x3 - dw AND db - as acimg_conv2d_wgrad_split3 below does: per product
+ * up to 2^-15 of |x gy|, no operand range and no floor while x and gy stay fp32-normal.
  * Replaces: Conv2DBackpropFilter / BiasAddGrad (trainer/mfcctrainer.py:72-79). */
 int acimg_conv2d_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
                        float* dw, float* db, void* ws, size_t ws_bytes, void* stream);
@@ -322,6 +337,11 @@ int acimg_conv2d_wgrad_affine(const AcimgConvDesc* d, int precision, const float
  *   kernel >= stride with overlap (unet_architecture.py:72,78 kernel [2,3]; unet_sound.py:82,85 kernels [3,2],
  *   [3,3]): zero-inserted copy of x in the workspace, then a stride-1 full correlation with the flipped kernel.
  * Every input pixel writes a disjoint RxS patch; the remaining positions get the bias only.
+ * ARITHMETIC: exact fp32 products EXCEPT the 2x2 / stride-2 layer with C = 32 and K = 8 from 65536 INPUT pixels on
+ * (wgrad_halo = 1; unet_architecture.py upsample_9), one 32 x 32 product per input pixel: acimg_deconv_fwd runs f16x3 - the
+ * operand range |w| < 63, |x| < 2.6e5 and the floors 2^-23 per activation / 2^-35 per weight of acimg_conv2d_fwd_split3 apply,
+ * the bias is added in fp32 - and acimg_deconv_dgrad / acimg_deconv_wgrad run bf16x3 (per product up to 2^-15 of |gy w| /
+ * |gy x|; no range, no floor); the bias gradient of that route is an fp32 sum of gy and never meets the split.
  * Replaces: tf.layers.conv2d_transpose  models/unet_acresnet.py:210-217 (call :86). */
 int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
                      float* y, void* ws, size_t ws_bytes, void* tickets, void* stream);

@@ -5,7 +5,11 @@ tensor; a batch norm follows every one of these convs and rescales each output c
 against the loudest channel can be large against a quiet one.  Here input and output channels differ by orders of magnitude
 (tests/split_format_ref.py: `channels`, `quiet`, `loud`, `deferred`), the reference is fp64 on the CPU, and every output
 element is held to the bound derived from the format in that module's docstring: |got - ref| <= bound elementwise, every
-output finite; a failure reports the largest error / bound.  Each case prints its largest ratio ("RATIO ..." lines)."""
+output finite; a failure reports the largest error / bound.  Each case prints its largest ratio ("RATIO ..." lines).
+
+The same 16-bit split arithmetic runs behind the fp32 entry points from 65536 pixels on (acimg_conv2d_fwd / _dgrad / _wgrad on
+the few-channel layers, acimg_deconv_* on the pointwise 32 -> 8 layer: sf.FP32_CASES); the second half of this file holds each
+of those routes to the same bounds, asserts that the route was taken, and looks at the memory round every output."""
 import ctypes as C
 import functools
 
@@ -100,6 +104,13 @@ def test_on_the_fly_f16x3_conv(device, case, name):
 def test_halo_form_f16x3_conv(device):
     """the halo form of acimg_conv2d_fwd_split3 (65536 pixels on, 32 -> 32 channels) on `channels`"""
     on_the_fly(device, "halo", "channels", want_rows=256)
+
+
+@pytest.mark.parametrize("name", sf.SETS)
+def test_halo_form_f16x3_conv_64_channels(device, name):
+    """the 64 -> 32 instance of the halo form (launch_conv_halo16<SplitF16, 3, 64, 32, 0>: two 32-channel chunks per tap, 18 K
+    steps) on every operand set, `deferred` with the consumer's own in_scale / in_relu; 149 x 147: tile rows and columns ragged"""
+    on_the_fly(device, "halo 64", name, want_rows=256)
 
 
 def test_few_channel_mfma_conv(device):
@@ -391,13 +402,286 @@ def test_bf16x3_backward_convs(device, case):
     torch.cuda.synchronize()
     failures = []
     path = "bf16x3 backward " + case
-    held(path, "dx", dx, sf.conv_dgrad(gy, w), sf.bound_bf16x3(o.gy, o.w, sf.fwd_ksteps(taps, taps, K), prod=sf.conv_dgrad),
-         failures)
+    fmt = sf.bwd_fmt(case)
+    held(path, "dx", dx, sf.conv_dgrad(gy, w),
+         sf.bound_bf16x3(o.gy, o.w, sf.fwd_ksteps(taps, taps, K), prod=sf.conv_dgrad, fmt=fmt), failures)
     wg = sf.conv_wgrad(taps)
     ksteps, slabs = sf.wgrad_counts(case, wgrad_slabs(ops, d))
     print("wgrad %s: %d K steps, %d slabs" % (case, ksteps, slabs))
-    held(path, "dw", dw, wg(x, gy), sf.bound_bf16x3(o.x, o.gy, ksteps, ranges=slabs, prod=wg), failures)
+    held(path, "dw", dw, wg(x, gy), sf.bound_bf16x3(o.x, o.gy, ksteps, ranges=slabs, prod=wg, fmt=fmt), failures)
     colsum = lambda a, b: (a * b).sum((0, 1, 2))
-    held(path, "db", db, gy.sum((0, 1, 2)), sf.bound_bf16x3(torch.ones_like(o.gy), o.gy, ksteps, ranges=slabs, prod=colsum),
-         failures)
+    held(path, "db", db, gy.sum((0, 1, 2)),
+         sf.bound_bf16x3(torch.ones_like(o.gy), o.gy, ksteps, ranges=slabs, prod=colsum, fmt=fmt), failures)
+    assert not failures, failures
+
+
+# =====================================================================================================================
+# the split-operand routes behind the fp32 entry points (sf.FP32_CASES)
+# =====================================================================================================================
+SENT = -7777.0            # pad channels, pad columns and the memory past the last pixel are pre-filled with it
+TAIL = 64                 # floats past the last pixel
+WS_BYTE = 0xA5            # ... and the plan's workspace with this byte, where its footprint tells the route
+FEW_FWD = [(c, n) for c, n in sf.FP32_FWD if sf.FP32_CASES[c][5] == "few"]
+FEW_BWD = [c for c in sf.FP32_BWD if sf.FP32_CASES[c][5] != "point"]
+FEW_WGRAD = [c for c in sf.FP32_WGRAD if sf.FP32_CASES[c][5] == "few"]
+FEW = sf.BF16_FMT_FEW
+
+
+def guarded(device, shape, ld):
+    """an output [..., ld] filled with the sentinel (the part to be written: NaN by the caller), TAIL floats more behind it"""
+    n = 1
+    for v in shape:
+        n *= v
+    flat = torch.full((n * ld + TAIL,), SENT, device=device)
+    return flat, flat[:n * ld].view(*shape, ld)
+
+
+def untouched(what, flat, view, lo, hi):
+    """channels [lo, hi) of every pixel and the tail still hold the sentinel"""
+    assert bool((view[..., lo:hi] == SENT).all()), what + ": pad channels written"
+    assert bool((flat[-TAIL:] == SENT).all()), what + ": memory past the last pixel written"
+
+
+def poisoned_workspace(plan, nbytes):
+    plan.ws.require(nbytes)
+    plan.ws.allocate()
+    plan.ws.buf.fill_(WS_BYTE)
+    return plan.ws.buf
+
+
+@functools.lru_cache(maxsize=None)
+def fp32_forward_reference(case, name):
+    """operands, fp64 product (no bias) and its bound - computed once per operand set, shared, never written"""
+    prod, ksteps = sf.fp32_products(case)["fwd"]
+    o = sf.fp32_operands(case, name)
+    return o, prod(o.xa.double(), o.w.double()), sf.bound_f16x3(o.xa, o.w, ksteps, prod=prod)
+
+
+@functools.lru_cache(maxsize=None)
+def fp32_grad_reference(case):
+    """backward operands, fp64 data gradient and its bound"""
+    prod, ksteps = sf.fp32_products(case)["dgrad"]
+    o = sf.fp32_grad_operands(case)
+    return o, prod(o.gy.double(), o.w.double()), sf.bound_bf16x3(o.gy, o.w, ksteps, prod=prod, fmt=FEW)
+
+
+@functools.lru_cache(maxsize=None)
+def fp32_wgrad_reference(case, impulse):
+    """weight-gradient operands (dense: the backward operands; or the `impulse` set), fp64 dw with its bound, fp64 db"""
+    wg = sf.fp32_products(case)["wgrad"]
+    if impulse:
+        o = sf.impulse_operands(case)
+        counts = (o.npix, 0)
+    else:
+        o, counts = fp32_grad_reference(case)[0], sf.fp32_wgrad_counts(case)
+    bound = sf.bound_bf16x3(o.x, o.gy, counts[0], ranges=counts[1], prod=wg, fmt=FEW)
+    return o, wg(o.x.double(), o.gy.double()), bound, o.gy.double().sum((0, 1, 2)), counts
+
+
+@pytest.mark.parametrize("case,name", FEW_FWD)
+def test_few_channel_forward_route(device, case, name):
+    """acimg_conv2d_fwd on conv_few16_kernel MODE 0 (f16x3; 8 -> 8, 4 -> 8 in the 8-channel image, 16 -> 16, 8 -> 32) over every
+    operand set - `loud` at the ends of the stated range, `deferred` with the affine the route takes
+    (acimg_conv2d_affine_input_ok) - into a wider pixel stride: every element within its bound, the statistics rows per
+    channel, pad channels and the memory past the last pixel untouched.  Route: one statistics row per workgroup, 512."""
+    from acimg import ops
+
+    N, H, W, Cc, K = sf.FP32_CASES[case][:5]
+    o, ref, bound = fp32_forward_reference(case, name)
+    d = ops.conv_desc(N, H, W, Cc, K, 3, 3, 1, "SAME", ldy=K + 4)
+    assert ops.conv2d_stats_rows(d) == 512
+    kw = {}
+    if o.in_scale is not None:
+        assert ops.conv2d_affine_input_ok(d, 0)
+        kw = dict(in_scale=o.in_scale.to(device), in_shift=torch.zeros(Cc, device=device), in_relu=1)
+    plan = ops.Plan(device, eager=True)
+    flat, y = guarded(device, (N, H, W), K + 4)
+    y[..., :K] = float("nan")
+    st = torch.full((512, 2, K), float("nan"), device=device)
+    ops.conv2d_fwd(plan, d, o.x.to(device), o.w.to(device), None, y, stats=st, **kw)
+    torch.cuda.synchronize()
+    failures = []
+    held("fp32 entry, " + case + " fwd", name, y[..., :K], ref, bound, failures)
+    stats_held("fp32 entry, " + case + " fwd", name, st, ref, bound, failures)
+    untouched(case + " fwd", flat, y, K, K + 4)
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("case", FEW_BWD)
+def test_few_channel_data_gradient_routes(device, case):
+    """acimg_conv2d_dgrad on conv_few16_kernel MODE 1 (bf16x3): stride 1, and stride 2 over the zero-inserted view of gy with
+    leading pads 0 (even sizes) and 1 (odd); the 8 -> 32 layer on the 16-row halo instance.  gy channels at 2^-30 .. 2^-10,
+    dx into a wider pixel stride with the pad channels and the memory behind it untouched.  Route: the workspace query's
+    own size for the narrow halo instance; for the few-channel kernel the shape rule of the conv it is - gy's K channels
+    into C (acimg_conv2d_stats_rows of that conv: 512) - and the workspace's footprint: the kernel's weight image
+    (2 x 16 rows x 96 or 160 bf16) and not a byte more, where the zero-inserted copy or the direct kernel would differ."""
+    import ctypes as C
+
+    from acimg import _lib, ops
+
+    N, H, W, Cc, K, kind = sf.FP32_CASES[case][:6]
+    o, ref, bound = fp32_grad_reference(case)
+    d = ops.conv_desc(N, H, W, Cc, K, 3, 3, 2 if kind == "few/2" else 1, "SAME")
+    assert (d.pad_t, d.pad_l) == ((H % 2, W % 2) if kind == "few/2" else (1, 1)) and o.gy.shape[1:3] == (d.OH, d.OW)
+    query = int(_lib.load().acimg_conv2d_dgrad_workspace(C.byref(d)))
+    narrow = K == 32
+    if narrow:
+        assert query == 2 * 16 * 288 * 2 + 256
+    else:
+        assert ops.conv2d_stats_rows(ops.conv_desc(N, H, W, K, Cc, 3, 3, 1, "SAME")) == 512
+    plan = ops.Plan(device, eager=True)
+    ws = poisoned_workspace(plan, query)
+    flat, dx = guarded(device, (N, H, W), Cc + 4)
+    dx[..., :Cc] = float("nan")
+    ops.conv2d_dgrad(plan, d, o.gy.to(device), K, o.w.to(device), dx, lddx=Cc + 4)
+    torch.cuda.synchronize()
+    image = 2 * 16 * (288 if narrow else (96 if K <= 8 else 160)) * 2
+    assert int(ws[image - 1]) != WS_BYTE and bool((ws[image:] == WS_BYTE).all()), "the workspace's footprint is another route's"
+    held("fp32 entry, " + case, "dx", dx[..., :Cc], ref, bound)
+    untouched(case + " dx", flat, dx, Cc, Cc + 4)
+
+
+@pytest.mark.parametrize("impulse", [False, True], ids=["dense", "impulse"])
+@pytest.mark.parametrize("case", FEW_WGRAD)
+def test_few_channel_weight_gradient_route(device, case, impulse):
+    """acimg_conv2d_wgrad on wgrad_halo16_kernel<16, 3> (bf16x3 on a zero-padded channel tile): dense gradients with the
+    launch's real counts (sf.fp32_wgrad_counts), and the `impulse` set - gy nonzero at a handful of pixels round the tensor's
+    ends and a tile's, a row's and an image's boundary - where each dw element is one or two products and the format term
+    alone is the bound; dw with pad columns, db.  Route: acimg_conv2d_affine_input_ok (forward AND weight gradient on the
+    halo kernels)."""
+    from acimg import ops
+
+    N, H, W, Cc, K = sf.FP32_CASES[case][:5]
+    o, ref, bound, dbref, counts = fp32_wgrad_reference(case, impulse)
+    d = ops.conv_desc(N, H, W, Cc, K, 3, 3, 1, "SAME", ldw=K + 4)
+    assert ops.conv2d_affine_input_ok(d, 0)
+    plan = ops.Plan(device, eager=True)
+    flat, dw = guarded(device, (3, 3, Cc), K + 4)
+    dw[..., :K] = float("nan")
+    db = torch.full((K + TAIL,), SENT, device=device)
+    ops.conv2d_wgrad(plan, d, o.x.to(device), o.gy.to(device), K, dw, db)
+    torch.cuda.synchronize()
+    failures = []
+    path, what = "fp32 entry, " + case, "impulse " if impulse else ""
+    print("wgrad %s: %d K steps, %d slabs" % (case, counts[0], counts[1]))
+    held(path, what + "dw", dw[..., :K], ref, bound, failures)
+    held(path, what + "db", db[:K], dbref,
+         sf.bound_bf16x3(torch.ones_like(o.gy), o.gy, counts[0], ranges=counts[1], prod=sf.colsum, fmt=FEW), failures)
+    untouched(case + " dw", flat, dw, K, K + 4)
+    assert bool((db[K:] == SENT).all()), "memory past db written"
+    assert not failures, failures
+
+
+def pointwise_desc(ops, **kw):
+    N, H, W, Cc, K = sf.FP32_CASES["pointwise"][:5]
+    assert N * H * W >= 65536 and N * H * W % 2 == 1           # the last 16-pixel group and 32-pixel block are ragged
+    return ops.deconv_desc(N, H, W, Cc, K, 2, 2, 2, **kw)
+
+
+@pytest.mark.parametrize("name", sf.FP32_CASES["pointwise"][6])
+def test_pointwise_forward_route(device, name):
+    """acimg_deconv_fwd on patch2_32x8_kernel<SplitF16, 0> (one 32-deep step per output element) with 65709 input pixels - the
+    last 16-pixel group has 3 dead lanes - on `channels`, `quiet` and `loud` (the ends of the stated range), with a bias of
+    each channel's own magnitude (one more fp32 rounding, of |bias|: where the bias outweighs the product that rounding IS
+    the bound, so ratios near 1 here are the add, not the format), into the upper channel slice of a wider pixel stride: the
+    lower slice and the memory behind the tensor untouched.  (Route: the three pointwise kernels share one shape rule;
+    test_pointwise_weight_gradient_route shows it taken by its workspace footprint.)"""
+    from acimg import ops
+
+    N, H, W, Cc, K = sf.FP32_CASES["pointwise"][:5]
+    o, ref, bound = fp32_forward_reference("pointwise", name)
+    g = torch.Generator().manual_seed(601)
+    bias = torch.randn(K, generator=g) * ref.reshape(-1, K).abs().amax(0).float()
+    d = pointwise_desc(ops, ldy=2 * K)
+    plan = ops.Plan(device, eager=True)
+    flat, y = guarded(device, (N, 2 * H, 2 * W), 2 * K)
+    y[..., K:] = float("nan")
+    ops.deconv_fwd(plan, d, o.x.to(device), o.w.to(device), bias.to(device), ops.Ptr(flat, K))
+    torch.cuda.synchronize()
+    held("fp32 entry, pointwise fwd", name, y[..., K:], ref + bias.double(), bound + U24 * bias.double().abs().expand_as(bound))
+    untouched("pointwise fwd", flat, y, 0, K)
+
+
+def test_pointwise_data_gradient_route(device):
+    """acimg_deconv_dgrad on patch2_32x8_kernel<SplitBF16, 1> with and without the ReLU mask (the layer's own post-ReLU
+    input: half of it zeros), gy channels at 2^-30 .. 2^-10, dx with pad channels; dead lanes as in the forward"""
+    from acimg import ops
+
+    N, H, W, Cc, K = sf.FP32_CASES["pointwise"][:5]
+    o, ref, bound = fp32_grad_reference("pointwise")
+    d = pointwise_desc(ops, ldx=Cc + 4)
+    plan = ops.Plan(device, eager=True)
+    gyd, wd = o.gy.to(device), o.w.to(device)
+    mask = o.x.to(device)
+    assert 0.3 < float((o.x > 0).float().mean()) < 0.7
+    failures = []
+    for what, m in (("dx", None), ("dx, ReLU mask", mask)):
+        flat, dx = guarded(device, (N, H, W), Cc + 4)
+        dx[..., :Cc] = float("nan")
+        ops.deconv_dgrad(plan, d, gyd, K, wd, dx, m, Cc if m is not None else 0)
+        torch.cuda.synchronize()
+        held("fp32 entry, pointwise", what, dx[..., :Cc], ref if m is None else ref * (o.x > 0).double(), bound, failures)
+        untouched("pointwise " + what, flat, dx, Cc, Cc + 4)
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("impulse", [False, True], ids=["dense", "impulse"])
+def test_pointwise_weight_gradient_route(device, impulse):
+    """acimg_deconv_wgrad on patch2_wgrad_32x8_kernel: 65709 pixels end the last 32-pixel block inside one lane's 8 pixels, and
+    rows of 147 and images of 21903 pixels end inside a lane's 8 pixels (the carry).  Dense gradients with the launch's
+    counts, and the `impulse` set: gy nonzero round a lane, block, row and image boundary, at the last live pixel and through
+    its lane group - each dw element one or two products.  The fused bias gradient against the fp64 column sum of gy, bound:
+    fp32 summation over the values each chain adds (sf.patch2_db_adds) - on `impulse` a dead lane's gy counted as live would be
+    far outside it.  dw with pad columns.  Route: the workspace's footprint - 256 slabs of 32 x ldw (pad columns unwritten)
+    and 256 x 8 bias partials, nothing behind them."""
+    import ctypes as C
+
+    from acimg import _lib, ops
+
+    N, H, W, Cc, K = sf.FP32_CASES["pointwise"][:5]
+    o, ref, bound, dbref, counts = fp32_wgrad_reference("pointwise", impulse)
+    ldw = Cc + 4
+    d = pointwise_desc(ops, ldw=ldw)
+    plan = ops.Plan(device, eager=True)
+    ws = poisoned_workspace(plan, int(_lib.load().acimg_deconv_workspace(C.byref(d))))
+    flat, dw = guarded(device, (2, 2, K), ldw)
+    dw[..., :Cc] = float("nan")
+    db = torch.full((K + TAIL,), SENT, device=device)
+    ops.deconv_wgrad(plan, d, o.x.to(device), o.gy.to(device), K, dw, db)
+    torch.cuda.synchronize()
+    foot = 256 * (32 * ldw + 8) * 4
+    slabs = ws[:256 * 32 * ldw * 4].view(256 * 32, ldw * 4)
+    assert bool((slabs[:, Cc * 4:] == WS_BYTE).all()) and bool((ws[foot:] == WS_BYTE).all()), "not the pointwise kernel's slabs"
+    assert not bool((ws[foot - 4:foot] == WS_BYTE).all()) and not bool((slabs[-1, Cc * 4 - 4:Cc * 4] == WS_BYTE).all())
+    failures = []
+    path, what = "fp32 entry, pointwise", "impulse " if impulse else ""
+    print("wgrad pointwise: %d K steps, %d slabs" % counts)
+    held(path, what + "dw", dw[..., :Cc], ref, bound, failures)
+    adds = sf.patch2_db_adds(N * H * W)
+    held(path, what + "db", db[:K], dbref, adds * U24 * o.gy.double().abs().sum((0, 1, 2)), failures)
+    untouched("pointwise dw", flat, dw, Cc, ldw)
+    assert bool((db[K:] == SENT).all()), "memory past db written"
+    assert not failures, failures
+
+
+def test_halo_weight_gradient_on_impulses(device):
+    """acimg_conv2d_wgrad_split3 at 64 -> 32 (wgrad_halo16_kernel<64, 3>, 4-row tiles) on the `impulse` set"""
+    from acimg import ops
+
+    case = "halo 64"
+    N, H, W, Cc, K, taps = sf.BWD_CASES[case][:6]
+    o = sf.impulse_operands(case)
+    wg = sf.conv_wgrad(taps)
+    d = ops.conv_desc(N, H, W, Cc, K, taps, taps, 1, "SAME")
+    assert ops.conv2d_affine_input_ok(d, 1)                   # forward and weight gradient on the halo kernels
+    plan = ops.Plan(device, eager=True)
+    dw = torch.full((taps, taps, Cc, K), float("nan"), device=device)
+    db = torch.full((K,), float("nan"), device=device)
+    ops.conv2d_wgrad_split3(plan, d, o.x.to(device), o.gy.to(device), K, dw, db)
+    torch.cuda.synchronize()
+    failures = []
+    held("bf16x3 backward " + case, "impulse dw", dw, wg(o.x.double(), o.gy.double()),
+         sf.bound_bf16x3(o.x, o.gy, o.npix, ranges=0, prod=wg, fmt=FEW), failures)
+    held("bf16x3 backward " + case, "impulse db", db, o.gy.double().sum((0, 1, 2)),
+         sf.bound_bf16x3(torch.ones_like(o.gy), o.gy, o.npix, ranges=0, prod=sf.colsum, fmt=FEW), failures)
     assert not failures, failures
