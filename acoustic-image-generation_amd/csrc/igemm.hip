@@ -14,6 +14,7 @@
 // unchanged.  Global->register prefetch of tile t+1 overlaps the MFMAs of tile t.
 #include "wgrad_split3_kernel.hpp"
 #include "wgrad_tap_kernel.hpp"
+#include "conv_tap_kernel.hpp"
 #include "igemm_split3d_kernel.hpp"
 #include "igemm_split3dp_kernel.hpp"
 #include "igemm_split3r_kernel.hpp"
@@ -2588,6 +2589,30 @@ static int launch_split3(IgemmParams& p, hipStream_t st) {
     return check_launch("igemm_split3");
 }
 
+// the tap-sharing form of the on-the-fly split convs (conv_tap_kernel.hpp): 3x3 / stride 1 / SAME, image rows of 32 or 48 pixels
+// (whole two-row tiles, the last of an odd height half empty), at least 64 reduction channels in whole 32-channel chunks, more than 32 output
+// columns stored with 16-byte accesses, the three-term product, no input affine and no statistics.  Everything else (the
+// one-term bf16 modes, in_scale / stats calls, the 12x16 layers, wide images) stays on igemm_split3_kernel.
+// Measured per shape at batch 32 (profiles/conv_tap/, tools/op_report.py, three reports each, per-tap kernel -> this form, us):
+// forward 128->128 87.1-88.4 -> 68.4-68.5 and 82.2-82.8 -> 67.0-68.4, 256->128 148.5-149.1 -> 123.0-123.3, 128->64 54.3-55.0 ->
+// 48.8-49.2, 64->64 33.3-34.4 -> 29.4-30.5; data gradient 64->64 34.8-35.3 -> 31.5-32.4, 128->64 55.8-56.7 -> 48.0-50.4, 128->128
+// 79.2-79.9 -> 64.8-65.1 and 86.5-87.5 -> 67.3-68.6, 256->128 145.2-146.6 -> 99.4-100.1: all ten beat the per-tap kernel's lowest
+// by more than its spread (the narrowest: 64->64, 2.4 and 2.8 us against spreads of 0.5 and 1.1), so none is routed back.
+static bool conv_tap_ok(const IgemmParams& p, int terms) {
+    return terms == 3 && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 && p.OH == p.H && p.OW == p.W &&
+           (p.W == 32 || p.W == 48) && p.C >= 64 && p.C % 32 == 0 && p.Ngemm > 32 && p.e.vec && (p.lda & 3) == 0 &&
+           aligned16(p.A) && aligned16(p.B) && p.M % (p.H * p.W) == 0 && !p.a_scale && !p.e.stats && p.splits == 1 && g_cfg.wgrad_halo;
+}
+template <typename TR>
+static int launch_conv_tap(const IgemmParams& p, hipStream_t st) {
+    const dim3 grid(p.M / (p.H * p.W) * cdiv(p.H, CT_TH), cdiv(p.Ngemm, p.Ngemm <= 64 ? 64 : 128), 1);
+#define ACIMG_CT(Wv, NBv) hipLaunchKernelGGL((conv_tap_kernel<TR, Wv, NBv>), grid, dim3(512), conv_tap_lds(Wv, NBv), st, p)
+    if (p.W == 48) { if (p.Ngemm <= 64) ACIMG_CT(48, 64); else ACIMG_CT(48, 128); }
+    else           { if (p.Ngemm <= 64) ACIMG_CT(32, 64); else ACIMG_CT(32, 128); }
+#undef ACIMG_CT
+    return check_launch("conv_tap");
+}
+
 static int fwd_split_onthefly(const AcimgConvDesc* d, const float* x, const void* wsplit, const float* bias, float* y,
                               const float* in_scale, const float* in_shift, int in_relu, float* stats, void* stream,
                               bool bf16) {
@@ -2623,6 +2648,7 @@ static int fwd_split_onthefly(const AcimgConvDesc* d, const float* x, const void
     p.a_bytes = (unsigned)a_bytes; p.b_bytes = (unsigned)b_bytes;
     p.e.Y = y; p.e.bias = bias; p.e.stats = stats;
     epi_vec_flag(p.e);
+    if (conv_tap_ok(p, bf16 ? 1 : 3)) return launch_conv_tap<SplitF16>(p, (hipStream_t)stream);
     if (bf16) return launch_split3<SplitBF16, 1>(p, (hipStream_t)stream);
     return launch_split3<SplitF16>(p, (hipStream_t)stream);
 }
@@ -2659,6 +2685,7 @@ static int dgrad_split_onthefly(const AcimgConvDesc* d, const float* gy, int ldg
     EpiParams& e = p.e;
     e.Y = dx; e.ldy = lddx; e.res = residual; e.ldres = ldres; e.mask = mask; e.ldmask = ldmask;
     epi_vec_flag(e);
+    if (conv_tap_ok(p, terms)) return launch_conv_tap<SplitBF16>(p, (hipStream_t)stream);
     if (terms == 1) return launch_split3<SplitBF16, 1>(p, (hipStream_t)stream);
     return launch_split3<SplitBF16>(p, (hipStream_t)stream);
 }

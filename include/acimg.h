@@ -153,6 +153,9 @@ size_t acimg_conv2d_fwd_workspace(const AcimgConvDesc* d);
  * "channels" of a tap are then the C / ldx consecutive pixels of an input row starting at ow*stride (windows of
  * neighbouring outputs overlap; (OW-1)*stride + C/ldx <= W).  The 7x7/2 stem on a zero-padded 4-channel frame is
  * such a conv: R = 7, S = 1, C = 32 = 7 pixels x 4 channels + one pixel of zero weights, ldx = 4.
+ * ARITHMETIC: on the 3x3 / stride 1 / SAME layers with image rows of 32 or 48 pixels, C >= 64 and K > 32 (no in_scale, no
+ * stats; wgrad_halo = 1) the same format with K summed chunk-major - 32 channels at a time, the nine taps inside - instead
+ * of tap-major: the same products in another order.
  * Replaces: slim layers.conv2d / conv2d_same in the trunk, models/resnet50.py:109-121. */
 size_t acimg_conv2d_split3_weight_bytes(const AcimgConvDesc* d);
 int acimg_conv2d_split3_prepare(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream);
@@ -170,7 +173,9 @@ int acimg_conv2d_fwd_split3(const AcimgConvDesc* d, const float* x, const void* 
  * outside fp16's range; bf16 keeps fp32's range, 16 mantissa bits, no scaling): a forward conv of gy with
  * the flipped + transposed kernel prepared by acimg_conv2d_split3_prepare_dgrad ([hi|lo][C][R*S*K] bf16,
  * acimg_conv2d_split3_dgrad_weight_bytes(d) bytes).  Needs K % 32 == 0.  residual / mask / lddx as in
- * acimg_conv2d_dgrad. */
+ * acimg_conv2d_dgrad.
+ * ARITHMETIC: on the 3x3 / SAME layers with image rows of 32 or 48 pixels, K >= 64 and C > 32 (wgrad_halo = 1) the same
+ * format with K summed chunk-major (32 gy channels at a time, the nine taps inside) instead of tap-major. */
 size_t acimg_conv2d_split3_dgrad_weight_bytes(const AcimgConvDesc* d);
 int acimg_conv2d_split3_prepare_dgrad(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream);
 int acimg_conv2d_dgrad_split3(const AcimgConvDesc* d, const float* gy, int ldgy, const void* wsplit_t, float* dx,
