@@ -1,17 +1,18 @@
-// fp32 implicit-GEMM convolution kernels for gfx950 (MI355X), exact-f32 MFMA
-// (v_mfma_f32_16x16x4_f32: bit-for-bit an fmaf chain, 64 FLOP/clk/SIMD).
-//
-// One kernel template covers every conv-shaped op of the acoustic-image train step:
-//   forward conv / strided conv / 1x1 / dense        A = im2col(x),  B = W[k][n]      (NN)
-//   data gradient (stride 1)                         A = im2col(gy), B = W^T flipped  (NT)
-//   kernel==stride patch ops (deconv fwd, pool dgrad)A = pixels,     B = W rows, scatter epilogue
-// and a second template does the weight gradient dW = im2col(x)^T * gy (TN, split over pixels).
-//
-// Tiling: 256 threads = 4 waves, block tile BM x BN x BK(=32), wave tile (BM/WGM) x (BN/WGN) made
-// of 16x16 MFMA tiles.  A is staged [row][k] (k contiguous, ds_read_b128 gives 4 k per lane), B is
-// staged [k][n] (NN, ds_read_b32) or [n][k] (NT, ds_read_b128).  The k order inside a 16-deep step
-// is permuted identically for A and B (lane group g owns k = 4g..4g+3), which leaves the sum
-// unchanged.  Global->register prefetch of tile t+1 overlaps the MFMAs of tile t.
+// Host side of the convolutions for gfx950 (MI355X): this file decides which kernel a call runs and launches it.  It holds
+// the tuning record (g_cfg), the *_shape / *_ok predicates with the measurements that justify each route, the workspace
+// formulas, the kernel selections (pick_*, TrunkVariant), every launch_* / dispatch_*, and the C entry points.  The device
+// code lives in one header per kernel family (kernels, their parameter structs, tile constants and design notes; no launch,
+// no predicate that reads g_cfg, no entry point):
+//   igemm_kernel.hpp          exact-f32 implicit GEMM (forward, data gradient, patch scatter) and its epilogue
+//   wgrad_f32_kernel.hpp      exact-f32 weight gradient; the slab reducers of every split weight gradient
+//   wgrad_halo_kernel.hpp     halo weight gradients: exact f32 (few channels) and bf16 / bf16x3 (<= 64 -> <= 32 channels)
+//   direct_conv_kernel.hpp    direct few-channel conv
+//   conv_few16_kernel.hpp     few-channel 3x3 conv on split 16-bit MFMAs
+//   patch2_kernel.hpp         2x2 / stride-2 transposed conv 32 -> 8: forward / data gradient, weight gradient
+//   conv_halo16_kernel.hpp    halo form of the 32- / 64-channel 3x3 forward conv and data gradient
+//   conv_aux_kernels.hpp      split-K reduce, sub-pixel weights, tap-GEMM helpers, column sums, statistics, fills, bricks
+//   igemm_split3*_kernel.hpp  split 16-bit implicit GEMM: on the fly (split3) and the pre-split trunk kernels (d, dp, r, h)
+//   wgrad_split3_kernel.hpp, wgrad_tap_kernel.hpp, conv_tap_kernel.hpp, skinny_kernel.hpp
 #include "wgrad_split3_kernel.hpp"
 #include "wgrad_tap_kernel.hpp"
 #include "conv_tap_kernel.hpp"
@@ -20,286 +21,19 @@
 #include "igemm_split3r_kernel.hpp"
 #include "igemm_split3h_kernel.hpp"
 #include "skinny_kernel.hpp"
+#include "wgrad_f32_kernel.hpp"
+#include "wgrad_halo_kernel.hpp"
+#include "direct_conv_kernel.hpp"
+#include "conv_few16_kernel.hpp"
+#include "patch2_kernel.hpp"
+#include "conv_halo16_kernel.hpp"
+#include "conv_aux_kernels.hpp"
 #include <cstdlib>
 #include <algorithm>
 #include <type_traits>
 
 namespace acimg {
 
-// split-K reducer: sums the slabs and runs the epilogue
-__global__ __launch_bounds__(256) void igemm_splitk_reduce_kernel(const float* slab, int splits,
-                                                                  int M, int Ngemm, int slab_ld,
-                                                                  const EpiParams e) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    const long total = (long)M * Ngemm;
-    if (idx >= total) return;
-    const int m = (int)(idx / Ngemm);
-    const int n = (int)(idx - (long)m * Ngemm);
-    float v = 0.f;
-    for (int z = 0; z < splits; ++z) v += slab[((long)z * M + m) * slab_ld + n];
-    if (n >= e.Nstore) return;
-    int cn, pixoff, r, q, oh, ow;
-    epi_col(e, n, cn, pixoff, r, q);
-    const long rp = epi_row_pix(e, m, oh, ow);
-    if (epi_lands(e, oh, ow, r, q)) epi_store(e, rp + pixoff, cn, v);
-}
-
-// ------------------------------------------------------------------------------------------
-// SUB-PIXEL form of the stride-2 transposed convolutions with overlapping taps (round 4): the transposed conv
-// `conv2d_transpose(k > 2, s = 2)` (models/unet_architecture.py:192-206: upconv_2D with (2,3) kernels) and the data
-// gradient of a stride-2 conv (the strided "pool" convs, :168-176).  Both compute
-//     Y[s i + a + oy0][s j + b + ox0][ko] = sum_{u, v, kin} A[i - u][j - v][kin] * w[a + 2 u][b + 2 v][ko][kin]
-// i.e. an output pixel of parity class (a, b) only sees the kernel taps of its class: ceil(R/2) x ceil(S/2) of them.
-// Round 1 ran these as a stride-1 correlation over a ZERO-INSERTED copy of A (4x the pixels, 3 of 4 products against
-// zeros, plus the copy's 4x write and read).  Here the four classes are the column groups of ONE implicit GEMM over A's own
-// grid - rows (i, j), K = (u', v', kin) with a ceil(R/2) x ceil(S/2) gather, columns (a, b, ko) - whose epilogue scatters
-// element (i, j, a, b, ko) to pixel (2 i + a + oy0, 2 j + b + ox0): the k <= s scatter of the non-overlapping transposed
-// convs, bounds-checked (EpiParams::scatter = 2).  The combined weight matrix is gathered from the layer's kernel by
-// `subpixel_weights_kernel` (the kernels change every step).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void subpixel_weights_kernel(const float* w, int R, int S, int Ko, int Kin, int ldw, int U,
-                                                               int V, float* wc, int total) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int ncol = 4 * Ko;
-    const int row = idx / ncol, col = idx - row * ncol;
-    const int kin = row % Kin, tap = row / Kin;
-    const int up = tap / V, vp = tap - up * V;
-    const int cls = col / Ko, ko = col - cls * Ko;
-    const int a = cls >> 1, b = cls & 1;
-    const int r = a + 2 * (U - 1 - up), q = b + 2 * (V - 1 - vp);
-    wc[idx] = (r < R && q < S) ? w[((long)(r * S + q) * Ko + ko) * ldw + kin] : 0.f;
-}
-
-// ------------------------------------------------------------------------------------------
-// weight gradient kernel: dW[kk][n] = sum_m A(m,kk) G[m][n]
-// ------------------------------------------------------------------------------------------
-// WGM x WGN = 4 waves: 2 x 2, or 4 x 1 for the 16-column tile of the few-column problems (N <= 16: conv_map's 12
-// outputs, the 8-channel layers of the RGB / spectrogram U-Nets) where a 32-wide tile would be mostly padding
-template <int BMO, int BN, int WGM = 2>
-__global__ __launch_bounds__(256) void wgrad_f32_kernel(const WgradParams p) {
-    constexpr int BKR = 16;  // pixels per step
-    constexpr int LDA_S = BMO + 4;
-    constexpr int LDB_S = BN + 4;
-    constexpr int WGN = 4 / WGM;
-    constexpr int WTM = BMO / WGM, WTN = BN / WGN;
-    static_assert(WTM % 16 == 0 && WTN % 16 == 0, "wave tile");
-    constexpr int TM = WTM / 16, TN = WTN / 16;
-    constexpr int AQ = BMO / 4;               // float4 per A row
-    constexpr int ARPP = 256 / AQ;            // A rows per pass
-    constexpr int NA = (BKR + ARPP - 1) / ARPP;
-    constexpr int BQ = BN / 4;
-    constexpr int BRPP = 256 / BQ;
-    constexpr int NB = (BKR + BRPP - 1) / BRPP;
-
-    __shared__ __attribute__((aligned(16))) float As[BKR * LDA_S];
-    __shared__ __attribute__((aligned(16))) float Bs[BKR * LDB_S];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WGN, wn = wid % WGN;
-    const int li = lane & 15, g = lane >> 4;
-    const int kk0 = blockIdx.x * BMO, n0 = blockIdx.y * BN;
-
-    const int m_begin = blockIdx.z * p.rows_per_split;
-    const int m_end = min(p.M, m_begin + p.rows_per_split);
-
-    // this thread's fixed A column (kk -> tap, c)
-    const int aq = tid % AQ;
-    const int arow0 = tid / AQ;
-    const int kk = kk0 + aq * 4;
-    const bool kk_ok = kk < p.KK;
-    const bool kk_ones = p.db_out != nullptr && kk == p.KK;   // the all-ones column (bias gradient)
-    int r = 0, s = 0, c = 0;
-    if (kk_ok) {
-        const int tap = kk / p.C;
-        c = kk - tap * p.C;
-        r = tap / p.S;
-        s = tap - r * p.S;
-    }
-    const int bq = tid % BQ;
-    const int brow0 = tid / BQ;
-    const int nb = n0 + bq * 4;
-    const bool nb_ok = nb < p.Nld;
-    const int ohw = p.OH * p.OW;
-
-    // pixel coordinates of this thread's A rows, advanced incrementally by BKR pixels per step (two integer
-    // divisions per load were the bulk of this kernel's time on the few-channel layers: no hardware divider)
-    int x_img[NA], x_oh[NA], x_ow[NA];
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int m = m_begin + arow0 + j * ARPP;
-        x_img[j] = m / ohw;
-        const int rem = m - x_img[j] * ohw;
-        x_oh[j] = rem / p.OW;
-        x_ow[j] = rem - x_oh[j] * p.OW;
-    }
-
-    float4 ra[NA], rb[NB];
-    auto load_tiles = [&](int mb) {
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            const int row = arow0 + j * ARPP;
-            const int m = mb + row;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < BKR && kk_ones && m < m_end) v.x = 1.f;
-            if (row < BKR && kk_ok && m < m_end) {
-                const int ih = x_oh[j] * p.stride - p.pad_t + r;
-                const int iw = x_ow[j] * p.stride - p.pad_l + s;
-                if ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W)
-                    v = *reinterpret_cast<const float4*>(
-                        p.X + ((long)(x_img[j] * p.H + ih) * p.W + iw) * p.ldx + c);
-            }
-            ra[j] = v;
-            x_ow[j] += BKR;                    // this row slot moves BKR pixels ahead for the next call
-            while (x_ow[j] >= p.OW) {
-                x_ow[j] -= p.OW;
-                if (++x_oh[j] == p.OH) {
-                    x_oh[j] = 0;
-                    ++x_img[j];
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int row = brow0 + j * BRPP;
-            const int m = mb + row;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < BKR && nb_ok && m < m_end)
-                v = *reinterpret_cast<const float4*>(p.G + (long)m * p.ldg + nb);
-            rb[j] = v;
-        }
-    };
-    auto store_tiles = [&]() {
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            const int row = arow0 + j * ARPP;
-            if (row < BKR) *reinterpret_cast<float4*>(&As[row * LDA_S + aq * 4]) = ra[j];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int row = brow0 + j * BRPP;
-            if (row < BKR) *reinterpret_cast<float4*>(&Bs[row * LDB_S + bq * 4]) = rb[j];
-        }
-    };
-
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (m_begin < m_end) {
-        load_tiles(m_begin);
-        store_tiles();
-    }
-    __syncthreads();
-    for (int mb = m_begin; mb < m_end; mb += BKR) {
-        const bool more = (mb + BKR) < m_end;
-        if (more) load_tiles(mb + BKR);
-        float af[TM][4], bf[TN][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i][t] = As[(4 * g + t) * LDA_S + wm * WTM + i * 16 + li];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[j][t] = Bs[(4 * g + t) * LDB_S + wn * WTN + j * 16 + li];
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][t], bf[j][t], acc[i][j], 0, 0, 0);
-        __syncthreads();
-        if (more) {
-            store_tiles();
-            __syncthreads();
-        }
-    }
-
-    float* out = p.out + (long)blockIdx.z * p.KK * p.ldo;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-            const int row = kk0 + wm * WTM + i * 16 + g * 4 + rg;
-            if (row > p.KK || (row == p.KK && p.db_out == nullptr)) continue;
-            float* dst = row < p.KK ? out + (long)row * p.ldo : p.db_out + (long)blockIdx.z * p.ldo;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + wn * WTN + j * 16 + li;
-                if (n < p.Ngemm) dst[n] = acc[i][j][rg];
-            }
-        }
-}
-
-// sums `splits` slabs of [rows][ld] (only cols < ncols) into out[rows][ld]; workgroups >= nb1 do the same for a
-// second, one-row job (the bias gradient of the same launch: one reduce launch per weight gradient, not two)
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* slab, int splits, long rows,
-                                                          int ncols, int ld, float* out, int nb1,
-                                                          const float* slab2, float* out2) {
-    long bid = blockIdx.x;
-    if (bid >= nb1) {
-        bid -= nb1;
-        slab = slab2;
-        out = out2;
-        rows = 1;
-    }
-    const long idx = bid * 256 + threadIdx.x;
-    if (idx >= rows * ncols) return;
-    const long row = idx / ncols;
-    const int col = (int)(idx - row * ncols);
-    float v = 0.f;
-    for (int z = 0; z < splits; ++z) v += slab[((long)z * rows + row) * ld + col];
-    out[row * ld + col] = v;
-}
-
-// the same for many slabs (few-channel weight gradients use up to 2048 pixel splits): OUTS outputs per workgroup, 256 / OUTS
-// lane groups walk the slabs with four loads in flight each, fixed-order combine -> deterministic.  OUTS = 32 for large
-// gradients; 8 when there are few outputs (a 9 x 8 x 8 kernel is 576 numbers: 18 workgroups of 32 outputs each walked 512
-// slabs in 16 dependent rounds - 8 to 20 us of pure latency per launch; 72 workgroups with 32 lane groups need 4 rounds)
-template <int OUTS>
-__global__ __launch_bounds__(256) void slab_reduce_wide_kernel(const float* slab, int splits, long rows,
-                                                               int ncols, int ld, float* out, int nb1,
-                                                               const float* slab2, float* out2) {
-    constexpr int NG = 256 / OUTS;
-    __shared__ float red[NG][OUTS];
-    const int ol = threadIdx.x % OUTS, rg = threadIdx.x / OUTS;
-    long bid = blockIdx.x;
-    if (bid >= nb1) {                  // second job: the one-row bias gradient
-        bid -= nb1;
-        slab = slab2;
-        out = out2;
-        rows = 1;
-    }
-    const long idx = bid * OUTS + ol;
-    const bool ok = idx < rows * ncols;
-    const long row = ok ? idx / ncols : 0;
-    const int col = ok ? (int)(idx - row * ncols) : 0;
-    const float* src = slab + row * ld + col;
-    const long zs = rows * ld;
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-    if (ok) {
-        int z = rg;
-        for (; z + 3 * NG < splits; z += 4 * NG) {
-            v0 += src[(long)z * zs];
-            v1 += src[(long)(z + NG) * zs];
-            v2 += src[(long)(z + 2 * NG) * zs];
-            v3 += src[(long)(z + 3 * NG) * zs];
-        }
-        for (; z < splits; z += NG) v0 += src[(long)z * zs];
-    }
-    red[rg][ol] = (v0 + v1) + (v2 + v3);
-    __syncthreads();
-    if (rg == 0 && ok) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < NG; ++i) t += red[i][ol];
-        out[row * ld + col] = t;
-    }
-}
 // slab [splits][rows][ld] -> out [rows][ld] (ncols of them); optionally slab2 [splits][ld] -> out2 [ncols] (bias gradient)
 static void launch_slab_reduce_wide(const float* slab, int splits, long rows, int ncols, int ld, float* out, const float* slab2,
                                     float* out2, hipStream_t st) {
@@ -312,417 +46,6 @@ static void launch_slab_reduce_wide(const float* slab, int splits, long rows, in
         const int nb1 = (int)cdiv(total, 32), nb2 = out2 ? cdiv(ncols, 32) : 0;
         hipLaunchKernelGGL(slab_reduce_wide_kernel<32>, dim3(nb1 + nb2), dim3(256), 0, st, slab, splits, rows, ncols, ld, out, nb1,
                            slab2, out2);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// "tap GEMM" form of a stride-1 VALID convolution with FEW output channels (conv_map: 3x4, 2048 -> 12):
-// as an implicit GEMM its N is one MFMA column and every output row gathers R*S*C inputs (no reuse across N:
-// L2-bound); instead Z[input pixel][tap*K + k] = X[input pixel][:] . W[tap][:][k] is ONE plain GEMM with
-// N = R*S*K columns that reads X once, and y[oh][ow][k] = sum_taps Z[oh+r][ow+s][tap*K + k] is a tiny gather.
-// The weight gradient is the same GEMM transposed: dWt = X^T . GZ with GZ the tap-scattered output gradient.
-// ------------------------------------------------------------------------------------------
-// wt[c][tap*K + k] = w[tap][c][k]
-__global__ __launch_bounds__(256) void tapconv_pack_kernel(const float* w, int taps, int C, int K, int ldw,
-                                                           float* wt, int ldwt) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    const int TK = taps * K;
-    if (idx >= (long)C * TK) return;
-    const int c = (int)(idx / TK), n = (int)(idx - (long)c * TK);
-    const int tap = n / K, k = n - tap * K;
-    wt[(long)c * ldwt + n] = w[((long)tap * C + c) * ldw + k];
-}
-
-// dw[tap][c][k] = dwt[c][tap*K + k] + decay * w[tap][c][k]
-__global__ __launch_bounds__(256) void tapconv_unpack_kernel(const float* dwt, int ldwt, int taps, int C, int K,
-                                                             int ldw, const float* w, float decay, float* dw) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)taps * C * K) return;
-    const int k = (int)(idx % K);
-    const long tc = idx / K;
-    const int c = (int)(tc % C), tap = (int)(tc / C);
-    float v = dwt[(long)c * ldwt + tap * K + k];
-    if (w) v = fmaf(decay, w[tc * ldw + k], v);
-    dw[tc * ldw + k] = v;
-}
-
-constexpr int TG_PPB = 32;     // output pixels per workgroup of the gather (= rows per batch-norm partial)
-// y[(n,oh,ow)][k] = sum_{r,s} z[(n,oh+r,ow+s)][(r*S+s)*K + k]; TG_PPB output pixels per workgroup, one thread per
-// (pixel, k); optional batch-norm partials stats[block][2][stats_ld] (rows past the end count as zeros)
-__global__ __launch_bounds__(256) void tapconv_gather_kernel(const float* z, int ldz, int H, int W, int R, int S,
-                                                             int K, int OH, int OW, long Mout, float* y, int ldy,
-                                                             float* stats, int stats_ld) {
-    extern __shared__ __attribute__((aligned(16))) float tg_smem[];     // [128][K] tile of outputs
-    const int ppb = TG_PPB;
-    const long m0 = (long)blockIdx.x * ppb;
-    for (int e = threadIdx.x; e < ppb * K; e += 256) {
-        const int pl = e / K, k = e - pl * K;
-        const long m = m0 + pl;
-        float acc = 0.f;
-        if (m < Mout) {
-            const int ow = (int)(m % OW);
-            const long t = m / OW;
-            const int oh = (int)(t % OH);
-            const long img = t / OH;
-            for (int r = 0; r < R; ++r)
-                for (int q = 0; q < S; ++q)
-                    acc += z[((img * H + oh + r) * W + ow + q) * ldz + (r * S + q) * K + k];
-            y[m * ldy + k] = acc;
-        }
-        tg_smem[e] = acc;
-    }
-    if (!stats) return;
-    __syncthreads();
-    if ((int)threadIdx.x < 2 * K) {
-        const int which = threadIdx.x / K, k = threadIdx.x - which * K;
-        float sum = 0.f;
-        for (int pl = 0; pl < ppb; ++pl) {
-            const float v = tg_smem[pl * K + k];
-            sum += which ? v * v : v;
-        }
-        stats[((long)blockIdx.x * 2 + which) * stats_ld + k] = sum;
-    }
-}
-
-// gz[(n,ih,iw)][(r*S+s)*K + k] = gy[(n,ih-r,iw-s)][k] (0 outside the output)
-__global__ __launch_bounds__(256) void tapconv_scatter_kernel(const float* gy, int ldgy, int H, int W, int R, int S,
-                                                              int K, int OH, int OW, long Min, float* gz, int ldgz) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    const int TK = R * S * K;
-    if (idx >= Min * TK) return;
-    const long pix = idx / TK;
-    const int n = (int)(idx - pix * TK);
-    const int tap = n / K, k = n - tap * K;
-    const int r = tap / S, q = tap - r * S;
-    const int iw = (int)(pix % W);
-    const long t = pix / W;
-    const int ih = (int)(t % H);
-    const long img = t / H;
-    const int oh = ih - r, ow = iw - q;
-    float v = 0.f;
-    if ((unsigned)oh < (unsigned)OH && (unsigned)ow < (unsigned)OW) v = gy[((img * OH + oh) * OW + ow) * ldgy + k];
-    gz[pix * ldgz + n] = v;
-}
-
-// column sums of G[rows][ld] (cols < ncols) -> out[ncols]; one block per 64 columns, 256 threads
-// = 4 row-groups x 64 columns.
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const float* G, long rows, int ncols,
-                                                             int ld, long rows_per_block,
-                                                             float* partial /*[gridDim.y][ncols]*/) {
-    __shared__ float red[4][64];
-    const int col = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int rg = threadIdx.x >> 6;
-    const long rb = (long)blockIdx.y * rows_per_block;
-    const long re = min(rows, rb + rows_per_block);
-    float s = 0.f;
-    if (col < ncols)
-        for (long r = rb + rg; r < re; r += 4) s += G[r * ld + col];
-    red[rg][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (rg == 0 && col < ncols)
-        partial[(long)blockIdx.y * ncols + col] = red[0][threadIdx.x] + red[1][threadIdx.x] +
-                                                  red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-// narrow variant (ncols <= 64, multiple of 4, ld % 4 == 0): a workgroup sweeps rows_per_block rows with float4
-// loads, (ncols/4) lanes per row; partial sums are combined in lane order -> deterministic
-__global__ __launch_bounds__(256) void colsum_narrow_kernel(const float* G, long rows, int ncols, int ld,
-                                                            long rows_per_block, float* partial) {
-    __shared__ float sm[256 * 4];
-    const int c4n = ncols >> 2;
-    const int tc = threadIdx.x % c4n, tr = threadIdx.x / c4n;
-    const int rstep = 256 / c4n;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (tr < rstep) {
-        const long r0 = (long)blockIdx.x * rows_per_block;
-        const long r1 = min(rows, r0 + rows_per_block);
-        // four rows in flight per thread, sums of their own, combined in a fixed order
-        float b[3][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        long r = r0 + tr;
-        for (; r + 3L * rstep < r1; r += 4L * rstep) {
-            const float4 v0 = *reinterpret_cast<const float4*>(G + r * ld + tc * 4);
-            const float4 v1 = *reinterpret_cast<const float4*>(G + (r + rstep) * ld + tc * 4);
-            const float4 v2 = *reinterpret_cast<const float4*>(G + (r + 2L * rstep) * ld + tc * 4);
-            const float4 v3 = *reinterpret_cast<const float4*>(G + (r + 3L * rstep) * ld + tc * 4);
-            a[0] += v0.x; a[1] += v0.y; a[2] += v0.z; a[3] += v0.w;
-            b[0][0] += v1.x; b[0][1] += v1.y; b[0][2] += v1.z; b[0][3] += v1.w;
-            b[1][0] += v2.x; b[1][1] += v2.y; b[1][2] += v2.z; b[1][3] += v2.w;
-            b[2][0] += v3.x; b[2][1] += v3.y; b[2][2] += v3.z; b[2][3] += v3.w;
-        }
-        for (; r < r1; r += rstep) {
-            const float4 v = *reinterpret_cast<const float4*>(G + r * ld + tc * 4);
-            a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = (a[k] + b[0][k]) + (b[1][k] + b[2][k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sm[threadIdx.x * 4 + k] = a[k];
-    __syncthreads();
-    if (threadIdx.x < c4n) {
-        float t[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int j = 0; j < rstep; ++j)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] += sm[(j * c4n + threadIdx.x) * 4 + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) partial[(long)blockIdx.x * ncols + threadIdx.x * 4 + k] = t[k];
-    }
-}
-// 256 threads = 4 part groups x 64 columns - or, for up to 16 columns (where the 4-group form is 64 dependent loads per
-// thread, ~13 us of latency for a kilobyte of result), 16 part groups x 16 columns; fixed-order combine
-__global__ __launch_bounds__(256) void colsum_final_kernel(const float* partial, int parts, int ncols, float* out) {
-    __shared__ float red[16][64];
-    const bool narrow = ncols <= 16;
-    const int cw = narrow ? 16 : 64, ng = 256 / cw;
-    const int cl = threadIdx.x % cw, pg = threadIdx.x / cw;
-    const int col = blockIdx.x * cw + cl;
-    float s0 = 0.f, s1 = 0.f;
-    if (col < ncols) {
-        int i = pg;
-        for (; i + ng < parts; i += 2 * ng) {
-            s0 += partial[(long)i * ncols + col];
-            s1 += partial[(long)(i + ng) * ncols + col];
-        }
-        if (i < parts) s0 += partial[(long)i * ncols + col];
-    }
-    red[pg][cl] = s0 + s1;
-    __syncthreads();
-    if (pg == 0 && col < ncols) {
-        float t = 0.f;
-        for (int g = 0; g < ng; ++g) t += red[g][cl];
-        out[col] = t;
-    }
-}
-
-// per-256-row-block column sums / sums of squares of y[M][K] (pixel stride ldy) -> stats[blk][2][ld]:
-// the batch-norm partials for convs that ran split-K (their epilogue never sees a full accumulator)
-__global__ __launch_bounds__(256) void partial_stats_kernel(const float* y, int ldy, int M, int K,
-                                                            float* stats, int ld, int rows_per_block) {
-    __shared__ float red[2][8][32];
-    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int r0 = blockIdx.x * rows_per_block;
-    const int r1 = min(M, r0 + rows_per_block);
-    for (int cb = 0; cb < K; cb += 32) {
-        const int c = cb + cl;
-        float s1 = 0.f, s2 = 0.f;
-        if (c < K) {
-            // four rows in flight per thread (one at a time this pass streamed 17 MB in 33 us)
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-            int r = r0 + rg;
-            for (; r + 24 < r1; r += 32) {
-                const float v0 = y[(long)r * ldy + c], v1 = y[(long)(r + 8) * ldy + c];
-                const float v2 = y[(long)(r + 16) * ldy + c], v3 = y[(long)(r + 24) * ldy + c];
-                a0 += v0; b0 += v0 * v0;
-                a1 += v1; b1 += v1 * v1;
-                a2 += v2; b2 += v2 * v2;
-                a3 += v3; b3 += v3 * v3;
-            }
-            for (; r < r1; r += 8) {
-                const float v = y[(long)r * ldy + c];
-                a0 += v;
-                b0 += v * v;
-            }
-            s1 = (a0 + a1) + (a2 + a3);
-            s2 = (b0 + b1) + (b2 + b3);
-        }
-        red[0][rg][cl] = s1;
-        red[1][rg][cl] = s2;
-        __syncthreads();
-        if (rg == 0 && c < K) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                a += red[0][i][cl];
-                b += red[1][i][cl];
-            }
-            stats[((long)blockIdx.x * 2 + 0) * ld + c] = a;
-            stats[((long)blockIdx.x * 2 + 1) * ld + c] = b;
-        }
-        __syncthreads();
-    }
-}
-
-// writes bias to the output positions of a kernel<stride transposed conv that no patch covers
-__global__ __launch_bounds__(256) void deconv_gap_fill_kernel(float* y, int ldy, const float* bias,
-                                                              long pixels, int OH, int OW, int K,
-                                                              int R, int S, int stride) {
-    const int k4 = K / 4;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= pixels * k4) return;
-    const long pix = idx / k4;
-    const int c = (int)(idx - pix * k4) * 4;
-    const int ox = (int)(pix % OW);
-    const int oy = (int)((pix / OW) % OH);
-    if ((oy % stride) < R && (ox % stride) < S) return;
-    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (bias) b = *reinterpret_cast<const float4*>(bias + c);
-    *reinterpret_cast<float4*>(y + pix * ldy + c) = b;
-}
-
-// zero insertion: out[n, h*s, w*s, :] = in[n, h, w, :], zeros elsewhere; out is [N][(H-1)s+1][(W-1)s+1][C].
-// Turns the data gradient of a stride-s conv (and the forward of a transposed conv whose kernel exceeds
-// its stride) into a stride-1 correlation over a 4x larger, mostly-zero tensor: used only for the small
-// stride-2 layers of the RGB / spectrogram U-Nets.
-__global__ __launch_bounds__(256) void dilate2d_kernel(const float* in, int ldin, float* out, long opixels,
-                                                       int H, int W, int OH, int OW, int C, int s) {
-    const int c4 = C / 4;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= opixels * c4) return;
-    const long pix = idx / c4;
-    const int c = (int)(idx - pix * c4) * 4;
-    const int ow = (int)(pix % OW);
-    const int oh = (int)((pix / OW) % OH);
-    const long n = pix / ((long)OW * OH);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (oh % s == 0 && ow % s == 0)
-        v = *reinterpret_cast<const float4*>(in + ((n * H + oh / s) * W + ow / s) * ldin + c);
-    *reinterpret_cast<float4*>(out + pix * C + c) = v;
-}
-
-// ------------------------------------------------------------------------------------------
-// Direct convolution for FEW-CHANNEL layers (C*K <= 512: the 4/8/16-channel full-resolution layers of the RGB /
-// spectrogram U-Nets, models/unet_architecture.py:55-60,78-85).  There the implicit GEMM is a bad fit: a
-// workgroup runs 3 K steps on tiles that are mostly padding and never amortises its prologue.  Here a lane owns
-// one output pixel and 8 output channels, walks the taps with 16-byte loads (neighbouring lanes hit the same
-// lines) and takes the weights as wave-uniform LDS broadcasts: 8 FMAs per input value, the work is VALU- and
-// HBM-shaped.  mode 0: forward, weights HWIO w[tap][c][k]; mode 1: stride-1 data gradient read as a forward
-// conv over gy with flipped taps, weights w[ntaps-1-tap][kout][cin].
-// ------------------------------------------------------------------------------------------
-struct DirectParams {
-    const float* x; int ldx, H, W, C;
-    float* y; int ldy, OH, OW, K;
-    int R, S, stride, pad_t, pad_l;
-    const float* w; int ldw, mode, wrows;   // wrows: rows per tap of the weight tensor (C fwd, Kout dgrad)
-    const float* bias; int act;
-    const float* res; int ldres;
-    float* stats; int stats_ld;   // optional: per-256-pixel-block (sum, sum^2) of conv + bias, [blocks][2][stats_ld]
-    long M;
-};
-
-// weights -> [K/8][ntaps][C][8] (8 consecutive output channels innermost), zero beyond K
-__global__ __launch_bounds__(256) void direct_prepare_kernel(const DirectParams p, float* wprep, int total) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int ntaps = p.R * p.S;
-    const int k = i & 7, c = (i >> 3) % p.C, tap = ((i >> 3) / p.C) % ntaps, kg = ((i >> 3) / p.C) / ntaps;
-    const int ko = kg * 8 + k;
-    float v = 0.f;
-    if (ko < p.K)
-        v = p.mode == 0 ? p.w[((long)tap * p.wrows + c) * p.ldw + ko]
-                        : p.w[((long)(ntaps - 1 - tap) * p.wrows + ko) * p.ldw + c];
-    wprep[i] = v;
-}
-
-// TR, TS, TC > 0: compile-time kernel extent / channel count (the tap and channel loops unroll completely: all the
-// pixel loads of a thread are in flight together and the weights arrive as batched scalar loads); 0: run-time
-template <int TR, int TS, int TC>
-__global__ __launch_bounds__(256) void direct_conv_kernel(const DirectParams p, const float* __restrict__ wprep) {
-    // the weight addresses below are wave-uniform: they become scalar loads (s_load_dwordx8), the FMAs take the
-    // weights from SGPRs, no LDS and no vector-memory traffic for them
-    const int R = TR ? TR : p.R, S = TS ? TS : p.S, C = TC ? TC : p.C;
-    const int ntaps = R * S;
-    // XCD-aware order: the dispatcher deals workgroups to the 8 XCDs round-robin, and a 256-pixel block shares its input
-    // rows with the blocks one image row above and below (and with the other output-channel groups of its own pixels).
-    // Dealt out in launch order those neighbours sit behind three different L2s and every input row is fetched three
-    // times (counters: 243 MB read per launch for a 68 MB input); here XCD j walks the contiguous range
-    // [j * per, (j + 1) * per) of (pixel block, channel group) pairs, channel groups innermost.
-    const int ny = (p.K + 7) >> 3;
-    const long total = ((p.M + 255) >> 8) * ny, per = (total + 7) >> 3;
-    const long unit = (long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (unit >= total) return;
-    const long bx = unit / ny;
-    const int by = (int)(unit - bx * ny);
-    const int kg = by * 8;
-    const float* __restrict__ wl = wprep + (long)by * ntaps * C * 8;
-    const long m_raw = bx * 256 + threadIdx.x;
-    const bool live = m_raw < p.M;
-    const long m = live ? m_raw : p.M - 1;         // dead lanes recompute the last pixel and contribute nothing
-    const int ow = (int)(m % p.OW);
-    const long t = m / p.OW;
-    const int oh = (int)(t % p.OH);
-    const long n = t / p.OH;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc2[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc2[k] = f32x2{0.f, 0.f};
-    const int ih0 = oh * p.stride - p.pad_t, iw0 = ow * p.stride - p.pad_l;
-    const float* const img = p.x + n * p.H * p.W * p.ldx;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int ih = ih0 + r;
-        const int ihc = min(max(ih, 0), p.H - 1);
-#pragma unroll
-        for (int q = 0; q < S; ++q) {
-            const int iw = iw0 + q;
-            const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-            // clamped address: the load is unconditional (and can be hoisted), padding taps are zeroed by select
-            const float* src = img + ((long)ihc * p.W + min(max(iw, 0), p.W - 1)) * p.ldx;
-            const float* __restrict__ wt = wl + (r * S + q) * C * 8;
-#pragma unroll
-            for (int c = 0; c < C; c += 4) {
-                float4 xv = *reinterpret_cast<const float4*>(src + c);
-                const float xs[4] = {ok ? xv.x : 0.f, ok ? xv.y : 0.f, ok ? xv.z : 0.f, ok ? xv.w : 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    // packed fp32 FMAs (v_pk_fma_f32: two accumulators per instruction, same rounding as fmaf)
-                    const f32x2 xx = {xs[i], xs[i]};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const f32x2 ww = *reinterpret_cast<const f32x2*>(wt + (c + i) * 8 + 2 * j);
-                        acc2[j] = __builtin_elementwise_fma(xx, ww, acc2[j]);
-                    }
-                }
-            }
-        }
-    }
-    float acc[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        acc[2 * k] = acc2[k][0];
-        acc[2 * k + 1] = acc2[k][1];
-    }
-    if (p.stats) {
-        // batch-norm partials of this 256-pixel row block (conv + bias, before any activation): lanes -> waves -> LDS
-        __shared__ float sred[4][16];
-        const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float v = live ? acc[k] + (p.bias && kg + k < p.K ? p.bias[kg + k] : 0.f) : 0.f;
-            const float s1 = wave_sum(v), s2 = wave_sum(v * v);
-            if (lane == 0) {
-                sred[wid][k] = s1;
-                sred[wid][8 + k] = s2;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 16 && kg + (threadIdx.x & 7) < p.K) {
-            const int k = threadIdx.x & 7, which = threadIdx.x >> 3;
-            p.stats[(bx * 2 + which) * p.stats_ld + kg + k] =
-                (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
-        }
-    }
-    if (!live) return;
-    float* dst = p.y + m * p.ldy + kg;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (kg + 4 * h >= p.K) break;
-        float4 o = make_float4(acc[4 * h], acc[4 * h + 1], acc[4 * h + 2], acc[4 * h + 3]);
-        if (p.bias) {
-            const float4 b = *reinterpret_cast<const float4*>(p.bias + kg + 4 * h);
-            o.x += b.x; o.y += b.y; o.z += b.z; o.w += b.w;
-        }
-        if (p.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(p.res + m * p.ldres + kg + 4 * h);
-            o.x += rr.x; o.y += rr.y; o.z += rr.z; o.w += rr.w;
-        }
-        o.x = apply_act(o.x, p.act); o.y = apply_act(o.y, p.act);
-        o.z = apply_act(o.z, p.act); o.w = apply_act(o.w, p.act);
-        const int left = p.K - (kg + 4 * h);          // pad columns (K % 4 != 0) are written as zeros
-        if (left < 4) {
-            o.w = 0.f;
-            if (left < 3) o.z = 0.f;
-            if (left < 2) o.y = 0.f;
-        }
-        *reinterpret_cast<float4*>(dst + 4 * h) = o;
     }
 }
 
@@ -743,7 +66,8 @@ static TileCfg pick_cfg(int M, int Ngemm) {
 
 // Tuning record (acimg_configure): plain ints, defaults compiled in, written only by acimg_configure and never by a
 // launch; the launch heuristics below read it instead of the process environment.
-static AcimgConfig g_cfg = {320, 768, 1, 128, 1, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0};
+static constexpr AcimgConfig DEFAULT_CFG = {320, 768, 1, 128, 1, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0};     // acimg_config_default
+static AcimgConfig g_cfg = DEFAULT_CFG;
 
 static int pick_splits(int M, int Ngemm, TileCfg c, int kiters) {
     // measured on the generator's 12x16 layers (192-288 tiles of 64x64, 36+ K steps: tools/splitk_sweep.sh):
@@ -926,7 +250,7 @@ static void wgrad_tile(int Ngemm, int& bmo, int& bn) {
 static int wgrad_split3_bn(int Ngemm) {      // column tile of the split-MFMA weight-gradient kernel
     return Ngemm > 64 ? 128 : (Ngemm > 32 ? 64 : 32);   // (64-column tiles for 144 columns: measured equal / slower)
 }
-// the part of wgrad_halo16_ok (below, with its kernel) that the sizing query knows: 3x3 taps of at most 64 channels into at
+// the part of wgrad_halo16_ok (below) that the sizing query knows: 3x3 taps of at most 64 channels into at
 // most 32 columns, from 65536 pixels on
 static bool wgrad_halo16_shape(long M, int KK, int Ngemm) { return Ngemm <= 32 && KK % 9 == 0 && KK <= 9 * 64 && M >= 65536; }
 // the part of wgrad_tap_ok (below) that depends on the shape alone: 3x3 taps of at least 64 channels into more than 32 columns
@@ -944,431 +268,11 @@ static size_t wgrad_ws_bytes(int M, int KK, int Ngemm, int ldo) {
     return s > 1 ? (size_t)(s + 1) * ((size_t)KK + 1) * ldo * sizeof(float) : 0;
 }
 
-// ------------------------------------------------------------------------------------------
-// few-channel weight gradient (C <= 16 input channels, <= 32 output channels; the full-resolution layers of the
-// RGB / spectrogram U-Nets: 72 x 8 ... 288 x 32 weights, millions of pixels).  As an implicit GEMM the im2col
-// gather re-reads x once per tap through L2 (9x for 3x3); here a workgroup stages an 8 x 32 output-pixel tile of
-// gy and the matching x tile WITH ITS HALO in LDS once and builds every tap from there:
-//   dW[kk][n] += x_patch(pixel, kk) * gy[pixel][n]   on exact-f32 MFMA (16x16x4: 16 kk rows x 16 columns x 4
-//   pixels), operands read from LDS per lane (ds_read_b32), the bias gradient as an all-ones row kk = KK.
-// Workgroups walk tiles grid-stride and keep their sums in registers; one partial slab per workgroup, then the
-// ordinary deterministic slab reduce.
-// ------------------------------------------------------------------------------------------
-struct WgradHaloParams {
-    const float* X; int H, W, C, ldx;
-    const float* G; int OH, OW, Kp, ldg;
-    int R, S, stride, pad_t, pad_l;
-    int XH, XW;                 // x tile extent incl. halo
-    int tiles_x, tiles_y; long tiles;
-    int KK;                     // R*S*C
-    float* out; float* db_out; int ldo;   // slabs [gridDim.x][KK][ldo], [gridDim.x][ldo]
-};
-constexpr int WH_TH = 8, WH_TW = 32, WH_MAXT = 10;
-
-// NT: 16-column tiles (1 or 2); NKT: 16-row tiles of (R*S*C + 1) the instance has accumulators for
-template <int NT, int NKT>
-__global__ __launch_bounds__(256, 3) void wgrad_halo_kernel(const WgradHaloParams p) {
-    extern __shared__ __attribute__((aligned(16))) float wh_smem[];
-    const int xsz = p.XH * p.XW * p.C;
-    float* xs = wh_smem;                       // [XH][XW][C], then {1.0f, 0.0f, 0, 0}
-    float* gs = wh_smem + xsz + 4;             // [8][32][Kp]
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int row16 = lane & 15, quad = lane >> 4;
-    // LDS offset of this lane's x element for row tile t, relative to the pixel's window origin; the bias row reads
-    // the constant 1, rows past it the constant 0 (absolute addresses: their pixel offset is masked away)
-    int xoff[NKT], xmask[NKT];
-#pragma unroll
-    for (int t = 0; t < NKT; ++t) {
-        const int kk = 16 * t + row16;
-        if (kk < p.KK) {
-            const int tap = kk / p.C, c = kk - tap * p.C;
-            const int r = tap / p.S, q = tap - r * p.S;
-            xoff[t] = (r * p.XW + q) * p.C + c;
-            xmask[t] = -1;
-        } else {
-            xoff[t] = xsz + (kk == p.KK ? 0 : 1);      // the constants 1 (bias row) and 0
-            xmask[t] = 0;
-        }
-    }
-    int bcol[NT];
-    float bscale[NT];               // columns past Kp multiply a valid (finite) element by 0
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        bscale[j] = row16 + 16 * j < p.Kp ? 1.f : 0.f;
-        bcol[j] = min(row16 + 16 * j, p.Kp - 1);
-    }
-    f32x4 acc[NKT][NT];
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (tid == 0) {
-        xs[xsz] = 1.f;
-        xs[xsz + 1] = 0.f;
-    }
-    const int c4n = p.C >> 2, k4n = p.Kp >> 2;
-    const int c4sh = c4n == 1 ? 0 : (c4n == 2 ? 1 : 2);
-    // Software pipeline: the global loads of tile i+1 are issued (into registers) before tile i is multiplied, so
-    // every workgroup keeps a tile's worth of HBM requests in flight all the time.
-    // Staging is division-free and branch-free (stride 1, R, S <= 3: at most 10 x 34 x pixels): wave w takes x rows
-    // w, w+4, w+8, its lanes the row's float4s lane, lane+64, lane+128; every load goes to a clamped (valid) address
-    // and is zeroed by select, so all 9 + 4 loads of a thread are in flight together.
-    float4 xv[3][3], gv[2][2];
-    const int rowlen = p.XW << c4sh;
-    auto issue = [&](long tile) {
-        const int tx = (int)(tile % p.tiles_x);
-        const long t2 = tile / p.tiles_x;
-        const int ty = (int)(t2 % p.tiles_y);
-        const long img = t2 / p.tiles_y;
-        const int oh0 = ty * WH_TH, ow0 = tx * WH_TW;
-        const int ih0 = oh0 * p.stride - p.pad_t, iw0 = ow0 * p.stride - p.pad_l;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int iy = wid + 4 * a;
-            const int ih = ih0 + iy;
-            const int ihc = min(max(ih, 0), p.H - 1);
-            const float* grow = p.X + ((img * p.H + ihc) * p.W) * p.ldx;
-#pragma unroll
-            for (int bq = 0; bq < 3; ++bq) {
-                const int e = lane + 64 * bq;
-                const int ix = e >> c4sh, c4 = e & (c4n - 1);
-                const int iw = iw0 + ix;
-                const bool ok = iy < p.XH && e < rowlen && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-                const float4 v = *reinterpret_cast<const float4*>(grow + (long)min(max(iw, 0), p.W - 1) * p.ldx + 4 * c4);
-                xv[a][bq] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int py = 2 * wid + half, px = lane & 31;
-            const int oh = oh0 + py, ow = ow0 + px;
-            const bool ok = oh < p.OH && ow < p.OW;
-            const float* gsrc = p.G + ((img * p.OH + min(oh, p.OH - 1)) * p.OW + min(ow, p.OW - 1)) * p.ldg;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k4 = (lane >> 5) + 2 * j;
-                const float4 v = *reinterpret_cast<const float4*>(gsrc + 4 * min(k4, k4n - 1));
-                gv[half][j] = ok && k4 < k4n ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int iy = wid + 4 * a;
-#pragma unroll
-            for (int bq = 0; bq < 3; ++bq) {
-                const int e = lane + 64 * bq;
-                if (iy < p.XH && e < rowlen)
-                    *reinterpret_cast<float4*>(xs + iy * p.XW * p.C + (e >> c4sh) * p.C + 4 * (e & (c4n - 1))) = xv[a][bq];
-            }
-        }
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k4 = (lane >> 5) + 2 * j;
-                if (k4 < k4n)
-                    *reinterpret_cast<float4*>(gs + ((2 * wid + half) * WH_TW + (lane & 31)) * p.Kp + 4 * k4) = gv[half][j];
-            }
-    };
-    issue(blockIdx.x);
-    for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-        __syncthreads();                                   // the previous tile has been consumed
-        commit();
-        __syncthreads();
-        if (tile + gridDim.x < p.tiles) issue(tile + gridDim.x);
-        // this wave: tile rows 2*wid, 2*wid+1 = 64 pixels, 4 at a time (quad = which of the 4); all addresses
-        // advance incrementally (4 pixels per step, one row jump half way)
-        {
-            // register double buffer: the LDS reads of step g+1 are issued before the MFMAs of step g (all NKT row
-            // tiles unconditionally - rows past KK + 1 read the constant 0 - so the loop has no branch)
-            int xb = ((2 * wid) * p.XW + quad) * p.C;
-            const float* gp = gs + ((2 * wid) * WH_TW + quad) * p.Kp;
-            float a[2][NKT], b[2][NT];
-#pragma unroll
-            for (int t = 0; t < NKT; ++t) a[0][t] = xs[xoff[t] + (xb & xmask[t])];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) b[0][j] = gp[bcol[j]] * bscale[j];
-#pragma unroll 1
-            for (int g2 = 0; g2 < 8; ++g2) {            // two steps per trip: buffers 0 -> 1 -> 0
-#pragma unroll
-                for (int cur = 0; cur < 2; ++cur) {
-                    const int nxt = cur ^ 1;
-                    const int gq = 2 * g2 + cur;
-                    if (gq < 15) {
-                        gp += 4 * p.Kp;
-                        xb += 4 * p.C + (gq == 7 ? (p.XW - WH_TW) * p.C : 0);
-#pragma unroll
-                        for (int t = 0; t < NKT; ++t) a[nxt][t] = xs[xoff[t] + (xb & xmask[t])];
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) b[nxt][j] = gp[bcol[j]] * bscale[j];
-                    }
-#pragma unroll
-                    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-                        for (int j = 0; j < NT; ++j)
-                            acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][t], b[cur][j], acc[t][j], 0, 0, 0);
-                }
-            }
-        }
-    }
-    // the 4 waves add their sums in wave order (deterministic) in LDS: red[kk][NT*16]
-    __syncthreads();
-    float* red = wh_smem;
-    const int rw = NT * 16;
-    for (int w = 0; w < 4; ++w) {
-        if (wid == w) {
-#pragma unroll
-            for (int t = 0; t < NKT; ++t) {
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float* dst = red + (16 * t + 4 * quad + i) * rw + 16 * j + row16;
-                        *dst = (w == 0 ? 0.f : *dst) + acc[t][j][i];
-                    }
-            }
-        }
-        __syncthreads();
-    }
-    float* out = p.out + (long)blockIdx.x * p.KK * p.ldo;
-    for (int e = tid; e < (p.KK + 1) * p.Kp; e += 256) {
-        const int kk = e / p.Kp, n = e - kk * p.Kp;
-        const float v = red[kk * rw + n];
-        if (kk < p.KK) out[(long)kk * p.ldo + n] = v;
-        else if (p.db_out) p.db_out[(long)blockIdx.x * p.ldo + n] = v;
-    }
-}
-
-static size_t wgrad_halo_lds(int R, int S, int C, int Kp, int stride) {
-    const int XH = (WH_TH - 1) * stride + R, XW = (WH_TW - 1) * stride + S;
-    const size_t stage = ((size_t)XH * XW * C + 4 + (size_t)WH_TH * WH_TW * Kp) * sizeof(float);
-    const size_t red = (size_t)WH_MAXT * 16 * (Kp > 16 ? 32 : 16) * sizeof(float);   // any instance's [16*NKT][16*NT]
-    return stage > red ? stage : red;
-}
+// the exact-f32 halo form (wgrad_halo_kernel): 4 / 8 / 16 input channels into at most 16 columns, from 65536 pixels on
 static bool wgrad_halo_ok(const WgradParams& p) {
     return (p.C == 4 || p.C == 8 || p.C == 16) && p.Nld <= 16 && p.Ngemm == p.Nld && p.stride == 1 && p.R <= 3 && p.S <= 3 && (long)p.M >= 65536 && (p.ldx & 3) == 0 && (p.ldg & 3) == 0 &&
            (p.KK + 1 + 15) / 16 <= WH_MAXT && wgrad_halo_lds(p.R, p.S, p.C, p.Nld, p.stride) <= 65536 &&
            g_cfg.wgrad_halo;
-}
-
-// db (optional): fused bias gradient, db[n] = sum_m G[m][n] for n < Ngemm
-// ------------------------------------------------------------------------------------------
-// HALO form of the bf16 / bf16x3 weight gradient of the 3x3 / stride-1 layers with 32 or 64 input channels and 32 output
-// channels (round 4; the 112x149 and 56x74 stages of the RGB / spectrogram U-Nets, models/unet_architecture.py:161-166,
-// configs[1]).  As an implicit GEMM (wgrad_split3_kernel) these layers re-gather x once per tap through L2 - nine times the
-// tensor for 2 x 576 x 32 MACs per pixel: 112x149 64->32 took 225 us against 41 us of HBM time for x and gy.  Here a
-// workgroup stages a TH x 32 output-pixel tile of gy and the x tile WITH ITS HALO once, as bf16 (hi [, lo]) planes in LDS
-// ([pixel][channel], 16-byte chunks swizzled by the pixel's COLUMN so that the transposing fragment reads - 4 pixels x 16
-// channels per 16-lane group - are conflict free at every tap shift, and row offsets stay compile-time immediates), and
-// forms all nine taps from there: K = the tile's pixels, one 32-pixel row per step, no barrier inside a tile.  gy^T sits in
-// the A slot (a lane's 4 accumulators are 4 consecutive output channels of one dW row: 16-byte slab stores); the bias
-// gradient rides as an MFMA against a constant ones fragment.  One workgroup per CU with the NEXT tile's global loads held in
-// registers while the current one is multiplied (2 waves per SIMD: the 256-register budget pays for that); workgroups walk
-// tiles grid-stride and keep their sums in registers: one partial slab each, then the deterministic slab reduce.
-// Waves: C = 64: 4 channel tiles x 2 column tiles; C = 32: 2 x 2 x the tile's even / odd rows (summed through LDS at the end).
-// ------------------------------------------------------------------------------------------
-// the producer's batch norm + ReLU on a staged item (after ALL of a tile's loads were issued: applied inside the load loop it
-// made every load wait for the one before it - 224x298 8->8 weight gradient 68 -> 132 us)
-__device__ __forceinline__ float4 affine_relu4(float4 v, const float4 sc, const float4 sh, const bool relu) {
-    v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
-    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    return v;
-}
-
-struct WgradHalo16Params {
-    const float* X; int H, W, ldx;
-    const float* G; int ldg;
-    int tiles_x, tiles_y; long tiles;
-    float* out; float* db_out; int ldo;      // slabs [gridDim.x][9 creal][ldo], [gridDim.x][ldo]
-    int creal, nreal;                        // channels really there (multiples of 4; the rest of the C x 32 tile is zeros)
-    // the producer's deferred batch norm on load: x' = relu(x * a_scale[c] + a_shift[c]) for pixels INSIDE the image (the
-    // conv's zero padding applies after the affine); null = x as stored
-    const float* a_scale; const float* a_shift; int a_relu;
-};
-
-// C: channel width of the x image (64, 32, or 16 for the few-channel layers: fewer real channels are zero padded);
-// NNT: 16-column tiles of gy (2, or 1 for <= 16 output channels: the waves that would multiply padding take tile rows instead)
-template <int C, int TERMS, int NNT = 2>
-__global__ __launch_bounds__(512, C == 16 ? 4 : 1) void wgrad_halo16_kernel(const WgradHalo16Params p) {
-    constexpr int TH = (TERMS == 1 || C == 16) ? 8 : 4, TW = 32, XH = TH + 2, XWV = TW + 2, XW = 36;
-    constexpr int PITCH = C * 2;                      // bytes per pixel and plane
-    constexpr int XPL = XH * XW * PITCH;              // one x plane
-    constexpr int GPL = TH * TW * 64;                 // one gy plane (32 columns of bf16)
-    constexpr int NCT = C / 16;                       // 16-channel tiles
-    constexpr int NJ = 8 / (NCT * NNT);               // row groups: waves with the same (channel tile, column tile)
-    constexpr int NXL = (XH * XWV * (C / 4) + 511) / 512, NGL = TH * TW * 8 / 512;     // float4 loads per thread and tile
-    static_assert((C == 64 || C == 32 || C == 16) && TH % NJ == 0 && TH * TW * 8 % 512 == 0, "shape");
-    extern __shared__ __attribute__((aligned(16))) float wh16_smem[];
-    char* const lds = reinterpret_cast<char*>(wh16_smem);
-    char* const gl = lds + (TERMS == 3 ? 2 : 1) * XPL;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int li = lane & 15, g = lane >> 4, q = li >> 2, pp = li & 3;
-    const int ct = wid % NCT, nt = (wid / NCT) % NNT, jh = wid / (NCT * NNT);
-    // (C = 16: 32-byte pixels, no room to swizzle: pixels 8 apart share banks, a 2-way conflict the HBM-bound kernel absorbs)
-    auto swx = [](int col) {
-        return C == 64 ? 2 * (((col >> 1) & 1) | (((col >> 3) & 1) << 1)) : (C == 32 ? 2 * ((col >> 3) & 1) : 0);
-    };
-    auto swg = [](int col) { return 2 * ((col >> 3) & 1); };
-
-    // fragment read addresses: lane (q, pp) of group g supplies pixel column s + 8 g + 4 h + q, channels 4 pp .. + 3 of its
-    // 16-channel tile; the tile row is a compile-time distance
-    int xb[3][2], gb[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int col = 8 * g + 4 * h + q;
-        gb[h] = (jh * TW + col) * 64 + (((2 * nt + (pp >> 1)) ^ swg(col)) << 4) + 8 * (pp & 1);
-#pragma unroll
-        for (int s_ = 0; s_ < 3; ++s_) {
-            const int cx = col + s_;
-            xb[s_][h] = (jh * XW + cx) * PITCH + (((2 * ct + (pp >> 1)) ^ swx(cx)) << 4) + 8 * (pp & 1);
-        }
-    }
-
-    // this thread's items of a tile: x float4 (pixel of the XH x 34 window, 4 channels), gy float4 (pixel, 4 columns)
-    float4 rx[NXL], rg[NGL];
-    unsigned okm = 0;                          // which of rx[] came from inside the image (the affine applies to those only)
-    // (a thread's x items are always the same four channels: 512 is a multiple of C / 4)
-    const bool aff_ch = p.a_scale != nullptr && (tid % (C / 4)) * 4 < p.creal;
-    const float4 asc = aff_ch ? *reinterpret_cast<const float4*>(p.a_scale + (tid % (C / 4)) * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const float4 ash = aff_ch ? *reinterpret_cast<const float4*>(p.a_shift + (tid % (C / 4)) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    auto load_tile = [&](long tile) {
-        okm = 0;
-        const int tx = (int)(tile % p.tiles_x);
-        const long t2 = tile / p.tiles_x;
-        const int ty = (int)(t2 % p.tiles_y);
-        const long img = t2 / p.tiles_y;
-        const float* xi = p.X + img * p.H * p.W * p.ldx;
-        const float* gi = p.G + img * p.H * p.W * p.ldg;
-#pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i % (C / 4), pix = i / (C / 4);
-            const int row = pix / XWV, col = pix - row * XWV;
-            const int iy = ty * TH + row - 1, ix = tx * TW + col - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < XH && c4 * 4 < p.creal && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) {
-                v = *reinterpret_cast<const float4*>(xi + ((long)iy * p.W + ix) * p.ldx + c4 * 4);
-                okm |= 1u << k;
-            }
-            rx[k] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < NGL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i & 7, pix = i >> 3;
-            const int row = pix / TW, col = pix - row * TW;
-            const int oy = ty * TH + row, ox = tx * TW + col;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (oy < p.H && ox < p.W && c4 * 4 < p.nreal) v = *reinterpret_cast<const float4*>(gi + ((long)oy * p.W + ox) * p.ldg + c4 * 4);
-            rg[k] = v;
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i % (C / 4), pix = i / (C / 4);
-            const int row = pix / XWV, col = pix - row * XWV;
-            if (row < XH) {
-                const int off = (row * XW + col) * PITCH + (((c4 >> 1) ^ swx(col)) << 4) + 8 * (c4 & 1);
-                uint2 hi, lo;
-                split4<SplitBF16>(p.a_scale && ((okm >> k) & 1u) ? affine_relu4(rx[k], asc, ash, p.a_relu != 0) : rx[k], hi, lo);
-                *reinterpret_cast<uint2*>(lds + off) = hi;
-                if (TERMS == 3) *reinterpret_cast<uint2*>(lds + XPL + off) = lo;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NGL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i & 7, pix = i >> 3;
-            const int col = pix & (TW - 1);
-            const int off = pix * 64 + (((c4 >> 1) ^ swg(col)) << 4) + 8 * (c4 & 1);
-            uint2 hi, lo;
-            split4<SplitBF16>(rg[k], hi, lo);
-            *reinterpret_cast<uint2*>(gl + off) = hi;
-            if (TERMS == 3) *reinterpret_cast<uint2*>(gl + GPL + off) = lo;
-        }
-    };
-    typedef short s16x4_ __attribute__((ext_vector_type(4)));
-    typedef short s16x8_ __attribute__((ext_vector_type(8)));
-    auto frag = [&](const char* base, int a0, int a1) -> b16x8 {
-        const s16x4_ v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(base + a0));
-        const s16x4_ v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(base + a1));
-        const s16x8_ v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        return __builtin_bit_cast(b16x8, v);
-    };
-
-    f32x4 acc[9], accb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const __bf16 one = (__bf16)1.f;
-    const b16x8 ones = {one, one, one, one, one, one, one, one};
-
-    long tile = blockIdx.x;
-    if (tile < p.tiles) load_tile(tile);
-    for (; tile < p.tiles; tile += gridDim.x) {
-        __syncthreads();                               // everyone has finished reading the previous tile
-        store_tile();
-        __syncthreads();
-        if (tile + gridDim.x < p.tiles) load_tile(tile + gridDim.x);     // in flight while this tile is multiplied
-#pragma unroll
-        for (int jj = 0; jj < TH / NJ; ++jj) {
-            const int j = jj * NJ;                     // (+ jh: in the lane bases)
-            const b16x8 gh = frag(gl + j * TW * 64, gb[0], gb[1]);
-            b16x8 glo;
-            if (TERMS == 3) glo = frag(gl + GPL + j * TW * 64, gb[0], gb[1]);
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int s_ = 0; s_ < 3; ++s_) {
-                    const char* xrow = lds + (j + r) * XW * PITCH;
-                    const b16x8 xh = frag(xrow, xb[s_][0], xb[s_][1]);
-                    if (TERMS == 3) {
-                        const b16x8 xl = frag(xrow + XPL, xb[s_][0], xb[s_][1]);
-                        acc[r * 3 + s_] = SplitBF16::mfma(glo, xh, acc[r * 3 + s_]);
-                        acc[r * 3 + s_] = SplitBF16::mfma(gh, xl, acc[r * 3 + s_]);
-                    }
-                    acc[r * 3 + s_] = SplitBF16::mfma(gh, xh, acc[r * 3 + s_]);
-                }
-            if (ct == 0) {
-                if (TERMS == 3) accb = SplitBF16::mfma(glo, ones, accb);
-                accb = SplitBF16::mfma(gh, ones, accb);
-            }
-        }
-    }
-    // the row groups of one (channel tile, column tile) meet through LDS (C = 32), then lane (li, g) of acc[tap] holds
-    // dW[tap * C + 16 ct + li][16 nt + 4 g .. + 3]
-    if (NJ > 1) {
-        // one round per row group (in group order: deterministic): its waves park their sums, group 0 adds them
-        f32x4* red = reinterpret_cast<f32x4*>(lds);
-        const int w0 = wid % (NCT * NNT);            // this wave's (channel tile, column tile) slot
-        for (int r = 1; r < NJ; ++r) {
-            __syncthreads();
-            if (jh == r) {
-#pragma unroll
-                for (int t = 0; t < 9; ++t) red[(w0 * 10 + t) * 64 + lane] = acc[t];
-                red[(w0 * 10 + 9) * 64 + lane] = accb;
-            }
-            __syncthreads();
-            if (jh == 0) {
-#pragma unroll
-                for (int t = 0; t < 9; ++t) acc[t] += red[(w0 * 10 + t) * 64 + lane];
-                accb += red[(w0 * 10 + 9) * 64 + lane];
-            }
-        }
-        if (jh != 0) return;
-    }
-    float* out = p.out + (long)blockIdx.x * (9 * p.creal) * p.ldo;
-    const bool nok = nt * 16 + 4 * g < p.nreal;
-    if (nok && ct * 16 + li < p.creal) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-            *reinterpret_cast<f32x4*>(out + (long)(t * p.creal + ct * 16 + li) * p.ldo + nt * 16 + 4 * g) = acc[t];
-    }
-    if (p.db_out && ct == 0 && li == 0 && nok)
-        *reinterpret_cast<f32x4*>(p.db_out + (long)blockIdx.x * p.ldo + nt * 16 + 4 * g) = accb;
 }
 
 // split3: the caller asked for 16-bit matrix-core arithmetic (acimg_conv2d_wgrad_split3 / _bf16).  The FEW-CHANNEL layers
@@ -1393,6 +297,42 @@ static bool wgrad_tap_ok(const WgradParams& p) {
            p.Ngemm % 4 == 0 && p.ldo >= p.Ngemm && p.M % (p.H * p.W) == 0 && !p.a_scale && g_cfg.wgrad_halo;
 }
 
+// The partial slabs of a split weight gradient in the caller's workspace: n slabs [KK][ldo], then the n bias rows [ldo].  The
+// kernel is handed the bias rows (db_out) only when a bias gradient was asked for; fits: the workspace holds all of it.
+struct WgradSlabs {
+    size_t need;
+    bool fits;
+    float *out, *db_rows, *db_out;
+};
+static WgradSlabs wgrad_slabs(const WgradParams& p, int n, const float* db, void* ws, size_t ws_bytes) {
+    WgradSlabs s{};
+    s.need = (size_t)n * ((size_t)p.KK + 1) * p.ldo * sizeof(float);
+    s.fits = ws != nullptr && ws_bytes >= s.need;
+    if (s.fits) {
+        s.out = static_cast<float*>(ws);
+        s.db_rows = s.out + (size_t)n * p.KK * p.ldo;
+        s.db_out = db ? s.db_rows : nullptr;
+    }
+    return s;
+}
+static int wgrad_ws_short(const WgradSlabs& s, size_t ws_bytes) {
+    return fail(ACIMG_EWORKSPACE, "wgrad: workspace %zu < %zu", ws_bytes, s.need);
+}
+// sums the n slabs into dw and the bias rows into db, in slab order: the wide kernel above 32 slabs, and always for the
+// halo forms (wide: one slab per workgroup, hundreds of them)
+static int wgrad_reduce(const WgradSlabs& s, int n, const WgradParams& p, float* dw, float* db, bool wide, hipStream_t st) {
+    if (wide || n > 32) {
+        launch_slab_reduce_wide(s.out, n, (long)p.KK, p.Ngemm, p.ldo, dw, s.db_out, db, st);
+    } else {
+        const long total = (long)p.KK * p.Ngemm;
+        const int nb1 = (int)cdiv(total, 256), nb2 = db ? cdiv(p.Ngemm, 256) : 0;
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(nb1 + nb2), dim3(256), 0, st, s.out, n, (long)p.KK, p.Ngemm, p.ldo, dw, nb1,
+                           s.db_rows, db);
+    }
+    return check_launch("wgrad_reduce");
+}
+
+// db (optional): fused bias gradient, db[n] = sum_m G[m][n] for n < Ngemm
 static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t st,
                         bool split3 = false, int terms = 3) {
     if ((p.C & 3) || (p.ldx & 3) || (p.ldg & 3) || (p.ldo & 3))
@@ -1418,11 +358,10 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         q.tiles = (long)(p.M / (p.H * p.W)) * q.tiles_x * q.tiles_y;
         int nb = p.C <= 16 ? 512 : 256;     // one workgroup per CU; two for the few-channel instances (56 KiB of LDS, tiny slabs:
         if (nb > q.tiles) nb = (int)q.tiles;       // their load / store / multiply phases overlap across workgroups)
-        const size_t need = (size_t)nb * ((size_t)p.KK + 1) * p.ldo * sizeof(float);
-        if (ws != nullptr && ws_bytes >= need) {      // (the sizing query covers it: pick_wgrad_splits gives these shapes >= 256 slabs)
-            q.out = static_cast<float*>(ws);
-            float* db_slab = q.out + (size_t)nb * p.KK * p.ldo;
-            q.db_out = db ? db_slab : nullptr;
+        const WgradSlabs sl = wgrad_slabs(p, nb, db, ws, ws_bytes);
+        if (sl.fits) {      // (the sizing query covers it: pick_wgrad_splits gives these shapes >= 256 slabs)
+            q.out = sl.out;
+            q.db_out = sl.db_out;
             const int xh = th + 2, planes = terms == 3 ? 2 : 1;
             int lds = planes * (xh * 36 * cpad * 2 + th * 32 * 64);
             if (lds < 4 * 10 * 64 * 16) lds = 4 * 10 * 64 * 16;                   // the row groups' final sums through LDS
@@ -1452,9 +391,7 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
             }
 #undef ACIMG_WH16
             int rc = check_launch("wgrad_halo16");
-            if (rc) return rc;
-            launch_slab_reduce_wide(q.out, nb, (long)p.KK, p.Ngemm, p.ldo, dw, db ? db_slab : nullptr, db, st);
-            return check_launch("wgrad_reduce");
+            return rc ? rc : wgrad_reduce(sl, nb, p, dw, db, true, st);
         }
     }
     if (p.a_scale) return fail(ACIMG_EWORKSPACE, "wgrad: workspace too small for the halo form, which the input affine needs");
@@ -1471,11 +408,10 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         if (nb > 768) nb = 768;                                      // 3 resident workgroups per CU, each pipelined
         if (nb > q.tiles) nb = (int)q.tiles;
         if (nb < 2) nb = 2;
-        const size_t need = (size_t)nb * ((size_t)p.KK + 1) * p.ldo * sizeof(float);
-        if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "wgrad: workspace %zu < %zu", ws_bytes, need);
-        q.out = static_cast<float*>(ws);
-        float* db_slab = q.out + (size_t)nb * p.KK * p.ldo;
-        q.db_out = db ? db_slab : nullptr;
+        const WgradSlabs sl = wgrad_slabs(p, nb, db, ws, ws_bytes);
+        if (!sl.fits) return wgrad_ws_short(sl, ws_bytes);
+        q.out = sl.out;
+        q.db_out = sl.db_out;
         const size_t lds = wgrad_halo_lds(p.R, p.S, p.C, p.Nld, p.stride);
         const int nkt = (p.KK + 1 + 15) / 16;
 #define ACIMG_WH(NTv, NKTv) hipLaunchKernelGGL((wgrad_halo_kernel<NTv, NKTv>), dim3(nb), dim3(256), lds, st, q)
@@ -1486,9 +422,7 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         else ACIMG_WH(1, 10);
 #undef ACIMG_WH
         int rc = check_launch("wgrad_halo");
-        if (rc) return rc;
-        launch_slab_reduce_wide(q.out, nb, (long)p.KK, p.Ngemm, p.ldo, dw, db ? db_slab : nullptr, db, st);
-        return check_launch("wgrad_reduce");
+        return rc ? rc : wgrad_reduce(sl, nb, p, dw, db, true, st);
     }
     if (split3) bn = wgrad_split3_bn(p.Ngemm);
     if (split3 && terms == 3 && wgrad_tap_ok(p)) {
@@ -1500,14 +434,12 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         // pixel splits: what the generic path is granted for this shape (the workspace is sized for it), one tile each at least
         int ns = pick_wgrad_splits(p.M, p.KK, p.Ngemm, bmo, bn);
         if (ns > q.tiles) ns = (int)q.tiles;
-        float* db_slab = nullptr;
+        const WgradSlabs sl = wgrad_slabs(p, ns, db, ws, ws_bytes);
         if (ns > 1) {
-            const size_t need = (size_t)ns * ((size_t)p.KK + 1) * p.ldo * sizeof(float);
-            if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "wgrad: workspace %zu < %zu", ws_bytes, need);
-            q.out = static_cast<float*>(ws);
-            db_slab = q.out + (size_t)ns * p.KK * p.ldo;
-            q.db_out = db ? db_slab : nullptr;
-        } else {
+            if (!sl.fits) return wgrad_ws_short(sl, ws_bytes);
+            q.out = sl.out;
+            q.db_out = sl.db_out;
+        } else {                // one slab: the kernel writes dW / db themselves, no reduce
             q.out = dw;
             q.db_out = db;
         }
@@ -1524,30 +456,18 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         if (bn == 128) hipLaunchKernelGGL((wgrad_tap_kernel<128>), grid, dim3(512), lds, st, q);
         else hipLaunchKernelGGL((wgrad_tap_kernel<64>), grid, dim3(512), lds, st, q);
         int rc = check_launch("wgrad_tap");
-        if (rc || ns == 1) return rc;
-        if (ns > 32) {
-            launch_slab_reduce_wide(q.out, ns, (long)p.KK, p.Ngemm, p.ldo, dw, db ? db_slab : nullptr, db, st);
-        } else {
-            const long total = (long)p.KK * p.Ngemm;
-            const int nb1 = (int)cdiv(total, 256), nb2 = db ? cdiv(p.Ngemm, 256) : 0;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(nb1 + nb2), dim3(256), 0, st, q.out, ns, (long)p.KK, p.Ngemm, p.ldo, dw, nb1,
-                               db_slab, db);
-        }
-        return check_launch("wgrad_reduce");
+        return (rc || ns == 1) ? rc : wgrad_reduce(sl, ns, p, dw, db, false, st);
     }
     p.splits = pick_wgrad_splits(p.M, p.KK, p.Ngemm, bmo, bn);
     int rps = cdiv(p.M, p.splits);
     rps = ((rps + 31) / 32) * 32;
     p.rows_per_split = rps;
     p.splits = cdiv(p.M, rps);
-    float* db_slab = nullptr;
+    const WgradSlabs sl = wgrad_slabs(p, p.splits, db, ws, ws_bytes);
     if (p.splits > 1) {
-        const size_t need = (size_t)p.splits * ((size_t)p.KK + 1) * p.ldo * sizeof(float);
-        if (ws == nullptr || ws_bytes < need)
-            return fail(ACIMG_EWORKSPACE, "wgrad: workspace %zu < %zu", ws_bytes, need);
-        p.out = static_cast<float*>(ws);
-        db_slab = p.out + (size_t)p.splits * p.KK * p.ldo;
-        p.db_out = db ? db_slab : nullptr;
+        if (!sl.fits) return wgrad_ws_short(sl, ws_bytes);
+        p.out = sl.out;
+        p.db_out = sl.db_out;
     } else {
         p.out = dw;
         p.db_out = db;
@@ -1565,19 +485,7 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
     else if (bn == 32) hipLaunchKernelGGL((wgrad_f32_kernel<128, 32>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((wgrad_f32_kernel<128, 16, 4>), grid, dim3(256), 0, st, p);
     int rc = check_launch("wgrad");
-    if (rc) return rc;
-    if (p.splits > 1) {
-        const long total = (long)p.KK * p.Ngemm;
-        if (p.splits > 32) {
-            launch_slab_reduce_wide(p.out, p.splits, (long)p.KK, p.Ngemm, p.ldo, dw, db ? db_slab : nullptr, db, st);
-        } else {
-            const int nb1 = (int)cdiv(total, 256), nb2 = db ? cdiv(p.Ngemm, 256) : 0;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(nb1 + nb2), dim3(256), 0, st, p.out, p.splits,
-                               (long)p.KK, p.Ngemm, p.ldo, dw, nb1, db_slab, db);
-        }
-        rc = check_launch("wgrad_reduce");
-    }
-    return rc;
+    return (rc || p.splits <= 1) ? rc : wgrad_reduce(sl, p.splits, p, dw, db, false, st);
 }
 
 // column sums; workspace: parts*ncols floats
@@ -1650,231 +558,6 @@ static int launch_direct(const DirectParams& q, void* ws, size_t ws_bytes, hipSt
     return check_launch("direct_conv");
 }
 
-// ------------------------------------------------------------------------------------------
-// MFMA form of the FEW-CHANNEL 3x3 / stride-1 / SAME layers (8 or 16 channels in, up to 32 out: the full-resolution
-// layers of the RGB / spectrogram U-Nets; round 4).  The direct kernel above does these with packed fp32 FMAs at ~2x its
-// VALU bound (224x298 8->8: 61 us for 27 us of bytes), every input value fetched nine times through the L1.  Here the taps
-// are the GEMM's K axis: a pixel's CIN channels are one 16- or 32-byte run of a 16-bit plane, so the 8 k-values a lane
-// holds of a 16x16x32 MFMA operand are ONE tap's channels of ONE pixel - a single ds_read_b128 at the tap's shift, four
-// (two) taps per MFMA, 9 taps in 3 (5) MFMAs per term with the spare tap slots multiplied by zero weights.  A workgroup
-// stages a 16 x 32 pixel tile WITH ITS HALO once (fp32 -> hi / lo planes on the way), keeps the whole weight image in
-// registers (weights in the A slot: a lane's 4 accumulators are 4 consecutive output channels of one pixel, 16-byte
-// stores), 3-term split product (fp32-class: f16 hi/lo forward, bf16 hi/lo for gradients).  MODE 0: forward - bias, raw
-// output, batch-norm partials of conv + bias: one statistics row per workgroup; MODE 1: data gradient as a forward conv of
-// gy with the flipped / transposed image, residual added.  Persistent workgroups, two per CU; XCD j walks the contiguous
-// tile range [j * per, (j + 1) * per) so that neighbouring tiles share an L2; the next tile's loads are held in registers
-// while the current one is multiplied.
-// ------------------------------------------------------------------------------------------
-struct FewParams {
-    const float* X; int H, W, ldx;               // H, W: the OUTPUT grid (tiles); the tensor that is convolved:
-    int Hin, Win, SH, SW, dil, pad_t, pad_l;     //   Hin x Win pixels, stored SH x SW (dil 2: zero-inserted view of a stride-2 gy)
-    const char* Wimg; unsigned w_lo_off;         // 16-bit image [NOUTP][KTOT] (k = tap slot * CIN + c), hi plane; lo plane w_lo_off bytes on
-    float* Y; int ldy, nout;                     // nout: real output channels (multiple of 4)
-    const float* bias; const float* res; int ldres;
-    float* stats; int stats_ld;                  // [gridDim.x][2][stats_ld] or null
-    int tiles_x, tiles_y; long tiles, per;
-    // the producer's deferred batch norm on load: x' = relu(x * a_scale[c] + a_shift[c]) for pixels INSIDE the image (the
-    // conv's zero padding applies after the affine); null = x as stored
-    const float* a_scale; const float* a_shift; int a_relu;
-    // weight preparation
-    const float* w; int ldw, wrows, cin, mode;
-};
-constexpr int FEW16_WGS = 512;
-constexpr int few16_ktot(int cin) { return ((9 + 32 / cin - 1) / (32 / cin)) * 32; }
-
-// w (fp32 HWIO, possibly the flipped / transposed view of a data gradient) -> the [NOUTP][KTOT] hi / lo image
-template <typename TR>
-__global__ __launch_bounds__(256) void few16_prepare_kernel(const FewParams p, int CIN, int NOUTP, typename TR::T* img) {
-    typedef typename TR::T T;
-    const int KTOT = few16_ktot(CIN);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= NOUTP * KTOT) return;
-    const int row = i / KTOT, k = i - row * KTOT;
-    const int slot = k / CIN, c = k - slot * CIN;
-    float v = 0.f;
-    if (slot < 9 && row < p.nout && c < p.cin)
-        v = p.mode == 0 ? p.w[((long)slot * p.wrows + c) * p.ldw + row] : p.w[((long)(8 - slot) * p.wrows + row) * p.ldw + c];
-    v *= TR::WSCALE;
-    const T h = (T)v;
-    img[i] = h;
-    img[(size_t)NOUTP * KTOT + i] = (T)(v - (float)h);
-}
-
-template <typename TR, int CIN, int NOUTP, int MODE, int CLOAD = CIN>
-__global__ __launch_bounds__(512, (NOUTP == 32 && MODE == 0) ? 2 : 4) void conv_few16_kernel(const FewParams p) {
-    typedef typename TR::V8 V8;
-    constexpr int TH = 16, TW = 32, XH = TH + 2, XWV = TW + 2, XW = 36;
-    constexpr int PB = CIN * 2;                        // bytes per pixel and plane
-    constexpr int XPL = XH * XW * PB;
-    constexpr int TPK = 32 / CIN;                      // taps per 32-deep MFMA
-    constexpr int NKB = (9 + TPK - 1) / TPK;           // MFMAs per term and tile
-    constexpr int KTOT = NKB * 32;
-    constexpr int NT = NOUTP / 16;
-    constexpr int NXL = (XH * XWV * (CLOAD / 4) + 511) / 512;
-    static_assert((CIN == 8 || CIN == 16) && (CLOAD == CIN || (CIN == 8 && CLOAD == 4)), "few-channel instance");
-    static_assert(2 * XPL >= 8 * 2 * NOUTP * 4, "statistics scratch");
-    __shared__ __attribute__((aligned(16))) char xl[2 * XPL];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int li = lane & 15, g = lane >> 4;
-
-    // the weight image -> registers (once per workgroup): lane (li, g) of (n, kb) holds row 16 n + li, k = 32 kb + 8 g .. + 7
-    V8 wh[NT][NKB], wlo[NT][NKB];
-#pragma unroll
-    for (int n = 0; n < NT; ++n)
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            const size_t off = ((size_t)(n * 16 + li) * KTOT + kb * 32 + g * 8) * 2;
-            wh[n][kb] = *reinterpret_cast<const V8*>(p.Wimg + off);
-            wlo[n][kb] = *reinterpret_cast<const V8*>(p.Wimg + p.w_lo_off + off);
-        }
-    // this lane's tap shift of each MFMA: slot = kb * TPK + g / (4 / TPK); spare slots read tap 0 (their weights are zero)
-    int boff[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-        int slot = kb * TPK + (CIN == 8 ? g : g >> 1);
-        if (slot > 8) slot = 0;
-        const int r = slot / 3, q = slot - 3 * r;
-        boff[kb] = (r * XW + q) * PB + (CIN == 8 ? 0 : (g & 1) * 16);
-    }
-
-    float4 rx[NXL];
-    unsigned okm = 0;                          // which of rx[] came from inside the image (the affine applies to those only)
-    // (a thread's items are always the same four channels: 512 is a multiple of CLOAD / 4)
-    const float4 asc = p.a_scale ? *reinterpret_cast<const float4*>(p.a_scale + (tid % (CLOAD / 4)) * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const float4 ash = p.a_scale ? *reinterpret_cast<const float4*>(p.a_shift + (tid % (CLOAD / 4)) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    auto load_tile = [&](long tile) {
-        okm = 0;
-        const int tx = (int)(tile % p.tiles_x);
-        const long t2 = tile / p.tiles_x;
-        const int ty = (int)(t2 % p.tiles_y);
-        const long img = t2 / p.tiles_y;
-        const float* xi = p.X + img * p.SH * p.SW * p.ldx;
-#pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i % (CLOAD / 4), pix = i / (CLOAD / 4);
-            const int row = pix / XWV, col = pix - row * XWV;
-            const int iy = ty * TH + row - p.pad_t, ix = tx * TW + col - p.pad_l;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool ok = row < XH && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
-            int sy = iy, sx = ix;
-            if (p.dil == 2) {               // the zero-inserted view: only the even positions hold data
-                ok = ok && !((iy | ix) & 1);
-                sy >>= 1; sx >>= 1;
-            }
-            if (ok) {
-                v = *reinterpret_cast<const float4*>(xi + ((long)sy * p.SW + sx) * p.ldx + c4 * 4);
-                okm |= 1u << k;
-            }
-            rx[k] = v;
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i % (CLOAD / 4), pix = i / (CLOAD / 4);
-            const int row = pix / XWV, col = pix - row * XWV;
-            if (row < XH) {
-                const int off = (row * XW + col) * PB + c4 * 8;
-                uint2 hi, lo;
-                split4<TR>(p.a_scale && ((okm >> k) & 1u) ? affine_relu4(rx[k], asc, ash, p.a_relu != 0) : rx[k], hi, lo);
-                *reinterpret_cast<uint2*>(xl + off) = hi;
-                *reinterpret_cast<uint2*>(xl + XPL + off) = lo;
-            }
-        }
-    };
-    if (CLOAD < CIN) {                      // 4 real channels in an 8-channel image: the upper half stays zero
-        for (int i = tid; i < 2 * XH * XW; i += 512)
-            *reinterpret_cast<uint2*>(xl + (i / (XH * XW)) * XPL + (i % (XH * XW)) * PB + 8) = make_uint2(0u, 0u);
-    }
-
-    f32x4 s1[NT], s2[NT], bv[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        s1[n] = s2[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        bv[n] = (MODE == 0 && p.bias && n * 16 + 4 * g < p.nout) ? *reinterpret_cast<const f32x4*>(p.bias + n * 16 + 4 * g)
-                                                                 : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    // XCD j = blockIdx.x % 8 walks tiles [j * per, (j + 1) * per), its gridDim.x / 8 workgroups interleaved
-    const int xcd = blockIdx.x & 7, nslot = gridDim.x >> 3;
-    const long t_end = min((long)(xcd + 1) * p.per, p.tiles);
-    long tile = (long)xcd * p.per + (blockIdx.x >> 3);
-    if (tile < t_end) load_tile(tile);
-    for (; tile < t_end; tile += nslot) {
-        __syncthreads();                               // everyone has finished reading the previous tile
-        store_tile();
-        __syncthreads();
-        const int tx = (int)(tile % p.tiles_x);
-        const long t2 = tile / p.tiles_x;
-        const int ty = (int)(t2 % p.tiles_y);
-        const long img = t2 / p.tiles_y;
-        if (tile + nslot < t_end) load_tile(tile + nslot);     // in flight while this tile is multiplied
-        // wave wid: tile rows 2 wid, 2 wid + 1, both 16-pixel halves
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int urow = 2 * wid + (u >> 1), ucol = (u & 1) * 16;
-            const int base = (urow * XW + ucol + li) * PB;
-            f32x4 acc[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) {
-                const V8 xh = *reinterpret_cast<const V8*>(xl + base + boff[kb]);
-                const V8 xlo = *reinterpret_cast<const V8*>(xl + XPL + base + boff[kb]);
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    acc[n] = TR::mfma(wlo[n][kb], xh, acc[n]);
-                    acc[n] = TR::mfma(wh[n][kb], xlo, acc[n]);
-                    acc[n] = TR::mfma(wh[n][kb], xh, acc[n]);
-                }
-            }
-            // lane (li, g) of acc[n] holds output pixel (row urow, column ucol + li), channels 16 n + 4 g .. + 3
-            const int oy = ty * TH + urow, ox = tx * TW + ucol + li;
-            if (oy < p.H && ox < p.W) {
-                const long pix = (img * p.H + oy) * p.W + ox;
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    if (n * 16 + 4 * g < p.nout) {
-                        f32x4 v = acc[n] * TR::OUTSCALE + bv[n];
-                        if (MODE == 1) {
-                            if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + pix * p.ldres + n * 16 + 4 * g);
-                        } else {
-                            s1[n] += v;
-                            s2[n] += v * v;
-                        }
-                        *reinterpret_cast<f32x4*>(p.Y + pix * p.ldy + n * 16 + 4 * g) = v;
-                    }
-                }
-            }
-        }
-    }
-    if (MODE == 0 && p.stats) {
-        // the workgroup's statistics row: 16 pixel lanes by DPP, 8 waves through LDS, in wave order
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(xl);     // [8][2][NOUTP]
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float a = row16_sum(s1[n][c]), b = row16_sum(s2[n][c]);
-                if (li == 0) {
-                    red[(wid * 2 + 0) * NOUTP + n * 16 + 4 * g + c] = a;
-                    red[(wid * 2 + 1) * NOUTP + n * 16 + 4 * g + c] = b;
-                }
-            }
-        __syncthreads();
-        if (tid < 2 * NOUTP) {
-            const int which = tid / NOUTP, n = tid % NOUTP;
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) t += red[(w * 2 + which) * NOUTP + n];
-            if (n < p.nout) p.stats[((long)blockIdx.x * 2 + which) * p.stats_ld + n] = t;
-        }
-    }
-}
-
 // shapes the few-channel MFMA kernel takes (cin = channels of the tensor that is convolved, nout = channels written)
 // cin = channels of the tensor that is convolved (4 forward only: an 8-channel image with a zero upper half), nout = written
 static bool few16_channels(int cin, int nout, long pixels) {
@@ -1920,211 +603,6 @@ static int dispatch_few16(const FewParams& q, int N, int cin, int nout, void* ws
     if (cin == 8) return nout <= 16 ? launch_few16<TR, 8, 16, MODE>(q, N, ws, st) : launch_few16<TR, 8, 32, MODE>(q, N, ws, st);
     return launch_few16<TR, 16, 16, MODE>(q, N, ws, st);
 }
-
-// ------------------------------------------------------------------------------------------
-// 2x2 / stride-2 transposed conv with 32 input and 8 output channels (models/unet_architecture.py upsample_9 at 112x149 ->
-// 224x298; round 4): patches do not overlap, so per INPUT pixel it is one 32 x 32 product - y'[(tap, k)] = W[(tap, k)][c] x[c],
-// dx[c] = W^T[c][(tap, k)] gy'[(tap, k)] - and both operands can be loaded from global memory directly in MFMA layout: a
-// lane's 8 k-values are 8 consecutive channels of one pixel (forward) or the 8 channels of one of the pixel's four output
-// positions (data gradient).  No LDS, no scatter pass: forward stores are 64 contiguous bytes per pixel and output row (1 KiB
-// runs per wave), data-gradient stores 128.  Weights (the 32 x 32 matrix, hi / lo) live in registers.  3-term split product:
-// f16 hi / lo forward, bf16 hi / lo for the gradient.  The implicit GEMM with a scatter epilogue these replace ran at 90 /
-// 65 us for 136 MB each way.
-// MODE 0: y[n][2i + r][2j + s][k] = bias[k] + sum_c x[n][i][j][c] w[r][s][k][c]
-// MODE 1: dx[n][i][j][c] = sum_{r,s,k} gy[n][2i + r][2j + s][k] w[r][s][k][c]   (optional ReLU mask on dx)
-// ------------------------------------------------------------------------------------------
-struct Patch2Params {
-    const float* X; int ldx;       // MODE 0: x [N][H][W] pixels of ldx floats; MODE 1: gy [N][2H][2W] pixels of ldx floats
-    float* Y; int ldy;             // MODE 0: y [N][2H][2W]; MODE 1: dx [N][H][W]
-    const float* w; int ldw;       // [2][2][8][ldw >= 32]
-    const float* bias; const float* mask; int ldmask; int act;
-    int H, W; long pixels;         // the low-resolution grid
-};
-
-template <typename TR, int MODE>
-__global__ __launch_bounds__(256) void patch2_32x8_kernel(const Patch2Params p) {
-    typedef typename TR::V8 V8;
-    typedef typename TR::T T;
-    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    // the weight matrix in the A slot, rows 16 n + li: MODE 0 rows are (tap, k) and the lane's 8 k-values channels 8 g ..;
-    // MODE 1 rows are channels c and the lane's 8 k-values are (tap g, k 0 .. 7)
-    V8 wh[2], wl[2];
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        float v[8];
-        if (MODE == 0) {
-            const float* src = p.w + (long)(16 * n + li) * p.ldw + 8 * g;
-            const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = p.w[(long)(g * 8 + k) * p.ldw + 16 * n + li];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float s_ = v[k] * TR::WSCALE;
-            const T h = (T)s_;
-            wh[n][k] = h;
-            wl[n][k] = (T)(s_ - (float)h);
-        }
-    }
-    f32x4 bv[2];
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-        bv[n] = (MODE == 0 && p.bias) ? *reinterpret_cast<const f32x4*>(p.bias + 4 * (g & 1)) : f32x4{0.f, 0.f, 0.f, 0.f};
-    const long groups = (p.pixels + 15) >> 4;
-    const long nwaves = (long)gridDim.x * 4;
-    for (long grp = (long)blockIdx.x * 4 + (threadIdx.x >> 6); grp < groups; grp += nwaves) {
-        const long pix_raw = grp * 16 + li;
-        const bool live = pix_raw < p.pixels;
-        const long pix = live ? pix_raw : p.pixels - 1;
-        const int j = (int)(pix % p.W);
-        const long t = pix / p.W;
-        const int i = (int)(t % p.H);
-        const long img = t / p.H;
-        // this lane's 8 values of the pixel operand
-        const float* src = MODE == 0 ? p.X + pix * p.ldx + 8 * g
-                                     : p.X + ((img * 2 * p.H + 2 * i + (g >> 1)) * (2L * p.W) + 2 * j + (g & 1)) * p.ldx;
-        const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-        uint2 h0, l0, h1, l1;
-        split4<TR>(a, h0, l0);
-        split4<TR>(b, h1, l1);
-        const V8 xh = __builtin_bit_cast(V8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-        const V8 xl = __builtin_bit_cast(V8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc = TR::mfma(wl[n], xh, acc);
-            acc = TR::mfma(wh[n], xl, acc);
-            acc = TR::mfma(wh[n], xh, acc);
-            f32x4 v = acc * TR::OUTSCALE + bv[n];
-            if (!live) continue;
-            if (MODE == 0) {
-                // rows 16 n + 4 g .. + 3 = tap 2 n + (g >> 1), channels 4 (g & 1) .. + 3: output pixel (2 i + n, 2 j + (g >> 1))
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = apply_act(v[c], p.act);
-                float* dst = p.Y + ((img * 2 * p.H + 2 * i + n) * (2L * p.W) + 2 * j + (g >> 1)) * p.ldy + 4 * (g & 1);
-                *reinterpret_cast<f32x4*>(dst) = v;
-            } else {
-                if (p.mask) {
-                    const f32x4 m = *reinterpret_cast<const f32x4*>(p.mask + pix * p.ldmask + 16 * n + 4 * g);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = m[c] > 0.f ? v[c] : 0.f;
-                }
-                *reinterpret_cast<f32x4*>(p.Y + pix * p.ldy + 16 * n + 4 * g) = v;
-            }
-        }
-    }
-}
-
-// Weight gradient of the same layer: dW[(tap, k)][c] = sum over input pixels of gy[n][2i + r][2j + s][k] x[n][i][j][c], a
-// 32 x 32 matrix reduced over all pixels.  The pixels are the MFMA's K axis here, so a lane's 8 k-values are the SAME
-// element of 8 consecutive pixels: 4-byte loads (16 lanes cover 64 contiguous bytes of a pixel, the texture addresser
-// coalesces them), bf16 hi / lo on the way, 12 MFMAs per 32 pixels, the 32 x 32 tile in 16 accumulators per wave; the
-// workgroup's sixteen waves are added through LDS in wave order into one slab per workgroup (slab_reduce_wide_kernel adds
-// those in slab order: deterministic).  No LDS staging, no transposing reads.  136 MB in 127 us before (gather GEMM).
-struct Patch2WgradParams {
-    const float* X; int ldx;       // x [N][H][W][32]
-    const float* G; int ldg;       // gy [N][2H][2W][8]
-    float* out; int ldo;           // slabs [gridDim.x][32][ldo]
-    float* db_part;                // [gridDim.x][8] partial bias gradients (sum of gy per channel) or null
-    int H, W; long pixels;
-};
-
-__global__ __launch_bounds__(1024) void patch2_wgrad_32x8_kernel(const Patch2WgradParams p) {
-    typedef SplitBF16 TR;
-    typedef TR::V8 V8;
-    typedef TR::T T;
-    constexpr int NW = 16;             // waves per workgroup: one workgroup per CU, few slabs for the reduce launch to walk
-    __shared__ float red[NW][32][33];
-    __shared__ float redb[NW][64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
-    float sdb = 0.f;               // this lane's share of the bias gradient: every gy value it loads has channel li & 7
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // row m = 16 mt + li of gy' is (tap, k) = (2 mt + (li >> 3), li & 7): its offset from the pixel's top-left output position
-    long offa[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) offa[mt] = ((long)mt * 2 * p.W + (li >> 3)) * p.ldg + (li & 7);
-    const long blocks = (p.pixels + 31) >> 5;
-    const long nwaves = (long)gridDim.x * NW;
-    for (long blk = (long)blockIdx.x * NW + wid; blk < blocks; blk += nwaves) {
-        // this lane's eight pixels: blk * 32 + 8 g + t
-        const long pix0 = blk * 32 + 8 * g;
-        long pc = pix0 < p.pixels ? pix0 : p.pixels - 1;
-        int j = (int)(pc % p.W);
-        long t_ = pc / p.W;
-        int i = (int)(t_ % p.H);
-        long img = t_ / p.H;
-        float av[2][8], bvv[2][8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const bool live = pix0 + t < p.pixels;
-            const float* gb = p.G + ((img * 2 * p.H + 2 * i) * (2L * p.W) + 2 * j) * p.ldg;
-            const float* xb = p.X + ((img * p.H + i) * (long)p.W + j) * p.ldx;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) av[mt][t] = live ? gb[offa[mt]] : 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) bvv[nt][t] = live ? xb[16 * nt + li] : 0.f;
-            if (live && pix0 + t + 1 < p.pixels) {       // the next pixel, by carry (no division)
-                if (++j == p.W) {
-                    j = 0;
-                    if (++i == p.H) { i = 0; ++img; }
-                }
-            }
-        }
-        V8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                sdb += av[q][t];
-                const T h = (T)av[q][t];
-                ah[q][t] = h;
-                al[q][t] = (T)(av[q][t] - (float)h);
-                const T hb = (T)bvv[q][t];
-                bh[q][t] = hb;
-                bl[q][t] = (T)(bvv[q][t] - (float)hb);
-            }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                acc[mt][nt] = TR::mfma(al[mt], bh[nt], acc[mt][nt]);
-                acc[mt][nt] = TR::mfma(ah[mt], bl[nt], acc[mt][nt]);
-                acc[mt][nt] = TR::mfma(ah[mt], bh[nt], acc[mt][nt]);
-            }
-    }
-    // lane (li, g) of acc[mt][nt] holds rows 16 mt + 4 g .. + 3, column 16 nt + li
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[wid][16 * mt + 4 * g + r][16 * nt + li] = acc[mt][nt][r];
-    redb[wid][lane] = sdb;
-    __syncthreads();
-    if (p.db_part && threadIdx.x < 8) {          // channel k: lanes k and k + 8 of every 16-lane row, every wave, in a fixed order
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) t += redb[w][16 * gg + threadIdx.x] + redb[w][16 * gg + 8 + threadIdx.x];
-        p.db_part[(long)blockIdx.x * 8 + threadIdx.x] = t;
-    }
-    float* slab = p.out + (long)blockIdx.x * 32 * p.ldo;
-    {
-        const int row = threadIdx.x >> 5, col = threadIdx.x & 31;      // 1024 threads = the 32 x 32 tile, waves added in order
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) t += red[w][row][col];
-        slab[row * p.ldo + col] = t;
-    }
-}
-static constexpr int PATCH2_WGRAD_WGS = 256;
 
 static bool patch2_shape(const AcimgConvDesc* d) {
     return d->R == 2 && d->S == 2 && d->stride == 2 && d->C == 32 && d->K == 8 && d->OH == 2 * d->H && d->OW == 2 * d->W &&
@@ -2211,7 +689,7 @@ static size_t dilated_bytes(int N, int H, int W, int C, int s) {
 }
 
 // data gradient of a 3x3 / stride-1 / SAME layer with 32 output and 4 - 16 input channels (configs[1]: 112x149 8 -> 32) through
-// the fp32 entry: a conv of the 32-channel gy on the 16-row instance of the halo kernel (defined with conv_halo16_kernel)
+// the fp32 entry: a conv of the 32-channel gy on the 16-row instance of the halo kernel (conv_halo16_kernel.hpp)
 static bool dgrad_halo16_narrow_shape(const AcimgConvDesc* d) {
     return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->OH == d->H && d->OW == d->W &&
            d->K == 32 && d->C <= 16 && (d->C & 3) == 0 && (long)d->N * d->H * d->W >= 65536 && g_cfg.wgrad_halo;
@@ -2234,210 +712,6 @@ static Split3Cfg pick_split3(int M, int K, bool allow32 = false) {
     return {128, 128};
 }
 
-// ------------------------------------------------------------------------------------------
-// HALO form of the FORWARD conv / DATA GRADIENT of the same 3x3 / stride-1 / SAME layers with 32 or 64 channels on either
-// side (round 4; configs[1]'s 112x149 and 56x74 stages).  As an implicit GEMM with a 32- or 64-column tile these layers
-// gather x once per tap through L2 (112x149 64->32 forward: 121 us against ~50 us of bytes).  Here a workgroup stages a
-// TH x 32 pixel tile of the input WITH ITS HALO once (fp32 -> 16-bit hi [, lo] planes, [pixel][channel] rows padded by 16
-// bytes: conflict-light ds_read_b128 fragments at every tap shift with no swizzle) and keeps the layer's whole weight image
-// in LDS (rows padded the same way); K walks (tap, 32-channel chunk); weights in the A slot, so a lane's 4 accumulators are
-// 4 consecutive output channels of one pixel (16-byte stores).  MODE 0: forward - bias, raw fp32 output, batch-norm partials
-// of conv + bias accumulated over the workgroup's tiles: ONE statistics row per workgroup.  MODE 1: data gradient - a
-// forward conv of gy with the flipped / transposed image of acimg_conv2d_split3_prepare_dgrad; residual and ReLU mask in the
-// epilogue.  One workgroup per CU, the next tile's loads held in registers while the current one is multiplied.
-// ------------------------------------------------------------------------------------------
-struct ConvHaloParams {
-    const float* X; int H, W, ldx;
-    const char* Wimg; unsigned w_lo_off;         // 16-bit image [rows][9 CIN], hi plane; lo plane w_lo_off bytes further
-    // the producer's deferred batch norm on load: x' = relu(x * a_scale[c] + a_shift[c]) for pixels INSIDE the image (the
-    // conv's zero padding applies after the affine); null = x as stored
-    const float* a_scale; const float* a_shift; int a_relu;
-    float* Y; int ldy, nout;                     // nout: channels written (0 = all NOUT; the image's further rows are zero)
-    const float* bias; const float* res; int ldres; const float* mask; int ldmask;
-    float* stats; int stats_ld;                  // [gridDim.x][2][stats_ld] or null
-    int tiles_x, tiles_y; long tiles;
-};
-
-template <typename TR, int TERMS, int CIN, int NOUT, int MODE>
-__global__ __launch_bounds__(512, 1) void conv_halo16_kernel(const ConvHaloParams p) {
-    typedef typename TR::V8 V8;
-    constexpr int TH = TERMS == 1 ? 8 : 4, TW = 32, XH = TH + 2, XWV = TW + 2, XW = 36;
-    constexpr int PITCH = CIN * 2 + 16;               // bytes per pixel and plane (padded)
-    constexpr int XPL = XH * XW * PITCH;
-    constexpr int KTOT = 9 * CIN;
-    constexpr int WROW = KTOT * 2 + 16;               // bytes per weight row and plane (padded)
-    constexpr int WPL = NOUT * WROW;
-    constexpr int NPL = TERMS == 3 ? 2 : 1;
-    constexpr int MT = TERMS == 1 ? 2 : 1;            // 16-pixel tiles per wave: a whole tile row, or half of one
-    constexpr int NT = NOUT / 16;
-    constexpr int NXL = (XH * XWV * (CIN / 4) + 511) / 512;
-    extern __shared__ __attribute__((aligned(16))) float ch16_smem[];
-    char* const xl = reinterpret_cast<char*>(ch16_smem);
-    char* const wl = xl + NPL * XPL;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int li = lane & 15, g = lane >> 4;
-    const int jrow = TERMS == 1 ? wid : wid >> 1;     // tile row of this wave
-    const int mcol0 = TERMS == 1 ? 0 : (wid & 1) * 16;
-
-    // the weight image -> LDS (once per workgroup): NOUT rows of KTOT 16-bit values, 16-byte chunks
-    for (int i = tid; i < NPL * NOUT * (KTOT / 8); i += 512) {
-        const int ch = i % (KTOT / 8), r2 = i / (KTOT / 8);
-        const int n = r2 % NOUT, pl = r2 / NOUT;
-        const uint4 v = *reinterpret_cast<const uint4*>(p.Wimg + (size_t)pl * p.w_lo_off + ((size_t)n * KTOT + ch * 8) * 2);
-        *reinterpret_cast<uint4*>(wl + pl * WPL + n * WROW + ch * 16) = v;
-    }
-
-    float4 rx[NXL];
-    unsigned okm = 0;                          // which of rx[] came from inside the image (the affine applies to those only)
-    // (a thread's items are always the same four channels: 512 is a multiple of CIN / 4)
-    const float4 asc = p.a_scale ? *reinterpret_cast<const float4*>(p.a_scale + (tid % (CIN / 4)) * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const float4 ash = p.a_scale ? *reinterpret_cast<const float4*>(p.a_shift + (tid % (CIN / 4)) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    auto load_tile = [&](long tile) {
-        okm = 0;
-        const int tx = (int)(tile % p.tiles_x);
-        const long t2 = tile / p.tiles_x;
-        const int ty = (int)(t2 % p.tiles_y);
-        const long img = t2 / p.tiles_y;
-        const float* xi = p.X + img * p.H * p.W * p.ldx;
-#pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i % (CIN / 4), pix = i / (CIN / 4);
-            const int row = pix / XWV, col = pix - row * XWV;
-            const int iy = ty * TH + row - 1, ix = tx * TW + col - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < XH && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) {
-                v = *reinterpret_cast<const float4*>(xi + ((long)iy * p.W + ix) * p.ldx + c4 * 4);
-                okm |= 1u << k;
-            }
-            rx[k] = v;
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            const int i = tid + 512 * k;
-            const int c4 = i % (CIN / 4), pix = i / (CIN / 4);
-            const int row = pix / XWV, col = pix - row * XWV;
-            if (row < XH) {
-                const int off = (row * XW + col) * PITCH + c4 * 8;
-                uint2 hi, lo;
-                split4<TR>(p.a_scale && ((okm >> k) & 1u) ? affine_relu4(rx[k], asc, ash, p.a_relu != 0) : rx[k], hi, lo);
-                *reinterpret_cast<uint2*>(xl + off) = hi;
-                if (TERMS == 3) *reinterpret_cast<uint2*>(xl + XPL + off) = lo;
-            }
-        }
-    };
-
-    f32x4 s1[NT], s2[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) s1[n] = s2[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 bv[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n)
-        bv[n] = (MODE == 0 && p.bias) ? *reinterpret_cast<const f32x4*>(p.bias + n * 16 + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int a_base = (jrow * XW + mcol0 + li) * PITCH + g * 16;       // + ((r * XW + s + 16 m) * PITCH + chunk * 64)
-    const int b_base = li * WROW + g * 16;                              // + (nt * 16 * WROW + (tap * CIN + chunk * 32) * 2)
-
-    long tile = blockIdx.x;
-    if (tile < p.tiles) load_tile(tile);
-    for (; tile < p.tiles; tile += gridDim.x) {
-        __syncthreads();                               // everyone has finished reading the previous tile (and the weights landed)
-        store_tile();
-        __syncthreads();
-        const int tx = (int)(tile % p.tiles_x);
-        const long t2 = tile / p.tiles_x;
-        const int ty = (int)(t2 % p.tiles_y);
-        const long img = t2 / p.tiles_y;
-        if (tile + gridDim.x < p.tiles) load_tile(tile + gridDim.x);     // in flight while this tile is multiplied
-        f32x4 acc[MT][NT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int s_ = 0; s_ < 3; ++s_)
-#pragma unroll
-                for (int ck = 0; ck < CIN / 32; ++ck) {
-                    V8 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) {
-                        const int off = a_base + (r * XW + s_ + 16 * m) * PITCH + ck * 64;
-                        ah[m] = *reinterpret_cast<const V8*>(xl + off);
-                        if (TERMS == 3) al[m] = *reinterpret_cast<const V8*>(xl + XPL + off);
-                    }
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        const int off = b_base + n * 16 * WROW + ((r * 3 + s_) * CIN + ck * 32) * 2;
-                        bh[n] = *reinterpret_cast<const V8*>(wl + off);
-                        if (TERMS == 3) bl[n] = *reinterpret_cast<const V8*>(wl + WPL + off);
-                    }
-#pragma unroll
-                    for (int m = 0; m < MT; ++m)
-#pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-                            if (TERMS == 3) {
-                                acc[m][n] = TR::mfma(bl[n], ah[m], acc[m][n]);
-                                acc[m][n] = TR::mfma(bh[n], al[m], acc[m][n]);
-                            }
-                            acc[m][n] = TR::mfma(bh[n], ah[m], acc[m][n]);
-                        }
-                }
-        // lane (li, g) of acc[m][n] holds output pixel (row jrow, column mcol0 + 16 m + li), channels 16 n + 4 g .. + 3
-        const int oy = ty * TH + jrow;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int ox = tx * TW + mcol0 + 16 * m + li;
-            if (oy < p.H && ox < p.W) {
-                const long pix = (img * p.H + oy) * p.W + ox;
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    if (NOUT == 16 && n * 16 + 4 * g >= p.nout) continue;      // (the 16-row instance serves 4 - 16 channels)
-                    f32x4 v = acc[m][n] * TR::OUTSCALE + bv[n];
-                    if (MODE == 1) {
-                        if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + pix * p.ldres + n * 16 + 4 * g);
-                        if (p.mask) {
-                            const f32x4 k = *reinterpret_cast<const f32x4*>(p.mask + pix * p.ldmask + n * 16 + 4 * g);
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) v[c] = k[c] > 0.f ? v[c] : 0.f;
-                        }
-                    } else {
-                        s1[n] += v;
-                        s2[n] += v * v;
-                    }
-                    *reinterpret_cast<f32x4*>(p.Y + pix * p.ldy + n * 16 + 4 * g) = v;
-                }
-            }
-        }
-    }
-    if (MODE == 0 && p.stats) {
-        // the workgroup's statistics row: 16 pixel lanes by DPP, 8 waves through LDS, in wave order
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(xl);     // [8][2][NOUT]
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float a = row16_sum(s1[n][c]), b = row16_sum(s2[n][c]);
-                if (li == 0) {
-                    red[(wid * 2 + 0) * NOUT + n * 16 + 4 * g + c] = a;
-                    red[(wid * 2 + 1) * NOUT + n * 16 + 4 * g + c] = b;
-                }
-            }
-        __syncthreads();
-        if (tid < 2 * NOUT) {
-            const int which = tid / NOUT, n = tid % NOUT;
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) t += red[(w * 2 + which) * NOUT + n];
-            p.stats[((long)blockIdx.x * 2 + which) * p.stats_ld + n] = t;
-        }
-    }
-}
-
 // shapes the halo forward / data-gradient kernel takes: 3x3, stride 1, one pixel of padding, (reduction, output) channels
 // (32 | 64, 32) forward and (32, 32 | 64) backward, from 65536 pixels on
 static bool conv_halo16_fwd_shape(const AcimgConvDesc* d) {
@@ -2449,7 +723,6 @@ static bool conv_halo16_dgrad_shape(const AcimgConvDesc* d) {
     return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->OH == d->H && d->OW == d->W &&
            (d->C == 32 || d->C == 64) && d->K == 32 && (long)d->N * d->H * d->W >= 65536 && g_cfg.wgrad_halo;
 }
-static constexpr int CONV_HALO16_WGS = 256;          // one workgroup per CU = statistics rows of the forward form
 
 template <typename TR, int TERMS, int CIN, int NOUT, int MODE>
 static int launch_conv_halo16(ConvHaloParams q, int N, hipStream_t st) {
@@ -2555,21 +828,6 @@ static TrunkPick pick_trunk(const AcimgConvDesc* d, int terms, bool two_pass) {
 static size_t split3_rowmajor_bytes(const AcimgConvDesc* d) { return (size_t)2 * d->ldw * d->R * d->S * d->C * 2; }
 static size_t split3_brick_bytes(const AcimgConvDesc* d) {
     return d->C % 32 ? 0 : (size_t)cdiv(d->ldw, 128) * (d->R * d->S * d->C / 32) * 2 * 8192;
-}
-// one thread per 16-byte chunk of the tile-ordered image: brick (nt, q, plane), row, physical chunk
-__global__ void split3_brick_kernel(const char* __restrict__ planes, char* __restrict__ bricks, const int Nrows,
-                                    const int Ktot, const long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int pch = (int)(i & 3), row = (int)((i >> 2) & 127), plane = (int)((i >> 9) & 1);
-    const long bq = i >> 10;
-    const int kit = Ktot / 32;
-    const int nt = (int)(bq / kit), q = (int)(bq - (long)nt * kit);
-    const int n = nt * 128 + row;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (n < Nrows)
-        v = *reinterpret_cast<const uint4*>(planes + (((long)plane * Nrows + n) * Ktot + q * 32 + ((pch ^ swz(row)) << 3)) * 2);
-    *reinterpret_cast<uint4*>(bricks + i * 16) = v;
 }
 
 template <typename TR, int TERMS = 3>
@@ -2976,7 +1234,7 @@ int acimg_conv2d_fwd_tiling(const AcimgConvDesc* d, int* out) {
 
 int acimg_config_default(AcimgConfig* c) {
     if (!c) return fail(ACIMG_EINVAL, "config_default: null");
-    *c = AcimgConfig{320, 768, 1, 128, 1, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0};
+    *c = DEFAULT_CFG;
     return ACIMG_OK;
 }
 

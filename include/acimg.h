@@ -105,9 +105,15 @@ typedef struct AcimgConfig {
     int32_t splitk_target;   /* ... otherwise split towards this many workgroups (768) */
     int32_t splitk_handoff;  /* 1: combine K ranges in-kernel when `tickets` is given; 0: always the reduce launch */
     int32_t wgrad_minpix;    /* weight gradients: at least this many pixels per slab (128) */
-    int32_t wgrad_halo;      /* 1: weight gradients that stage a tile with its halo once and form every tap from it: the halo
-                                kernels of the few-channel layers and the tap-sharing kernel of the wide 3x3 layers with 32- /
-                                48-pixel rows; 0: the per-tap kernels */
+    int32_t wgrad_halo;      /* 1: the kernels that stage a tile with its halo once and form every tap from it, and the other
+                                special forms of the U-Net layers - not weight gradients alone (the name stays, with the
+                                record's layout and ACIMG_NO_WGRAD_HALO): the halo weight gradients of the few-channel and
+                                32- / 64-channel layers and the tap-sharing weight gradient of the wide 3x3 layers with 32- /
+                                48-pixel rows; the few-channel MFMA forward conv and data gradient; the narrow halo data
+                                gradient (32 -> 4..16 channels); the pointwise 2x2 / stride-2 forms (32 -> 8: forward, data
+                                and weight gradient); the halo forward conv / data gradient of the 32- / 64-channel layers;
+                                the tap-sharing forward and data-gradient convs.  0: the per-tap / implicit-GEMM / direct
+                                kernels for all of them */
     int32_t split3_tile_bm;  /* 0 = per-shape choice; else force the split-MFMA tile (experiments): 128x128, 64x128, */
     int32_t split3_tile_bn;  /*     128x64 */
     int32_t tail_split;      /* 1: trunk kernel cuts the tiles of the last partial round into K ranges */
