@@ -157,6 +157,8 @@ PROTOTYPES = {
     "acimg_mask_iou": (_I, [_P, _P, _I, _I, _P, _P]),
     "acimg_box_iou": (_I, [_P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
     "acimg_box_iou_workspace": (_SZ, [_I]),
+    "acimg_overlay_render": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _L, _L, _I, _P, _SZ, _P]),
+    "acimg_overlay_render_workspace": (_SZ, [_I]),
     "acimg_knn_topk": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "acimg_knn_topk_workspace": (_SZ, [_I, _I, _I, _I]),
     "acimg_knn_vote": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),

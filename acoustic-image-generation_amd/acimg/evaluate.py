@@ -5,7 +5,10 @@ trapezoid rule (areaundercurve.py:26-40, sklearn.metrics.auc).  The per-sample w
 exp pixels, two means, two mask counts) runs on the GPU; the 11-point curve is host arithmetic.
 
 `BoxIoU` is the Flickr-SoundNet variant (showimages_bb.py:286-320): the generated image's mask, resized to the
-224 x 298 frame, against the consensus map of up to three annotators' boxes (`acimg_box_iou`)."""
+224 x 298 frame, against the consensus map of up to three annotators' boxes (`acimg_box_iou`).
+
+`OverlayRenderer` draws what those scripts plot (showvideo.py:213-233, showimages.py:136-154, showimages_bb.py:240-285):
+the jet-coloured energy map at alpha 0.7 over the grey frame, as RGB8 pixels on the device (`acimg_overlay_render`)."""
 import numpy as np
 import torch
 
@@ -57,6 +60,78 @@ class BoxIoU(object):
         c = counts.cpu().numpy().astype(np.float64)
         with np.errstate(invalid="ignore", divide="ignore"):
             return c[:, 0] / c[:, 1]
+
+
+class OverlayRenderer(object):
+    """Owns the two colour tables (device, [256,3] uint8) and the blend weight alpha = (num, den).  `base` / `over`: a
+    name of `acimg.colormaps` or a [256,3] uint8 table, used as given."""
+
+    H, W = 224, 298
+
+    def __init__(self, device, base="gray", over="jet", alpha=(7, 10)):
+        self.device = torch.device(device)
+        self.fe = FrontEnd(self.device)
+        self.lut_base, self.lut_over = self._table(base), self._table(over)
+        self.alpha = (int(alpha[0]), int(alpha[1]))
+        if not (1 <= self.alpha[1] <= 255 and 0 <= self.alpha[0] <= self.alpha[1]):
+            raise ValueError("alpha = num / den wants 0 <= num <= den, 1 <= den <= 255, got %r" % (alpha,))
+
+    def _table(self, t):
+        if isinstance(t, str):
+            from . import colormaps
+            t = colormaps.byte_table(t)
+        t = torch.as_tensor(t)
+        if t.dtype != torch.uint8 or tuple(t.shape) != (256, 3):
+            raise ValueError("a colour table is [256,3] uint8, got %s %s" % (t.dtype, tuple(t.shape)))
+        return t.to(self.device).contiguous()
+
+    def energy(self, generated_or_logen):
+        """[n,36,48,12] MFCC image (through `FrontEnd.find_logen`) or an energy map [n,36,48] / [n,1728] as it is"""
+        x = generated_or_logen.to(device=self.device, dtype=torch.float32)
+        if x.dim() == 4 and x.shape[-1] == 12:
+            x = self.fe.find_logen(x)
+        return x.reshape(x.shape[0], 36 * 48).contiguous()
+
+    def _render_into(self, frames, logen, boxes, out, row_bytes, image_bytes):
+        n = frames.shape[0]
+        if tuple(frames.shape[:3]) != (n, self.H, self.W) or frames.dim() != 4 or frames.shape[3] < 3:
+            raise ValueError("frames are [n,224,298,>=3], got %s" % (tuple(frames.shape),))
+        if logen.shape[0] != n:
+            raise ValueError("%d frames, %d energy maps" % (n, logen.shape[0]))
+        b = None
+        if boxes is not None:
+            b = boxes.to(device=self.device, dtype=torch.int32).reshape(n, 4, 3).contiguous()
+        ops.overlay_render(self.fe.plan, frames, frames.shape[3], logen, b, self.lut_base, self.lut_over, self.alpha[0],
+                           self.alpha[1], out, row_bytes, image_bytes, n)
+
+    def _frames(self, frames):
+        return frames.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def render(self, frames, generated_or_logen, boxes=None, out=None):
+        """frames: float32 [n,224,298,c >= 3] (the loaders' video tensor; the first three channels are read);
+        generated_or_logen: see `energy`; boxes: int32 [n,4,3] or None -> uint8 [n,224,298,3] device tensor"""
+        f = self._frames(frames)
+        n = f.shape[0]
+        if out is None:
+            out = torch.empty(n, self.H, self.W, 3, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, self.H, self.W, 3) or not out.is_contiguous():
+            raise ValueError("out is a contiguous uint8 [n,224,298,3] tensor")
+        self._render_into(f, self.energy(generated_or_logen), boxes, out, self.W * 3, self.H * self.W * 3)
+        return out
+
+    def render_pair(self, frames, real, generated, gap=8, fill=255, out=None):
+        """the two panels of showimages.py:136-154 on one canvas uint8 [n,224,2*298+gap,3]: the real acoustic image's
+        map on the left, the generated one's on the right (the order of `namesimage`); the gap columns keep the
+        canvas's fill (`fill` for a canvas made here, whatever `out` holds otherwise)"""
+        f = self._frames(frames)
+        n, wide = f.shape[0], 2 * self.W + int(gap)
+        if out is None:
+            out = torch.full((n, self.H, wide, 3), int(fill), dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, self.H, wide, 3) or not out.is_contiguous():
+            raise ValueError("out is a contiguous uint8 [n,224,%d,3] tensor" % wide)
+        for energy, x0 in ((self.energy(real), 0), (self.energy(generated), self.W + int(gap))):
+            self._render_into(f, energy, None, out[:, :, x0:], wide * 3, self.H * wide * 3)
+        return out
 
 
 def mean_iou(ious):

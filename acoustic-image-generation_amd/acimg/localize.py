@@ -13,7 +13,7 @@ mode: BN moving statistics, keep_prob 1).  Output, next to the checkpoint in the
   files areaundercurve.py reads;
 * `localization.json`: the per-sample IoUs (NaN -> null), the 11-point curve, its area (areaundercurve.py:26-40), the
   mean IoU over the finite samples and the NaN count.
-No plots (matplotlib / cv2 are not dependencies)."""
+The pictures of the same scripts - the energy map over the frame, with the boxes - are `python -m acimg.show`."""
 import argparse
 import json
 import math

@@ -858,6 +858,16 @@ def box_iou(plan, logen, boxes, N, iou, counts=None, mask_out=None):
              _WsBytes(plan.ws))
 
 
+def overlay_render(plan, frames, ldf, logen, boxes, lut_base, lut_over, alpha_num, alpha_den, out, row_bytes,
+                   image_bytes, N):
+    """localisation overlay (showvideo.py:213-233): frames [N,224,298,ldf] float32, logen [N,36*48] float32, boxes
+    [N,4,3] int32 or None, two [256,3] uint8 tables -> RGB8 rows of 894 bytes at out + n * image_bytes + y * row_bytes"""
+    plan.ws.require(_L().acimg_overlay_render_workspace(int(N)))
+    plan.add("overlay_render", _L().acimg_overlay_render, frames, int(ldf), logen, boxes, lut_base, lut_over,
+             int(alpha_num), int(alpha_den), out, int(row_bytes), int(image_bytes), int(N), _WsPtr(plan.ws),
+             _WsBytes(plan.ws))
+
+
 def knn_topk(plan, query, ldq, Q, gallery, ldg, G, D, K, dist2, idx):
     """exact K nearest gallery rows per query row (retrieve.py:53-57, knn.py:102-104): fp64 [Q,ldq] / [G,ldg] ->
     dist2 float64 [Q,K], idx int32 [Q,K] ascending by (dist2, index); -1 / +inf past G"""

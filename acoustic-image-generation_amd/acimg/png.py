@@ -1,0 +1,32 @@
+"""A PNG writer on the standard library alone (zlib + struct): 8-bit RGB, colour type 2, no interlace, every scanline
+with filter 0, one IDAT chunk.  It is what `python -m acimg.show` saves its frames with - no PIL, imageio or cv2."""
+import struct
+import zlib
+
+import numpy as np
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def _chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def encode_png(rgb_uint8, level=6):
+    """[H,W,3] uint8 -> the bytes of a PNG file"""
+    a = np.asarray(rgb_uint8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png wants a [H,W,3] uint8 array, got %s %s" % (a.dtype, a.shape))
+    h, w = a.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)            # filter byte 0 in front of every scanline
+    rows[:, 1:] = a.reshape(h, 3 * w)
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)
+    return (SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(rows.tobytes(), int(level)))
+            + _chunk(b"IEND", b""))
+
+
+def write_png(path, rgb_uint8, level=6):
+    data = encode_png(rgb_uint8, level)
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(data)

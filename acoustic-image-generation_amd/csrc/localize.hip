@@ -18,32 +18,9 @@
 
 #pragma clang fp contract(off)
 
+#include "resize_linear.hpp"
+
 namespace acimg {
-
-constexpr int LOC_H = 36, LOC_W = 48, LOC_P = LOC_H * LOC_W;
-constexpr int FRAME_H = 224, FRAME_W = 298;
-constexpr int BOX_BANDS = 8, BAND_ROWS = FRAME_H / BOX_BANDS;   // 28 output rows per workgroup
-constexpr int BAND_SRC_ROWS = 8;                                 // the bands need 5 or 6 source rows
-static_assert(BAND_ROWS * BOX_BANDS == FRAME_H, "bands tile the frame");
-
-// cv::resize INTER_LINEAR coefficients of one output coordinate (resize.cpp, the !area_mode branch): source index s and
-// float32 weights (w0, w1) on s and s1 = min(s + 1, n_in - 1); f = 0 where the border clamps s.
-__host__ __device__ inline void linear_coef(int d, double scale, int n_in, int& s, int& s1, float& w0, float& w1) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) {
-        s = 0;
-        f = 0.f;
-    }
-    if (s >= n_in - 1) {
-        s = n_in - 1;
-        f = 0.f;
-    }
-    s1 = s + 1 < n_in ? s + 1 : n_in - 1;
-    w0 = 1.f - f;
-    w1 = f;
-}
 
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
@@ -176,15 +153,10 @@ int acimg_box_iou(const float* logen, const int32_t* boxes, int N, float* iou, i
     if (!logen || !boxes || !iou || !ws) return fail(ACIMG_EINVAL, "box_iou: null argument");
     if (ws_bytes < acimg_box_iou_workspace(N))
         return fail(ACIMG_EWORKSPACE, "box_iou: workspace %zu < %zu bytes", ws_bytes, acimg_box_iou_workspace(N));
-    // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale (host fp64, as OpenCV computes it)
-    const double scale_x = 1.0 / ((double)FRAME_W / LOC_W), scale_y = 1.0 / ((double)FRAME_H / LOC_H);
-    for (int b = 0; b < BOX_BANDS; ++b) {   // every band's source rows fit the LDS table
-        int lo, hi, t;
-        float w0, w1;
-        linear_coef(b * BAND_ROWS, scale_y, LOC_H, lo, t, w0, w1);
-        linear_coef(b * BAND_ROWS + BAND_ROWS - 1, scale_y, LOC_H, t, hi, w0, w1);
-        if (hi - lo + 1 > BAND_SRC_ROWS) return fail(ACIMG_EINVAL, "box_iou: band %d needs %d source rows", b, hi - lo + 1);
-    }
+    const double scale_x = resize_scale_x(), scale_y = resize_scale_y();
+    for (int b = 0; b < BOX_BANDS; ++b)   // every band's source rows fit the LDS table
+        if (band_rows_needed(b) > BAND_SRC_ROWS)
+            return fail(ACIMG_EINVAL, "box_iou: band %d needs %d source rows", b, band_rows_needed(b));
     hipStream_t s = (hipStream_t)stream;
     int* part = (int*)ws;
     hipLaunchKernelGGL(box_iou_partial_kernel, dim3(BOX_BANDS, N), dim3(256), 0, s, logen, boxes, scale_x, scale_y, part,

@@ -629,6 +629,38 @@ int acimg_box_iou(const float* logen, const int32_t* boxes, int N, float* iou, i
                   void* ws, size_t ws_bytes, void* stream);
 size_t acimg_box_iou_workspace(int N);
 
+/* Localisation overlay, the picture of showvideo.py:213-233, showimages.py:136-154 and showimages_bb.py:240-285: the
+ * energy map in the `lut_over` colours blended at alpha = alpha_num / alpha_den over the grey frame in the `lut_base`
+ * colours (the reference: jet at 0.7 over gray), RGB8 at the frame's native 224 x 298.  Per sample n < N, inputs finite:
+ *   g    = (F0 * 0.114f + F1 * 0.587f) + F2 * 0.299f in fp32, every product and sum rounded on its own: cv2.cvtColor(im,
+ *          COLOR_BGR2GRAY) on a float image (:224 / :144 / :246), restated, not pinned
+ *   g    = 1.0f on the outline of every annotator k < 3 with xmax[k] != 0 (boxes != NULL): with the corners sorted as
+ *          acimg_box_iou sorts them, x0 <= x1 and y0 <= y1, a pixel (x, y) of the frame is on the outline when
+ *          x0-1 <= x <= x1+1 and y0-1 <= y <= y1+1 and it is not strictly inside (x0+2 <= x <= x1-2 and y0+2 <= y <=
+ *          y1-2).  This stands for cv2.rectangle(imgray, ..., (1, 1, 1), 3) (showimages_bb.py:247-250); it is THIS
+ *          LIBRARY'S rule for a 3-pixel line - restated, not pinned, and the corner pixels are ours, not OpenCV's
+ *   v    = cv2.resize(map, (298, 224)) of the energy map promoted to float64 (find_logen returns float64): INTER_LINEAR,
+ *          half-pixel mapping, float32 weights clamped at the borders, float64 products and sums, horizontal then
+ *          vertical, no fused multiply-adds - acimg_box_iou's resize before its threshold
+ *   gmin, gmax over the sample's 224 x 298 values of g (outlines included); vmin, vmax over its values of v
+ *   index(a) = trunc(t * 256) with t = (a - amin) / (amax - amin), an IEEE-correct division; 255 where t * 256 == 256;
+ *          0 where amax == amin; fp32 for g, fp64 for v; clamped to 0..255 - matplotlib's Normalize() + colormap lookup
+ *          (plt.imshow without vmin / vmax), pinned against matplotlib by the tests
+ *   out[y][x][c] = (alpha_num * lut_over[index(v)][c] + (alpha_den - alpha_num) * lut_base[index(g)][c] + alpha_den / 2)
+ *          / alpha_den in integer arithmetic: alpha_num = 0 gives the base layer, alpha_num = alpha_den the overlay.
+ * frames: [N][224][298] pixels of ldf >= 3 floats (the first three are read); logen: [N][36*48] float32
+ * (acimg_find_logen outputs); boxes: [N][4][3] int32 as acimg_box_iou reads them, or NULL (no outlines); lut_base,
+ * lut_over: [256][3] uint8 device tables, used as given.  0 <= alpha_num <= alpha_den, 1 <= alpha_den <= 255.
+ * out: sample n, row y starts at out + n * image_bytes + y * row_bytes and receives 894 bytes; row_bytes >= 894,
+ * image_bytes >= 223 * row_bytes + 894; no other byte of the canvas is touched, so two panels side by side are two
+ * calls with `out` offset.  ws: acimg_overlay_render_workspace(N) bytes, 8-byte aligned.  A null or ill-sized argument
+ * is ACIMG_EINVAL, a short workspace ACIMG_EWORKSPACE, both before any launch.
+ * Stream-ordered, deterministic, no atomics. */
+int acimg_overlay_render(const float* frames, int ldf, const float* logen, const int32_t* boxes, const uint8_t* lut_base,
+                         const uint8_t* lut_over, int alpha_num, int alpha_den, uint8_t* out, long row_bytes,
+                         long image_bytes, int N, void* ws, size_t ws_bytes, void* stream);
+size_t acimg_overlay_render_workspace(int N);
+
 /* Exact K nearest gallery rows of every query row, fp64 (what retrieve.py:53-57 computes with scipy cdist + argsort per
  * anchor, and knn.py:102-104 with KNeighborsClassifier(n_neighbors=15).kneighbors):
  *   dist2[q][j] = sum_d (query[q][d] - gallery[g][d])^2, summed in fp64 in direct-difference form (not the
