@@ -162,6 +162,8 @@ PROTOTYPES = {
     "acimg_knn_topk": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "acimg_knn_topk_workspace": (_SZ, [_I, _I, _I, _I]),
     "acimg_knn_vote": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "acimg_batch_gather": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "acimg_batch_gather_workspace": (_SZ, [_I, _I]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

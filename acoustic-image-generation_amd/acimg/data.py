@@ -9,13 +9,22 @@ audio [n,12])), `.num_samples`, `.total_batches` (:117,214,973-976).
   `acimg_sequence_example_decode`: `_parse_sequence`, :263-343, with its LR + UD flip), the audio front end on the
   device (`acimg_filtfilt` = `butter_lowpass_filter`, :558-575; `acimg_mfcc_frontend` = `_build_spectrograms_function`,
   :796-876, with `_normalize_mfcc`, :696-703), the per-frame maps of :634-703 on the host, unbatch to frames and batch
-  (:99-104).  The tf.data machinery around it (parallel map, prefetch, shuffle buffer) is host plumbing the reference
-  leaves to TensorFlow: here a plain Python generator (SURVEY §2 #16 keeps that pipeline out of scope).
+  (:99-104): a plain Python generator, one record at a time, `shuffle=False`.
+* `DeviceDataLoader` (round 5): the same files through the tf.data machinery the reference wraps around the parser -
+  parallel map (`num_parallel_calls=4`), prefetch, and the shuffle buffer of :104-105 (`shuffle=True,
+  buffer_size=FLAGS.buffer_size`, main.py:112-116) with `reshuffle_each_iteration`.  Decoded frames stay on the device
+  in their raw form (video as bytes); a batch is assembled by `acimg_batch_gather`, which applies the per-frame maps
+  while it gathers, and is handed out as device tensors.
 * `BoxRecordLoader`: the box-annotated Flickr-SoundNet records of dataloader/frames.py (`ActionsDataLoader(...,
   embedding=1, nr_frames=1, sample_length=1, shuffle=False)`, written by convert_data2.py:200-307): 8-tuples (acoustic
   zeros [n,36,48,12], mfcc [n,12], video [n,224,298,3], xmin, xmax, ymin, ymax, typescene [n,3] int32) that
   showimages_bb.py:86-93 indexes.  Records through `acimg_box_sequence_example_decode`; the MFCC of the whole clip is
   `box_mfcc` on the host (the [1, L] reading of `_build_spectrograms_function`)."""
+import collections
+import concurrent.futures
+import ctypes
+import time
+
 import numpy as np
 import torch
 
@@ -133,6 +142,560 @@ class TFRecordDataLoader(object):
                     pend = [rest] if have else []
         if have:
             yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(6))
+
+
+# ---- the tf.data machinery of dataloader/outdoor_data_mfcc.py:99-105 -------------------------------------------------
+_END = object()
+
+
+def epoch_rng(seed, epoch):
+    """the generator of one pass over the data: `reshuffle_each_iteration` is a new `epoch`"""
+    return np.random.Generator(np.random.PCG64([int(seed), int(epoch)]))
+
+
+def shuffle_stream(inputs, buffer_size, rng):
+    """tf.data's shuffle buffer over an iterator: fill to `buffer_size`; every output takes a uniformly drawn occupied
+    position, which is refilled with the next input; when the input ends the buffer drains (the last occupied position
+    moves into the hole).  Only the procedure is TensorFlow's: its random stream cannot be reproduced and is not claimed."""
+    inputs = iter(inputs)
+    buf = []
+    while len(buf) < buffer_size:
+        x = next(inputs, _END)
+        if x is _END:
+            break
+        buf.append(x)
+    while buf:
+        j = int(rng.integers(len(buf)))
+        out = buf[j]
+        x = next(inputs, _END)
+        if x is _END:
+            buf[j] = buf[-1]
+            buf.pop()
+        else:
+            buf[j] = x
+        yield out
+
+
+def shuffle_order(n_frames, buffer_size, rng):
+    """emission order of `n_frames` inputs 0, 1, ... through a shuffle buffer of `buffer_size` (1: the identity)"""
+    if buffer_size < 1:
+        raise ValueError("buffer_size must be at least 1, got %r" % (buffer_size,))
+    return list(shuffle_stream(range(int(n_frames)), int(buffer_size), rng))
+
+
+def epoch_files(files, shuffle, shard, rng):
+    """the record files of one pass: permuted with the pass's generator when shuffling (`_shuffle_and_repeat_lists`,
+    :218-225), then entries i % world == rank of that list for shard = (rank, world)"""
+    files = list(files)
+    if shuffle:
+        files = [files[i] for i in rng.permutation(len(files))]
+    if shard is not None:
+        rank, world = int(shard[0]), int(shard[1])
+        if not 0 <= rank < world:
+            raise ValueError("shard = (rank, world) with 0 <= rank < world, got %r" % (shard,))
+        files = files[rank::world]
+    return files
+
+
+def pool_pages(buffer_size, prefetch):
+    """pages that always suffice: at most `buffer_size` un-emitted frames sit in the shuffle buffer and one frame can
+    pin a page; one record is being fed into the buffer; `prefetch` records are uploaded ahead; one page to upload into"""
+    return int(buffer_size) + int(prefetch) + 2
+
+
+class FramePages(object):
+    """Bookkeeping of the frame pool, no device in sight: pages of `frames` slots; a page is taken for one record, counts
+    that record's un-emitted frames, and comes back once its last frame's gather has been enqueued (`release`).  The pool
+    starts with `size` pages and may grow to `limit`."""
+
+    def __init__(self, size, limit, frames):
+        self.frames, self.limit, self.size = int(frames), int(limit), min(int(size), int(limit))
+        self.live = [0] * self.size
+        self.free = list(range(self.size - 1, -1, -1))
+        self.pending = []
+
+    def acquire(self):
+        """a page that holds no un-emitted frame, or None"""
+        if not self.free:
+            return None
+        page = self.free.pop()
+        assert self.live[page] == 0, "page %d handed out with %d live frames" % (page, self.live[page])
+        return page
+
+    def fill(self, page, n):
+        assert 0 < n <= self.frames and self.live[page] == 0
+        self.live[page] = n
+
+    def emit(self, slot):
+        page = slot // self.frames
+        assert self.live[page] > 0
+        self.live[page] -= 1
+        if self.live[page] == 0:
+            self.pending.append(page)
+
+    def release(self):
+        """every emitted frame's gather is enqueued: the emptied pages may be uploaded into again (stream order)"""
+        self.free.extend(reversed(self.pending))
+        self.pending = []
+
+    def grow(self):
+        """double the pool up to `limit`; returns the new size (unchanged at the limit)"""
+        new = min(self.limit, max(2 * self.size, 1))
+        self.free = list(range(new - 1, self.size - 1, -1)) + self.free
+        self.live += [0] * (new - self.size)
+        self.size = new
+        return new
+
+
+class BatchFeeder(object):
+    """One pass: records -> pages -> shuffle buffer -> batches of slots.  Everything that touches a device is a callback,
+    so the page logic runs on a fake pool in the tests:
+      records      iterator of decoded records, in file order (`next` may block on a worker)
+      ready()      True when `next(records)` would not block (only such records are uploaded ahead of need)
+      upload(page, record) -> frames in the record (enqueues the copies and the audio front end)
+      gather(slots, offset) enqueues the gather of these slots into rows offset.. of the batch being assembled
+      grow(pages)  the pool now has `pages` pages
+    A batch is gathered in one call unless a page is wanted while the only candidates are pages emptied by THIS batch:
+    then the rows chosen so far are gathered first, which frees them."""
+
+    def __init__(self, records, pages, batch_size, buffer_size, prefetch, rng, upload, gather, grow=None, ready=None):
+        self.records, self.pages = iter(records), pages
+        self.batch_size, self.buffer_size, self.prefetch, self.rng = int(batch_size), int(buffer_size), int(prefetch), rng
+        self.upload, self.gather, self.grow_cb, self.ready = upload, gather, grow, ready or (lambda: True)
+        self.ahead = collections.deque()      # (page, frames) uploaded, not yet fed into the shuffle buffer
+        self.done = False
+        self.batch, self.flushed = [], 0
+
+    def _admit(self):
+        rec = next(self.records, None)
+        if rec is None:
+            self.done = True
+            return False
+        page = self.pages.acquire()
+        if page is None and self.pages.pending:
+            self._flush()
+            page = self.pages.acquire()
+        if page is None and self.pages.size < self.pages.limit:
+            size = self.pages.grow()
+            if self.grow_cb is not None:
+                self.grow_cb(size)
+            page = self.pages.acquire()
+        assert page is not None, "frame pool exhausted: %d pages (buffer_size + prefetch + 2) must suffice" % self.pages.limit
+        self.pages.fill(page, self.upload(page, rec))
+        self.ahead.append((page, self.pages.live[page]))
+        return True
+
+    def _slots(self):
+        while self.ahead or (not self.done and self._admit()):
+            page, n = self.ahead.popleft()
+            for i in range(n):
+                yield page * self.pages.frames + i
+
+    def _flush(self):
+        if self.flushed < len(self.batch):
+            self.gather(self.batch[self.flushed:], self.flushed)
+            self.flushed = len(self.batch)
+        self.pages.release()
+
+    def _top_up(self):
+        while (len(self.ahead) < self.prefetch and not self.done and self.ready()
+               and (self.pages.free or self.pages.size < self.pages.limit)):
+            self._admit()
+
+    def __iter__(self):
+        """yields the size of each batch once its gather is enqueued"""
+        for slot in shuffle_stream(self._slots(), self.buffer_size, self.rng):
+            self.batch.append(slot)
+            self.pages.emit(slot)
+            if len(self.batch) == self.batch_size:
+                self._flush()
+                self._top_up()
+                yield len(self.batch)
+                self.batch, self.flushed = [], 0
+        if self.batch:
+            self._flush()
+            yield len(self.batch)
+            self.batch, self.flushed = [], 0
+
+
+def _inflate_file(path, verify):
+    """worker stage 1: file -> (inflated image, record offsets, record lengths, seconds spent inflating / indexing)"""
+    from . import _lib
+    lib = _lib.load()
+    t0 = time.perf_counter()
+    raw = np.fromfile(path, dtype=np.uint8)
+    gz = raw.size >= 18 and raw[0] == 0x1f and raw[1] == 0x8b
+    # a GZIP member ends with its inflated size mod 2^32: the first guess, so that most files are inflated once
+    guess = int(raw[-4:].view("<u4")[0]) if gz else raw.size
+    produced = ctypes.c_size_t(0)
+    buf = np.empty(max(guess, 1), dtype=np.uint8)
+    rc = lib.acimg_gzip_inflate(raw.ctypes.data, raw.size, buf.ctypes.data, buf.size, ctypes.byref(produced))
+    if rc == -2:
+        buf = np.empty(max(produced.value, 1), dtype=np.uint8)
+        rc = lib.acimg_gzip_inflate(raw.ctypes.data, raw.size, buf.ctypes.data, buf.size, ctypes.byref(produced))
+    _lib.check(rc, "gzip_inflate")
+    t1 = time.perf_counter()
+    n = produced.value
+    count = lib.acimg_tfrecord_index(buf.ctypes.data, n, None, None, 0, int(bool(verify)))
+    if count < 0:
+        raise IOError("%s: %s" % (path, _lib.last_error()))
+    off = np.zeros(max(count, 1), dtype=np.uint64)
+    ln = np.zeros(max(count, 1), dtype=np.uint64)
+    lib.acimg_tfrecord_index(buf.ctypes.data, n, off.ctypes.data, ln.ctypes.data, count, 0)
+    keep = [i for i in range(count) if ln[i]]
+    return buf, [int(off[i]) for i in keep], [int(ln[i]) for i in keep], t1 - t0, time.perf_counter() - t1
+
+
+def _record_dims(buf, off, ln):
+    """AcimgSequenceDims of the serialized SequenceExample at buf[off:off + ln] (sizes only)"""
+    from . import _lib
+    dims = _lib.SequenceDims()
+    _lib.check(_lib.load().acimg_sequence_example_decode(buf.ctypes.data + off, ln, ctypes.byref(dims), None, 0, None, 0,
+                                                         None, 0), "sequence_example_decode")
+    return dims
+
+
+class _Staging(object):
+    """pinned host buffers of one record (video bytes, acoustic floats, audio samples, labels) + the event behind the
+    uploads that read them"""
+
+    def __init__(self, frames, pixels3, elems):
+        self.video = torch.empty(frames, pixels3, dtype=torch.uint8).pin_memory()
+        self.acoustic = torch.empty(frames, elems, dtype=torch.float32).pin_memory()
+        self.audio = torch.empty(frames, 1024, dtype=torch.int32).pin_memory()
+        self.labels = torch.empty(frames, 2, dtype=torch.int32).pin_memory()
+        self.event = None
+        self.n = 0
+
+
+def _decode_record(buf, off, ln, st, dims0):
+    """worker stage 2: one serialized SequenceExample -> the pinned buffers of `st`; returns seconds spent"""
+    from . import _lib
+    lib = _lib.load()
+    t0 = time.perf_counter()
+    base = buf.ctypes.data + off
+    dims = _record_dims(buf, off, ln)
+    n = int(dims.video_steps)
+    shape = (int(dims.audio_height), int(dims.audio_width), int(dims.audio_depth), int(dims.video_height),
+             int(dims.video_width), int(dims.video_depth))
+    if not (dims.audio_image_steps == n and dims.audio_data_values == n * 1024 and dims.samples == 1024):
+        raise ValueError("record with %d video / %d acoustic steps, %d audio values of %d samples"
+                         % (n, dims.audio_image_steps, dims.audio_data_values, dims.samples))
+    if shape != dims0 or not 0 < n <= st.video.shape[0]:
+        raise ValueError("record of %d frames with dimensions %r in a data set of <= %d frames with %r"
+                         % (n, shape, st.video.shape[0], dims0))
+    _lib.check(lib.acimg_sequence_example_decode(base, ln, ctypes.byref(dims), st.acoustic.data_ptr(), st.acoustic.numel(),
+                                                 st.audio.data_ptr(), st.audio.numel(), st.video.data_ptr(),
+                                                 st.video.numel()), "sequence_example_decode")
+    st.labels[:n, 0] = int(dims.classes)
+    st.labels[:n, 1] = int(dims.location)
+    st.n = n
+    return time.perf_counter() - t0
+
+
+class DeviceDataLoader(object):
+    """`ActionsDataLoader(txt_file, mode, batch_size, ..., embedding=1, shuffle=..., buffer_size=...)` of the reference for
+    the MFCC path, with the tf.data stages around the record parser: the same 6-tuples as `TFRecordDataLoader`, same
+    order, shapes and dtypes, ON `device`.
+
+    * workers: `workers` (<= 16) threads read, inflate, index and decode records into pinned staging buffers through the
+      C ABI (ctypes drops the GIL); records are consumed in file order whatever order the workers finish in; a staging
+      buffer is written again only after the event behind its upload has completed.
+    * pool: decoded records live on the device in pages of `frames_per_record` slots (video as stored bytes, the
+      acoustic image as decoded, the raw audio, the two MFCC rows, the labels): one upload per modality and record.  The
+      audio front end (`FrontEnd`, per record as in `TFRecordDataLoader`) fills the MFCC rows in place.  Uploads, front
+      end and gathers share ONE stream, so a page emptied by a gather may be uploaded into right away.
+      `pool_pages(buffer_size, prefetch)` pages suffice (asserted); the pool starts small and doubles up to that.
+    * shuffle: frames leave in `shuffle_order` (tf.data's shuffle buffer, un-batched frames, :104-105) drawn from
+      `epoch_rng(seed, epoch)`, epoch = the number of `__iter__` calls before this one; with `shuffle=True` the file list
+      is permuted first with the same generator.  `shuffle=False` is a buffer of one.
+    * batches are gathered (`acimg_batch_gather`) into one of `ring` output sets: a yielded batch stays valid until the
+      iterator has advanced `ring` more times.  The consumer's current stream waits for the gather's event on the GPU;
+      nothing synchronises the host.  One pass at a time: starting a new one ends the previous iterator.
+    * shard = (rank, world): files i % world == rank of the (permuted) list.
+    `times` accumulates the host seconds of the stages (inflate, index, decode in the workers; upload, wait on the
+    consuming thread)."""
+
+    MAX_WORKERS = 16
+    FIRST_PAGES = 16
+
+    def __init__(self, files, batch_size, shuffle=False, buffer_size=None, seed=0, workers=4, prefetch=2, ring=4,
+                 shard=None, num_actions=10, num_locations=61, device="cuda:0", compression_verify=True,
+                 frames_per_record=12):
+        from . import ops
+        from .flags import FLAGS
+        from .frontend import FrontEnd
+        if isinstance(files, str):
+            with open(files) as f:
+                files = [ln.strip() for ln in f if ln.strip()]
+        self.files = list(files)
+        self.batch_size = int(batch_size)
+        self.shuffle = bool(shuffle)
+        self.buffer_size = (int(FLAGS.buffer_size if buffer_size is None else buffer_size)) if self.shuffle else 1
+        self.seed, self.shard = int(seed), shard
+        self.workers = max(1, min(int(workers), self.MAX_WORKERS))
+        self.prefetch, self.ring = max(0, int(prefetch)), int(ring)
+        if self.batch_size < 1 or self.buffer_size < 1 or self.ring < 1:
+            raise ValueError("batch_size, buffer_size and ring must be at least 1")
+        epoch_files(self.files, False, shard, None)      # validates `shard`
+        self.num_actions, self.num_locations = int(num_actions), int(num_locations)
+        self.frames = int(frames_per_record)
+        self.verify = bool(compression_verify)
+        self.device = torch.device(device)
+        self.fe = FrontEnd(self.device)
+        self.plan = ops.Plan(self.device, eager=True)
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.data = self
+        self.times = dict(inflate=0.0, index=0.0, decode=0.0, upload=0.0, wait=0.0)
+        # decode window: enough records in the workers' hands to cover a batch while the consumer is away
+        self._window = max(self.workers + self.prefetch, -(-self.batch_size // self.frames) + self.workers)
+        self._num_samples = None
+        self._epoch = 0
+        self._pass = 0            # the pass whose iterator may touch the pool
+        self._exec = None
+        self._dims = None
+        self._pool, self._pool_pages = None, 0
+        self._outs = None
+
+    # ---- :117, :973-976 ---------------------------------------------------------------------------------------------
+    @property
+    def num_samples(self):
+        """frames this loader yields per pass (its shard of the files), counted once from the decoded dimensions"""
+        if self._num_samples is None:
+            total = 0
+            files = epoch_files(self.files, False, self.shard, None)
+            for buf, offs, lens, _, _ in self._executor().map(lambda p: _inflate_file(p, False), files):
+                total += sum(int(_record_dims(buf, off, ln).video_steps) for off, ln in zip(offs, lens))
+            self._num_samples = total
+        return self._num_samples
+
+    @property
+    def total_batches(self):
+        return -(-self.num_samples // self.batch_size)
+
+    def _executor(self):
+        if self._exec is None:
+            self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="acimg-loader")
+        return self._exec
+
+    def close(self):
+        """end the current pass and stop the worker threads"""
+        self._pass += 1
+        if self._exec is not None:
+            self._exec.shutdown(wait=True)
+            self._exec = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- device buffers -----------------------------------------------------------------------------------------------
+    def _setup(self, dims):
+        """pool, output ring, staging and slot buffers for records of these dimensions (known from the first record)"""
+        ah, aw, ad, vh, vw, vd = dims
+        if vd != 3:
+            raise ValueError("video depth %d: the gather reverses three channels" % vd)
+        self._dims = dims
+        self.pixels, self.elems = vh * vw, ah * aw * ad
+        self.vstride = -(-self.pixels * 3 // 16) * 16
+        dev, bs = self.device, self.batch_size
+        self._slot_rows = 8                      # slot lists in flight between the host and the gathers that read them
+        with torch.cuda.stream(self.stream):     # every device buffer of the loader belongs to its stream
+            self._outs = [(torch.empty(bs, ah, aw, ad, device=dev), torch.empty(bs, 12, device=dev),
+                           torch.empty(bs, vh, vw, 3, device=dev), torch.empty(bs, self.num_actions, device=dev),
+                           torch.empty(bs, self.num_locations, device=dev), torch.empty(bs, 12, device=dev))
+                          for _ in range(self.ring)]
+            self._slots_dev = torch.empty(self._slot_rows, bs, dtype=torch.int32, device=dev)
+        self._staging = collections.deque(_Staging(self.frames, self.pixels * 3, self.elems)
+                                          for _ in range(self._window + 2))
+        self._slots_host = torch.empty(self._slot_rows, bs, dtype=torch.int32).pin_memory()
+        self._slot_events = [None] * self._slot_rows
+        self._slot_next = 0
+        self._pool, self._pool_pages = None, 0
+
+    def _alloc_pool(self, pages):
+        """(re)allocate the pool at `pages` pages on the loader's stream, keeping the pages it holds"""
+        n, dev = pages * self.frames, self.device
+        with torch.cuda.stream(self.stream):
+            new = dict(video=torch.empty(n, self.vstride, dtype=torch.uint8, device=dev),
+                       acoustic=torch.empty(n, self.elems, device=dev),
+                       audio=torch.empty(n, 1024, dtype=torch.int32, device=dev), low=torch.empty(n, 1024, device=dev),
+                       mfcc=torch.empty(n, 12, device=dev), mfcc_low=torch.empty(n, 12, device=dev),
+                       labels=torch.empty(n, 2, dtype=torch.int32, device=dev))
+            if self._pool is not None:
+                old = self._pool_pages * self.frames
+                for k, t in new.items():
+                    t[:old].copy_(self._pool[k])
+            self._pool, self._pool_pages = new, pages
+
+    # ---- one pass -------------------------------------------------------------------------------------------------------
+    def _records(self, files, alive):
+        """decoded records in file order: (staging set) per record; files are inflated `workers` ahead, records decoded
+        `_window` ahead, each into a staging set taken - in record order - once its last upload has completed"""
+        ex = self._executor()
+        file_q, rec_q = collections.deque(), collections.deque()
+        files = iter(files)
+        state = dict(cur=None, files_done=False)
+
+        def more_files():
+            while not state["files_done"] and len(file_q) < self.workers:
+                p = next(files, None)
+                if p is None:
+                    state["files_done"] = True
+                else:
+                    file_q.append(ex.submit(_inflate_file, p, self.verify))
+
+        def more_records(block=True):
+            while len(rec_q) < self._window:
+                if state["cur"] is None:
+                    more_files()
+                    if not file_q or not (block or file_q[0].done()):
+                        return
+                    t0 = time.perf_counter()
+                    buf, offs, lens, t_inf, t_idx = file_q.popleft().result()
+                    self.times["wait"] += time.perf_counter() - t0
+                    self.times["inflate"] += t_inf
+                    self.times["index"] += t_idx
+                    more_files()
+                    state["cur"] = (buf, collections.deque(zip(offs, lens)))
+                buf, todo = state["cur"]
+                if not todo:
+                    state["cur"] = None
+                    continue
+                off, ln = todo.popleft()
+                if self._dims is None:           # the first record of the first pass sizes every buffer
+                    d = _record_dims(buf, off, ln)
+                    self._setup((int(d.audio_height), int(d.audio_width), int(d.audio_depth), int(d.video_height),
+                                 int(d.video_width), int(d.video_depth)))
+                st = (self._staging.popleft() if self._staging
+                      else _Staging(self.frames, self.pixels * 3, self.elems))
+                if st.event is not None:
+                    st.event.synchronize()
+                    st.event = None
+                rec_q.append((st, ex.submit(_decode_record, buf, off, ln, st, self._dims)))
+
+        self._more_records = more_records
+        self._rec_q = rec_q
+        try:
+            while alive():
+                more_records(block=not rec_q)
+                if not rec_q:
+                    return
+                st, fut = rec_q.popleft()
+                t0 = time.perf_counter()
+                self.times["decode"] += fut.result()
+                self.times["wait"] += time.perf_counter() - t0
+                yield st
+        finally:
+            for fut in file_q:
+                fut.cancel()
+            for st, fut in rec_q:
+                fut.cancel()
+            concurrent.futures.wait([f for f in file_q] + [f for _, f in rec_q])
+            for st, _ in rec_q:
+                self._staging.append(st)
+
+    def _ready(self):
+        self._more_records(block=False)
+        return bool(self._rec_q) and self._rec_q[0][1].done()
+
+    def _upload(self, page, st):
+        t0 = time.perf_counter()
+        n, lo = st.n, page * self.frames
+        pool = self._pool
+        with torch.cuda.stream(self.stream):
+            pool["video"][lo:lo + n, :self.pixels * 3].copy_(st.video[:n], non_blocking=True)
+            pool["acoustic"][lo:lo + n].copy_(st.acoustic[:n], non_blocking=True)
+            pool["audio"][lo:lo + n].copy_(st.audio[:n], non_blocking=True)
+            pool["labels"][lo:lo + n].copy_(st.labels[:n], non_blocking=True)
+            st.event = torch.cuda.Event()
+            st.event.record(self.stream)
+            frames = pool["audio"][lo:lo + n]
+            self.fe._build_spectrograms_function(frames, normalize=True, out=pool["mfcc"][lo:lo + n])
+            low = self.fe.butter_lowpass_filter(frames, out=pool["low"][lo:lo + n])
+            self.fe._build_spectrograms_function(low, normalize=True, out=pool["mfcc_low"][lo:lo + n])
+        self._staging.append(st)
+        self.times["upload"] += time.perf_counter() - t0
+        return n
+
+    def _gather(self, slots, offset, out, wait):
+        """enqueue the gather of `slots` into rows offset.. of the output set `out`; the first gather into a set waits
+        (on the GPU) for what its consumer had enqueued when the iterator was advanced"""
+        from . import ops
+        n, row = len(slots), self._slot_next
+        self._slot_next = (row + 1) % self._slot_rows
+        if self._slot_events[row] is not None:
+            self._slot_events[row].synchronize()
+        self._slots_host[row, :n] = torch.tensor(slots, dtype=torch.int32)
+        pool = self._pool
+        with torch.cuda.stream(self.stream):
+            self._slots_dev[row, :n].copy_(self._slots_host[row, :n], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+            self._slot_events[row] = ev
+            if wait is not None:
+                self.stream.wait_event(wait)
+            ac, mf, vid, act, loc, mfl = (t[offset:offset + n] for t in out)
+            ops.batch_gather(self.plan, pool["video"], self.vstride, pool["acoustic"], pool["mfcc"], pool["mfcc_low"],
+                             pool["labels"], self._slots_dev[row], n, self.pixels, self.elems, vid, ac, mf, mfl, act,
+                             self.num_actions, loc, self.num_locations)
+
+    def __iter__(self):
+        epoch, self._epoch = self._epoch, self._epoch + 1
+        self._pass += 1
+        me = self._pass
+        rng = epoch_rng(self.seed, epoch)
+        files = epoch_files(self.files, self.shuffle, self.shard, rng)
+        return self._iterate(files, rng, me)
+
+    def _iterate(self, files, rng, me):
+        def alive():
+            if self._pass != me:
+                raise RuntimeError("DeviceDataLoader: this iterator was ended by a later pass over the same loader")
+            return True
+
+        records = self._records(files, alive)
+        first = next(records, None)          # sizes the buffers on the first pass
+        if first is None:
+            return
+        limit = pool_pages(self.buffer_size, self.prefetch)
+        # (a pool grown by an earlier pass is kept)
+        pages = FramePages(min(limit, max(self.FIRST_PAGES, self._pool_pages)), limit, self.frames)
+        if self._pool_pages < pages.size:
+            self._alloc_pool(pages.size)
+
+        def chain():
+            yield first
+            for st in records:
+                yield st
+
+        state = dict(k=0, wait=None)
+
+        def gather(slots, offset):
+            self._gather(slots, offset, self._outs[state["k"] % self.ring], state["wait"])
+            state["wait"] = None
+
+        feeder = BatchFeeder(chain(), pages, self.batch_size, self.buffer_size, self.prefetch, rng, self._upload, gather,
+                             grow=self._alloc_pool, ready=self._ready)
+        try:
+            for n in feeder:
+                done = torch.cuda.Event()
+                done.record(self.stream)
+                cur = torch.cuda.current_stream(self.device)
+                cur.wait_event(done)
+                yield tuple(t[:n] for t in self._outs[state["k"] % self.ring])
+                alive()
+                # the consumer may have enqueued reads of every batch yielded so far: the next gather into the set that
+                # is `ring` batches old starts behind them
+                cur = torch.cuda.current_stream(self.device)
+                consumed = torch.cuda.Event()
+                consumed.record(cur)
+                state["k"] += 1
+                state["wait"] = consumed
+        finally:
+            records.close()
 
 
 def box_mfcc(audio):

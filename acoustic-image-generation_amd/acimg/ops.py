@@ -883,6 +883,16 @@ def knn_vote(plan, idx, ldidx, Q, K, gallery_labels, query_labels, num_classes, 
              int(num_classes), pred, first_hit)
 
 
+def batch_gather(plan, pool_video, video_stride, pool_acoustic, pool_mfcc, pool_mfcc_low, pool_labels, slots, N, pixels,
+                 elems, video, acoustic, mfcc, mfcc_low, action, num_actions, location, num_locations):
+    """frames slots[0..N) (int32 on the device, every one inside the pool) of a pool of decoded records -> one batch:
+    video uint8 BGR -> float32 RGB / 255, acoustic image min-max normalised, MFCC rows copied, labels one-hot"""
+    plan.ws.require(_L().acimg_batch_gather_workspace(int(N), int(elems)))
+    plan.add("batch_gather", _L().acimg_batch_gather, pool_video, int(video_stride), pool_acoustic, pool_mfcc, pool_mfcc_low,
+             pool_labels, slots, int(N), int(pixels), int(elems), int(num_actions), int(num_locations), video, acoustic, mfcc,
+             mfcc_low, action, location, _WsPtr(plan.ws), _WsBytes(plan.ws))
+
+
 def adam_lr_t(lr, step, beta1=0.9, beta2=0.999):
     """TF-1 Adam effective step size for 1-based step t."""
     return lr * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step)

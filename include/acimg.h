@@ -685,6 +685,37 @@ size_t acimg_knn_topk_workspace(int Q, int G, int D, int K);
 int acimg_knn_vote(const int32_t* idx, int ldidx, int Q, int K, const int32_t* gallery_labels,
                    const int32_t* query_labels, int num_classes, int32_t* pred, int32_t* first_hit, void* stream);
 
+/* Batch assembly out of a device-resident pool of decoded frames (acimg/data.py: DeviceDataLoader): the per-frame maps
+ * of dataloader/outdoor_data_mfcc.py:634-703 applied while the N frames slots[0..N) of a batch are gathered.  (Added
+ * without raising ACIMG_VERSION: nothing existing changed, and the number is pinned by the host tests.)
+ * The pool, per slot s < nslots (the CALLER's number; it is not passed):
+ *   pool_video    + s * video_stride  uint8 [pixels][3], stored (BGR) order; video_stride in BYTES, a multiple of 16 and
+ *                                     >= 3 * pixels (else ACIMG_EINVAL); pool_video 16-byte aligned
+ *   pool_acoustic + s * elems         float32 [elems], as acimg_sequence_example_decode leaves it (already flipped)
+ *   pool_mfcc, pool_mfcc_low + s * 12 float32 [12]: the MFCC rows of the raw and of the low-passed audio frame
+ *   pool_labels   + s * 2             int32 {class, location}
+ * slots: int32 [N] ON THE DEVICE; repeats and any order are allowed.  PRECONDITION: 0 <= slots[n] < nslots - the host
+ * cannot see the values, so nothing checks them, and an index outside the pool reads outside the pool.
+ * Outputs, dense, frame n < N:
+ *   video    [N][pixels][3]  video[n][p][c] = (float)pool[slots[n]][p][2 - c] * (float)(1.0 / 255.0): one fp32 multiply,
+ *            bit-equal to NumPy's `v[..., ::-1].astype(np.float32) * np.float32(1.0 / 255.0)`
+ *   acoustic [N][elems]      (a - min(a)) / max(a - min(a)) over the whole frame: a correctly rounded subtraction and
+ *            DIVISION (no reciprocal), bit-equal to NumPy on finite input; a constant frame gives NaN (0 / 0) as NumPy
+ *            does; non-finite input: unspecified.  elems <= 32768 (the frame is held in LDS), else ACIMG_EINVAL
+ *   mfcc, mfcc_low [N][12]   the rows copied
+ *   action [N][num_actions], location [N][num_locations]  one-hot float32; a label outside [0, width) leaves a zero row
+ * ws: acimg_batch_gather_workspace(N, elems) bytes, 16-byte aligned (short = ACIMG_EWORKSPACE): receives [N][4] floats
+ * {min(a), max(a - min(a)), 0, 0}, the two statistics of each frame's normalisation.  N <= 0, N > 65535, a null pointer,
+ * a non-positive size: ACIMG_EINVAL; every refusal precedes the first launch.
+ * TWO launches on `stream` (the video stream: 16-pixel chunks as 16-byte loads and float4 stores, a scalar path for the
+ * pixels past the last chunk and for pixels % 4 != 0 or an unaligned `video`; then one workgroup per frame for everything
+ * else), no atomics, reductions in a fixed order: bit-identical from run to run. */
+int acimg_batch_gather(const uint8_t* pool_video, size_t video_stride, const float* pool_acoustic, const float* pool_mfcc,
+                       const float* pool_mfcc_low, const int32_t* pool_labels, const int32_t* slots, int N, int pixels,
+                       int elems, int num_actions, int num_locations, float* video, float* acoustic, float* mfcc,
+                       float* mfcc_low, float* action, float* location, void* ws, size_t ws_bytes, void* stream);
+size_t acimg_batch_gather_workspace(int N, int elems);
+
 /* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.

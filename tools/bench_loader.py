@@ -1,0 +1,163 @@
+"""Rate of the two record loaders on one GPU, in images/s: `TFRecordDataLoader` (one host thread, float32 video through
+host memory) against `DeviceDataLoader` (worker threads, frames resident on the device, `acimg_batch_gather`).
+
+Writes --files synthetic GZIP TFRecord files of --records 12-frame SequenceExamples each to a temporary directory, once
+per --content: `random` video bytes (the worst case for deflate) and a `smooth` image (the best); real frames lie
+between.  Then --repeats passes per loader, alternating, over the same files: one epoch of the loader alone (the batches
+are consumed by nothing; the device is synchronised at the end), or with --train one epoch of `Trainer.train()` (a
+one-file validation pass included, the same for both).  One JSON line per pass, a summary line per content with the
+spread of each loader and whether the device loader's slowest pass beats the host loader's fastest by more than the two
+spreads together, and the device loader's host seconds per stage.
+
+    python tools/bench_loader.py --files 16 --records 4 --batch 32 --repeats 3 [--train] [--shuffle]
+"""
+import argparse
+import concurrent.futures
+import json
+import os
+import sys
+import tempfile
+import time
+from collections import OrderedDict
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "acoustic-image-generation_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def video_frames(content, rng):
+    if content == "random":
+        return rng.randint(0, 256, size=(12, 224, 298, 3)).astype(np.uint8)
+    y, x = np.mgrid[0:224, 0:298]
+    out = np.empty((12, 224, 298, 3), np.uint8)
+    for f in range(12):
+        for c in range(3):
+            ph = rng.rand() * 6.28
+            out[f, :, :, c] = (127.5 + 100 * np.sin(x / (40.0 + 9 * c) + ph) * np.cos(y / (55.0 + 7 * f) + ph)).astype(np.uint8)
+    return out
+
+
+def write_file(path, content, records, seed):
+    from acimg import tfio
+    rng = np.random.RandomState(seed)
+    recs = []
+    for r in range(records):
+        ai = rng.rand(12, 36, 48, 12).astype(np.float32) * 5 - 1
+        sa = (rng.randn(12, 1024) * 800).astype(np.int32)
+        vi = video_frames(content, rng)
+        ctx = OrderedDict([("classes", np.array([(seed + r) % 10])), ("location", np.array([seed % 61])),
+                           ("audio_image/height", np.array([36])), ("audio_image/width", np.array([48])),
+                           ("audio_image/depth", np.array([12])), ("audio_data/mics", np.array([1])),
+                           ("audio_data/samples", np.array([1024])), ("video/height", np.array([224])),
+                           ("video/width", np.array([298])), ("video/depth", np.array([3]))])
+        lists = OrderedDict([("audio/image", [a.tobytes() for a in ai]), ("audio/data", [s.tobytes() for s in sa]),
+                             ("video/image", [v.tobytes() for v in vi])])
+        recs.append(tfio.build_sequence_example(ctx, lists))
+    tfio.write_tfrecord(path, recs, compression="GZIP")
+    return path
+
+
+def make_loader(kind, files, a, dev, shuffle=False):
+    from acimg.data import DeviceDataLoader, TFRecordDataLoader
+    if kind == "host":
+        return TFRecordDataLoader(files, a.batch, device=dev)
+    return DeviceDataLoader(files, a.batch, shuffle=shuffle, seed=1, workers=a.workers, prefetch=a.prefetch, device=dev)
+
+
+def loader_pass(loader, dev):
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    n = 0
+    for b in loader.data:
+        n += int(b[0].shape[0])
+    torch.cuda.synchronize(dev)
+    return n, time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=16)
+    ap.add_argument("--records", type=int, default=4, help="12-frame records per file")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--content", nargs="+", default=["random", "smooth"], choices=["random", "smooth"])
+    ap.add_argument("--loaders", nargs="+", default=["host", "device"], choices=["host", "device"])
+    ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--prefetch", type=int, default=2)
+    ap.add_argument("--shuffle", action="store_true", help="also time the device loader with shuffle=True")
+    ap.add_argument("--train", action="store_true", help="time an epoch of Trainer.train() through each loader")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    tr = None
+    if a.train:
+        from acimg.flags import FLAGS
+        from acimg.session import Session
+        from acimg.trainer import Trainer
+        from acimg.unet_acresnet import UNetAc
+        from acimg.vision import ResNet50Model
+        FLAGS.model, FLAGS.ae, FLAGS.checkpoint_dir = "UNet", 0, None
+        FLAGS.restore_checkpoint = FLAGS.init_checkpoint = None
+        FLAGS.acoustic_init_checkpoint = FLAGS.visual_init_checkpoint = None
+        tr = Trainer(UNetAc(input_shape=[36, 48, 12], embedding=False, num_skip=1),
+                     ResNet50Model(input_shape=[224, 298, 3], num_classes=None), display_freq=10 ** 9, num_epochs=1,
+                     session=Session(dev))
+        tr.log = lambda line: None
+        tr._build_functions(batch_size=a.batch)
+    kinds = list(a.loaders) + (["device_shuffle"] if a.shuffle and "device" in a.loaders else [])
+    with tempfile.TemporaryDirectory(prefix="acimg_loader_") as tmp:
+        for content in a.content:
+            t0 = time.perf_counter()
+            with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:      # zlib drops the GIL
+                files = list(ex.map(lambda i: write_file(os.path.join(tmp, "%s_%03d.tfrecord" % (content, i)), content,
+                                                         a.records, i), range(a.files)))
+            size = sum(os.path.getsize(p) for p in files)
+            frames = a.files * a.records * 12
+            print(json.dumps(dict(content=content, files=a.files, frames=frames, gzip_mb=round(size / 1e6, 1),
+                                  written_s=round(time.perf_counter() - t0, 1))), flush=True)
+            loaders = {k: make_loader("host" if k == "host" else "device", files, a, dev, shuffle=k == "device_shuffle")
+                       for k in kinds}
+            for k in kinds:                                                       # untimed: first-use costs of either
+                warm = make_loader("host" if k == "host" else "device", files[:1], a, dev)
+                loader_pass(warm, dev)
+                getattr(warm, "close", lambda: None)()
+            if tr is not None:
+                tr.train(make_loader("host", files[:1], a, dev), make_loader("host", files[:1], a, dev))
+            rates = {k: [] for k in kinds}
+            for rep in range(a.repeats):
+                for k in kinds:
+                    if tr is None:
+                        n, dt = loader_pass(loaders[k], dev)
+                    else:
+                        valid = make_loader("host" if k == "host" else "device", files[:1], a, dev)
+                        torch.cuda.synchronize(dev)
+                        t0 = time.perf_counter()
+                        tr.train(loaders[k], valid)
+                        torch.cuda.synchronize(dev)
+                        n, dt = frames, time.perf_counter() - t0
+                        getattr(valid, "close", lambda: None)()
+                    rates[k].append(n / dt)
+                    print(json.dumps(dict(content=content, loader=k, mode="train" if tr else "loader", repeat=rep,
+                                          frames=n, seconds=round(dt, 4), images_per_s=round(n / dt, 1))), flush=True)
+            summary = dict(content=content, mode="train" if tr else "loader", batch=a.batch, workers=a.workers,
+                           prefetch=a.prefetch)
+            for k in kinds:
+                summary[k] = dict(min=round(min(rates[k]), 1), max=round(max(rates[k]), 1))
+            if "host" in rates and "device" in rates:
+                spread = (max(rates["host"]) - min(rates["host"])) + (max(rates["device"]) - min(rates["device"]))
+                summary["device_above_host_by_more_than_the_spreads"] = bool(min(rates["device"]) - max(rates["host"]) > spread)
+            print(json.dumps(summary), flush=True)
+            for k in kinds:
+                if k != "host":
+                    t = loaders[k].times
+                    print(json.dumps(dict(content=content, loader=k, host_seconds_over_all_passes={
+                        s: round(v, 3) for s, v in t.items()})), flush=True)
+                    loaders[k].close()
+            for p in files:
+                os.remove(p)
+
+
+if __name__ == "__main__":
+    main()
