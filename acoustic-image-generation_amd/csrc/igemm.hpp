@@ -1,4 +1,4 @@
-// Internal descriptors of the fp32 implicit-GEMM kernels (igemm.hip).
+// Internal descriptors of the implicit-GEMM and weight-gradient kernels (host side: conv_host.hpp and the conv_*.hip sources).
 #pragma once
 #include "common.hpp"
 

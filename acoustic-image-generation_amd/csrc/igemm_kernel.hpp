@@ -1,4 +1,4 @@
-// fp32 implicit-GEMM kernel, version 2 (gfx950).  See igemm.hip for the op mapping.
+// fp32 implicit-GEMM kernel, version 2 (gfx950).  See conv_f32.hip for the op mapping.
 //
 //   * global loads are branch-free `buffer_load_dwordx4` through a resource descriptor: padding taps,
 //     rows past M and columns past N get an out-of-range offset and the hardware returns zeros;

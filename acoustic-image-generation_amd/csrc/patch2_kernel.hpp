@@ -208,6 +208,5 @@ __global__ __launch_bounds__(1024) void patch2_wgrad_32x8_kernel(const Patch2Wgr
         slab[row * p.ldo + col] = t;
     }
 }
-static constexpr int PATCH2_WGRAD_WGS = 256;
 
 }  // namespace acimg

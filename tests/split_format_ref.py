@@ -339,7 +339,7 @@ def bwd_fmt(case):
 def wgrad_counts(case, slabs):
     """(ksteps, ranges) of a weight gradient's accumulation term.  A K step is 32 pixels and a range is one pixel slab; `slabs`
     is the most the workspace query allows (at most 2048), and with only an upper limit known the longest chain is all the
-    K steps in one slab: ksteps = pixels / 32.  The halo kernel's counts are fixed by its launch (csrc/igemm.hip,
+    K steps in one slab: ksteps = pixels / 32.  The halo kernel's counts are fixed by its launch (csrc/conv_wgrad.hip,
     acimg_conv2d_wgrad_split3): 256 workgroups, one slab each, walk the tiles of 4 x 32 pixels (4 K steps) in turn and add
     their 4 row groups through LDS at the end; with the caps (2086 + 256) that path sat at 0.0008 of its bound."""
     N, H, W = BWD_CASES[case][:3]
@@ -350,7 +350,7 @@ def wgrad_counts(case, slabs):
 
 
 # ---- the same formats behind the fp32 entry points ------------------------------------------------------------------------
-# From 65536 pixels on acimg_conv2d_fwd / _dgrad / _wgrad and acimg_deconv_* leave the exact-f32 implicit GEMM (csrc/igemm.hip):
+# From 65536 pixels on acimg_conv2d_fwd / _dgrad / _wgrad and acimg_deconv_* leave the exact-f32 implicit GEMM (csrc/conv_f32.hip, conv_wgrad.hip):
 #   few     3x3 / 1 / SAME, 4 - 16 channels convolved: conv_few16_kernel (f16x3 forward, bf16x3 data gradient); the data
 #           gradient of 8 -> 32 is the 16-row instance of the halo kernel; weight gradient wgrad_halo16_kernel<16, 3> (bf16x3)
 #   few/2   3x3 / 2 / SAME data gradient: conv_few16_kernel over the zero-inserted view of gy

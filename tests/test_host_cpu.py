@@ -505,6 +505,62 @@ def test_no_wide_buffer_store_with_register_soffset(tmp_path):
     assert not bad, "16-byte buffer stores with a REGISTER soffset (gfx950 store-data hazard):\n" + "\n".join(bad[:10])
 
 
+def test_every_kernel_is_compiled_into_one_object(tmp_path):
+    """The convolutions' host code is several translation units (csrc/conv_*.hip) over shared kernel headers: a template kernel
+    instantiated by two of them links, but exists twice on the device (two targets for one hipFuncSetAttribute call, twice the
+    code).  The kernel-descriptor symbols (`<kernel>.kd`) of every gfx950 code object of libacimg.so are listed from the
+    symbol tables: none may occur in two objects, and none of the convolutions' 133 may have gone missing."""
+    import shutil
+
+    from acimg import _lib
+
+    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    if not os.path.exists(objdump):
+        pytest.skip("no llvm-objdump")
+    so = tmp_path / "libacimg.so"
+    shutil.copy(_lib.LIB_PATH, so)
+    subprocess.check_call([objdump, "--offloading", str(so)], stdout=subprocess.DEVNULL, cwd=str(tmp_path))
+    objs = sorted(f for f in os.listdir(tmp_path) if "amdgcn" in f and "gfx950" in f)
+    assert len(objs) >= 5, objs                   # one code object per translation unit that has kernels
+    owner, twice, conv = {}, [], 0
+    for f in objs:
+        syms = subprocess.check_output([objdump, "-t", str(tmp_path / f)]).decode()
+        kernels = set(re.findall(r"(\S+)\.kd\s*$", syms, re.M))
+        assert kernels, f
+        for k in sorted(kernels):
+            if k in owner:
+                twice.append("%s: %s and %s" % (k, owner[k], f))
+            owner[k] = f
+        if any("igemm_" in k or "wgrad_" in k for k in kernels):       # a code object of the convolutions
+            conv += len(kernels)
+    assert not twice, "kernels compiled into two objects:\n" + "\n".join(twice[:10])
+    assert conv >= 133, conv
+    assert len(owner) > conv                      # and the other sources' kernels were seen too
+
+
+def test_one_tuning_record_for_every_conv_source(lib):
+    """acimg_configure writes ONE record that all the convolutions' translation units read: wgrad_halo = 0 changes, together, an
+    answer of the exact-f32 file (acimg_conv2d_stats_rows), of the on-the-fly split file (acimg_conv2d_fwd_split3_stats_rows)
+    and of the weight-gradient file (acimg_conv2d_affine_input_ok), and the defaults bring all three back."""
+    from acimg import _lib, ops
+
+    d8 = ops.conv_desc(32, 224, 298, 8, 8, 3, 3, 1, "SAME")
+    d32 = ops.conv_desc(32, 112, 149, 32, 32, 3, 3, 1, "SAME")
+
+    def answers():
+        return (ops.conv2d_stats_rows(d8), ops.conv2d_fwd_split3_stats_rows(d32), ops.conv2d_affine_input_ok(d8, 0),
+                ops.conv2d_affine_input_ok(d32, 1))
+
+    assert answers() == (512, 256, True, True)    # FEW16_WGS, CONV_HALO16_WGS: one statistics row per workgroup
+    try:
+        _lib.configure(wgrad_halo=0)
+        # the direct kernel's 256-pixel blocks; the on-the-fly kernel's 128-row tiles; no halo weight gradient for the affine
+        assert answers() == (32 * 224 * 298 // 256, 32 * 112 * 149 // 128, False, False)
+    finally:
+        _lib.configure()
+    assert answers() == (512, 256, True, True)
+
+
 def test_library_reads_no_environment_and_configure_validates(lib):
     """include/acimg.h: the only process-wide state is the tuning record of acimg_configure; the library never calls
     getenv (the Python host maps ACIMG_* variables onto acimg_configure once, at load time)"""

@@ -660,7 +660,7 @@ def test_unet_vae_batch_16_selects_the_benched_kernels():
     """bench.py times UNet at batch 32; tests/test_unet_vae_gpu.py::test_unet_vae_train_step_at_the_benched_selection checks
     that selection against the fp64 oracle at batch 16, where the host plan is the same: the call sequence, the layers whose
     batch norm is applied while the consumer stages its tiles, the split / bf16 layers and the layers that take an input
-    affine.  The size rules behind them (acimg/unet_vae.py `_use_split`, csrc/igemm.hip's 65536-pixel forms) decide this."""
+    affine.  The size rules behind them (acimg/unet_vae.py `_use_split`, the 65536-pixel forms of csrc/conv_f32.hip, conv_split.hip and conv_wgrad.hip) decide this."""
     from acimg import ops
     from acimg.session import Session
     from acimg.trainer_vae import TrainerVAE

@@ -75,7 +75,7 @@ FORMS = (("one-tile whole", dict(trunk_persistent=0, tail_split=0, trunk_ring=0)
 
 
 def _halo_fits(W):
-    return ((W + 16) >> 4) + 8 + (W >> 4) + 1 <= 18      # csrc/igemm.hip halo_applies: an 18-brick patch
+    return ((W + 16) >> 4) + 8 + (W >> 4) + 1 <= 18      # csrc/conv_trunk.hip halo_applies: an 18-brick patch
 
 
 @pytest.mark.parametrize("case", [(7, 28, 38, 128, 512, 1),      # rows % 16 = 8 (the trunk's own residue, N odd)
