@@ -133,6 +133,8 @@ PROTOTYPES = {
     "acimg_spatial_sum": (_I, [_P, _I, _P, _I, _I, _I, _P]),
     "acimg_spatial_sum_relu_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "acimg_clip_softmax_ce": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "acimg_clip_eval_state_bytes": (_SZ, [_I]),
+    "acimg_clip_eval": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "acimg_bn_bwd_workspace": (_SZ, [_L, _I]),
     "acimg_bn_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _L, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     "acimg_loss_scratch_bytes": (_SZ, []),

@@ -67,10 +67,13 @@ class TFRecordDataLoader(object):
     the MFCC path (FLAGS.mfcc): one record = one second = 12 frames; frames are unbatched and re-batched to
     `batch_size` (:99-104).  `files`: a list of TFRecord paths, or the path of a text file listing them (:214-236).
     device: where the audio front end runs (a GPU: there is no CPU fallback); tensors are returned on the host, like the
-    reference's session.run results, and `Trainer._feed` copies them up."""
+    reference's session.run results, and `Trainer._feed` copies them up.
+    embedding=0 is the path without `unbatch` (:102-107): `batch_size` counts records (clips); the frame tensors come out
+    as [B*12, ...] with each clip's frames consecutive and in record order, the two label tensors as ONE row per clip
+    ([B, num_actions], [B, num_locations]); `num_samples` / `total_batches` count clips."""
 
     def __init__(self, files, batch_size, num_actions=10, num_locations=61, device="cuda:0", frames_per_record=12,
-                 compression_verify=True):
+                 compression_verify=True, embedding=1):
         from .frontend import FrontEnd
         if isinstance(files, str):
             with open(files) as f:
@@ -80,6 +83,7 @@ class TFRecordDataLoader(object):
         self.num_actions, self.num_locations = int(num_actions), int(num_locations)
         self.frames = int(frames_per_record)
         self.verify = bool(compression_verify)
+        self.embedding = _embedding(embedding)
         self.device = torch.device(device)
         self.fe = FrontEnd(self.device)
         self.data = self
@@ -88,10 +92,12 @@ class TFRecordDataLoader(object):
     # ---- :117, :973-976 ---------------------------------------------------------------------------------------------
     @property
     def num_samples(self):
-        """frames in the data set (every record is `frames_per_record` frames): counted once from the record index"""
+        """frames in the data set (every record is `frames_per_record` frames), clips with embedding=0: counted once
+        from the record index"""
         if self._num_samples is None:
             from . import tfio
-            self._num_samples = sum(len(tfio.read_tfrecord_native(p, verify=False)) for p in self.files) * self.frames
+            records = sum(len(tfio.read_tfrecord_native(p, verify=False)) for p in self.files)
+            self._num_samples = records * (self.frames if self.embedding else 1)
         return self._num_samples
 
     @property
@@ -125,8 +131,33 @@ class TFRecordDataLoader(object):
         return (torch.from_numpy(a), mfcc.cpu(), torch.from_numpy(np.ascontiguousarray(v)), torch.from_numpy(act),
                 torch.from_numpy(loc), mfcc_low.cpu())
 
+    def _clip_batch(self, pend):
+        """whole records -> one clip batch: frames concatenated, the two label tensors cut to one row per record"""
+        for p_ in pend:
+            if p_[0].shape[0] != self.frames:
+                raise ValueError("clip mode wants records of %d frames, got one of %d" % (self.frames, p_[0].shape[0]))
+        return tuple(torch.cat([(p_[k][:1] if k in (3, 4) else p_[k]) for p_ in pend], 0) for k in range(6))
+
+    def _iter_clips(self):
+        from . import tfio
+        pend = []
+        for path in self.files:
+            for rec in tfio.read_tfrecord_native(path, verify=self.verify):
+                if len(rec) == 0:
+                    continue
+                pend.append(self._record(rec))
+                if len(pend) == self.batch_size:
+                    yield self._clip_batch(pend)
+                    pend = []
+        if pend:
+            yield self._clip_batch(pend)
+
     def __iter__(self):
         from . import tfio
+        if not self.embedding:
+            for b in self._iter_clips():
+                yield b
+            return
         pend, have = [], 0
         for path in self.files:
             for rec in tfio.read_tfrecord_native(path, verify=self.verify):
@@ -146,6 +177,13 @@ class TFRecordDataLoader(object):
 
 # ---- the tf.data machinery of dataloader/outdoor_data_mfcc.py:99-105 -------------------------------------------------
 _END = object()
+
+
+def _embedding(embedding):
+    """the reference's `embedding` argument: 1 un-batches records to frames, 0 keeps records whole (clips)"""
+    if embedding not in (0, 1, False, True):
+        raise ValueError("embedding is 1 (frames) or 0 (clips), got %r" % (embedding,))
+    return int(embedding)
 
 
 def epoch_rng(seed, epoch):
@@ -199,7 +237,10 @@ def epoch_files(files, shuffle, shard, rng):
 
 def pool_pages(buffer_size, prefetch):
     """pages that always suffice: at most `buffer_size` un-emitted frames sit in the shuffle buffer and one frame can
-    pin a page; one record is being fed into the buffer; `prefetch` records are uploaded ahead; one page to upload into"""
+    pin a page; one record is being fed into the buffer; `prefetch` records are uploaded ahead; one page to upload into.
+    With whole records as the units (`BatchFeeder(..., units="records")`) `buffer_size` counts records: an un-emitted
+    record pins exactly its own page, so the same `buffer_size + prefetch + 2` holds (the pages emptied by the batch
+    being assembled come back at its gather, which `_admit` forces when it finds no free page)."""
     return int(buffer_size) + int(prefetch) + 2
 
 
@@ -256,9 +297,15 @@ class BatchFeeder(object):
       gather(slots, offset) enqueues the gather of these slots into rows offset.. of the batch being assembled
       grow(pages)  the pool now has `pages` pages
     A batch is gathered in one call unless a page is wanted while the only candidates are pages emptied by THIS batch:
-    then the rows chosen so far are gathered first, which frees them."""
+    then the rows chosen so far are gathered first, which frees them.
+    units="records" (the loaders' embedding=0): the shuffle buffer holds whole records and `batch_size` counts them; a
+    record's slots enter the batch together, in record order."""
 
-    def __init__(self, records, pages, batch_size, buffer_size, prefetch, rng, upload, gather, grow=None, ready=None):
+    def __init__(self, records, pages, batch_size, buffer_size, prefetch, rng, upload, gather, grow=None, ready=None,
+                 units="frames"):
+        if units not in ("frames", "records"):
+            raise ValueError("units is 'frames' or 'records', got %r" % (units,))
+        self.by_record = units == "records"
         self.records, self.pages = iter(records), pages
         self.batch_size, self.buffer_size, self.prefetch, self.rng = int(batch_size), int(buffer_size), int(prefetch), rng
         self.upload, self.gather, self.grow_cb, self.ready = upload, gather, grow, ready or (lambda: True)
@@ -286,8 +333,12 @@ class BatchFeeder(object):
         return True
 
     def _slots(self):
+        """the shuffle buffer's inputs: single slots, or one tuple of slots per record"""
         while self.ahead or (not self.done and self._admit()):
             page, n = self.ahead.popleft()
+            if self.by_record:
+                yield tuple(page * self.pages.frames + i for i in range(n))
+                continue
             for i in range(n):
                 yield page * self.pages.frames + i
 
@@ -304,14 +355,17 @@ class BatchFeeder(object):
 
     def __iter__(self):
         """yields the size of each batch once its gather is enqueued"""
-        for slot in shuffle_stream(self._slots(), self.buffer_size, self.rng):
-            self.batch.append(slot)
-            self.pages.emit(slot)
-            if len(self.batch) == self.batch_size:
+        units = 0
+        for unit in shuffle_stream(self._slots(), self.buffer_size, self.rng):
+            for slot in (unit if self.by_record else (unit,)):
+                self.batch.append(slot)
+                self.pages.emit(slot)
+            units += 1
+            if units == self.batch_size:
                 self._flush()
                 self._top_up()
                 yield len(self.batch)
-                self.batch, self.flushed = [], 0
+                self.batch, self.flushed, units = [], 0, 0
         if self.batch:
             self._flush()
             yield len(self.batch)
@@ -413,6 +467,12 @@ class DeviceDataLoader(object):
       iterator has advanced `ring` more times.  The consumer's current stream waits for the gather's event on the GPU;
       nothing synchronises the host.  One pass at a time: starting a new one ends the previous iterator.
     * shard = (rank, world): files i % world == rank of the (permuted) list.
+    * embedding=0 (the path without `unbatch`, :102-107): `batch_size` counts records (clips) and the shuffle buffer
+      holds whole records - same procedure, seeding and file permutation, records as the units.  A clip batch is only
+      another slot list for the same gather: frame tensors [B*12, ...] with each clip's frames consecutive and in record
+      order; the label tensors are the strided view of the gathered rows that keeps one row per clip ([B, num_actions],
+      [B, num_locations]).  `num_samples` / `total_batches` count clips; every record must hold `frames_per_record`
+      frames.  `pool_pages` states why the page bound is the same with records as the units.
     `times` accumulates the host seconds of the stages (inflate, index, decode in the workers; upload, wait on the
     consuming thread)."""
 
@@ -421,7 +481,7 @@ class DeviceDataLoader(object):
 
     def __init__(self, files, batch_size, shuffle=False, buffer_size=None, seed=0, workers=4, prefetch=2, ring=4,
                  shard=None, num_actions=10, num_locations=61, device="cuda:0", compression_verify=True,
-                 frames_per_record=12):
+                 frames_per_record=12, embedding=1):
         from . import ops
         from .flags import FLAGS
         from .frontend import FrontEnd
@@ -440,6 +500,8 @@ class DeviceDataLoader(object):
         epoch_files(self.files, False, shard, None)      # validates `shard`
         self.num_actions, self.num_locations = int(num_actions), int(num_locations)
         self.frames = int(frames_per_record)
+        self.embedding = _embedding(embedding)
+        self._rows = self.batch_size * (1 if self.embedding else self.frames)      # frame rows of a full batch
         self.verify = bool(compression_verify)
         self.device = torch.device(device)
         self.fe = FrontEnd(self.device)
@@ -448,7 +510,7 @@ class DeviceDataLoader(object):
         self.data = self
         self.times = dict(inflate=0.0, index=0.0, decode=0.0, upload=0.0, wait=0.0)
         # decode window: enough records in the workers' hands to cover a batch while the consumer is away
-        self._window = max(self.workers + self.prefetch, -(-self.batch_size // self.frames) + self.workers)
+        self._window = max(self.workers + self.prefetch, -(-self._rows // self.frames) + self.workers)
         self._num_samples = None
         self._epoch = 0
         self._pass = 0            # the pass whose iterator may touch the pool
@@ -460,11 +522,15 @@ class DeviceDataLoader(object):
     # ---- :117, :973-976 ---------------------------------------------------------------------------------------------
     @property
     def num_samples(self):
-        """frames this loader yields per pass (its shard of the files), counted once from the decoded dimensions"""
+        """frames (embedding=0: clips) this loader yields per pass (its shard of the files), counted once from the
+        decoded dimensions"""
         if self._num_samples is None:
             total = 0
             files = epoch_files(self.files, False, self.shard, None)
             for buf, offs, lens, _, _ in self._executor().map(lambda p: _inflate_file(p, False), files):
+                if not self.embedding:
+                    total += len(offs)
+                    continue
                 total += sum(int(_record_dims(buf, off, ln).video_steps) for off, ln in zip(offs, lens))
             self._num_samples = total
         return self._num_samples
@@ -500,7 +566,7 @@ class DeviceDataLoader(object):
         self._dims = dims
         self.pixels, self.elems = vh * vw, ah * aw * ad
         self.vstride = -(-self.pixels * 3 // 16) * 16
-        dev, bs = self.device, self.batch_size
+        dev, bs = self.device, self._rows
         self._slot_rows = 8                      # slot lists in flight between the host and the gathers that read them
         with torch.cuda.stream(self.stream):     # every device buffer of the loader belongs to its stream
             self._outs = [(torch.empty(bs, ah, aw, ad, device=dev), torch.empty(bs, 12, device=dev),
@@ -604,6 +670,8 @@ class DeviceDataLoader(object):
     def _upload(self, page, st):
         t0 = time.perf_counter()
         n, lo = st.n, page * self.frames
+        if not self.embedding and n != self.frames:
+            raise ValueError("clip mode wants records of %d frames, got one of %d" % (self.frames, n))
         pool = self._pool
         with torch.cuda.stream(self.stream):
             pool["video"][lo:lo + n, :self.pixels * 3].copy_(st.video[:n], non_blocking=True)
@@ -678,14 +746,17 @@ class DeviceDataLoader(object):
             state["wait"] = None
 
         feeder = BatchFeeder(chain(), pages, self.batch_size, self.buffer_size, self.prefetch, rng, self._upload, gather,
-                             grow=self._alloc_pool, ready=self._ready)
+                             grow=self._alloc_pool, ready=self._ready, units="frames" if self.embedding else "records")
         try:
             for n in feeder:
                 done = torch.cuda.Event()
                 done.record(self.stream)
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(done)
-                yield tuple(t[:n] for t in self._outs[state["k"] % self.ring])
+                out = tuple(t[:n] for t in self._outs[state["k"] % self.ring])
+                if not self.embedding:           # one label row per clip: the first of its 12 identical gathered rows
+                    out = out[:3] + (out[3][::self.frames], out[4][::self.frames]) + out[5:]
+                yield out
                 alive()
                 # the consumer may have enqueued reads of every batch yielded so far: the next gather into the set that
                 # is `ring` batches old starts behind them

@@ -8,7 +8,11 @@ exp pixels, two means, two mask counts) runs on the GPU; the 11-point curve is h
 224 x 298 frame, against the consensus map of up to three annotators' boxes (`acimg_box_iou`).
 
 `OverlayRenderer` draws what those scripts plot (showvideo.py:213-233, showimages.py:136-154, showimages_bb.py:240-285):
-the jet-coloured energy map at alpha 0.7 over the grey frame, as RGB8 pixels on the device (`acimg_overlay_render`)."""
+the jet-coloured energy map at alpha 0.7 over the grey frame, as RGB8 pixels on the device (`acimg_overlay_render`).
+
+`ClipEvaluator` is the classification experiment's pass over a data set (trainer_reconstructed_class.py:262-298,
+saveimagesresnet.py): loss, accuracy and the confusion matrix of clip logits, accumulated on the device
+(`acimg_clip_eval`) and read back once."""
 import numpy as np
 import torch
 
@@ -132,6 +136,44 @@ class OverlayRenderer(object):
         for energy, x0 in ((self.energy(real), 0), (self.energy(generated), self.W + int(gap))):
             self._render_into(f, energy, None, out[:, :, x0:], wide * 3, self.H * wide * 3)
         return out
+
+
+class ClipEvaluator(object):
+    """One evaluation pass: `reset()`, `update(...)` per batch (a kernel launch, nothing read back), `result()` (the
+    pass's only synchronisation).  The state's layout is that of include/acimg.h."""
+
+    HEAD = 32         # double loss_sum, int64 clips, correct, invalid
+
+    def __init__(self, device, num_classes, nr_frames=12):
+        from . import _lib
+        self.device = torch.device(device)
+        self.num_classes, self.nr_frames = int(num_classes), int(nr_frames)
+        nbytes = int(_lib.load().acimg_clip_eval_state_bytes(self.num_classes))
+        if nbytes != self.HEAD + 4 * self.num_classes ** 2:
+            raise ValueError("clip evaluation wants 1..64 classes, got %d" % self.num_classes)
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.plan = ops.Plan(self.device, eager=True)
+
+    def reset(self):
+        self.state.zero_()
+        return self
+
+    def update(self, plan, logits, ldl, clips, labels, clip_loss=None, clip_pred=None):
+        """logits [clips * nr_frames, ldl] float32 and labels [clips] int32 on the device.  plan: record the call there
+        (it then runs with that plan, every time); None: launch now on the current stream."""
+        ops.clip_eval(self.plan if plan is None else plan, logits, ldl, clips, self.nr_frames, self.num_classes, labels,
+                      self.state, clip_loss, clip_pred)
+
+    def result(self):
+        """{loss (mean over the valid clips), accuracy (correct / clips, from the integer counts), clips, correct,
+        invalid, loss_sum, confusion int64 [K, K] (row = label, column = prediction)}"""
+        raw = self.state.cpu().numpy()
+        K = self.num_classes
+        loss_sum = float(raw[:8].view(np.float64)[0])
+        clips, correct, invalid = (int(v) for v in raw[8:32].view(np.int64))
+        confusion = raw[32:].view(np.int32).reshape(K, K).astype(np.int64)
+        return dict(loss=loss_sum / clips if clips else float("nan"), accuracy=correct / clips if clips else float("nan"),
+                    clips=clips, correct=correct, invalid=invalid, loss_sum=loss_sum, confusion=confusion)
 
 
 def mean_iou(ious):

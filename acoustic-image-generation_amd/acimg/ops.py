@@ -783,6 +783,13 @@ def clip_softmax_ce(plan, logits, ldl, clips, F, K, labels, out, g_logits, ldg):
              int(ldg))
 
 
+def clip_eval(plan, logits, ldl, clips, F, K, labels, state, clip_loss=None, clip_pred=None):
+    """accumulate `clips` clips into the evaluation state (include/acimg.h: acimg_clip_eval); `state` is a zeroed uint8
+    tensor of acimg_clip_eval_state_bytes(K) bytes"""
+    plan.add("clip_eval", _L().acimg_clip_eval, logits, int(ldl), int(clips), int(F), int(K), labels, clip_loss,
+             clip_pred, state)
+
+
 _LOSS_SCRATCH = {}
 
 def loss_scratch(device):

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, dp, ops
 from .flags import FLAGS
-from .session import Graph, Session, draw_noise, loss_dict
+from .session import Graph, Session, draw_noise, loss_dict, write_saver_bundle
 from .unet_acresnet import Z
 
 _FRAMES_PER_SECOND = 12
@@ -620,7 +620,6 @@ class Trainer(object):
         the Adam slots `<var>/Adam`, `<var>/Adam_1`, `beta1_power`, `beta2_power` and `global_step` — so the
         reference's own `_restore_model` / `init_model` (:214-247) can read it.  Data-parallel: every rank calls this
         (the BN moving statistics are averaged over ranks first, a collective); only rank 0 writes."""
-        from . import tfio
         self.flush_pipeline()
         if self.comm is not None and self.comm.enabled:
             self.sync_moving_statistics()
@@ -630,30 +629,8 @@ class Trainer(object):
         os.makedirs(checkpoint_dir, exist_ok=True)
         model_name = 'epoch_{}.ckpt'.format(epoch)
         self.log('{}: {} - Saving model to {}/{}'.format(datetime.now(), FLAGS.exp_name, checkpoint_dir, model_name))
-        store = session.store
-        import numpy as np
-        tensors = OrderedDict((k, v.numpy()) for k, v in store.state_dict().items())
-        train = set(n for n in store.grad_dict())
-        for which, sfx in (("m", "/Adam"), ("v", "/Adam_1")):
-            for k, v in store.slot_dict(which).items():
-                if k in train:
-                    tensors[k + sfx] = v.numpy()
-        t = max(int(self.global_step), 0)
-        tensors["beta1_power"] = np.float32(0.9 ** (t + 1))     # TF-1 Adam: the powers start at beta and are
-        tensors["beta2_power"] = np.float32(0.999 ** (t + 1))   # multiplied once per apply_gradients
-        tensors["global_step"] = np.int64(t)
         path = '{}/{}'.format(checkpoint_dir, model_name)
-        tfio.write_checkpoint(path, tensors)
-        self._saved = [p for p in getattr(self, "_saved", []) if p != path] + [path]
-        while len(self._saved) > 11:   # Saver(max_to_keep=11), :81
-            old = self._saved.pop(0)
-            for f in (old + ".index", old + ".data-00000-of-00001"):
-                if os.path.exists(f):
-                    os.remove(f)
-        with open(os.path.join(checkpoint_dir, "checkpoint"), "w") as f:   # tf.train.CheckpointState, text format
-            f.write('model_checkpoint_path: "%s"\n' % os.path.basename(self._saved[-1]))
-            for p in self._saved:
-                f.write('all_model_checkpoint_paths: "%s"\n' % os.path.basename(p))
+        self._saved = write_saver_bundle(session.store, path, self.global_step, getattr(self, "_saved", []), 11)   # :81
         return path
 
     def train(self, train_data=None, valid_data=None):

@@ -723,6 +723,79 @@ __global__ __launch_bounds__(64) void clip_softmax_ce_kernel(const float* logits
     }
 }
 
+// Dataset-level evaluation of clip logits (acimg_clip_eval).  ONE workgroup of four waves walks all clips in chunks of
+// CLIP_EVAL_CHUNK: a wave takes one clip at a time and applies clip_softmax_ce_kernel's per-clip arithmetic (fp32 sum of
+// the F frame logits in frame order / F, max-subtracted softmax, lowest index among exact ties); the integer counters and
+// the confusion matrix collect in LDS (integer atomics commute), and after each chunk thread 0 folds that chunk's losses
+// in clip order onto a double that started from state->loss_sum.  No float atomics, so two identical passes leave
+// identical bits.  A label outside [0, K) adds to `invalid` alone (clip_loss 0, clip_pred still the argmax).
+static constexpr int CLIP_EVAL_CHUNK = 64;
+struct ClipEvalHead {
+    double loss_sum;
+    long long clips, correct, invalid;
+};
+static_assert(sizeof(ClipEvalHead) == 32, "include/acimg.h documents a 32-byte head before confusion[K][K]");
+
+__global__ __launch_bounds__(256) void clip_eval_kernel(const float* logits, int ldl, int clips, int F, int K,
+                                                        const int* labels, float* clip_loss, int* clip_pred,
+                                                        void* state) {
+    __shared__ int conf[64 * 64];
+    __shared__ float loss_s[CLIP_EVAL_CHUNK];
+    __shared__ int cnt[3];              // valid clips, correct, invalid
+    ClipEvalHead* head = static_cast<ClipEvalHead*>(state);
+    int* confusion = reinterpret_cast<int*>(head + 1);
+    const int c = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < K * K; i += 256) conf[i] = 0;
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    double acc = threadIdx.x == 0 ? head->loss_sum : 0.0;
+    __syncthreads();
+    for (int base = 0; base < clips; base += CLIP_EVAL_CHUNK) {
+        const int nchunk = min(CLIP_EVAL_CHUNK, clips - base);
+        for (int i = wave; i < nchunk; i += 4) {
+            const int n = base + i;
+            float m = -INFINITY;
+            if (c < K) {
+                float a = 0.f;
+                for (int f = 0; f < F; ++f) a += logits[((long)n * F + f) * ldl + c];
+                m = a / (float)F;
+            }
+            const float mx = wave_max(m);
+            const float e = c < K ? expf(m - mx) : 0.f;
+            const float se = wave_sum(e);
+            int am = c < K && m == mx ? c : 1 << 20;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
+            const int lab = labels[n];
+            const bool valid = lab >= 0 && lab < K;
+            const float ml = __shfl(m, lab & 63, 64);
+            if (c == 0) {
+                const float loss = valid ? -(ml - mx - logf(se)) : 0.f;
+                loss_s[i] = loss;
+                if (clip_loss) clip_loss[n] = loss;
+                if (clip_pred) clip_pred[n] = am;
+                if (valid) {
+                    atomicAdd(&conf[lab * K + am], 1);
+                    atomicAdd(&cnt[0], 1);
+                    if (am == lab) atomicAdd(&cnt[1], 1);
+                } else {
+                    atomicAdd(&cnt[2], 1);
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < nchunk; ++i) acc += (double)loss_s[i];
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < K * K; i += 256) confusion[i] += conf[i];
+    if (threadIdx.x == 0) {
+        head->loss_sum = acc;
+        head->clips += cnt[0];
+        head->correct += cnt[1];
+        head->invalid += cnt[2];
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // reconstruction loss (MSE + Huber delta=1) and gradient w.r.t. pre-sigmoid logits
 // ------------------------------------------------------------------------------------------
@@ -1317,6 +1390,23 @@ int acimg_clip_softmax_ce(const float* logits, int ldl, int clips, int F, int K,
     hipLaunchKernelGGL(clip_softmax_ce_kernel, dim3(clips), dim3(64), 0, (hipStream_t)stream, logits, ldl, F, K, labels,
                        clips, out, g_logits, ldg);
     return check_launch("clip_softmax_ce");
+}
+
+size_t acimg_clip_eval_state_bytes(int K) {
+    if (K <= 0 || K > 64) return 0;
+    return sizeof(ClipEvalHead) + (size_t)K * K * sizeof(int);
+}
+
+int acimg_clip_eval(const float* logits, int ldl, int clips, int F, int K, const int* labels, float* clip_loss,
+                    int* clip_pred, void* state, void* stream) {
+    if (K <= 0 || K > 64) return fail(ACIMG_EINVAL, "clip_eval: classes must be in 1..64 (got %d)", K);
+    if (F <= 0 || clips <= 0) return fail(ACIMG_EINVAL, "clip_eval: %d clips of %d frames", clips, F);
+    if (ldl < K) return fail(ACIMG_EINVAL, "clip_eval: row stride %d < %d classes", ldl, K);
+    if (!logits || !labels || !state) return fail(ACIMG_EINVAL, "clip_eval: logits, labels and state must be given");
+    if (reinterpret_cast<uintptr_t>(state) & 7) return fail(ACIMG_EINVAL, "clip_eval: state must be 8-byte aligned");
+    hipLaunchKernelGGL(clip_eval_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, ldl, clips, F, K, labels,
+                       clip_loss, clip_pred, state);
+    return check_launch("clip_eval");
 }
 
 // partial-sum workgroups of the reduce pass: one per CU (round 4 measured four per CU: 22 launches 1133 -> 1223 us, the

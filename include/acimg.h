@@ -399,6 +399,27 @@ int acimg_spatial_sum_relu_bwd(const float* x, int ldx, const float* gy, float* 
 int acimg_clip_softmax_ce(const float* logits, int ldl, int clips, int F, int K, const int* labels, float* out,
                           float* g_logits, int ldg, void* stream);
 
+/* Dataset-level evaluation of clip logits, accumulated on the device: a whole validation / test pass calls this once per
+ * batch and reads `state` back once at its end.  Per clip the rule is acimg_clip_softmax_ce's: the fp32 sum of the F
+ * frame logits in frame order, divided by F; softmax cross-entropy against labels[clip]; prediction = the lowest index
+ * among exact ties at the maximum (tf.argmax).
+ * state (acimg_clip_eval_state_bytes(K) = 32 + 4*K*K bytes, 8-byte aligned, ZEROED BY THE CALLER before a pass):
+ *   double  loss_sum            sum of the per-clip losses
+ *   int64   clips               clips with a label in [0, K)
+ *   int64   correct             of those, prediction == label
+ *   int64   invalid             clips with a label outside [0, K): counted here and in nothing else
+ *   int32   confusion[K][K]     row = label, column = prediction
+ * loss_sum is a SEQUENTIAL fold: starting from the value already in state, the fp32 loss of clip 0, 1, ..., clips-1
+ * (converted to double) is added in that order, clips with an invalid label skipped.  The counters are integers; no
+ * float atomics are used, so two identical passes leave bit-identical state.
+ * clip_loss [clips] float32 (optional): per-clip loss, 0 for an invalid label.  clip_pred [clips] int32 (optional): the
+ * prediction (also for an invalid label).  One launch per call whatever `clips` is (any clips >= 1); no host
+ * synchronisation.  1 <= K <= 64, F >= 1, ldl >= K; logits, labels and state must be given (else ACIMG_EINVAL).
+ * acimg_clip_eval_state_bytes returns 0 for K outside 1..64. */
+size_t acimg_clip_eval_state_bytes(int K);
+int acimg_clip_eval(const float* logits, int ldl, int clips, int F, int K, const int* labels, float* clip_loss,
+                    int* clip_pred, void* state, void* stream);
+
 /* Training-mode batch-norm + ReLU backward for the conv-BN-ReLU stacks of the RGB / spectrogram U-Nets
  * (tf.layers.batch_normalization(training=True) + relu, models/unet_architecture.py:161-166,
  * models/unet_sound.py:155-160).  x = the pre-BN conv output (bias included), gy = gradient w.r.t. the ReLU
