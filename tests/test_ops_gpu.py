@@ -1625,7 +1625,7 @@ def test_pipeline_lanes_are_measured(device):
         assert ops.side_lane(device) == lanes[0]
 
 
-@pytest.mark.parametrize("case", [(32, 28416, 300), (5, 4096, 152), (64, 8192, 300), (17, 4100, 16)])
+@pytest.mark.parametrize("case", [(32, 28416, 300), (5, 4096, 152), (64, 8192, 300), (17, 4100, 16), (40, 4096, 152)])
 def test_skinny_dense_gradients(device, case):
     """the dense layers over a few batch rows (the 28 416 -> 300 VAE heads, models/unet_acresnet.py:73-76) take the
     skinny kernels inside acimg_conv2d_fwd / _dgrad / _wgrad (csrc/skinny_kernel.hpp: the weight matrix read / written
