@@ -30,6 +30,10 @@ class DualCamHybridModel(Model):
         self.embedding = embedding
         self.session = None
 
+    def clone_kwargs(self):
+        return dict(input_shape=[self.height, self.width, self.channels], num_classes=self.num_classes,
+                    num_frames=self.num_frames, embedding=self.embedding)
+
     # ---- variables (TF names: models/base.py:11-12,27-28,64-65) ---------------------------------------------
     def _register(self, store):
         s = self.scope

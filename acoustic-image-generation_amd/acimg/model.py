@@ -79,12 +79,27 @@ class Model(object):
     """`scope` names the model's variables in the session's parameter store; `_register(store)` adds them."""
     scope = None
     session = None
+    _original = None         # of a replica: the instance whose variables it shares
 
     def _attach(self, session):
-        """first step of every `_build_model`: join the session, register the variables"""
+        """first step of every `_build_model`: join the session, register the variables (a replica: adopt them)"""
         self.session = session or get_default_session()
-        self._register(self.session.store)
+        if self._original is None:
+            self._register(self.session.store)
+        else:
+            self._adopt(self._original)
         return self.session
+
+    def replica(self):
+        """a second instance over the SAME variables, not yet built: another batch size (the last, partial batch) gets
+        new buffers and plans from it.  Its constructor arguments are the model's own record of them (`clone_kwargs`), so
+        it records the same kernel path as the original."""
+        m = type(self)(**self.clone_kwargs())
+        m._original = self
+        return m
+
+    def _adopt(self, original):
+        """a replica takes over what `_register` created besides the store's variables (default: nothing)"""
 
     # weight / grad pointers (resolved once the flat buffers exist)
     def _P(self, name):

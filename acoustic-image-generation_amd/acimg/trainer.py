@@ -46,11 +46,19 @@ class Trainer(object):
         self.global_step = 0
         self.graphs = {}
         self.comm = None
+        self.group = None              # enable_data_parallel: the process group and the form of the gradient exchange
+        self.exchange = "auto"
         self.noise_seed = 1237
+        self._noise_calls = 0          # draws of the latent noise so far: each takes a fresh Philox counter range
         self.log = print
         self.hold_exchange = False     # True while micro-batch gradients are being accumulated (train_step_sharded)
         self._acc = None
         self._pipe = None              # state of the two-lane pipeline (train_step_pipelined)
+        self._lane_cache = None        # ((caller's stream, lanes wanted), the streams measured to run beside it)
+        # the lanes beside the caller's stream as high-priority streams was measured in round 3
+        # (profiles/r03/pipeline_lane_priority_r03al.txt)
+        self.lane_priority = 0
+        self._saved = []               # the checkpoints _save_checkpoint keeps (Saver(max_to_keep=11))
 
     # ------------------------------------------------------------------------------------------------
     # graph construction
@@ -125,9 +133,9 @@ class Trainer(object):
         g.plan_train = p
         # the calls [head_calls, head_calls + frozen_calls) are the FROZEN trunk (train_step_pipelined's lane A)
         g.head_calls = head_calls
-        g.frozen_calls = getattr(modelimages, "frozen_calls", None)
-        g.stage_calls = getattr(modelimages, "stage_calls", None) if getattr(modelimages, "stages", 1) == 2 else None
-        g.stage_read_calls = getattr(modelimages, "stage_read_calls", None)
+        g.frozen_calls = modelimages.frozen_calls
+        g.stage_calls = modelimages.stage_calls            # None with one trunk stage
+        g.stage_read_calls = modelimages.stage_read_calls
         # ---- evaluation step (is_training = 0: moving statistics; MSE only, :411-442) ----
         e = sess.new_plan()
         head(e)
@@ -145,20 +153,9 @@ class Trainer(object):
     def _graph_for(self, N):
         if N in self.graphs:
             return self.graphs[N]
-        # a different batch size (last partial batch): same variables, new buffers + plans
-        # (every constructor argument that shapes the recorded plan comes from the model's own record of them, so the
-        #  partial batch runs the same kernel path - two-pass rule included - as the primary graph)
-        mi = type(self.modelimages)(**self.modelimages.clone_kwargs())
-        ma = type(self.modelac)(input_shape=[36, 48, 12], embedding=self.modelac.embedding,
-                                num_skip=self.modelac.num_skip, precision=self.modelac.precision,
-                                side_lane=self.modelac.side_lane)
-        mi._register = lambda store: None
-        ma_heads = self.modelac.heads
-
-        def _reuse(store, ma=ma):
-            ma.heads = ma_heads
-        ma._register = _reuse
-        return self._build_graph(N, mi, ma)
+        # a different batch size (last partial batch): same variables, new buffers + plans, the same kernel path - two-pass
+        # rule included - as the primary graph (Model.replica)
+        return self._build_graph(N, self.modelimages.replica(), self.modelac.replica())
 
     def _bucket_ready(self, i, join=None):
         if self.comm is not None and not self.hold_exchange:
@@ -189,7 +186,7 @@ class Trainer(object):
         self.flush_pipeline()
         store = self.session.store
         rng = [(v.offset, v.numel) for n, v in store.vars.items() if v.group == "state" and "/moving_" in n]
-        dp.average_moving_statistics(store.flat["state"], rng, getattr(self, "group", None))
+        dp.average_moving_statistics(store.flat["state"], rng, self.group)
         store.version += 1
 
     # ------------------------------------------------------------------------------------------------
@@ -208,7 +205,7 @@ class Trainer(object):
         if eps is not None:
             g.eps.copy_(eps.reshape(g.N, Z), non_blocking=True)
         else:
-            self._noise_calls = getattr(self, "_noise_calls", 0) + 1
+            self._noise_calls += 1
             draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
 
     def train_step(self, batch=None, eps=None, sync=True, probe=None):
@@ -222,7 +219,7 @@ class Trainer(object):
             self._feed(g, batch, eps)
         else:
             self._noise(g, eps)
-        whole = self.comm is not None and getattr(self, "exchange", "auto") == "whole"
+        whole = self.comm is not None and self.exchange == "whole"
         held, self.hold_exchange = self.hold_exchange, self.hold_exchange or whole
         try:
             if probe is None:
@@ -274,10 +271,8 @@ class Trainer(object):
         # streams onto a few hardware queues (4 by default; RCCL takes some) and two streams on one queue serialise
         want = (2 if g.stage_calls is not None else 1) + 1
         key = (cur.cuda_stream, want)
-        if getattr(self, "_lane_cache", None) is None or self._lane_cache[0] != key:
-            # (lane_priority: attribute, 0 by default - the lanes beside the caller's stream as high-priority streams was
-            #  measured in round 3, profiles/r03/pipeline_lane_priority_r03al.txt)
-            self._lane_cache = (key, ops.concurrent_streams(dev, cur, want, priority=getattr(self, "lane_priority", 0)))
+        if self._lane_cache is None or self._lane_cache[0] != key:
+            self._lane_cache = (key, ops.concurrent_streams(dev, cur, want, priority=self.lane_priority))
         lanes = list(self._lane_cache[1])
         side_b = lanes.pop() if len(lanes) == want else None
         while len(lanes) < want - 1:
@@ -324,7 +319,7 @@ class Trainer(object):
             # buckets, no separate exchange stream): the trained part has a whole tick of slack behind the trunk stages,
             # so nothing needs to overlap inside it; every collective call costs host time, and every stream beyond the
             # runtime's 4 hardware queues shares a queue with one of the lanes (RCCL's own stream is the fourth)
-            bucketed = getattr(self, "exchange", "auto") == "bucketed" and item.get("accum") is None
+            bucketed = self.exchange == "bucketed" and item.get("accum") is None
             held, self.hold_exchange = self.hold_exchange, self.hold_exchange or not bucketed
             try:
                 if probe is None:
@@ -623,14 +618,14 @@ class Trainer(object):
         self.flush_pipeline()
         if self.comm is not None and self.comm.enabled:
             self.sync_moving_statistics()
-        if not dp.is_writer(getattr(self, "group", None)):
+        if not dp.is_writer(self.group):
             return None
         checkpoint_dir = '{}/{}'.format(FLAGS.checkpoint_dir, FLAGS.exp_name)
         os.makedirs(checkpoint_dir, exist_ok=True)
         model_name = 'epoch_{}.ckpt'.format(epoch)
         self.log('{}: {} - Saving model to {}/{}'.format(datetime.now(), FLAGS.exp_name, checkpoint_dir, model_name))
         path = '{}/{}'.format(checkpoint_dir, model_name)
-        self._saved = write_saver_bundle(session.store, path, self.global_step, getattr(self, "_saved", []), 11)   # :81
+        self._saved = write_saver_bundle(session.store, path, self.global_step, self._saved, 11)   # :81
         return path
 
     def train(self, train_data=None, valid_data=None):
@@ -646,7 +641,7 @@ class Trainer(object):
         best_epoch, best_loss = -1, 10000
         for epoch in range(start_epoch, start_epoch + self.num_epochs):
             step = 0
-            pipelined = bool(getattr(self.modelimages, "_split", False)) and FLAGS.pipeline
+            pipelined = self.modelimages._split and FLAGS.pipeline
 
             def report(i, r):
                 if i % self.display_freq == 0:
@@ -683,7 +678,7 @@ class Trainer(object):
                 if total_loss <= best_loss:
                     best_epoch, best_loss = epoch, total_loss
                     self._save_checkpoint(session, epoch)
-                    if dp.is_writer(getattr(self, "group", None)):
+                    if dp.is_writer(self.group):
                         with open('{}/{}'.format(FLAGS.checkpoint_dir, FLAGS.exp_name) + "/model.txt", "w") as outfile:
                             outfile.write('{}: {}\nBest Epoch: {}\nValidation_mse_Loss: {:6f}\n'.format(
                                 datetime.now(), FLAGS.exp_name, best_epoch, best_loss))
@@ -707,7 +702,7 @@ class Trainer(object):
             loss_sum += r["mse"] * n
         if self.comm is not None and self.comm.enabled:     # every rank validates its own shard of `data`
             loss_sum, data_set_size = dp.allreduce_sums([loss_sum, data_set_size], self.session.device,
-                                                        getattr(self, "group", None))
+                                                        self.group)
         return loss_sum / data_set_size
 
     def test(self, test_data=None):
@@ -731,7 +726,7 @@ class Trainer(object):
         test_loss, l0, l1, l2, l3 = [s / data_set_size for s in sums]
         line = '{} - Testing_Loss: {:6f}\t  Testing_Loss0: {:6f}\t Testing_Loss1: {:6f}\t Testing_Loss2: {:6f}\t ' \
                'Testing_Loss3: {:6f}'.format(datetime.now(), test_loss, l0, l1, l2, l3)
-        if FLAGS.restore_checkpoint is not None and dp.is_writer(getattr(self, "group", None)):
+        if FLAGS.restore_checkpoint is not None and dp.is_writer(self.group):
             name_folder = str.join('/', FLAGS.restore_checkpoint.split('/')[:-1])
             tag = FLAGS.restore_checkpoint.split('/')[-1].split('.')[0].split('_')[-1]
             with open('{}'.format(name_folder) + "/test_accuracy_{}.txt".format(tag), "w") as outfile:

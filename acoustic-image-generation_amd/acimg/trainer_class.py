@@ -60,6 +60,8 @@ class TrainerClass(object):
         self.source = source
         self.global_step = 0
         self.noise_seed = 1237
+        self._noise_calls = 0           # draws of the latent noise so far: each takes a fresh Philox counter range
+        self._saved = []                # the checkpoints _save_checkpoint keeps (Saver(max_to_keep=5))
         self.graphs = {}                # clips -> Graph
         self.evaluator = None
         self.last_evaluation = None     # `ClipEvaluator.result()` of the latest `_evaluate`
@@ -141,23 +143,10 @@ class TrainerClass(object):
         buffers and plans, as `Trainer._graph_for` does"""
         if clips in self.graphs:
             return self.graphs[clips]
-        m0 = self.model
-        m = type(m0)(input_shape=[m0.height, m0.width, m0.channels], num_classes=m0.num_classes,
-                     num_frames=m0.num_frames, embedding=m0.embedding)
-        m._register = lambda store: None
         mi = ma = None
         if self.source == "generated":
-            mi0, ma0 = self.model_encoder_images, self.model_encoder_acoustic
-            mi = type(mi0)(**mi0.clone_kwargs())
-            ma = type(ma0)(input_shape=[36, 48, 12], embedding=ma0.embedding, num_skip=ma0.num_skip,
-                           precision=ma0.precision, side_lane=ma0.side_lane)
-            mi._register = lambda store: None
-            heads = ma0.heads
-
-            def _reuse(store, ma=ma):
-                ma.heads = heads
-            ma._register = _reuse
-        g = self._build_graph(clips * self.nr_frames, m, mi, ma)
+            mi, ma = self.model_encoder_images.replica(), self.model_encoder_acoustic.replica()
+        g = self._build_graph(clips * self.nr_frames, self.model.replica(), mi, ma)
         g.off, g.numel = self.off, self.numel
         return g
 
@@ -206,7 +195,7 @@ class TrainerClass(object):
         if eps is not None:
             g.eps.copy_(eps.reshape(g.N, Z), non_blocking=True)
         else:
-            self._noise_calls = getattr(self, "_noise_calls", 0) + 1
+            self._noise_calls += 1
             draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
 
     def train_step(self, batch=None, eps=None):
@@ -304,7 +293,7 @@ class TrainerClass(object):
         scope = self.model.scope + "/"
         conv1 = scope + "conv1/weights"
         shapes = {conv1: tuple(self.model.state_dict_tf()[conv1].shape)}
-        self._saved = write_saver_bundle(session.store, path, self.global_step, getattr(self, "_saved", []), 5,
+        self._saved = write_saver_bundle(session.store, path, self.global_step, self._saved, 5,
                                          slots_of=lambda n: n.startswith(scope), tf_shapes=shapes)
         return path
 

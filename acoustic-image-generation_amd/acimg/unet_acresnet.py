@@ -47,6 +47,13 @@ class UNetAc(ConvModel):
         assert self.num_skip in (0, 1, 2)
         self.session = None
 
+    def clone_kwargs(self):
+        return dict(input_shape=[self.height, self.width, self.channels], num_frames=self.num_frames,
+                    embedding=self.embedding, num_skip=self.num_skip, precision=self.precision, side_lane=self.side_lane)
+
+    def _adopt(self, original):
+        self.heads = original.heads
+
     # ---- variables ------------------------------------------------------------------------------------
     def _conv_specs(self):
         ns = self.num_skip

@@ -17,7 +17,7 @@ statistics of round 4): BN + shortcut + ReLU + split then run in the conv's own 
 Activations live in a few reusable arenas (about 1.2 GB at batch 32), so consecutive layers hit the 256 MiB Infinity
 Cache instead of streaming 6.5 GB of distinct tensors.
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -31,6 +31,11 @@ WEIGHT_DECAY = 5e-4   # resnet_arg_scope(weight_decay=5e-4), models/vision.py:54
 BN_DECAY = 0.997
 BN_EPS = 1e-5
 PLANE_SLACK = 2 * 15 * 2048 * 2 + 512   # a split-format plane ends on a whole 16-pixel brick: <= 15 pixels more, twice
+
+# The activation arenas of one pipeline stage.  a / b: the unit inputs and outputs, ping-pong (split planes; fp32 in the
+# f32 trunk); p1 / p2: the split planes conv2 / conv3 read (None in the f32 trunk); r1 / r2 / r3 / sc: the raw fp32
+# outputs of conv1 / conv2 / conv3 / the projection shortcut.  tag: "" or "2", the stage's part of every lane name.
+Stage = namedtuple("Stage", "tag a b p1 p2 r1 r2 r3 sc")
 
 
 class ResNet50Model(Model):
@@ -90,10 +95,16 @@ class ResNet50Model(Model):
         self.session = None
         self.output = None
         self.network = None
+        # marks in plan_train, set while it is recorded (the trainer's pipeline cuts the plan there): the calls
+        # [0, frozen_calls) are the frozen trunk; with two stages, stage 2 begins at stage_calls and has read the boundary
+        # tensor by stage_read_calls.  None: not marked (only the split trunk marks its end, only two stages a boundary)
+        self.frozen_calls = None
+        self.stage_calls = None
+        self.stage_read_calls = None
 
     def clone_kwargs(self):
-        """constructor arguments of a second instance that records the same plan shape (Trainer._graph_for: another
-        batch size over the same variables)"""
+        """constructor arguments of a second instance that records the same plan shape (Model.replica: another batch
+        size over the same variables)"""
         return dict(self._ctor)
 
     # ---- variable inventory (TF names) --------------------------------------------------------------
@@ -165,7 +176,7 @@ class ResNet50Model(Model):
         self.plan_eval = sess.new_plan()
         self._record_forward(self.plan_train, True)
         self._record_forward(self.plan_eval, False)
-        self.wsplit = torch.zeros(max(self._sp3_bytes, 16), dtype=torch.uint8, device=sess.device)
+        self._alloc_reserved()
         self.network = OrderedDict(input=visual_images, is_training=None, keep_prob=None)
         self.network[self.scope + "/conv_map"] = self.output
         cm = self.scope + "/conv_map"
@@ -185,53 +196,42 @@ class ResNet50Model(Model):
         ph, _ = ops.same_out_pad(oh1, 3, 2)
         pw, _ = ops.same_out_pad(ow1, 3, 2)
         self.pool_hw = (ph, pw)
-        # arena sizes over all units
+        # arena sizes in elements, [io, r1, r2, r3]: over all units, and over the units of stage 2 alone, which only ever
+        # holds unit outputs in its io planes (its first input is the boundary tensor, `xb` elements)
+        two = self.stages == 2
         h, w = ph, pw
-        mx_io = N * h * w * 64
-        mx_r1 = mx_r2 = mx_r3 = 0
+        mx, mx2, xb = [N * h * w * 64, 0, 0, 0], [0, 0, 0, 0], 0
         nch = 64
-        for scope, din, d, db, s in self._units():
+        for k, (scope, din, d, db, s) in enumerate(self._units()):
             oh, _ = ops.same_out_pad(h, 1, s)
             ow, _ = ops.same_out_pad(w, 1, s)
-            mx_r1 = max(mx_r1, N * h * w * db)
-            mx_r2 = max(mx_r2, N * oh * ow * db)
-            mx_r3 = max(mx_r3, N * oh * ow * d)
-            mx_io = max(mx_io, N * h * w * din, N * oh * ow * d)
+            r = [N * h * w * db, N * oh * ow * db, N * oh * ow * d]
+            mx = [max(a, b) for a, b in zip(mx, [max(N * h * w * din, N * oh * ow * d)] + r)]
+            if two and k == self.STAGE_CUT - 1:
+                xb = N * oh * ow * d
+            if two and k >= self.STAGE_CUT:
+                mx2 = [max(a, b) for a, b in zip(mx2, [N * oh * ow * d] + r)]
             h, w = oh, ow
             nch += (d if din != d else 0) + 2 * db + d
         self.final_hw = (h, w)
-        self.arena_a = z(mx_io)
-        self.arena_b = z(mx_io)
-        self.arena_r1 = z(mx_r1)
-        self.arena_r2 = z(mx_r2)
-        self.arena_r3 = z(mx_r3)
-        self.arena_sc = z(mx_r3)
-        if self._split:
-            # split-format arenas (two fp16 planes per tensor = the bytes of the fp32 tensor)
-            u8 = lambda n: torch.zeros(int(n), dtype=torch.uint8, device=sess.device)  # noqa: E731
-            self.planes_a, self.planes_b = u8(4 * mx_io + PLANE_SLACK), u8(4 * mx_io + PLANE_SLACK)
-            self.planes_1, self.planes_2 = u8(4 * mx_r1 + PLANE_SLACK), u8(4 * mx_r2 + PLANE_SLACK)
-            if self.stages == 2:
-                # stage 2's own arenas (sized for its units) and the tensor that crosses the stage boundary
-                hh, ww = ph, pw
-                io2 = r12 = r22 = r32 = xb = 0
-                for k, (scope, din, d, db, s_) in enumerate(self._units()):
-                    oh, _ = ops.same_out_pad(hh, 1, s_)
-                    ow, _ = ops.same_out_pad(ww, 1, s_)
-                    if k == self.STAGE_CUT - 1:
-                        xb = N * oh * ow * d
-                    if k >= self.STAGE_CUT:
-                        r12, r22 = max(r12, N * hh * ww * db), max(r22, N * oh * ow * db)
-                        r32, io2 = max(r32, N * oh * ow * d), max(io2, N * oh * ow * d)
-                    hh, ww = oh, ow
-                self.planes_x = u8(4 * xb + PLANE_SLACK)
-                self.planes_a2, self.planes_b2 = u8(4 * io2 + PLANE_SLACK), u8(4 * io2 + PLANE_SLACK)
-                self.planes_12, self.planes_22 = u8(4 * r12 + PLANE_SLACK), u8(4 * r22 + PLANE_SLACK)
-                self.arena_r12, self.arena_r22 = z(r12), z(r22)
-                self.arena_r32, self.arena_sc2 = z(r32), z(r32)
+        io32 = (z(mx[0]), z(mx[0]))
+        raw = [z(mx[1]), z(mx[2]), z(mx[3]), z(mx[3])]
+        if not self._split:
+            self.arenas = [Stage("", io32[0], io32[1], None, None, *raw)]
+        else:
+            # split-format arenas (two fp16 planes per tensor = the bytes of the fp32 tensor); stage 1 keeps the size of
+            # the one-stage trunk, stage 2 has its own (sized for its units), the boundary tensor crosses between them
+            u8 = lambda n: torch.zeros(int(4 * n + PLANE_SLACK), dtype=torch.uint8, device=sess.device)  # noqa: E731
+            self._io32 = io32       # the split trunk has no fp32 unit outputs: allocated as ever, used by nothing
+            self.arenas = [Stage("", u8(mx[0]), u8(mx[0]), u8(mx[1]), u8(mx[2]), *raw)]
+            if two:
+                self.planes_x = u8(xb)
+                planes2 = [u8(mx2[0]), u8(mx2[0]), u8(mx2[1]), u8(mx2[2])]
+                self.arenas.append(Stage("2", *planes2, z(mx2[1]), z(mx2[2]), z(mx2[3]), z(mx2[3])))
         self.xfinal = z(N, h, w, 2048)          # block4 output, kept for the conv_map weight gradient
         self.affine = z(2 * (nch + 64 + 16))    # scale/shift of every BN layer
         self._aff_off = 0
+        self._aff_cache = {}                    # scope -> (scale, shift), slices of `affine`
         fh, fw = h - 3 + 1, w - 4 + 1
         self.feat_hw = (fh, fw)
         self.raw_cm = z(N, fh, fw, 12)
@@ -240,8 +240,13 @@ class ResNet50Model(Model):
         self.save_invstd = z(16)
         self.g_output = z(N, fh, fw, 12)        # filled by the generator's backward (min-max bwd)
         self.g_raw_cm = z(N, fh, fw, 12)
-        self.stats = None
-        self._stats_need = 0
+        # per-lane buffers, (kind, lane) -> tensor.  A lane is what may run at the same time as another: a pipeline stage
+        # ("" / "2"), its side lane ("_side" + stage), and conv_map ("cm": the first layer of the TRAINED part of the step,
+        # which the two-lane pipeline of acimg/trainer.py runs beside the frozen trunk of the next batch).  Every lane has
+        # a statistics buffer ("stats", floats: `_lane_stats`), a tail workspace and a Gram workspace ("tail" / "gram",
+        # bytes: `_lane_ws`) of its own; two lanes never share one
+        self.lane_bufs = {}
+        self._stats_need = {}                   # lane -> floats its statistics buffer must hold (_alloc_reserved)
         if self._split:
             # stem as a row-run conv on the split-MFMA kernel: zero-padded 4-channel frame (+ slack for the last run),
             # kernel re-laid as [7][32 = 7 pixels x 4 channels + 4 zero rows][64]
@@ -258,57 +263,79 @@ class ResNet50Model(Model):
             self.cm_z = z(N * h * w, 144)
             self.cm_gz = z(N * h * w, 144)
             self.cm_dwt = z(2048, 144)
-        # f16x3: split + transposed copies of the frozen kernels, refreshed when the store changes
+        # f16x3: split + transposed copies of the frozen kernels (`_split_image`), refreshed when the store changes
         self._sp3 = {}
         self._sp3_bytes = 0
         self._sp3_version = -1
         self.plan_prepare = sess.new_plan()
-        self.wsplit = None
+        self.wsplit = None                      # _alloc_reserved
+        # sum of squares of the frozen kernels (record_regularizer)
+        self._trunk_ss = None
+        self._trunk_ss_version = -1
+        self._plan_reg = None
 
-    def _new_affine(self, c):
-        sc = self.affine[self._aff_off:self._aff_off + c]
-        sh = self.affine[self._aff_off + c:self._aff_off + 2 * c]
-        self._aff_off += 2 * c
-        assert self._aff_off <= self.affine.numel()
-        return sc, sh
+    def _alloc_reserved(self):
+        """what the recorded calls reach through lazy pointers, once both forward plans have said how much they need: the
+        split images of the frozen kernels and every lane's statistics buffer"""
+        self.wsplit = torch.zeros(max(self._sp3_bytes, 16), dtype=torch.uint8, device=self.session.device)
+        for lane, need in self._stats_need.items():
+            self.lane_bufs["stats", lane] = self.session.zeros(need)
 
-    # ---- plan recording ------------------------------------------------------------------------------
-    def _conv_bn(self, plan, scope, x, hw, cin, kh, kw, cout, stride, padding, out, in_aff, training,
-                 save=False):
-        """raw conv + BN statistics -> (scale, shift) of this layer; returns (OH, OW, scale, shift)"""
-        st = self.session.store
-        P = lambda n: ops.LazyPtr(lambda n=n: st.p(n))  # noqa: E731
-        d = ops.conv_desc(self.N, hw[0], hw[1], cin, cout, kh, kw, stride, padding, ldx=cin, ldy=up4(cout),
-                          ldw=up4(cout))
-        sp3 = False   # the f16x3 trunk goes through _conv_bn_planes; conv1 (C=3) and conv_map stay exact-f32
-        rows = ops.conv2d_fwd_split3_stats_rows(d) if sp3 else ops.conv2d_stats_rows(d)
-        self._stats_need = max(self._stats_need, rows * 2 * up4(cout))
-        stats = ops.LazyPtr(lambda: self.stats)
-        isc, ish = (in_aff if in_aff is not None else (None, None))
-        if sp3:
-            if scope not in self._sp3:
-                off = self._sp3_bytes
-                self._sp3[scope] = off
-                self._sp3_bytes += -(-ops.conv2d_split3_weight_bytes(d) // 256) * 256
-                ops.conv2d_split3_prepare(self.plan_prepare, d, P(scope + "/weights"),
-                                       ops.LazyPtr(lambda off=off: self.wsplit[off:]))
-            off = self._sp3[scope]
-            ops.conv2d_fwd_split3(plan, d, x, ops.LazyPtr(lambda off=off: self.wsplit[off:]), out, isc, ish, 1,
-                               stats if training else None)
-        else:
-            ops.conv2d_fwd(plan, d, x, P(scope + "/weights"), None, out, isc, ish, 1,
-                           stats if training else None)
-        if not hasattr(self, "_aff_cache"):
-            self._aff_cache = {}
+    def _lane_stats(self, lane, floats):
+        """reserves `floats` floats of `lane`'s statistics buffer -> lazy pointer to it"""
+        self._stats_need[lane] = max(self._stats_need.get(lane, 0), floats)
+        return ops.LazyPtr(lambda: self.lane_bufs["stats", lane])
+
+    def _lane_ws(self, kind, lane, nbytes):
+        """`lane`'s workspace of `kind` ("tail" | "gram") with at least `nbytes` bytes, zero at start.  A tensor at once, not
+        a lazy pointer: the call records its byte count.  One that is too small is replaced; a call recorded with the
+        smaller one keeps the buffer it was recorded with."""
+        ws = self.lane_bufs.get((kind, lane))
+        if ws is None or ws.numel() < nbytes:
+            ws = self.lane_bufs[kind, lane] = torch.zeros(nbytes, dtype=torch.uint8, device=self.session.device)
+        return ws
+
+    def _affine(self, scope, cout):
+        """(scale, shift) of BN layer `scope`: two runs of `affine`, handed out on first use"""
         if scope not in self._aff_cache:
-            self._aff_cache[scope] = self._new_affine(up4(cout))
-        sc, sh = self._aff_cache[scope]
+            c = up4(cout)
+            self._aff_cache[scope] = (self.affine[self._aff_off:self._aff_off + c],
+                                      self.affine[self._aff_off + c:self._aff_off + 2 * c])
+            self._aff_off += 2 * c
+            assert self._aff_off <= self.affine.numel()
+        return self._aff_cache[scope]
+
+    # ---- the steps every layer is recorded from ----------------------------------------------------------
+    def _var(self, name):
+        """variable `name` (full TF name) in the store's flat buffers, resolved once they exist"""
+        st = self.session.store
+        return ops.LazyPtr(lambda: st.p(name))
+
+    def _grad(self, name):
+        st = self.session.store
+        return ops.LazyPtr(lambda: st.g(name))
+
+    def _split_image(self, scope, d, w=None):
+        """the split image of frozen kernel `scope` (w: its fp32 source, default the variable `scope`/weights): a run of
+        `wsplit`, registered on first use, when its prepare launch joins `plan_prepare` -> lazy pointer"""
+        if scope not in self._sp3:
+            off = self._sp3[scope] = self._sp3_bytes
+            self._sp3_bytes += -(-ops.conv2d_split3_weight_bytes(d) // 256) * 256
+            ops.conv2d_split3_prepare(self.plan_prepare, d, w if w is not None else self._var(scope + "/weights"),
+                                      ops.LazyPtr(lambda: self.wsplit[off:]))
+        off = self._sp3[scope]
+        return ops.LazyPtr(lambda: self.wsplit[off:])
+
+    def _bn_finalize(self, plan, scope, cout, stats, rows, count, training, save=False, side=False):
+        """statistics partials (training) or the moving statistics -> (scale, shift) of BN layer `scope`.  save: keep the
+        batch mean / inverse deviation for the backward pass (conv_map); side: on the plan's side lane"""
+        sc, sh = self._affine(scope, cout)
         b = scope + "/BatchNorm/"
         ops.bn_finalize(plan, stats if training else None, rows if training else 0, cout, up4(cout),
-                        self.N * d.OH * d.OW if training else 0, P(b + "gamma"), P(b + "beta"),
-                        P(b + "moving_mean"), P(b + "moving_variance"), sc, sh, BN_DECAY, BN_EPS, training,
-                        self.save_mean if save else None, self.save_invstd if save else None)
-        return d.OH, d.OW, sc, sh
+                        count if training else 0, self._var(b + "gamma"), self._var(b + "beta"),
+                        self._var(b + "moving_mean"), self._var(b + "moving_variance"), sc, sh, BN_DECAY, BN_EPS, training,
+                        self.save_mean if save else None, self.save_invstd if save else None, side=side)
+        return sc, sh
 
     def _refresh_split_weights(self):
         """host hook at the head of the forward plans: re-split the frozen kernels iff they changed"""
@@ -325,53 +352,39 @@ class ResNet50Model(Model):
         whole 16-pixel x 32-channel bricks (include/acimg.h, pre-split activation format)"""
         return -(-rows // 16) * 16 * c * 2
 
+    # ---- plan recording ------------------------------------------------------------------------------
+    def _conv_bn(self, plan, scope, x, hw, cin, kh, kw, cout, stride, padding, out, in_aff, training,
+                 save=False):
+        """raw conv + BN statistics -> (scale, shift) of this layer, exact f32 (the f32 trunk; the f16x3 / f16 trunk goes
+        through _conv_bn_planes, _stem_bn and _conv_map_tap); returns (OH, OW, scale, shift)"""
+        d = ops.conv_desc(self.N, hw[0], hw[1], cin, cout, kh, kw, stride, padding, ldx=cin, ldy=up4(cout),
+                          ldw=up4(cout))
+        rows = ops.conv2d_stats_rows(d)
+        stats = self._lane_stats("", rows * 2 * up4(cout))
+        isc, ish = (in_aff if in_aff is not None else (None, None))
+        ops.conv2d_fwd(plan, d, x, self._var(scope + "/weights"), None, out, isc, ish, 1, stats if training else None)
+        sc, sh = self._bn_finalize(plan, scope, cout, stats, rows, self.N * d.OH * d.OW, training, save=save)
+        return d.OH, d.OW, sc, sh
+
     def _conv_bn_planes(self, plan, scope, xplanes, hw, cin, kh, kw, cout, stride, padding, out, training, side=False,
                         tag=""):
         """like _conv_bn, for an input in split format (pre-normalised fp16 hi/lo planes).  side: conv + finalize on the
         plan's side lane (the projection shortcut beside conv1..conv3 of its unit); tag "2": second pipeline stage.
         Every (stage, lane) pair has a statistics buffer and a tail workspace (tickets) of its own: they may run at the
         same time"""
-        st = self.session.store
-        P = lambda n: ops.LazyPtr(lambda n=n: st.p(n))  # noqa: E731
         d = ops.conv_desc(self.N, hw[0], hw[1], cin, cout, kh, kw, stride, padding, ldx=cin, ldy=up4(cout),
                           ldw=up4(cout))
         rows = ops.conv2d_fwd_split3p_stats_rows(d) if self._terms == 3 else ops.conv2d_fwd_split3_stats_rows(d)
         lane = ("_side" if side else "") + tag
-        if lane:
-            self._lane_stats_need = getattr(self, "_lane_stats_need", {})
-            self._lane_stats_need[lane] = max(self._lane_stats_need.get(lane, 0), rows * 2 * up4(cout))
-            stats = ops.LazyPtr(lambda lane=lane: self.lane_stats[lane])
-        else:
-            self._stats_need = max(self._stats_need, rows * 2 * up4(cout))
-            stats = ops.LazyPtr(lambda: self.stats)
-        if scope not in self._sp3:
-            off = self._sp3_bytes
-            self._sp3[scope] = off
-            self._sp3_bytes += -(-ops.conv2d_split3_weight_bytes(d) // 256) * 256
-            ops.conv2d_split3_prepare(self.plan_prepare, d, P(scope + "/weights"),
-                                      ops.LazyPtr(lambda off=off: self.wsplit[off:]))
-        off = self._sp3[scope]
-        ws_attr = "_tail_ws" + lane
-        if getattr(self, ws_attr, None) is None:
-            # partial sums + tile tickets of the trunk kernel's tail split; used by nothing else, zero at start
-            setattr(self, ws_attr, torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8,
-                                               device=self.session.device))
+        stats = self._lane_stats(lane, rows * 2 * up4(cout))
+        # partial sums + tile tickets of the trunk kernel's tail split; used by nothing else
         # (recording the staged trunk WITHOUT the tail split — the other stages fill the partial last rounds anyway —
         #  was measured: 7.21 -> 7.13 ms/step pipelined, but 8.96 -> 9.22 ms on one stream and 249 -> 223 TFLOP/s for
         #  the kernel with the chip to itself; the plan is shared by both entry points, so the split stays)
-        tail_ws = getattr(self, ws_attr)
-        ops.conv2d_fwd_split3p(plan, d, xplanes, self._lo_off(self.N * hw[0] * hw[1], cin),
-                               ops.LazyPtr(lambda off=off: self.wsplit[off:]), out, stats if training else None,
-                               tail_ws=tail_ws, terms=self._terms, side=side)
-        if not hasattr(self, "_aff_cache"):
-            self._aff_cache = {}
-        if scope not in self._aff_cache:
-            self._aff_cache[scope] = self._new_affine(up4(cout))
-        sc, sh = self._aff_cache[scope]
-        b = scope + "/BatchNorm/"
-        ops.bn_finalize(plan, stats if training else None, rows if training else 0, cout, up4(cout),
-                        self.N * d.OH * d.OW if training else 0, P(b + "gamma"), P(b + "beta"),
-                        P(b + "moving_mean"), P(b + "moving_variance"), sc, sh, BN_DECAY, BN_EPS, training, side=side)
+        tail_ws = self._lane_ws("tail", lane, ops.conv2d_fwd_split3p_workspace(d))
+        ops.conv2d_fwd_split3p(plan, d, xplanes, self._lo_off(self.N * hw[0] * hw[1], cin), self._split_image(scope, d),
+                               out, stats if training else None, tail_ws=tail_ws, terms=self._terms, side=side)
+        sc, sh = self._bn_finalize(plan, scope, cout, stats, rows, self.N * d.OH * d.OW, training, side=side)
         return d.OH, d.OW, sc, sh
 
     def _conv3_two_pass(self, plan, scope, xplanes, hw, cin, cout, sc_planes, out_planes, training, tag="", proj=None):
@@ -380,54 +393,25 @@ class ResNet50Model(Model):
         mode the affine comes from the moving statistics and the first pass is not needed.  proj = (raw fp32 output of the
         unit's shortcut conv, its scale, its shift) for a unit with a projection shortcut, else the identity shortcut is
         read from `sc_planes`."""
-        st = self.session.store
-        P = lambda n: ops.LazyPtr(lambda n=n: st.p(n))  # noqa: E731
         d = ops.conv_desc(self.N, hw[0], hw[1], cin, cout, 1, 1, 1, "SAME", ldx=cin, ldy=cout, ldw=cout)
-        rows = -(-self.N * hw[0] * hw[1] // 128)
-        if tag:
-            self._lane_stats_need = getattr(self, "_lane_stats_need", {})
-            self._lane_stats_need[tag] = max(self._lane_stats_need.get(tag, 0), rows * 2 * cout)
-            stats = ops.LazyPtr(lambda lane=tag: self.lane_stats[lane])
-        else:
-            self._stats_need = max(self._stats_need, rows * 2 * cout)
-            stats = ops.LazyPtr(lambda: self.stats)
-        if scope not in self._sp3:
-            off = self._sp3_bytes
-            self._sp3[scope] = off
-            self._sp3_bytes += -(-ops.conv2d_split3_weight_bytes(d) // 256) * 256
-            ops.conv2d_split3_prepare(self.plan_prepare, d, P(scope + "/weights"),
-                                      ops.LazyPtr(lambda off=off: self.wsplit[off:]))
-        off = self._sp3[scope]
-        wsplit = ops.LazyPtr(lambda off=off: self.wsplit[off:])
-        ws_attr = "_tail_ws" + tag
-        if getattr(self, ws_attr, None) is None:
-            setattr(self, ws_attr, torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8,
-                                               device=self.session.device))
-        tail_ws = getattr(self, ws_attr)
-        lo = self._lo_off(self.N * hw[0] * hw[1], cin)
-        lo_out = self._lo_off(self.N * hw[0] * hw[1], cout)
-        if not hasattr(self, "_aff_cache"):
-            self._aff_cache = {}
-        if scope not in self._aff_cache:
-            self._aff_cache[scope] = self._new_affine(up4(cout))
-        sc, sh = self._aff_cache[scope]
-        b = scope + "/BatchNorm/"
         M = self.N * hw[0] * hw[1]
+        rows = -(-M // 128)
+        stats = self._lane_stats(tag, rows * 2 * cout)
+        wsplit = self._split_image(scope, d)
+        tail_ws = self._lane_ws("tail", tag, ops.conv2d_fwd_split3p_workspace(d))
+        lo = self._lo_off(M, cin)
+        lo_out = self._lo_off(M, cout)
         if training and self.gram and ops.gram_stats_workspace(M, cin) > 0:
             # statistics from the conv's input (one workspace per pipeline stage: the stages run side by side)
-            need = ops.gram_stats_workspace(M, cin)
-            gw_attr = "_gram_ws" + tag
-            if getattr(self, gw_attr, None) is None or getattr(self, gw_attr).numel() < need:
-                setattr(self, gw_attr, torch.zeros(need, dtype=torch.uint8, device=self.session.device))
-            gws = getattr(self, gw_attr)     # (a unit that needed a smaller one keeps the buffer it was recorded with)
-            ops.gram_stats(plan, xplanes, lo, M, cin, P(scope + "/weights"), cout, cout, P(b + "gamma"), P(b + "beta"),
-                           P(b + "moving_mean"), P(b + "moving_variance"), sc, sh, gws, BN_DECAY, BN_EPS)
+            sc, sh = self._affine(scope, cout)
+            b = scope + "/BatchNorm/"
+            ops.gram_stats(plan, xplanes, lo, M, cin, self._var(scope + "/weights"), cout, cout, self._var(b + "gamma"),
+                           self._var(b + "beta"), self._var(b + "moving_mean"), self._var(b + "moving_variance"), sc, sh,
+                           self._lane_ws("gram", tag, ops.gram_stats_workspace(M, cin)), BN_DECAY, BN_EPS)
         else:
             if training:
                 ops.conv2d_fwd_split3p_stats(plan, d, xplanes, lo, wsplit, stats, tail_ws=tail_ws)
-            ops.bn_finalize(plan, stats if training else None, rows if training else 0, cout, up4(cout),
-                            M if training else 0, P(b + "gamma"), P(b + "beta"),
-                            P(b + "moving_mean"), P(b + "moving_variance"), sc, sh, BN_DECAY, BN_EPS, training)
+            sc, sh = self._bn_finalize(plan, scope, cout, stats, rows, M, training)
         if proj is not None:
             ops.conv2d_fwd_split3p_tail_proj(plan, d, xplanes, lo, wsplit, sc, sh, proj[0], proj[1], proj[2], out_planes,
                                              lo_out, tail_ws=tail_ws)
@@ -461,85 +445,77 @@ class ResNet50Model(Model):
         ph, pw = self.pool_hw
         _, pt = ops.same_out_pad(oh, 3, 2)
         _, pl = ops.same_out_pad(ow, 3, 2)
-        cur, nxt = self.planes_a, self.planes_b
+        cur, nxt = self.arenas[0].a, self.arenas[0].b
         ops.bn_relu_maxpool_split(plan, self.raw0, sc, sh, cur, self._lo_off(N * ph * pw, 64), N, oh, ow, 64, ph, pw,
                                   pt, pl)
         h, w = ph, pw
         units = list(self._units())
-        two = self.stages == 2
+        # (without two stages no unit is the first of stage 2 or the last of stage 1)
+        first2, last1 = (self.STAGE_CUT, self.STAGE_CUT - 1) if self.stages == 2 else (None, None)
         for i, (scope, din, d, db, s) in enumerate(units):
             last = i == len(units) - 1
-            st2 = two and i >= self.STAGE_CUT
-            tag = "2" if st2 else ""
-            r1, r2, r3, asc = ((self.arena_r12, self.arena_r22, self.arena_r32, self.arena_sc2) if st2 else
-                               (self.arena_r1, self.arena_r2, self.arena_r3, self.arena_sc))
-            p1, p2 = (self.planes_12, self.planes_22) if st2 else (self.planes_1, self.planes_2)
-            if two and i == self.STAGE_CUT:
+            st = self.arenas[1 if first2 is not None and i >= first2 else 0]
+            if i == first2:
                 # stage 2 starts here: it reads the boundary tensor and ping-pongs inside its own arena
                 if training:
                     self.stage_calls = len(plan.calls)
-                cur, nxt = self.planes_x, self.planes_a2
+                cur, nxt = self.planes_x, st.a
+            nxt_out = self.planes_x if i == last1 else nxt      # the last unit of stage 1 writes the boundary tensor
+
+            def shortcut_conv(side):
+                """the unit's projection shortcut -> (its raw fp32 output, scale, shift)"""
+                _, _, ssc, tsc = self._conv_bn_planes(plan, scope + "/shortcut", cur, (h, w), din, 1, 1, d, s, "SAME",
+                                                      st.sc, training, side=side, tag=st.tag)
+                return st.sc, ssc, tsc
+
             beside = din != d and self.side_lane
             if beside:
                 # the projection shortcut reads the same planes as conv1 and meets the main branch only in the unit's
                 # last pass: it runs on the plan's side lane beside conv1 .. conv3 (their tails leave slots)
                 plan.fork()
-                _, _, ssc, tsc = self._conv_bn_planes(plan, scope + "/shortcut", cur, (h, w), din, 1, 1, d, s, "SAME",
-                                                      asc, training, side=True, tag=tag)
-            oh1, ow1, s1, t1 = self._conv_bn_planes(plan, scope + "/conv1", cur, (h, w), din, 1, 1, db, 1, "SAME",
-                                                    r1, training, tag=tag)
-            ops.bn_relu_split(plan, r1, s1, t1, 1, p1, self._lo_off(N * h * w, db), N * h * w, db)
-            oh2, ow2, s2, t2 = self._conv_bn_planes(plan, scope + "/conv2", p1, (h, w), db, 3, 3, db, s,
-                                                    "SAME" if s == 1 else 1, r2, training, tag=tag)
-            ops.bn_relu_split(plan, r2, s2, t2, 1, p2, self._lo_off(N * oh2 * ow2, db), N * oh2 * ow2, db)
-            if two and i == self.STAGE_CUT - 1:
-                nxt_out = self.planes_x          # the last unit of stage 1 writes the boundary tensor
-            else:
-                nxt_out = nxt
-            if s == 1 and not last and self._two_pass_ok((oh2, ow2), db, d):
-                # conv3 twice: the raw [N, oh, ow, d] tensor and its BN pass never exist
-                proj = None
-                if din != d:
-                    if beside:
-                        plan.join()
-                    else:
-                        _, _, ssc, tsc = self._conv_bn_planes(plan, scope + "/shortcut", cur, (h, w), din, 1, 1, d, s,
-                                                              "SAME", asc, training, tag=tag)
-                    proj = (asc, ssc, tsc)
-                self._conv3_two_pass(plan, scope + "/conv3", p2, (oh2, ow2), db, d, cur, nxt_out, training, tag=tag,
-                                     proj=proj)
-                h, w = oh2, ow2
-                if two and i == self.STAGE_CUT and training:
-                    self.stage_read_calls = len(plan.calls)
-                if two and i == self.STAGE_CUT:
-                    cur, nxt = self.planes_a2, self.planes_b2
-                else:
-                    cur, nxt = nxt, cur
-                continue
-            oh3, ow3, s3, t3 = self._conv_bn_planes(plan, scope + "/conv3", p2, (oh2, ow2), db, 1, 1, d, 1,
-                                                    "SAME", r3, training, tag=tag)
-            out_planes = None if last else nxt_out
-            out_lo = 0 if last else self._lo_off(N * oh3 * ow3, d)
-            out32 = self.xfinal if last else None
-            if din != d:
+                forked = shortcut_conv(True)
+
+            def shortcut():
+                """where the main branch needs the projection shortcut: join the side lane, or record the conv in place;
+                None for an identity unit"""
+                if din == d:
+                    return None
                 if beside:
                     plan.join()
-                else:
-                    _, _, ssc, tsc = self._conv_bn_planes(plan, scope + "/shortcut", cur, (h, w), din, 1, 1, d, s,
-                                                          "SAME", asc, training, tag=tag)
-                ops.bn_add_relu_split(plan, r3, s3, t3, asc, ssc, tsc, None, 0, out_planes, out_lo,
-                                      out32, N, oh3, ow3, d, oh3, ow3, 1)
+                    return forked
+                return shortcut_conv(False)
+
+            oh1, ow1, s1, t1 = self._conv_bn_planes(plan, scope + "/conv1", cur, (h, w), din, 1, 1, db, 1, "SAME",
+                                                    st.r1, training, tag=st.tag)
+            ops.bn_relu_split(plan, st.r1, s1, t1, 1, st.p1, self._lo_off(N * h * w, db), N * h * w, db)
+            oh2, ow2, s2, t2 = self._conv_bn_planes(plan, scope + "/conv2", st.p1, (h, w), db, 3, 3, db, s,
+                                                    "SAME" if s == 1 else 1, st.r2, training, tag=st.tag)
+            ops.bn_relu_split(plan, st.r2, s2, t2, 1, st.p2, self._lo_off(N * oh2 * ow2, db), N * oh2 * ow2, db)
+            if s == 1 and not last and self._two_pass_ok((oh2, ow2), db, d):
+                # conv3 twice: the raw [N, oh, ow, d] tensor and its BN pass never exist (the shortcut is recorded first)
+                self._conv3_two_pass(plan, scope + "/conv3", st.p2, (oh2, ow2), db, d, cur, nxt_out, training, tag=st.tag,
+                                     proj=shortcut())
             else:
-                ops.bn_add_relu_split(plan, r3, s3, t3, None, None, None, cur, self._lo_off(N * h * w, din),
-                                      out_planes, out_lo, out32, N, oh3, ow3, d, h, w, s)
-            h, w = oh3, ow3
-            if two and i == self.STAGE_CUT and training:
-                self.stage_read_calls = len(plan.calls)      # stage 2 no longer reads the boundary tensor from here on
-            if not last:
-                if two and i == self.STAGE_CUT:
-                    cur, nxt = self.planes_a2, self.planes_b2
+                # (conv3 is recorded before a shortcut conv in place: the order of the recorded calls is pinned)
+                _, _, s3, t3 = self._conv_bn_planes(plan, scope + "/conv3", st.p2, (oh2, ow2), db, 1, 1, d, 1, "SAME",
+                                                    st.r3, training, tag=st.tag)
+                out_planes = None if last else nxt_out
+                out_lo = 0 if last else self._lo_off(N * oh2 * ow2, d)
+                out32 = self.xfinal if last else None
+                proj = shortcut()
+                if proj is not None:
+                    ops.bn_add_relu_split(plan, st.r3, s3, t3, proj[0], proj[1], proj[2], None, 0, out_planes, out_lo,
+                                          out32, N, oh2, ow2, d, oh2, ow2, 1)
                 else:
-                    cur, nxt = nxt, cur
+                    ops.bn_add_relu_split(plan, st.r3, s3, t3, None, None, None, cur, self._lo_off(N * h * w, din),
+                                          out_planes, out_lo, out32, N, oh2, ow2, d, h, w, s)
+            h, w = oh2, ow2
+            if i == first2:
+                if training:
+                    self.stage_read_calls = len(plan.calls)  # stage 2 no longer reads the boundary tensor from here on
+                cur, nxt = st.a, st.b
+            else:
+                cur, nxt = nxt, cur
         fh, fw = self.feat_hw
         if training:
             # everything recorded so far is the FROZEN trunk (no trainable variable is read): the trainer may run it
@@ -547,78 +523,40 @@ class ResNet50Model(Model):
             self.frozen_calls = len(plan.calls)
         scm, tcm = self._conv_map_tap(plan, training)
         ops.bn_relu(plan, self.raw_cm, scm, tcm, self.output, N * fh * fw, 12, 12, 12)
-        if self.stats is None or self.stats.numel() < self._stats_need:
-            self.stats = self.session.zeros(self._stats_need)
-        self.lane_stats = getattr(self, "lane_stats", {})
-        for lane, need in getattr(self, "_lane_stats_need", {}).items():
-            if lane not in self.lane_stats or self.lane_stats[lane].numel() < need:
-                self.lane_stats[lane] = self.session.zeros(need)
 
     def _stem_bn(self, plan, training):
         """conv1 (7x7/2 after 3+3 explicit zero padding) + BN statistics as a row-run conv (include/acimg.h,
         acimg_conv2d_fwd_split3) on the split-MFMA kernel"""
-        st = self.session.store
-        P = lambda n: ops.LazyPtr(lambda n=n: st.p(n))  # noqa: E731
         scope = self.scope + "/conv1"
         d = self._stem_d
         rows = ops.conv2d_fwd_split3_stats_rows(d)
-        self._stats_need = max(self._stats_need, rows * 2 * 64)
-        stats = ops.LazyPtr(lambda: self.stats)
-        if scope not in self._sp3:
-            off = self._sp3_bytes
-            self._sp3[scope] = off
-            self._sp3_bytes += -(-ops.conv2d_split3_weight_bytes(d) // 256) * 256
-            ops.conv2d_split3_prepare(self.plan_prepare, d, self.stem_w, ops.LazyPtr(lambda off=off: self.wsplit[off:]))
-        off = self._sp3[scope]
-        ops.conv2d_fwd_split3(plan, d, self.stem_frame, ops.LazyPtr(lambda off=off: self.wsplit[off:]), self.raw0,
+        stats = self._lane_stats("", rows * 2 * 64)
+        ops.conv2d_fwd_split3(plan, d, self.stem_frame, self._split_image(scope, d, self.stem_w), self.raw0,
                               None, None, 0, stats if training else None)
-        if not hasattr(self, "_aff_cache"):
-            self._aff_cache = {}
-        if scope not in self._aff_cache:
-            self._aff_cache[scope] = self._new_affine(64)
-        sc, sh = self._aff_cache[scope]
-        b = scope + "/BatchNorm/"
-        ops.bn_finalize(plan, stats if training else None, rows if training else 0, 64, 64,
-                        self.N * d.OH * d.OW if training else 0, P(b + "gamma"), P(b + "beta"),
-                        P(b + "moving_mean"), P(b + "moving_variance"), sc, sh, BN_DECAY, BN_EPS, training)
+        sc, sh = self._bn_finalize(plan, scope, 64, stats, rows, self.N * d.OH * d.OW, training)
         return d.OH, d.OW, sc, sh
 
     def _conv_map_tap(self, plan, training):
         """conv_map (3x4 VALID, 2048 -> 12) + BN statistics on the split-MFMA path: one GEMM over the INPUT pixels
         with 12 taps x 12 channels = 144 columns, then a 12-tap gather (ops.tapconv_*); the kernel trains, so its
         packed / split image is rebuilt in the plan (two tiny launches)"""
-        st = self.session.store
-        P = lambda n: ops.LazyPtr(lambda n=n: st.p(n))  # noqa: E731
         cm = self.scope + "/conv_map"
         d, d1 = self._cm_d, self._cm_d1
         fh, fw = self.feat_hw
-        ops.tapconv_pack(plan, d, P(cm + "/weights"), self.cm_wt, 144)
+        ops.tapconv_pack(plan, d, self._var(cm + "/weights"), self.cm_wt, 144)
         ops.conv2d_split3_prepare(plan, d1, self.cm_wt, self.cm_wsplit)
         ops.conv2d_fwd_split3(plan, d1, self.xfinal, self.cm_wsplit, self.cm_z)
         rows = ops.tapconv_stats_rows(d)
-        # a statistics buffer of its own: conv_map is the first layer of the TRAINED part of the step, which the
-        # two-lane pipeline (acimg/trainer.py) runs beside the frozen trunk of the next batch
-        if getattr(self, "stats_cm", None) is None or self.stats_cm.numel() < rows * 2 * 12:
-            self.stats_cm = self.session.zeros(rows * 2 * 12)
-        stats = self.stats_cm
+        stats = self._lane_stats("cm", rows * 2 * 12)       # a lane of its own: see _alloc
         ops.tapconv_gather(plan, d, self.cm_z, 144, self.raw_cm, stats if training else None)
-        if not hasattr(self, "_aff_cache"):
-            self._aff_cache = {}
-        if cm not in self._aff_cache:
-            self._aff_cache[cm] = self._new_affine(12)
-        sc, sh = self._aff_cache[cm]
-        b = cm + "/BatchNorm/"
-        ops.bn_finalize(plan, stats if training else None, rows if training else 0, 12, 12,
-                        self.N * fh * fw if training else 0, P(b + "gamma"), P(b + "beta"),
-                        P(b + "moving_mean"), P(b + "moving_variance"), sc, sh, BN_DECAY, BN_EPS, training,
-                        self.save_mean, self.save_invstd)
-        return sc, sh
+        return self._bn_finalize(plan, cm, 12, stats, rows, self.N * fh * fw, training, save=True)
 
     def _record_forward(self, plan, training):
         if self._split:
             return self._record_forward_split(plan, training)
         N = self.N
         H, W = self.height, self.width
+        st = self.arenas[0]
         plan.add_hook(self._refresh_split_weights)
         ops.pad_channels(plan, self.images, self.xpad, N * H * W, 3, 4)
         oh, ow, sc, sh = self._conv_bn(plan, self.scope + "/conv1", self.xpad, (H, W), 4, 7, 7, 64, 2, 3,
@@ -626,26 +564,25 @@ class ResNet50Model(Model):
         ph, pw = self.pool_hw
         _, pt = ops.same_out_pad(oh, 3, 2)
         _, pl = ops.same_out_pad(ow, 3, 2)
-        cur, nxt = self.arena_a, self.arena_b
+        cur, nxt = st.a, st.b
         ops.bn_relu_maxpool(plan, self.raw0, sc, sh, cur, N, oh, ow, 64, ph, pw, pt, pl)
         h, w = ph, pw
         units = list(self._units())
         for i, (scope, din, d, db, s) in enumerate(units):
             last = i == len(units) - 1
             oh1, ow1, s1, t1 = self._conv_bn(plan, scope + "/conv1", cur, (h, w), din, 1, 1, db, 1, "SAME",
-                                             self.arena_r1, None, training)
-            oh2, ow2, s2, t2 = self._conv_bn(plan, scope + "/conv2", self.arena_r1, (h, w), db, 3, 3, db, s,
-                                             "SAME" if s == 1 else 1, self.arena_r2, (s1, t1), training)
-            oh3, ow3, s3, t3 = self._conv_bn(plan, scope + "/conv3", self.arena_r2, (oh2, ow2), db, 1, 1, d, 1,
-                                             "SAME", self.arena_r3, (s2, t2), training)
+                                             st.r1, None, training)
+            oh2, ow2, s2, t2 = self._conv_bn(plan, scope + "/conv2", st.r1, (h, w), db, 3, 3, db, s,
+                                             "SAME" if s == 1 else 1, st.r2, (s1, t1), training)
+            oh3, ow3, s3, t3 = self._conv_bn(plan, scope + "/conv3", st.r2, (oh2, ow2), db, 1, 1, d, 1,
+                                             "SAME", st.r3, (s2, t2), training)
             out = self.xfinal if last else nxt
             if din != d:
                 _, _, ssc, tsc = self._conv_bn(plan, scope + "/shortcut", cur, (h, w), din, 1, 1, d, s, "SAME",
-                                               self.arena_sc, None, training)
-                ops.bn_add_relu(plan, self.arena_r3, s3, t3, self.arena_sc, ssc, tsc, out, N, oh3, ow3, d,
-                                oh3, ow3, 1)
+                                               st.sc, None, training)
+                ops.bn_add_relu(plan, st.r3, s3, t3, st.sc, ssc, tsc, out, N, oh3, ow3, d, oh3, ow3, 1)
             else:
-                ops.bn_add_relu(plan, self.arena_r3, s3, t3, cur, None, None, out, N, oh3, ow3, d, h, w, s)
+                ops.bn_add_relu(plan, st.r3, s3, t3, cur, None, None, out, N, oh3, ow3, d, h, w, s)
             h, w = oh3, ow3
             if not last:
                 cur, nxt = nxt, cur
@@ -653,31 +590,27 @@ class ResNet50Model(Model):
         _, _, scm, tcm = self._conv_bn(plan, self.scope + "/conv_map", self.xfinal, (h, w), 2048, 3, 4, 12, 1,
                                        "VALID", self.raw_cm, None, training, save=True)
         ops.bn_relu(plan, self.raw_cm, scm, tcm, self.output, N * fh * fw, 12, 12, 12)
-        if self.stats is None or self.stats.numel() < self._stats_need:
-            self.stats = self.session.zeros(self._stats_need)
 
     def record_backward(self, plan):
         """conv_map backward: g(output) -> BN/ReLU backward -> weight gradient (+ L2 term).  The trunk
         below conv_map receives no gradient (it is not in var_list, trainer/mfcctrainer.py:64)."""
-        st = self.session.store
         cm = self.scope + "/conv_map"
-        P = lambda n: ops.LazyPtr(lambda n=n: st.p(n))  # noqa: E731
-        G = lambda n: ops.LazyPtr(lambda n=n: st.g(n))  # noqa: E731
         N = self.N
         fh, fw = self.feat_hw
         h, w = self.final_hw
-        ops.bn_relu_bwd(plan, self.raw_cm, self.output, self.g_output, P(cm + "/BatchNorm/gamma"),
-                        self.save_mean, self.save_invstd, self.g_raw_cm, G(cm + "/BatchNorm/gamma"),
-                        G(cm + "/BatchNorm/beta"), N * fh * fw, 12)
+        ops.bn_relu_bwd(plan, self.raw_cm, self.output, self.g_output, self._var(cm + "/BatchNorm/gamma"),
+                        self.save_mean, self.save_invstd, self.g_raw_cm, self._grad(cm + "/BatchNorm/gamma"),
+                        self._grad(cm + "/BatchNorm/beta"), N * fh * fw, 12)
         if self._split:
             # tap-GEMM form: dWt[2048][144] = xfinal^T . (tap-scattered g_raw_cm), then back to HWIO + the L2 term
             ops.tapconv_scatter(plan, self._cm_d, self.g_raw_cm, 12, self.cm_gz, 144)
             ops.conv2d_wgrad_split3(plan, self._cm_d1, self.xfinal, self.cm_gz, 144, self.cm_dwt, None)
-            ops.tapconv_unpack(plan, self._cm_d, self.cm_dwt, 144, P(cm + "/weights"), WEIGHT_DECAY, G(cm + "/weights"))
+            ops.tapconv_unpack(plan, self._cm_d, self.cm_dwt, 144, self._var(cm + "/weights"), WEIGHT_DECAY,
+                               self._grad(cm + "/weights"))
             return
         d = ops.conv_desc(N, h, w, 2048, 12, 3, 4, 1, "VALID", ldx=2048, ldy=12, ldw=12)
-        ops.conv2d_wgrad(plan, d, self.xfinal, self.g_raw_cm, 12, G(cm + "/weights"), None)
-        ops.axpy(plan, WEIGHT_DECAY, P(cm + "/weights"), G(cm + "/weights"), 3 * 4 * 2048 * 12)
+        ops.conv2d_wgrad(plan, d, self.xfinal, self.g_raw_cm, 12, self._grad(cm + "/weights"), None)
+        ops.axpy(plan, WEIGHT_DECAY, self._var(cm + "/weights"), self._grad(cm + "/weights"), 3 * 4 * 2048 * 12)
 
     def record_regularizer(self, plan, accum):
         """adds sum(w^2) over every conv kernel of the scope into accum[0] (slim l2_regularizer terms
@@ -685,9 +618,8 @@ class ResNet50Model(Model):
         (trainer/mfcctrainer.py:64), so its 23.5 M-element sum is computed when the parameters are (re)loaded and
         only added here; conv_map trains and is summed every step."""
         st = self.session.store
-        if not hasattr(self, "_trunk_ss"):
+        if self._trunk_ss is None:
             self._trunk_ss = self.session.zeros(4)
-            self._trunk_ss_version = -1
             self._plan_reg = self.session.new_plan()
             ops.zero(self._plan_reg, self._trunk_ss)
             ops.sumsq(self._plan_reg, flat_ptr(st, "trunkw"), st._sizes["trunkw"], self._trunk_ss)

@@ -48,8 +48,13 @@ def configurations(gpu=False):
     split rule (13824 / 27648 rows)."""
     gen = [dict(num_skip=0), dict(num_skip=1), dict(num_skip=2), dict(num_skip=1, embedding=True),
            dict(num_skip=1, precision="f32"), dict(num_skip=1, side_lane=False)]
-    if gpu:       # the lanes are what a CPU session cannot see: the generator's configurations alone
-        return [_keyed("trainer", kw, (16,)) for kw in gen]
+    # the trunk's variants (ResNet50Model keyword sets) under one generator.  N = 7 / 8: at 7 the 56x75 and 28x38 layers
+    # have row counts that are 8 mod 16, so every brick round-up of a split-format plane is exercised; 8 is the aligned case
+    trunk = [dict(num_skip=1, trunk=t) for t in (
+        dict(precision="f32"), dict(precision="f16"), dict(stages=1), dict(stages=1, side_lane=False), dict(gram=False),
+        dict(two_pass=False), dict(stage_cut=5), dict(two_pass_max_cin=128))]
+    if gpu:       # the lanes are what a CPU session cannot see: the generator's and the trunk's configurations alone
+        return [_keyed("trainer", kw, (16,)) for kw in gen + trunk]
     out = [_keyed("trainer", kw, (8, 16)) for kw in gen]
     for model in ("UNet", "UNetSound"):
         for precision in ("split", "bf16", "f32"):
@@ -62,6 +67,7 @@ def configurations(gpu=False):
     out.append(_keyed("class", dict(), (12, 24)))
     for mode in ("all", "fusion", "onlyaudiovideo"):
         out.append(_keyed("multi", dict(mode=mode), (2, 16)))
+    out += [_keyed("trainer", kw, (7, 8)) for kw in trunk]
     return out
 
 
@@ -87,9 +93,10 @@ def build(kind, kw, N, device):
     sess = Session(torch.device(device))
     if kind == "trainer":
         kw = dict(kw)
+        trunk = kw.pop("trunk", {})
         FLAGS.model, FLAGS.ae = "UNet", int(kw.get("embedding", False))
         ma = UNetAc(input_shape=[36, 48, 12], **kw)
-        mi = ResNet50Model(input_shape=[224, 298, 3], num_classes=None)
+        mi = ResNet50Model(input_shape=[224, 298, 3], num_classes=None, **trunk)
         tr, models = Trainer(ma, mi, session=sess), [mi, ma]
     elif kind == "vae":
         kw = dict(kw)

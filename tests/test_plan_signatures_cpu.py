@@ -51,3 +51,27 @@ def test_recorded_plans_match_the_golden(golden, key, kind, kw, N):
                                                                  mk._dump(sig[i]) if i < len(sig) else None))
         pytest.fail("%s N=%d %s: the plan's SHA-256 differs, in a call whose %d hex digits do not" % (key, N, pname, H))
     assert hashlib.sha256(mk._dump(full["plan_train"]).encode()).hexdigest() == wplans["plan_train"]["sha256"]
+
+
+def _without_workspace_sizes(sig):
+    """the signature with every shared-workspace byte count masked: a trainer's graphs share one workspace, sized by the
+    largest of them"""
+    def arg(a):
+        return {k: None for k in a} if isinstance(a, dict) and ("ws_bytes" in a or "side_ws_bytes" in a) else a
+    return [c if isinstance(c, str) else [c[0], c[1], [arg(a) for a in c[2]]] for c in sig]
+
+
+@pytest.mark.parametrize("kind,kw,N,other,fresh_N", [
+    ("trainer", dict(num_skip=1), 8, 7, 7), ("trainer", dict(num_skip=1, embedding=True), 8, 7, 7),
+    ("class", dict(), 24, 1, 12)], ids=["trainer", "trainer-embedding", "class"])
+def test_graph_for_another_batch_size_records_what_a_fresh_trainer_records(kind, kw, N, other, fresh_N):
+    """`_graph_for(other)` after a larger primary graph (replicas of the models: the same variables, new buffers and
+    plans; `other` counts frames for Trainer, clips of 12 frames for TrainerClass) records the plans a fresh trainer
+    builds at that size"""
+    tr, _, _, _ = mk.build(kind, kw, N, "cpu")
+    g = tr._graph_for(other)
+    assert g is not tr.primary and g.N == fresh_N
+    got = {p: _without_workspace_sizes(mk.signature(getattr(g, p))) for p in ("plan_train", "plan_eval")}
+    _, _, fresh, _ = mk.build(kind, kw, fresh_N, "cpu")
+    for p, sig in got.items():
+        assert sig == _without_workspace_sizes(mk.signature(getattr(fresh, p))), p
