@@ -161,6 +161,9 @@ PROTOTYPES = {
     "acimg_box_iou_workspace": (_SZ, [_I]),
     "acimg_overlay_render": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _L, _L, _I, _P, _SZ, _P]),
     "acimg_overlay_render_workspace": (_SZ, [_I]),
+    "acimg_summary_images": (_I, [_P, _I, _L, _I, _I, _I, _P, _P]),
+    "acimg_histogram_segments": (_I, [_P, _P, _I, _P, _I, _L, _P, _P, _P, _P, _SZ, _P]),
+    "acimg_histogram_segments_workspace": (_SZ, [_I, _I, _L]),
     "acimg_knn_topk": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "acimg_knn_topk_workspace": (_SZ, [_I, _I, _I, _I]),
     "acimg_knn_vote": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),

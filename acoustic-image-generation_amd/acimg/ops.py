@@ -875,6 +875,21 @@ def overlay_render(plan, frames, ldf, logen, boxes, lut_base, lut_over, alpha_nu
              _WsBytes(plan.ws))
 
 
+def summary_images(plan, x, ldc, HW, c0, G, n_images, out):
+    """tf.summary.image on float input (trainer/mfcctrainer.py:278-297): x [N,HW,ldc] float32 -> out uint8
+    [n_images,G,HW,3], group g = channels c0 + 3g .. c0 + 3g + 2 normalised over the slice's finite values"""
+    plan.add("summary_images", _L().acimg_summary_images, x, int(ldc), int(HW), int(c0), int(G), int(n_images), out)
+
+
+def histogram_segments(plan, base, segments, V, limits, L, total_elements, counts, stats, nonfinite):
+    """TF's summary histogram of V boxes of the flat fp32 buffer `base`: segments int64 [V,13] (offset, dims[4], lo[4],
+    hi[4]) and limits float64 [L] on the device -> counts uint64 [V,L] (int64 tensors hold them), stats float64 [V,4] =
+    min, max, sum, sum of squares, nonfinite uint64 [V]"""
+    plan.ws.require(_L().acimg_histogram_segments_workspace(int(V), int(L), int(total_elements)))
+    plan.add("histogram_segments", _L().acimg_histogram_segments, base, segments, int(V), limits, int(L),
+             int(total_elements), counts, stats, nonfinite, _WsPtr(plan.ws), _WsBytes(plan.ws))
+
+
 def knn_topk(plan, query, ldq, Q, gallery, ldg, G, D, K, dist2, idx):
     """exact K nearest gallery rows per query row (retrieve.py:53-57, knn.py:102-104): fp64 [Q,ldq] / [G,ldg] ->
     dist2 float64 [Q,K], idx int32 [Q,K] ascending by (dist2, index); -1 / +inf past G"""

@@ -12,8 +12,17 @@ One step = ONE recorded plan of C-ABI kernel launches on fixed device buffers:
   zero loss sums -> tile -> trunk forward (BN batch statistics, moving averages advance) ->
   generator forward -> reconstruction loss (+ its gradient) -> L2 regulariser -> loss scalars ->
   generator backward -> conv_map backward -> [bucketed RCCL all-reduce, overlapped] -> Adam (1 launch).
-The eight TensorBoard image summaries the reference evaluates every step (:278-297,343-344) are not
-part of the step; scalars are returned as a dict.
+The recorded plans hold the step alone; scalars are returned as a dict.
+
+The reference's TensorBoard log (:255-297,343-357,373-378) is written while `trainer.logger` is a `logger.Logger`
+(None, the default: nothing below runs and `train()` is what it was).  On every step with step % display_freq == 0
+`train()` writes, at event step = `global_step` after that batch's update: the scalars l2_loss / l1_loss / train_loss /
+latent_loss (by FLAGS.MSE, FLAGS.huber_loss, --ae), the eight images mfcc0..3 (target) and reconstructed0..3 (the
+training-mode forward output) of image 0 of the batch, channel groups 0-2 .. 9-11, and - `log_histograms` - one histogram
+per trainable TF variable after that step's Adam update; per epoch `valid_loss` at step = epoch.  The images are
+rendered and the histograms reduced ON THE DEVICE (ops.summary_images, ops.histogram_segments), behind the trained part
+on its stream, for the displayed batches only, outside the recorded plans; they are read back when the batch's losses
+are.  Data parallel: only the writer rank (`dp.is_writer`) is given a logger.
 """
 import os
 from collections import OrderedDict
@@ -23,6 +32,7 @@ import torch
 
 from . import _lib, dp, ops
 from .flags import FLAGS
+from .logger import histogram_fields
 from .session import Graph, Session, draw_noise, loss_dict, write_saver_bundle
 from .unet_acresnet import Z
 
@@ -59,6 +69,11 @@ class Trainer(object):
         # (profiles/r03/pipeline_lane_priority_r03al.txt)
         self.lane_priority = 0
         self._saved = []               # the checkpoints _save_checkpoint keeps (Saver(max_to_keep=11))
+        self.logger = None             # a logger.Logger: train() writes the reference's TensorBoard summaries
+        self.log_histograms = False    # with a logger: also one histogram per trainable TF variable
+        self._rendered = {}            # tag of a displayed batch -> what _render_summaries left on the device for it
+        self._summary_plan = None      # eager plan (and workspace) of the summary launches
+        self._hist_table = None        # (names, segments, limits, total elements) of the trainable variables
 
     # ------------------------------------------------------------------------------------------------
     # graph construction
@@ -208,11 +223,12 @@ class Trainer(object):
             self._noise_calls += 1
             draw_noise(self.session, g.eps, self.noise_seed, self._noise_calls * 65536)
 
-    def train_step(self, batch=None, eps=None, sync=True, probe=None):
+    def train_step(self, batch=None, eps=None, sync=True, probe=None, tag=None):
         """One optimisation step (the body of the reference's hot loop, trainer/mfcctrainer.py:343-349).
         batch: (acoustic [N,36,48,12], mfcc [N,12], video [N,224,298,3], ...) or None to reuse the
         tensors already resident in the graph's input buffers.  Returns {mse, huber, latent, reg, loss}
-        (python floats; sync=False returns the device tensor instead and does not block)."""
+        (python floats; sync=False returns the device tensor instead and does not block).  tag: with a logger, render
+        this batch's summaries behind the step (`train()` reads them back under that tag)."""
         g = self.primary if batch is None else self._graph_for(int(batch[1].reshape(-1, 12).shape[0]))
         self.flush_pipeline()
         if batch is not None:
@@ -237,6 +253,8 @@ class Trainer(object):
             scale = self.comm.grad_scale
         self.global_step += 1
         self.session.adam_step(self.learning_rate, self.global_step, grad_scale=scale)
+        if tag is not None and self.logger is not None:
+            self._rendered[tag] = self._render_summaries(g)
         if not sync:
             return g.losses
         return self._scalars(g)
@@ -367,6 +385,8 @@ class Trainer(object):
             if acc is None and item.get("tag") is not None:
                 # a private copy of this batch's losses (the graph's buffer is rewritten by the next batch)
                 pipe["finished"].append((item["tag"], g.losses[:5].clone()))
+                if self.logger is not None:
+                    self._rendered[item["tag"]] = self._render_summaries(g)
             pipe["ev"]["b"].record(pipe["sb"])
         pipe["recorded"].add("b")
 
@@ -534,6 +554,110 @@ class Trainer(object):
     def _scalars(self, g):
         return loss_dict(g.losses)
 
+    # ---- TensorBoard summaries (trainer/mfcctrainer.py:255-297,343-357) ---------------------------------------------
+    def _histogram_table(self):
+        """built once: the TF names of the trainable variables and, on the device, their boxes in the flat trainable
+        buffer (13 int64 each: offset, internal dims, lo, hi; a fused head is a column box of the shared matrix) and TF's
+        default bucket limits"""
+        if self._hist_table is None:
+            from . import events
+            store = self.session.store
+            names, rows, total = [], [], 0
+
+            def seg(var, lo, hi):
+                dims = list(var.shape) + [1] * (4 - len(var.shape))
+                return [var.offset] + dims + list(lo) + [0] * (4 - len(lo)) + list(hi) + [1] * (4 - len(hi))
+
+            fused_internal = set()
+            for h in store.fused:
+                fused_internal.update((h.kernel.name, h.bias.name))
+                rows_k = h.hh * h.hw * h.cp
+                for i, name in enumerate(h.tf_names):          # n0 kernel, n0 bias [, n1 kernel, n1 bias]
+                    c_lo = (i // 2) * h.z
+                    names.append(name)
+                    if i % 2 == 0:
+                        rows.append([h.kernel.offset, h.hh * h.hw, h.cp, h.kernel.shape[1], 1,
+                                     0, 0, c_lo, 0, h.hh * h.hw, h.cin, c_lo + h.z, 1])
+                        assert h.kernel.shape[0] == rows_k, (h.kernel.shape, rows_k)
+                        total += h.kernel.numel
+                    else:
+                        rows.append(seg(h.bias, (c_lo,), (c_lo + h.z,)))
+                        total += h.bias.numel
+            for name, v in store.vars.items():
+                if v.group == "train" and name not in fused_internal:
+                    names.append(name)
+                    rows.append(seg(v, (0,) * len(v.tf_shape), v.tf_shape))
+                    total += v.numel
+            dev = self.session.device
+            limits = events.default_bucket_limits()
+            self._hist_table = (names, torch.tensor(rows, dtype=torch.int64, device=dev),
+                                torch.tensor(limits, dtype=torch.float64, device=dev), int(total), limits)
+        return self._hist_table
+
+    def _render_summaries(self, g):
+        """on the CURRENT stream, behind the step that just ran on it: the eight [36,48,3] images of image 0 of the batch
+        (4 channel groups of the target, 4 of the generated image) into a fresh uint8 tensor and, with `log_histograms`,
+        the histograms of the flat trainable buffer (after this step's Adam update) into fresh tensors.  Nothing is read
+        back here."""
+        dev = self.session.device
+        if self._summary_plan is None:
+            self._summary_plan = ops.Plan(dev, eager=True)
+        plan = self._summary_plan
+        images = torch.empty((8, 36, 48, 3), dtype=torch.uint8, device=dev)
+        ops.summary_images(plan, g.acoustic, 12, 36 * 48, 0, 4, 1, images[:4])
+        ops.summary_images(plan, g.modelac.output, 12, 36 * 48, 0, 4, 1, images[4:])
+        out = dict(step=self.global_step, images=images, stream=torch.cuda.current_stream(dev), hist=None)
+        if self.log_histograms:
+            names, table, limits, total, _ = self._histogram_table()
+            V, L = len(names), limits.numel()
+            counts = torch.empty((V, L), dtype=torch.int64, device=dev)
+            stats = torch.empty((V, 4), dtype=torch.float64, device=dev)
+            bad = torch.empty((V,), dtype=torch.int64, device=dev)
+            ops.histogram_segments(plan, self.session.store.flat["train"], table, V, limits, L, total, counts, stats, bad)
+            out["hist"] = (counts, stats, bad)
+        return out
+
+    def _register_summaries(self):
+        """the registrations of trainer/mfcctrainer.py:266-297 (+ the variables' histograms), merged"""
+        lg = self.logger
+        if lg.summary_op is not None:
+            return
+        if FLAGS.MSE:
+            lg.log_scalar('l2 loss', "mse")
+        if FLAGS.huber_loss:
+            lg.log_scalar('l1 loss', "huber")
+        lg.log_scalar('train_loss', "loss")
+        if not FLAGS.ae:
+            lg.log_scalar('latent_loss', "latent")       # losses[2]: FLAGS.latent_loss * mean KL, the weighted term
+        for i in range(4):
+            lg.log_image('mfcc{}'.format(i), i, max_outputs=1)
+        for i in range(4):
+            lg.log_image('reconstructed{}'.format(i), 4 + i, max_outputs=1)
+        if self.log_histograms:
+            for v, name in enumerate(self._histogram_table()[0]):
+                lg.log_histogram(name + ":0", v)
+        lg.merge_summary()
+
+    def _write_summaries(self, losses, rendered):
+        """read one displayed batch's images (and histograms) back behind the stream that rendered them and write the
+        step's summary"""
+        with torch.cuda.stream(rendered["stream"]):
+            images = rendered["images"].cpu().numpy()
+            hist = None if rendered["hist"] is None else [t.cpu().numpy() for t in rendered["hist"]]
+        names = limits = None
+        if hist is not None:
+            names, _, _, _, limits = self._histogram_table()
+
+        def fetch(kind, source):
+            if kind == "scalar":
+                return losses[source]
+            if kind == "image":
+                return images[source:source + 1]
+            counts, stats, bad = hist
+            return histogram_fields(names[source] + ":0", counts[source], stats[source], bad[source], limits)
+
+        self.logger.write_summary(self.logger.summary(fetch), rendered["step"])
+
     def eval_step(self, batch=None, eps=None):
         """forward in inference mode (BN moving statistics); returns mse + the four per-3-channel MSEs"""
         g = self.primary if batch is None else self._graph_for(int(batch[1].reshape(-1, 12).shape[0]))
@@ -639,6 +763,8 @@ class Trainer(object):
             self._save_checkpoint(session, 'random')
         start_epoch = int(self.global_step)
         best_epoch, best_loss = -1, 10000
+        if self.logger is not None:
+            self._register_summaries()
         for epoch in range(start_epoch, start_epoch + self.num_epochs):
             step = 0
             pipelined = self.modelimages._split and FLAGS.pipeline
@@ -647,6 +773,8 @@ class Trainer(object):
                 if i % self.display_freq == 0:
                     self.log('{}: {} - Iteration: [{:3}]\t Training_mse_Loss: {:6f}\t Training_Loss: {:6f}'.format(
                         datetime.now(), FLAGS.exp_name, i, r["mse"], r["loss"]))
+                    if self.logger is not None:
+                        self._write_summaries(r, self._rendered.pop(i))
 
             for next_batch in train_data.data:
                 acoustic, mfcc, images, _, _ = self._retrieve_batch(next_batch)
@@ -658,7 +786,8 @@ class Trainer(object):
                     for i, r in self.pop_finished():
                         report(i, r)
                 else:
-                    report(step, self.train_step((acoustic, mfcc, images)))
+                    report(step, self.train_step((acoustic, mfcc, images),
+                                                 tag=step if step % self.display_freq == 0 else None))
                 step += 1
             if pipelined:
                 self.flush_pipeline()
@@ -672,6 +801,10 @@ class Trainer(object):
             total_loss = self._evaluate(session, 'validation', valid_data)
             self.log('{}: {} - Epoch: {}\t Validation_mse_Loss: {:6f}'.format(datetime.now(), FLAGS.exp_name, epoch,
                                                                               total_loss))
+            if self.logger is not None:
+                from . import events
+                self.logger.write_summary([events.scalar_value("valid_loss", total_loss)], epoch)
+                self.logger.flush_writer()
             if FLAGS.checkpoint_dir is not None:
                 if epoch % 10 == 0:
                     self._save_checkpoint(session, epoch)

@@ -682,6 +682,53 @@ int acimg_overlay_render(const float* frames, int ldf, const float* logen, const
                          long image_bytes, int N, void* ws, size_t ws_bytes, void* stream);
 size_t acimg_overlay_render_workspace(int N);
 
+/* ------------------------------------------------------------------------------------------
+ * TensorBoard summaries (acimg/logger.py, the logger of trainer/mfcctrainer.py:255-297,343-357): the two reductions that
+ * turn device tensors into summary values without copying the tensors to the host.  (Added without raising
+ * ACIMG_VERSION: nothing existing changed, and the number is pinned by the host tests.)
+ * ---------------------------------------------------------------------------------------- */
+/* tf.summary.image on float input (TF 1.x NormalizeFloatImage, restated, not pinned), three channels at a time.
+ * x: images of HW pixels of ldc floats, image n at x + n * HW * ldc.  For every image n < n_images and group g < G the
+ * slice S = channels c0 + 3g .. c0 + 3g + 2 of that image's HW pixels is rendered, in fp32:
+ *   image_min, image_max = min / max over the FINITE values of S (+inf / -inf when there is none)
+ *   image_min < 0:  m = max(|image_min|, |image_max|), scale = m < 1e-6f ? 0 : 127 / m, offset = 128
+ *   otherwise:      scale = image_max < 1e-6f ? 0 : 255 / image_max, offset = 0          (IEEE-correct divisions)
+ *   a pixel with a non-finite channel -> (255, 0, 0)
+ *   every other channel value v -> (uint8) trunc(v * scale + offset): an fp32 multiply FOLLOWED BY an fp32 add, two
+ *   roundings, never one fused operation (the source is compiled with contraction off); the integer is clamped to
+ *   0 .. 255, which no finite v of S leaves.
+ * out: uint8 [n_images][G][HW][3], dense, any alignment.  0 <= c0, c0 + 3G <= ldc, HW, G, n_images >= 1, no null
+ * pointer: otherwise ACIMG_EINVAL before the launch.  ONE launch, one workgroup per (image, group): the reduction (min
+ * and max: the same value in any order), then the store pass with plain vector-memory byte stores.  No atomics, no
+ * workspace, stream-ordered, bit-identical from run to run. */
+int acimg_summary_images(const float* x, int ldc, long HW, int c0, int G, int n_images, uint8_t* out, void* stream);
+
+/* TF's summary histogram (histogram/histogram.cc, restated) of V boxes of one flat fp32 buffer in one launch sequence.
+ * segments: V records of 13 int64 ON THE DEVICE: offset (floats from `base`), dims[4] (row-major internal dims, unused
+ *   trailing dims 1), lo[4], hi[4]: the elements with lo[k] <= coordinate[k] < hi[k] for every k are the VALUES of the
+ *   segment; the others (zero pads, another variable's columns) are read and ignored.  lo / hi are clamped to the dims; a
+ *   record with a non-positive dim or a negative offset is an empty segment.
+ * limits: L ascending doubles on the device, used as given.  Per segment v:
+ *   counts[v][b]   uint64 [V][L]: values whose bucket is b = the index of the first limit greater than (double)value
+ *                  (std::upper_bound; numpy.searchsorted(limits, value, side="right")); a value not below the last
+ *                  limit is counted in bucket L - 1 (TF's table ends with DBL_MAX)
+ *   stats[v]       double [V][4] = {min, max, sum, sum_squares} over the values, in fp64; {+inf, -inf, 0, 0} if none
+ *   nonfinite[v]   uint64 [V]: values that are NaN or +-inf; they are left out of counts and stats
+ * fp32 denormals are values, not zeros.  counts, min and max are exact; sum and sum_squares are summed in a fixed order
+ * (per thread, lanes, waves, 8192-element chunks, then one workgroup per segment): bit-identical from run to run.  The
+ * counters are privatised in LDS and reach `counts` through 64-bit INTEGER atomics; there is no floating atomic.
+ * total_elements: the sum over the records of dims[0] * dims[1] * dims[2] * dims[3], the CALLER's promise (the host
+ *   cannot see the table): it sizes the workspace, and the chunks of a table that holds more are not read.
+ * PRECONDITION: every [offset, offset + product of dims) lies inside the buffer at `base`.
+ * ws: 8-byte aligned, the workspace query's bytes (pure host arithmetic; 0 for a non-positive argument); short =
+ * ACIMG_EWORKSPACE.  V, L, total_elements >= 1, L <= 4096, no null pointer: otherwise ACIMG_EINVAL.  Every refusal
+ * precedes the first launch.  Three launches on `stream`: zero + chunk prefix, partial histograms (16-byte loads where
+ * dims[3] % 4 == 0 and base + offset is 16-byte aligned, scalar loads otherwise), per-segment finish. */
+int acimg_histogram_segments(const float* base, const int64_t* segments, int V, const double* limits, int L,
+                             long total_elements, uint64_t* counts, double* stats, uint64_t* nonfinite, void* ws,
+                             size_t ws_bytes, void* stream);
+size_t acimg_histogram_segments_workspace(int V, int L, long total_elements);
+
 /* Exact K nearest gallery rows of every query row, fp64 (what retrieve.py:53-57 computes with scipy cdist + argsort per
  * anchor, and knn.py:102-104 with KNeighborsClassifier(n_neighbors=15).kneighbors):
  *   dist2[q][j] = sum_d (query[q][d] - gallery[g][d])^2, summed in fp64 in direct-difference form (not the
