@@ -74,3 +74,22 @@ def box_iou(energy, boxes):
     m2 = resize_mask(energy_mask(energy))
     num, den, iou = score(m2, boxes)
     return num, den, iou, m2
+
+
+def boxes_of(*quads):
+    """(xmin, xmax, ymin, ymax) per annotator -> [4,3] int32"""
+    b = np.zeros((4, 3), np.int32)
+    for k, q in enumerate(quads):
+        b[:, k] = q
+    return b
+
+
+def random_boxes(rng, N):
+    """[N,4,3] int32 boxes that reach past the frame, some with reversed corners, some annotators absent"""
+    b = rng.randint(-30, 330, size=(N, 4, 3)).astype(np.int32)
+    b[:, 2:] = rng.randint(-30, 250, size=(N, 2, 3))
+    rev = rng.rand(N, 3) < 0.2                           # reversed corners
+    b[:, 0][rev], b[:, 1][rev] = b[:, 1][rev], b[:, 0][rev].copy()
+    off = rng.rand(N, 3) < 0.25
+    b[:, 1][off] = 0                                     # xmax == 0: that annotator is absent
+    return b

@@ -2,6 +2,9 @@
 the frame in float32 with every product and sum rounded on its own, the 3-pixel box outlines painted as 1, the energy map
 resized to the frame in float64 (`localize_ref.linear_coefs`: cv2.resize's INTER_LINEAR), each layer autoscaled, indexed
 as matplotlib indexes a colormap (trunc(t * 256), 256 -> 255, a flat layer -> 0) and blended in integer arithmetic."""
+import struct
+import zlib
+
 import numpy as np
 
 from localize_ref import FRAME_H, FRAME_W, linear_coefs
@@ -73,3 +76,25 @@ def render(frame, energy, lut_base, lut_over, boxes=None, alpha=(7, 10)):
         g[outline_mask(boxes)] = np.float32(1.0)
     v = resize_map(energy)
     return blend(colorize(g, lut_base), colorize(v, lut_over), alpha)
+
+
+def read_png(data):
+    """a reader for what write_png promises: signature, chunk CRCs, IHDR 8-bit RGB, one IDAT, filter 0 on every line"""
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    pos, chunks = 8, []
+    while pos < len(data):
+        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        (crc,) = struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])
+        assert crc == zlib.crc32(kind + body) & 0xFFFFFFFF, kind
+        chunks.append((kind, body))
+        pos += 12 + n
+    assert pos == len(data)
+    assert [k for k, _ in chunks] == [b"IHDR", b"IDAT", b"IEND"] and chunks[2][1] == b""
+    w, h, depth, ctype, comp, flt, lace = struct.unpack(">IIBBBBB", chunks[0][1])
+    assert (depth, ctype, comp, flt, lace) == (8, 2, 0, 0, 0)
+    raw = zlib.decompress(chunks[1][1])
+    assert len(raw) == h * (1 + 3 * w)
+    rows = np.frombuffer(raw, np.uint8).reshape(h, 1 + 3 * w)
+    assert not rows[:, 0].any()
+    return rows[:, 1:].reshape(h, w, 3)

@@ -80,3 +80,16 @@ def retrieval(features, features1, labels, numcl):
     rates = [1.0 * ranks[r] / G for r in (1, 2, 5, 10, 30)]
     text = "Accuracy {:6f} rank2 {:6f} rank5 {:6f} rank10 {:6f} rank30 {:6f}".format(*rates)
     return text, ranks, cm1, cm5, cm10
+
+
+def int_features(rng, Q, G, D):
+    """integer-valued queries and gallery (every distance exact in any order) with duplicated rows and zero distances"""
+    q = rng.randint(-8, 9, size=(Q, D)).astype(np.float64)
+    g = rng.randint(-8, 9, size=(G, D)).astype(np.float64)
+    if G > 1:
+        dup = rng.randint(0, G, size=(G // 3, 2))     # duplicated gallery rows: exact ties broken by index
+        g[dup[:, 0]] = g[dup[:, 1]]
+    if G > 2 and Q > 0:
+        g[-1] = q[0]                                  # a zero distance
+        g[G // 2] = q[0]
+    return q, g

@@ -485,3 +485,66 @@ def impulse_operands(case):
     o.gy = torch.where(keep, o.gy, torch.zeros_like(o.gy))
     o.npix = len(px)
     return o
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the activation-plane layout (include/acimg.h, "Pre-split activation format"): two fp16 planes, hi at byte 0 and lo at
+# lo_off, each of whole 16-pixel x 32-channel bricks of 1 KiB
+# ----------------------------------------------------------------------------------------------------------------------
+def plane_bytes(rows, Cc):
+    """bytes of one split-format plane: whole 16-pixel x 32-channel bricks"""
+    return -(-rows // 16) * 16 * Cc * 2
+
+
+def brick_index(rows, Cc):
+    """fp16 element index inside a split-format plane of every element of a [rows, C] tensor, row-major: brick (row >> 4,
+    c >> 5) of 1 KiB, inside it row & 15 at 64 bytes and 16-byte group (c >> 3) & 3 at group ((c >> 3) ^ -(row >> 2)) & 3"""
+    r = torch.arange(rows).view(-1, 1)
+    c = torch.arange(Cc).view(1, -1)
+    off = ((r >> 4) * (Cc // 32) + (c >> 5)) * 1024 + (r & 15) * 64 + ((((c >> 3) ^ (-(r >> 2))) & 3) << 4) + (c & 7) * 2
+    return (off // 2).reshape(-1)
+
+
+def unsplit(planes, lo_off, rows, Cc):
+    """two fp16 planes in LDS-tile order (uint8 buffer) -> float64 [rows, C] (undoing the 2^-2 scale)"""
+    idx = brick_index(rows, Cc).to(planes.device)
+    n = plane_bytes(rows, Cc)
+    hi = planes[:n].view(torch.float16)[idx].double()
+    lo = planes[lo_off: lo_off + n].view(torch.float16)[idx].double()
+    return ((hi + lo) * 4.0).reshape(rows, Cc).cpu()
+
+
+def valid_halves(buf, lo_off, rows, Cc):
+    """the valid rows' fp16 elements of both planes as int16 (bit patterns), row-major"""
+    idx = brick_index(rows, Cc).to(buf.device)
+    n = plane_bytes(rows, Cc)
+    return torch.cat([buf[o:o + n].view(torch.int16)[idx] for o in (0, lo_off)])
+
+
+# what the bytes of split planes outside the valid rows' elements may hold (include/acimg.h: unspecified): fp16 NaN, and a
+# large finite value (0x7b7b = 6.2e4 per half, 2.5e5 after the x4 scale) that a ReLU or a max cannot hide; (fill byte, gap
+# between the hi plane's end and lo_off)
+POISONS = ((0xFF, 0), (0x7B, 4096))
+
+
+def repack(planes, lo_off, rows, Cc, fill, gap=0, slack=4096):
+    """a copy of split-format planes that keeps only the valid rows' elements: every other byte - the pad rows of the last
+    brick row, a `gap`-byte hole between the planes, `slack` bytes after the lo plane - holds `fill`.  -> (buffer, lo_off)"""
+    n = plane_bytes(rows, Cc)
+    lo2 = n + gap
+    out = torch.full((lo2 + n + slack,), fill, dtype=torch.uint8, device=planes.device)
+    idx = brick_index(rows, Cc).to(planes.device)
+    for src, dst in ((0, 0), (lo_off, lo2)):
+        out[dst:dst + n].view(torch.float16)[idx] = planes[src:src + n].view(torch.float16)[idx]
+    return out, lo2
+
+
+def make_planes(plan, device, x, rows, Cc, relu=0):
+    """split planes of x [.., C] (identity affine) through ops.bn_relu_split, in a zeroed buffer: (planes, lo_off)"""
+    from acimg import ops
+
+    lo = plane_bytes(rows, Cc)
+    planes = torch.zeros(2 * lo, dtype=torch.uint8, device=device)
+    ops.bn_relu_split(plan, x.reshape(rows, Cc).float().contiguous().to(device), torch.ones(Cc, device=device),
+                      torch.zeros(Cc, device=device), relu, planes, lo, rows, Cc)
+    return planes, lo

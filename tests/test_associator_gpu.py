@@ -1,6 +1,7 @@
 """Latent associators and joint-latent fusion MLPs (models/multimodal.py) and the
 single-associator step of trainer/trainer_proietta.py against the frozen unet_z decoder: outputs, losses and every
 gradient vs the fp64 oracle, through the C ABI; only the associator's variables move."""
+import functools
 import os
 import sys
 from collections import OrderedDict
@@ -13,12 +14,13 @@ for p in (ROOT, os.path.join(ROOT, "acoustic-image-generation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from model_support import noconc_masks  # noqa: E402
+from op_support import rel_err  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 
 @pytest.mark.parametrize("which", ["AssociatorVideoAc", "AssociatorAudioAc"])
@@ -29,7 +31,6 @@ def test_associator_step(which):
     from acimg.unet_acoustic import UNetAcZ
     from oracle import multimodal as om
     from oracle import unet_acoustic as oa
-    from tests.test_unet_acoustic_gpu import _masks
 
     dev = torch.device("cuda:0")
     N = 6
@@ -55,7 +56,7 @@ def test_associator_step(which):
         if not last:
             masks_a[name] = (y[:, :d.K] > 0).cpu()
     p = {k: v.clone().requires_grad_(True) for k, v in pa.items()}
-    ref = om.step_loss(p, which, pd, x, eps, stats[:, :din], stats[:, din:], masks_a, _masks(md))
+    ref = om.step_loss(p, which, pd, x, eps, stats[:, :din], stats[:, din:], masks_a, noconc_masks(md))
     assert rel(ma.mean, ref["mean"].detach()) < 1e-4 and rel(ma.std, ref["std"].detach()) < 1e-4
     assert rel(md.output, ref["output"].detach()) < 1e-4
     for k in ("mse", "huber", "latent", "loss"):
@@ -151,7 +152,6 @@ def test_conv_associator_audio_step():
     from oracle import multimodal as om
     from oracle import unet_acoustic as oa
     from oracle import unet_vae as ouv
-    from tests.test_unet_acoustic_gpu import _masks
 
     dev = torch.device("cuda:0")
     N = 4
@@ -181,7 +181,7 @@ def test_conv_associator_audio_step():
     assert rel(ma.mean, free["mean"]) < 1e-4 and rel(ma.std, free["std"]) < 1e-4       # forward vs the free-running oracle
     p = {k: v.clone().requires_grad_(True) for k, v in pa.items()}
     ref = om.step_loss_audio(p, pd, spec, x, eps, {k: v.reshape(free["masks_a"][k].shape) for k, v in masks_a.items()},
-                             _masks(md))
+                             noconc_masks(md))
     assert rel(ma.mean, ref["mean"].detach()) < 1e-4 and rel(ma.std, ref["std"].detach()) < 1e-4
     assert rel(md.output, ref["output"].detach()) < 1e-4
     for k in ("mse", "huber", "latent", "reg", "loss"):

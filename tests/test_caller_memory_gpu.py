@@ -23,52 +23,23 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from caller_memory_cases import DECONV_CASES, DGRAD_CASES, FWD_CASES, RTOL, WGRAD_CASES
 from guard_arena import CANARY, GuardArena
+from localize_ref import random_boxes
+from op_support import close_at, conv_geom, raw_lib, tf_conv_ref, up4, widen
+from retrieval_ref import int_features
+from split_format_ref import brick_index, make_planes, plane_bytes, unsplit
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 2e-5            # tests/test_ops_gpu.py: exact-f32 MFMA paths against fp64
 STATS_TOL = 2e-4       # ... and its batch-norm partial sums (fp32 sums of many signed terms)
 SENT = 0x7B            # 0x7B7B7B7B = 1.3e36 as a float, 2071690107 as an int: finite, never a result
 WS_FILL = 0xFF         # NaN in every float format
-
-
-def _lib():
-    from acimg import _lib as m
-    return m, m.load()
-
-
-def close(got, ref, tol=RTOL, what=""):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    err = (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-12)
-    print("%s: rel err %.3e (tol %.1e)" % (what, err, tol))
-    assert np.isfinite(err) and err <= tol, "%s: rel err %.3e > %.1e" % (what, err, tol)
+close = close_at(RTOL, show=True)
 
 
 def f32(g, *shape, scale=1.0):
     return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).float()
-
-
-def tf_conv_ref(x, w, stride, pads, bias=None):
-    xt = F.pad(x.permute(0, 3, 1, 2), (pads[2], pads[3], pads[0], pads[1]))
-    return F.conv2d(xt, w.permute(3, 2, 0, 1), bias, stride=stride).permute(0, 2, 3, 1)
-
-
-def geom(H, W, R, S, stride, padding):
-    def same(size, k, s):
-        out = -(-size // s)
-        tot = max((out - 1) * s + k - size, 0)
-        return out, tot // 2, tot - tot // 2
-    if padding == "SAME":
-        OH, pt, pb = same(H, R, stride)
-        OW, pl, pr = same(W, S, stride)
-        return OH, OW, (pt, pb, pl, pr)
-    return (H - R) // stride + 1, (W - S) // stride + 1, (0, 0, 0, 0)
-
-
-def up4(v):
-    return (v + 3) & ~3
 
 
 def last_lt(shape, n):
@@ -124,7 +95,7 @@ def _bits(t):
 
 def run_case(device, case, what):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     st = ops.current_stream_handle(device)
     q = case.query
     tbytes = 4 * ops.TICKET_WORDS
@@ -245,43 +216,15 @@ def run_case(device, case, what):
 def conv_inputs(case, seed, wscale=0.1):
     N, H, W, Cc, K, R, S, stride, padding = case
     g = torch.Generator().manual_seed(seed)
-    OH, OW, pads = geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     x, w, b = f32(g, N, H, W, Cc), f32(g, R, S, Cc, K, scale=wscale), f32(g, K)
     gy, res, mask = f32(g, N, OH, OW, K), f32(g, N, H, W, Cc), f32(g, N, H, W, Cc)
     return g, OH, OW, pads, x, w, b, gy, res, mask
 
 
-def padded(t, ld, fill=float("nan")):
-    """[..., C] -> fp32 [..., ld]; the pad columns are never read: NaN there would show"""
-    out = torch.full((*t.shape[:-1], ld), fill, dtype=torch.float32)
-    out[..., : t.shape[-1]] = t
-    return out
-
-
-# (shape, act, stats, branch, tolerance of y; the existing test of that path)
-FWD_CASES = OrderedDict([
-    # split-K (64x64 tiles, 9 K ranges): test_splitk_handoff_equals_reduce_launch, 1e-5
-    ("splitk_reduce_launch", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), 1, False, "splitk", 1e-5)),
-    ("splitk_handoff", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), 1, False, "splitk+tickets", 1e-5)),
-    # split-K + statistics (the small pass over y afterwards): test_conv2d_fwd_affine_stats_slice's path
-    ("splitk_stats", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), 0, True, "splitk+tickets", 1e-5)),
-    # 8 K steps per tap... kiters = 2 < 8: never split, query 0 (test_conv2d_fwd CONV_CASES[3])
-    ("unsplit_query0", ((2, 13, 10, 64, 32, 1, 1, 1, "SAME"), 1, True, "unsplit", RTOL)),
-    # K = 12 <= 16: the 256x16 tile, split 6 ways (CONV_CASES[5])
-    ("tile_256x16", ((2, 14, 19, 64, 12, 3, 4, 1, "VALID"), 1, False, "256x16", RTOL)),
-    # the VAE heads' dense layer on the skinny kernels: test_skinny_dense_gradients, 2e-6
-    ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), 0, False, "skinny", 2e-6)),
-    # few-channel MFMA (act NONE, >= 65536 pixels), one statistics row per workgroup: test_few_channel_mfma_conv_matches_fp64
-    ("few_channel_mfma", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), 0, True, "few16", 2e-6)),
-    # the direct kernel (ReLU keeps it off the MFMA form) and its stride-2 form: test_few_channel_direct_conv
-    ("direct_relu", ((2, 200, 180, 8, 8, 3, 3, 1, "SAME"), 1, True, "direct", RTOL)),
-    ("direct_stride2", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), 0, True, "direct", RTOL)),
-])
-
-
 def fwd_case(device, name, configure=None):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     shape, act, with_stats, branch, tol = FWD_CASES[name]
     N, H, W, Cc, K, R, S, stride, padding = shape
     g, OH, OW, pads, x, w, b, _, _, _ = conv_inputs(shape, 11 + sum(v for v in shape if isinstance(v, int)),
@@ -331,34 +274,9 @@ def test_conv2d_fwd_caller_memory(device, name):
     run_case(device, fwd_case(device, name), "conv2d_fwd[%s]" % name)
 
 
-# (shape, residual, mask, tickets, branch, tolerance; the existing test of that path)
-DGRAD_CASES = OrderedDict([
-    # stride-1 split-K, both combine forms: test_splitk_handoff_equals_reduce_launch / test_conv2d_dgrad_wgrad
-    ("s1_splitk_reduce_launch", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), True, True, False, RTOL)),
-    ("s1_splitk_handoff", ((4, 12, 16, 128, 128, 3, 3, 1, "SAME"), True, True, True, RTOL)),
-    # stride == R == S, no padding: patch scatter (query 0 at this size)
-    ("patch_scatter", ((2, 36, 48, 16, 32, 3, 3, 3, "SAME"), True, True, True, RTOL)),
-    # stride 2, >= 16 channels written: the sub-pixel form (combined weights + its own split-K slabs)
-    ("subpixel_3x3_same", ((1, 16, 20, 64, 64, 3, 3, 2, "SAME"), True, True, True, RTOL)),
-    ("subpixel_2x3_valid", ((2, 12, 15, 32, 32, 2, 3, 2, "VALID"), True, True, False, RTOL)),
-    # stride 2, 8 channels written: zero-inserted copy of gy in the workspace, then the stride-1 form behind it
-    ("dilated_3x3_same", ((2, 17, 23, 8, 8, 3, 3, 2, "SAME"), True, True, True, RTOL)),
-    ("dilated_3x2_valid", ((2, 15, 18, 8, 16, 3, 2, 2, "VALID"), True, True, False, RTOL)),
-    # >= 65536 pixels: the few-channel MFMA form reads the zero-inserted view itself (no mask): test_few_channel_direct_conv, 3e-5
-    ("few_channel_stride2", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), True, False, False, 3e-5)),
-    # ... and with a ReLU mask neither MFMA nor direct form applies: dilated copy, then the implicit GEMM (exact f32)
-    ("dilated_then_igemm_65536", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), True, True, True, 3e-5)),
-    # 112x149 8 -> 32: the 16-row instance of the halo kernel (test_few_channel_mfma_conv_matches_fp64 (3,147,161,8,32), 3e-5)
-    ("halo16_narrow", ((4, 112, 149, 8, 32, 3, 3, 1, "SAME"), True, True, False, 3e-5)),
-    # not 3x3, <= 16 gy channels, >= 65536 pixels, no mask: the direct kernel (3e-5 as its stride-2 cases)
-    ("direct", ((2, 200, 190, 8, 16, 2, 3, 1, "VALID"), True, False, False, 3e-5)),
-    ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), True, True, False, 2e-6)),
-])
-
-
 def dgrad_case(device, name):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     shape, with_res, with_mask, tickets, tol = DGRAD_CASES[name]
     N, H, W, Cc, K, R, S, stride, padding = shape
     small = name in ("halo16_narrow", "few_channel_stride2", "dilated_then_igemm_65536")
@@ -375,8 +293,8 @@ def dgrad_case(device, name):
     ref = gx + (res.double() if with_res else 0)
     if with_mask:
         ref = ref * (mask > 0).double()
-    gyd, wd = padded(gy, ldgy).to(device), w.to(device)
-    resd, maskd = padded(res, Cc + 8).to(device), padded(mask, Cc + 4).to(device)
+    gyd, wd = widen(gy, ldgy).to(device), w.to(device)
+    resd, maskd = widen(res, Cc + 8).to(device), widen(mask, Cc + 4).to(device)
     outs = OrderedDict(dx=Out(torch.float32, (N, H, W, lddx), last_lt((N, H, W, lddx), Cc)))
 
     def call(ws, nb, p, tick):
@@ -394,32 +312,9 @@ def test_conv2d_dgrad_caller_memory(device, name):
     run_case(device, dgrad_case(device, name), "conv2d_dgrad[%s]" % name)
 
 
-# (shape, entry, tolerance; the existing test of that path)
-WGRAD_CASES = OrderedDict([
-    # 128 columns: 128-column tiles, 18 slabs (test_conv2d_dgrad_wgrad (2,18,24,256,128), RTOL; split3: 3e-5 as
-    # test_wgrad_split3_geometries)
-    ("cols128_f32", ((2, 18, 24, 256, 128, 3, 3, 1, "SAME"), "f32", RTOL)),
-    ("cols128_split3", ((2, 18, 24, 256, 128, 3, 3, 1, "SAME"), "split3", 3e-5)),
-    # 133 (padded 136) and 144 columns: 64-column tiles
-    ("cols133_f32", ((8, 12, 16, 128, 133, 3, 3, 1, "SAME"), "f32", RTOL)),
-    ("cols144_f32", ((8, 12, 16, 128, 144, 3, 3, 1, "SAME"), "f32", RTOL)),
-    ("cols144_split3", ((8, 12, 16, 128, 144, 3, 3, 1, "SAME"), "split3", 3e-5)),
-    # few channels through the fp32 entry onto the halo-16 kernel, 512 slabs: test_few_channel_wgrad_on_the_halo16_kernel, 2e-5
-    ("few_channel_halo", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), "f32", 2e-5)),
-    # 32 -> 32 at 112x149 on the halo-16 kernel, 256 slabs ("one slab per CU"): test_wgrad_halo16_matches_fp64, 4e-5 / 2e-5
-    ("halo16_split3", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "split3", 4e-5)),
-    ("halo16_bf16", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "bf16", 2e-5)),
-    # ... with the producer's batch norm applied on load: test_batch_norm_affine_applied_while_staging, 2e-5 against the same
-    # entry on the materialised tensor
-    ("halo16_affine_split3", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "affine1", 2e-5)),
-    ("few_channel_affine", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), "affine0", 2e-5)),
-    ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), "f32", 2e-6)),
-])
-
-
 def wgrad_case(device, name):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     shape, entry, tol = WGRAD_CASES[name]
     N, H, W, Cc, K, R, S, stride, padding = shape
     g, OH, OW, pads, x, w, b, gy, _, _ = conv_inputs(shape, 3 + sum(v for v in shape if isinstance(v, int)))
@@ -437,7 +332,7 @@ def wgrad_case(device, name):
         scd, shd = scale.to(device), shift.to(device)
     rnd_ = (lambda t: t.to(torch.bfloat16).double()) if entry == "bf16" else (lambda t: t.double())   # bf16: fp64 of the ROUNDED operands
     xd = x.to(device)
-    gyd = padded(gy, ldgy, 0.0).to(device)           # columns K .. kp are operands (zero); beyond kp never read
+    gyd = widen(gy, ldgy, fill=0.0).to(device)           # columns K .. kp are operands (zero); beyond kp never read
     gyd[..., kp:] = float("nan")
     st = ops.current_stream_handle(device)
     if affine:
@@ -489,19 +384,9 @@ def test_conv2d_wgrad_caller_memory(device, name):
     run_case(device, wgrad_case(device, name), "conv2d_wgrad[%s]" % name)
 
 
-# (shape, tolerances fwd / dgrad / wgrad; test_deconv: RTOL, test_deconv_dgrad_few_channels_direct: 2e-6 / 3e-5 / 2e-5)
-DECONV_CASES = OrderedDict([
-    ("scatter_gap_fill", ((2, 12, 16, 128, 128, 2, 2, 3), RTOL, RTOL, RTOL)),       # kernel < stride: gaps receive the bias
-    ("subpixel", ((2, 7, 9, 64, 32, 2, 3, 2), RTOL, RTOL, RTOL)),                   # kernel > stride, >= 16 outputs
-    ("dilated", ((2, 6, 8, 32, 8, 3, 3, 2), RTOL, RTOL, RTOL)),                     # kernel > stride, 8 outputs: zero-inserted x
-    ("pointwise_patch2", ((5, 112, 149, 32, 8, 2, 2, 2), 2e-6, 3e-5, 2e-5)),        # patch2_32x8 kernels, one slab per workgroup
-    ("direct_dgrad", ((2, 190, 180, 8, 8, 2, 2, 2), RTOL, 3e-5, RTOL)),             # <= 16 gy channels, >= 65536 pixels, no mask
-])
-
-
 def deconv_cases(device, name):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     shape, tol_f, tol_d, tol_w = DECONV_CASES[name]
     N, H, W, Cc, K, R, S, s = shape
     g = torch.Generator().manual_seed(77 + N + Cc)
@@ -518,7 +403,7 @@ def deconv_cases(device, name):
     mask = f32(g, N, H, W, Cc)
     with_mask = name != "direct_dgrad"
     q = int(L.acimg_deconv_workspace(C.byref(d)))
-    xd, wd, bd, gyd, maskd = x.to(device), w.to(device), b.to(device), padded(gy, ldy).to(device), mask.to(device)
+    xd, wd, bd, gyd, maskd = x.to(device), w.to(device), b.to(device), widen(gy, ldy).to(device), mask.to(device)
     st = ops.current_stream_handle(device)
     keep = (xd, wd, bd, gyd, maskd, d)
     fwd = Case(q, OrderedDict(y=Out(torch.float32, (N, OH, OW, ldy), last_lt((N, OH, OW, ldy), K))),
@@ -555,7 +440,7 @@ def test_queries_follow_the_tuning_record(device):
     counts (split-K towards 96 workgroups instead of 768: 4 K ranges over 24 tiles instead of 9; 64 pixels per slab
     instead of 128: 19 slabs instead of 12): the queries must move with the launches"""
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     dflt = (int(L.acimg_conv2d_fwd_workspace(C.byref(ops.conv_desc(4, 12, 16, 128, 128, 3, 3, 1, "SAME")))),
             ops.conv2d_fwd_tiling(ops.conv_desc(4, 12, 16, 128, 128, 3, 3, 1, "SAME"))[2],
             int(L.acimg_conv2d_wgrad_workspace(C.byref(ops.conv_desc(8, 12, 16, 128, 144, 3, 3, 1, "SAME", ldw=148)))))
@@ -575,39 +460,6 @@ def test_queries_follow_the_tuning_record(device):
 # =====================================================================================================================
 # pre-split planes: split3p / split1p / stats / tail / tail_proj with the tail-split workspace; gram_stats
 # =====================================================================================================================
-def plane_bytes(rows, Cc):
-    return -(-rows // 16) * 16 * Cc * 2
-
-
-def brick_index(rows, Cc):
-    r = torch.arange(rows).view(-1, 1)
-    c = torch.arange(Cc).view(1, -1)
-    off = ((r >> 4) * (Cc // 32) + (c >> 5)) * 1024 + (r & 15) * 64 + ((((c >> 3) ^ (-(r >> 2))) & 3) << 4) + (c & 7) * 2
-    return (off // 2).reshape(-1)
-
-
-def unsplit(planes, lo_off, rows, Cc):
-    idx = brick_index(rows, Cc).to(planes.device)
-    n = plane_bytes(rows, Cc)
-    hi = planes[:n].view(torch.float16)[idx].double()
-    lo = planes[lo_off: lo_off + n].view(torch.float16)[idx].double()
-    return ((hi + lo) * 4.0).reshape(rows, Cc).cpu()
-
-
-def make_planes(device, x2d):
-    """split-format planes of a [rows, C] tensor through the library's own producer"""
-    from acimg import ops
-    m, L = _lib()
-    rows, Cc = x2d.shape
-    lo = plane_bytes(rows, Cc)
-    planes = torch.zeros(2 * lo, dtype=torch.uint8, device=device)
-    xd, one, zero = x2d.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device)
-    m.check(L.acimg_bn_relu_split(xd.data_ptr(), one.data_ptr(), zero.data_ptr(), 1, planes.data_ptr(), lo, rows, Cc,
-                                  ops.current_stream_handle(device)), "bn_relu_split")
-    torch.cuda.synchronize()
-    return planes, lo
-
-
 PRESPLIT_SHAPES = OrderedDict([("3x3_128_128", (8, 56, 75, 128, 128, 3, 3)), ("1x1_256_1024", (32, 28, 38, 256, 1024, 1, 1))])
 # acimg_conv2d_fwd_split3_tiling under the default tuning record: (BM, BN, kernel: 0 one tile per workgroup, 1 persistent,
 # 2 ring).  No query exposes whether the tail split engages for a shape: that it needs the workspace at all shows only in
@@ -623,7 +475,7 @@ def test_presplit_conv_caller_memory(device, shape, entry):
     bn_pass), 2e-4 statistics sums; split1p (operands keep 11 bits) against fp64 of the hi planes' values at the 2e-6 of
     test_fp16_operand_storage_conv"""
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     N, H, W, Cc, K, R, S = PRESPLIT_SHAPES[shape]
     g = torch.Generator().manual_seed(3 + Cc + K)
     x = torch.rand(N, H, W, Cc, generator=g)
@@ -631,7 +483,7 @@ def test_presplit_conv_caller_memory(device, shape, entry):
     d = ops.conv_desc(N, H, W, Cc, K, R, S, 1, "SAME")
     rows = N * H * W
     st = ops.current_stream_handle(device)
-    xp, lo_x = make_planes(device, x.reshape(rows, Cc))
+    xp, lo_x = make_planes(ops.Plan(device, eager=True), device, x, rows, Cc, relu=1)
     wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
     m.check(L.acimg_conv2d_split3_prepare(C.byref(d), w.to(device).data_ptr(), wsplit.data_ptr(), st), "prepare")
     torch.cuda.synchronize()
@@ -683,7 +535,7 @@ def test_presplit_conv_caller_memory(device, shape, entry):
         assert rows % 16 == 0                                # no pad rows: every byte of both planes is documented
         outs = OrderedDict(planes=Out(torch.uint8, (2 * lo_y,)))
         if entry == "tail":
-            sp, _ = make_planes(device, short.reshape(rows, K))
+            sp, _ = make_planes(ops.Plan(device, eager=True), device, short, rows, K, relu=1)
             shortcut = unsplit(sp, lo_y, rows, K)
 
             def call(ws, nb, p, tick):
@@ -708,7 +560,7 @@ def test_presplit_conv_caller_memory(device, shape, entry):
 def test_gram_stats_caller_memory(device, shape):
     """acimg_gram_stats: scale / shift at 3e-6, moving averages at 2e-6 (test_gram_statistics_match_fp64); a short
     workspace is refused (tests/test_host_cpu.py::test_gram_stats_host_side: ACIMG_EINVAL)"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     rows, Cc, K = shape
     g = torch.Generator().manual_seed(11 + rows % 97 + Cc)
@@ -718,7 +570,7 @@ def test_gram_stats_caller_memory(device, shape):
     w[:, :K] = torch.randn(Cc, K, generator=g) * (2.6 / Cc) ** 0.5
     gamma, beta = torch.rand(K, generator=g) + 0.5, torch.rand(K, generator=g) - 0.5
     mm0, mv0 = torch.randn(K, generator=g) * 0.1, torch.rand(K, generator=g) + 0.5
-    xp, lo = make_planes(device, x)
+    xp, lo = make_planes(ops.Plan(device, eager=True), device, x, rows, Cc, relu=1)
     xv = unsplit(xp, lo, rows, Cc).double()
     y = xv @ w[:, :K].double()
     mean = y.mean(0)
@@ -751,7 +603,7 @@ def test_gram_stats_caller_memory(device, shape):
 def test_minmax_caller_memory(device):
     """acimg_minmax_fwd / _bwd, 1728 pixels x 133 channels (32 chunks per sample), the output a slice at column 4 of a
     wider buffer: forward RTOL, mm exact, backward 1e-4 (test_minmax_float)"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     N, P, Cn, ldx, ldo, off = 2, 1728, 133, 136, 148, 4
     g = torch.Generator().manual_seed(P + Cn)
@@ -763,7 +615,7 @@ def test_minmax_caller_memory(device):
     q = int(L.acimg_minmax_workspace(N, P, Cn))
     assert q == N * 32 * 2 * 4
     st = ops.current_stream_handle(device)
-    xd = padded(x.detach(), ldx).to(device)
+    xd = widen(x.detach(), ldx).to(device)
     cols = torch.arange(ldo)
     omask = ((cols >= off) & (cols < off + Cn)).expand(N, P, ldo)
     outs = OrderedDict(out=Out(torch.float32, (N, P, ldo), omask), mm=Out(torch.float32, (N + 2, 4), first_lt((N + 2, 4), N)))
@@ -793,7 +645,7 @@ def test_minmax_caller_memory(device):
 def test_bn_bwd_caller_memory(device):
     """acimg_bn_bwd at 2 x 224 x 298 rows x 32 channels (256 partial blocks): gx RTOL, dgamma / dbeta 1e-4
     (test_bn_bwd_float); short = ACIMG_EWORKSPACE (test_bn_bwd_workspace_refused)"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     rows, Cn, ld = 133504, 32, 36
     g = torch.Generator().manual_seed(rows + Cn)
@@ -812,7 +664,7 @@ def test_bn_bwd_caller_memory(device):
     gx = gamma * invstd * (gm - dbeta / rows - xhat * (dgamma / rows))
     q = int(L.acimg_bn_bwd_workspace(rows, Cn))
     st = ops.current_stream_handle(device)
-    xd, gyd = padded(x, ld).to(device), padded(gy, ld).to(device)
+    xd, gyd = widen(x, ld).to(device), widen(gy, ld).to(device)
     pv = [t.float().to(device) for t in (scale, shift, mean, invstd, gamma)]
     outs = OrderedDict(gx=Out(torch.float32, (rows, ld), last_lt((rows, ld), Cn)), dgamma=Out(torch.float32, (Cn + 4,), first_lt((Cn + 4,), Cn)),
                        dbeta=Out(torch.float32, (Cn + 4,), first_lt((Cn + 4,), Cn)))
@@ -833,7 +685,7 @@ def test_triplet_caller_memory(device, hard):
     """acimg_triplet_loss_fwd + _bwd, B = 300 (several row blocks): the forward leaves the backward's state in the workspace,
     so it is poisoned before the forward only and both calls are guarded.  Tolerances of test_triplet_random: loss and
     fraction 1e-4, counts, gradients 1e-3"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     from oracle import triplet as ot
     B, D, ld = 300, 64, 68
@@ -845,7 +697,7 @@ def test_triplet_caller_memory(device, hard):
     ga, gb = torch.autograd.grad(loss, [a, b])
     q = ops.triplet_loss_workspace(B)
     st = ops.current_stream_handle(device)
-    ad, bd = padded(e0, ld).to(device), padded(e1, ld).to(device)
+    ad, bd = widen(e0, ld).to(device), widen(e1, ld).to(device)
     lab, sc = labels.int().to(device), scenario.int().to(device)
     outs = OrderedDict(out=Out(torch.float32, (8,), first_lt((8,), 4)), g0=Out(torch.float32, (B, ld), last_lt((B, ld), D)),
                        g1=Out(torch.float32, (B, ld), last_lt((B, ld), D)))
@@ -873,7 +725,7 @@ def test_triplet_caller_memory(device, hard):
 def test_filtfilt_caller_memory(device):
     """acimg_filtfilt, 150 rows (more than one workgroup) of 1024 float32 samples: bit-identical to SciPy
     (test_lowpass_filtfilt_matches_reference_golden)"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     from acimg.frontend import butter_lowpass, lfilter_zi
     from scipy import signal
@@ -896,10 +748,9 @@ def test_filtfilt_caller_memory(device):
 def test_box_iou_caller_memory(device):
     """acimg_box_iou, 64 samples, all optional outputs: counts and mask exact, IoU to 1e-7 (tests/test_localize_gpu.py); a
     short workspace is ACIMG_EWORKSPACE, a NULL one a null argument (ACIMG_EINVAL), as tests/test_host_cpu.py pins them"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     import localize_ref as lref
-    from test_localize_gpu import random_boxes
     N = 64
     rng = np.random.RandomState(N)
     logen = (rng.rand(N, 36, 48) * rng.rand(N, 1, 1) * 3).astype(np.float32)
@@ -930,14 +781,13 @@ def test_box_iou_caller_memory(device):
 def test_knn_topk_caller_memory(device, Q, G, D, K):
     """acimg_knn_topk on integer-valued features (exact: tests/test_retrieval_gpu.py), the gallery cut into slabs that meet
     in the workspace, and a small gallery (K > G: -1 / +inf slots); include/acimg.h: short = ACIMG_EWORKSPACE"""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     import retrieval_ref as rref
-    from test_retrieval_gpu import int_features
     rng = np.random.RandomState(Q * 7 + G + D + K)
     qf, gf = int_features(rng, Q, G, D)
     want_d, want_i = rref.kneighbors(qf, gf, K)
-    qd, gd = padded(torch.from_numpy(qf), D + 3).double().to(device), padded(torch.from_numpy(gf), D + 5).double().to(device)
+    qd, gd = widen(torch.from_numpy(qf), D + 3).double().to(device), widen(torch.from_numpy(gf), D + 5).double().to(device)
     qd[:, :D], gd[:, :D] = torch.from_numpy(qf).to(device), torch.from_numpy(gf).to(device)
     q = int(L.acimg_knn_topk_workspace(Q, G, D, K))
     st = ops.current_stream_handle(device)
@@ -955,7 +805,7 @@ def test_loss_scratch_caller_memory(device):
     """acimg_recon_loss / acimg_sumsq with the dedicated scratch (zeroed once, as the header demands; its ticket back at
     zero after every call): 327 683 elements reach the workgroup cap.  RTOL (test_recon_loss_float, test_sumsq).  Without the
     scratch the header documents float atomics: the NULL run is compared at that tolerance instead of bit for bit."""
-    m, L = _lib()
+    m, L = raw_lib()
     from acimg import ops
     count = 327683
     g = torch.Generator().manual_seed(3)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import classify_ref
-from test_loader_cpu import FakePool
+from data_support import FakePool
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------

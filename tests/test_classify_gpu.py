@@ -2,6 +2,7 @@
 between guard bands, the loaders' clip mode against their frame mode on the same GZIP record files, the baseline
 sources of `TrainerClass` against the CPU oracle, its train / test loops and Saver-V2 bundles, the `Trainer` bundle's bytes
 across the extraction of the shared writer, and `python -m acimg.classify --mode compare` against the trainers."""
+import functools
 import json
 import os
 import re
@@ -13,14 +14,14 @@ import torch
 
 import classify_ref
 from guard_arena import GuardArena
-from test_loader_gpu import _write_records
-from test_ops_gpu import close
-from test_small_ops_gpu import dyadic, strided
-from test_trainer_surface_gpu import make
+from data_support import write_outdoor_records
+from model_support import make
+from op_support import close_at, dyadic, rel_err, widen
 
 pytestmark = pytest.mark.gpu
 
 K10 = 10
+close = close_at(2e-5)           # tests/test_ops_gpu.py RTOL
 
 
 @pytest.fixture(autouse=True)
@@ -73,7 +74,7 @@ def test_clip_eval(device, case):
     if K > 1 and clips >= 2:
         assert ref["clip_pred"][0] == labels[0] and ref["clip_pred"][1] < labels[1]      # the tie went to the lower index
     ldl = K + 3
-    ld = strided(logits, ldl, float("nan")).to(device)
+    ld = widen(logits, ldl, fill=float("nan")).to(device)
     lab = labels.to(torch.int32).to(device)
     nstate = lib.acimg_clip_eval_state_bytes(K)
     assert nstate == 32 + 4 * K * K
@@ -155,7 +156,7 @@ def records(device, tmp_path_factory):
     """three GZIP files of one 12-frame record each (classes 2, 5, 8) and the 36 frames the frame-mode host loader makes
     of them (computed once, never written to)"""
     from acimg.data import TFRecordDataLoader
-    paths = _write_records(tmp_path_factory.mktemp("clips"))
+    paths = write_outdoor_records(tmp_path_factory.mktemp("clips"), 11, [(2 + 3 * r, 7 + r) for r in range(3)], wide=True)
     (frames,) = list(TFRecordDataLoader(paths, 64, device=device).data)
     assert frames[0].shape[0] == 36
     return paths, frames
@@ -236,9 +237,7 @@ def test_frame_mode_is_unchanged(device, records):
 
 
 # ---- the baseline sources ------------------------------------------------------------------------------------------------
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 
 def _baseline(device, source, lr=1e-3, epochs=1, K=K10):

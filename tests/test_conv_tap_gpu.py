@@ -10,11 +10,11 @@ inside NaN-filled buffers, so anything read from outside the tensor shows.  Shap
 on the per-tap kernel; the per-element bounds of tests/split_format_ref.py hold both forms over the stated operand range."""
 import functools
 
-import numpy as np
 import pytest
 import torch
 
 import conv_tap_cases as ct
+import op_support
 import split_format_ref as sf
 
 pytestmark = pytest.mark.gpu
@@ -23,16 +23,7 @@ FWD_TOL, BWD_TOL = 2e-6, 3e-5      # tests/test_ops_gpu.py::test_split3_generato
 GSCALE = 1e-7
 SENT = 1.25e30
 GUARD = 4096                       # NaN floats in front of and behind x / gy
-
-
-def close(got, ref, tol, what=""):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    scale = max(ref.abs().max().item(), 1e-12)
-    err = (got - ref).abs().max().item() / scale
-    print("%s: rel err %.3e (tol %.1e)" % (what, err, tol))
-    assert np.isfinite(err) and err <= tol, "%s: rel err %.3e > %.1e" % (what, err, tol)
+close = functools.partial(op_support.close, show=True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,7 +38,7 @@ def reference(N, H, W, Cc, K):
     return dict(x=x, w=w, b=b, gy=gy, res=res, mask=mask, sc=sc, y=sf.conv_fwd(x, w) + b, dx=sf.conv_dgrad(gy, w))
 
 
-def guarded(t, ld, device):
+def nan_guarded(t, ld, device):
     """[N, H, W, n] -> an ops.Ptr to the tensor with row pitch ld inside a NaN-filled buffer (NaN in the columns past n too)"""
     from acimg import ops
 
@@ -89,7 +80,7 @@ def run_fwd(device, case, ldx=None, affine=False, stats=False, check=True):
         x = torch.relu(ref["x"] * ref["sc"])
     if stats:
         kw["stats"] = torch.zeros(ops.conv2d_fwd_split3_stats_rows(d), 2, K, device=device)
-    ops.conv2d_fwd_split3(plan, d, guarded(ref["x"], ldx, device), wf, ops.Ptr(ybuf, K), bias=ref["b"].float().to(device), **kw)
+    ops.conv2d_fwd_split3(plan, d, nan_guarded(ref["x"], ldx, device), wf, ops.Ptr(ybuf, K), bias=ref["b"].float().to(device), **kw)
     torch.cuda.synchronize()
     assert bool((ybuf[..., :K] == SENT).all()), "the lower half of the concat buffer was written"
     y = ybuf[..., K:]
@@ -111,7 +102,7 @@ def run_dgrad(device, case, ldg=None, fused=True, check=True):
     plan, wt = prepared(device, d, ref["w"], dgrad=True)
     dx = torch.full((N, H, W, lddx), SENT, device=device)
     args = (ref["res"].float().to(device), Cc, ref["mask"].float().to(device), Cc) if fused else ()
-    ops.conv2d_dgrad_split3(plan, d, guarded(ref["gy"], ldg, device), ldg, wt, dx, *args, lddx=lddx)
+    ops.conv2d_dgrad_split3(plan, d, nan_guarded(ref["gy"], ldg, device), ldg, wt, dx, *args, lddx=lddx)
     torch.cuda.synchronize()
     assert bool((dx[..., Cc:] == SENT).all()), "columns past C of dx were written"
     got = dx[..., :Cc]
@@ -203,7 +194,7 @@ def test_replay_and_old_kernel(device):
 
 
 # ---- per-element bounds over the stated operand range (tests/conv_tap_cases.py, tests/split_format_ref.py) -------------------
-def held(what, got, ref, bound):
+def tap_held(what, got, ref, bound):
     r = sf.max_ratio(got, ref, bound)
     print("RATIO %s | %.4f" % (what, r))
     assert r <= 1.0, "%s: %.4f of the bound" % (what, r)
@@ -220,7 +211,7 @@ def test_forward_per_element_bound(device, name):
     y = torch.full((N, H, W, K), float("nan"), device=device)
     ops.conv2d_fwd_split3(plan, d, o.x.to(device), wf, y)
     torch.cuda.synchronize()
-    held("conv tap f16x3 forward | " + name, y, ref, bound)
+    tap_held("conv tap f16x3 forward | " + name, y, ref, bound)
 
 
 def test_dgrad_per_element_bound(device):
@@ -233,4 +224,4 @@ def test_dgrad_per_element_bound(device):
     dx = torch.full((N, H, W, Cc), float("nan"), device=device)
     ops.conv2d_dgrad_split3(plan, d, o.gy.to(device), K, wt, dx)
     torch.cuda.synchronize()
-    held("conv tap bf16x3 data gradient", dx, ref, bound)
+    tap_held("conv tap bf16x3 data gradient", dx, ref, bound)

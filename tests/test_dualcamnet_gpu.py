@@ -1,6 +1,7 @@
 """DualCamNet classifier head (BASELINE configs[4]): parity of forward, clip-level softmax
 cross-entropy, accuracy and every gradient against the CPU oracle (fp64), and the classifier-on-generated-images
 train step of trainer/trainer_reconstructed_class.py end to end."""
+import functools
 import os
 import sys
 
@@ -13,12 +14,12 @@ for p in (ROOT, os.path.join(ROOT, "acoustic-image-generation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from op_support import rel_err  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 
 def test_dualcamnet_forward_backward():

@@ -32,16 +32,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_support import exact, pad_last, up4, widen
+
 pytestmark = pytest.mark.gpu
 
 LIM = float(2 ** 24)
 NAN = float("nan")
 A = (1, 229, 287)
 B = (2, 181, 182)
-
-
-def up4(v):
-    return (v + 3) & ~3
 
 
 def ints(g, lo, hi, *shape):
@@ -53,31 +51,8 @@ def sparse_signs(g, *shape):
     return (torch.rand(*shape, generator=g) < 1.0 / 16).double() * (2 * torch.randint(0, 2, shape, generator=g).double() - 1)
 
 
-def exact(got, ref, what):
-    """bit-for-bit agreement with the fp64 reference; on a mismatch, say which cells differ (they name the tile, tap or row)"""
-    got = got.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    if not torch.equal(got, ref):
-        bad = got != ref            # (NaN != anything)
-        first = [(tuple(i), got[tuple(i)].item(), ref[tuple(i)].item()) for i in bad.nonzero()[:8].tolist()]
-        raise AssertionError("%s: %d of %d elements differ; (index, got, ref): %s" % (what, int(bad.sum()), bad.numel(), first))
-
-
-def untouched(t, what):
+def still_nan(t, what):
     assert bool(torch.isnan(t).all()), "%s: written to" % what
-
-
-def in_slice(t, ld, off, device, fill=NAN):
-    """t [..., c] as channels off .. off + c of a [..., ld] device buffer whose other channels hold `fill`"""
-    buf = torch.full(tuple(t.shape[:-1]) + (ld,), fill, dtype=torch.float32)
-    buf[..., off:off + t.shape[-1]] = t.float()
-    return buf.to(device)
-
-
-def pad_last(t, n):
-    out = torch.zeros(*t.shape[:-1], n, dtype=t.dtype)
-    out[..., : t.shape[-1]] = t
-    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -151,8 +126,8 @@ def test_wgrad_halo_exact(device, case, opset):
     ref_db = pad_last(gy.sum((0, 1, 2)), Kp)
 
     ldx, xoff, ldgy, goff, ldw = Cc + 8, 4, Kp + 8, 4, Kp + 4
-    xd = in_slice(x, ldx, xoff, device)
-    gyd = in_slice(pad_last(gy, Kp), ldgy, goff, device)       # (the layer's own pad channels K..up4(K) are zeros)
+    xd = widen(x, ldx, xoff).to(device)
+    gyd = widen(pad_last(gy, Kp), ldgy, goff).to(device)       # (the layer's own pad channels K..up4(K) are zeros)
     d = ops.conv_desc(N, H, W, Cc, K, R, S, 1, padding, ldx=ldx, ldw=ldw)
     assert (d.OH, d.OW, d.pad_t, d.pad_l) == (OH, OW, pads[0], pads[2])
 
@@ -165,13 +140,13 @@ def test_wgrad_halo_exact(device, case, opset):
         dw, db = dw.cpu(), db.cpu()
         what = "%s %s, %s" % (name, opset, what)
         exact(dw[:KK, :Kp], ref_dw, what + ": dw[kk][n]")
-        untouched(dw[KK:], what + ": dw rows past R S C")
-        untouched(dw[:, Kp:], what + ": dw columns past up4(K)")
+        still_nan(dw[KK:], what + ": dw rows past R S C")
+        still_nan(dw[:, Kp:], what + ": dw columns past up4(K)")
         if with_db:
             exact(db[:Kp], ref_db, what + ": db")
-            untouched(db[Kp:], what + ": db past up4(K)")
+            still_nan(db[Kp:], what + ": db past up4(K)")
         else:
-            untouched(db, what + ": db (not asked for)")
+            still_nan(db, what + ": db (not asked for)")
         return dw, db
 
     dw1, db1 = run("one tile per workgroup")
@@ -237,7 +212,7 @@ def test_direct_conv_1x1(device, case, opset):
     assert pre.shape == (N, OH, OW, K)
 
     ldx, xoff, ldy, yoff = Cc + 4, 4, Kp + 8, 4
-    xd = in_slice(x, ldx, xoff, device)
+    xd = widen(x, ldx, xoff).to(device)
     wd = pad_last(w, Kp).float().reshape(1, 1, Cc, Kp).to(device)
     bd = pad_last(b, Kp).float().to(device)
     plan = ops.Plan(device, eager=True)
@@ -250,8 +225,8 @@ def test_direct_conv_1x1(device, case, opset):
         torch.cuda.synchronize()
         y = y.cpu()
         what = "1x1 %s %s act %d" % (name, opset, act)
-        untouched(y[..., :yoff], what + ": channels before the slice")
-        untouched(y[..., yoff + Kp:], what + ": channels past up4(K)")
+        still_nan(y[..., :yoff], what + ": channels before the slice")
+        still_nan(y[..., yoff + Kp:], what + ": channels past up4(K)")
         exact(y[..., yoff + K:yoff + Kp], torch.zeros(N, OH, OW, Kp - K, dtype=torch.float64), what + ": channels K..up4(K)")
         return y[..., yoff:yoff + K], what
 
@@ -322,7 +297,7 @@ def test_direct_conv_data_gradient(device, case, opset):
     ref = dgrad(gy, w, res)
 
     ldgy, goff, lddx, xoff = Kp + 4, 4, Cc + 8, 4
-    gyd = in_slice(pad_last(gy, Kp), ldgy, goff, device)
+    gyd = widen(pad_last(gy, Kp), ldgy, goff).to(device)
     wd = pad_last(w, Kp).float().to(device)
     dx = torch.full((N, H, W, lddx), NAN, device=device)
     d = ops.conv_desc(N, H, W, Cc, K, R, S, 1, padding)
@@ -333,5 +308,5 @@ def test_direct_conv_data_gradient(device, case, opset):
     dx = dx.cpu()
     what = "data gradient %s %s" % (name, opset)
     exact(dx[..., xoff:xoff + Cc], ref, what)
-    untouched(dx[..., :xoff], what + ": channels before the slice")
-    untouched(dx[..., xoff + Cc:], what + ": channels past C")
+    still_nan(dx[..., :xoff], what + ": channels before the slice")
+    still_nan(dx[..., xoff + Cc:], what + ": channels past C")

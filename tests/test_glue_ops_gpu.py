@@ -14,6 +14,7 @@ last element hold a sentinel.
 Min-max normalisation: constant samples (max == min) divide by zero exactly as the TensorFlow graph does; they are out
 of scope and kept out of the inputs.
 """
+import functools
 import math
 
 import numpy as np
@@ -22,15 +23,17 @@ import torch
 import torch.nn.functional as F
 
 import randn_ref as rr
-from test_ops_gpu import close, dev, rnd, same_pads
-from test_small_ops_gpu import (SENTINEL, assert_exact_sum, assert_f32, bits_equal, bn_bwd_dyadic_inputs, bn_bwd_ref,
-                                dyadic, exact, pads_untouched, rel_err, strided)
+import op_support
+from op_support import (SENTINEL, assert_exact_sum, assert_f32, bits_equal, bn_bwd_dyadic_inputs, bn_bwd_ref, close_at, dev, dyadic,
+                        exact, pads_untouched, rnd, same_pads, widen)
 
 pytestmark = pytest.mark.gpu
 
 SWEEP = 4096 * 256          # work items of one pass of a capped grid
 TAIL = 8                    # sentinel floats kept past the last element of every output (32 bytes)
 EINVAL = -1
+close = close_at(2e-5)           # tests/test_ops_gpu.py RTOL
+rel_err = functools.partial(op_support.rel_err, floor=1e-12)
 
 
 def out_rows(device, rows, ld, fill=SENTINEL):
@@ -182,7 +185,7 @@ def test_grad_slice(device, case):
     assert_f32(src_d + dst0, "src + dst")
     mask = torch.randint(-1, 3, (pixels, C), generator=g).double() * rnd(g, pixels, C).abs().float().double()
     assert (mask == 0).any() and (mask < 0).any() and (mask > 0).any()
-    maskd = strided(mask, ldmask, float("nan")).to(device)
+    maskd = widen(mask, ldmask, fill=float("nan")).to(device)
 
     def src_buffer(t):
         buf = torch.full((pixels, ldsrc), float("nan"), dtype=torch.float32)
@@ -394,7 +397,7 @@ def test_bn_relu(device, case):
     sc, sh = dyadic_affine(g, C)
     ref = affine_exact(x, sc, sh, "bn").clamp_(min=0.0)
     flat, y = out_rows(device, rows, ldy)
-    ops.bn_relu(plan_of(device), strided(x, ldx, float("nan")).to(device), dev(sc, device), dev(sh, device), y, rows, C,
+    ops.bn_relu(plan_of(device), widen(x, ldx, fill=float("nan")).to(device), dev(sc, device), dev(sh, device), y, rows, C,
                 ldx, ldy)
     torch.cuda.synchronize()
     exact(y[:, :C], ref, "bn_relu")
@@ -488,7 +491,7 @@ def test_minmax_dyadic(device, regime, N):
     assert_f32(o_ref, "o")
     mm_ref = torch.stack([mn, mn + MINMAX_D, torch.full((N,), float(K_MIN), dtype=torch.float64),
                           torch.full((N,), float(K_MAX), dtype=torch.float64)], 1)
-    xd = strided(x, ldx, float("nan")).to(device)
+    xd = widen(x, ldx, fill=float("nan")).to(device)
     flat, cat = out_rows(device, N * P, ldo)
     cat = cat.view(N, P, ldo)
     mmf, mm = out_rows(device, N, 4)
@@ -549,7 +552,7 @@ def test_minmax_float(device, regime):
     o = a / a.amax(dim=(1, 2), keepdim=True)
     go = rnd(g, N, P, C).float().double()
     o.backward(go)
-    xd = strided(x.detach(), ldx, float("nan")).to(device)
+    xd = widen(x.detach(), ldx, fill=float("nan")).to(device)
     flat, cat = out_rows(device, N * P, ldo)
     cat = cat.view(N, P, ldo)
     mm = torch.empty(N, 4, device=device)

@@ -671,13 +671,13 @@ def test_joint_oracle_tables_reduce_to_the_12x16_feature_map():
 
 def test_wrappers_require_at_least_the_queried_workspace(lib):
     """Every ops.* wrapper that sizes the plan's workspace (`plan.ws.require`) must ask for at least what the C query of the
-    entry point it actually calls reports - over the case table of tests/test_caller_memory_gpu.py, recorded into a non-eager
+    entry point it actually calls reports - over the case tables of tests/caller_memory_cases.py, recorded into a non-eager
     Plan(None) (no GPU, nothing runs).  A wrapper that required another entry point's query (or none) would hand the kernel a
     short buffer that only a guarded run notices."""
     import ctypes as C
 
     from acimg import ops
-    from test_caller_memory_gpu import DECONV_CASES, DGRAD_CASES, FWD_CASES, WGRAD_CASES
+    from caller_memory_cases import DECONV_CASES, DGRAD_CASES, FWD_CASES, WGRAD_CASES
 
     t = torch.zeros(1)
 
@@ -802,3 +802,35 @@ def test_short_or_missing_workspace_is_refused_before_any_launch(lib):
         for ws, nb in ((a, 16), (None, 0)):
             assert lib.acimg_deconv_wgrad(C.byref(d5), a, a, 2 * d5.K, a, a, ws, nb, None) == EW
             assert "bias gradient" in _lib.last_error()
+
+
+def test_test_modules_are_no_libraries_and_helpers_have_one_home():
+    """tests/*.py and tools/**/*.py import no test module (a scoped run of one kernel's tests must not load another's), and no
+    helper - a top-level function that is neither a test nor a pytest fixture - is defined in two files of tests/"""
+    import ast
+    import glob
+
+    def fixture(node):
+        return any("fixture" in ast.dump(d) for d in node.decorator_list)
+
+    tests = sorted(glob.glob(os.path.join(ROOT, "tests", "*.py")))
+    tools = sorted(glob.glob(os.path.join(ROOT, "tools", "**", "*.py"), recursive=True))
+    assert len(tests) > 40 and tools
+    borrowed, homes = [], {}
+    for path in tests + tools:
+        with open(path) as f:
+            tree = ast.parse(f.read(), path)
+        for node in ast.walk(tree):
+            names = []
+            if isinstance(node, ast.Import):
+                names = [a.name for a in node.names]
+            elif isinstance(node, ast.ImportFrom):
+                names = [node.module or ""] + ["%s.%s" % (node.module, a.name) for a in node.names]
+            borrowed += [(os.path.relpath(path, ROOT), n) for n in names if any(p.startswith("test_") for p in n.split("."))]
+        if path in tests:
+            for node in tree.body:
+                if isinstance(node, ast.FunctionDef) and not node.name.startswith("test_") and not fixture(node):
+                    homes.setdefault(node.name, []).append(os.path.basename(path))
+    assert not borrowed, borrowed
+    twice = {name: files for name, files in homes.items() if len(files) > 1}
+    assert not twice, twice

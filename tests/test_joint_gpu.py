@@ -1,6 +1,7 @@
 """The joint-latent step of trainer/trainermulti.py:32-96: `Unet2`, `UNetSound22`, `UNetAc2` encoders ->
 `Jointmvae` -> the three decoders; losses, reconstructions, features, every gradient of the fusion MLP, the batch-norm
 moving averages and the Adam step against the CPU oracle (oracle/joint.py), through the C ABI; only `Jointmvae/` moves."""
+import functools
 import os
 import sys
 from collections import OrderedDict
@@ -13,12 +14,12 @@ for p in (ROOT, os.path.join(ROOT, "acoustic-image-generation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from op_support import rel_err  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 
 def _device_masks(tr):

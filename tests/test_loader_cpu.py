@@ -5,6 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from data_support import FakePool
+
 SIZES = [(1, 1), (24, 1), (24, 5), (24, 24), (24, 100), (1000, 100)]
 
 
@@ -44,35 +46,6 @@ def test_shuffle_order_refuses_an_empty_buffer():
     from acimg.data import epoch_rng, shuffle_order
     with pytest.raises(ValueError):
         shuffle_order(5, 0, epoch_rng(0, 0))
-
-
-class FakePool(object):
-    """what the loader's device side does, as sets: a page's frames are `resident` from upload until gathered"""
-
-    def __init__(self, frames):
-        self.frames = frames
-        self.resident = {}          # page -> set of global frame numbers uploaded and not yet gathered
-        self.where = {}             # slot -> global frame number
-        self.emitted = []           # global frame numbers in gather order
-        self.rows = []              # (offset, count) of every gather call
-        self.pages_seen = set()
-        self.next_frame = 0
-
-    def upload(self, page, nframes):
-        assert not self.resident.get(page), "page %d handed out with un-emitted frames %r" % (page, self.resident[page])
-        self.pages_seen.add(page)
-        self.resident[page] = set(range(self.next_frame, self.next_frame + nframes))
-        for i in range(nframes):
-            self.where[page * self.frames + i] = self.next_frame + i
-        self.next_frame += nframes
-        return nframes
-
-    def gather(self, slots, offset):
-        self.rows.append((offset, len(slots)))
-        for s in slots:
-            f = self.where[s]
-            self.resident[s // self.frames].remove(f)
-            self.emitted.append(f)
 
 
 @pytest.mark.parametrize("n,B", SIZES)

@@ -1,7 +1,6 @@
 """`acimg_batch_gather` against NumPy (every element equal, between guard bands) and `acimg.data.DeviceDataLoader`
 against `TFRecordDataLoader` on the same GZIP record files: order without shuffle, the shuffle buffer's order with it,
 page / ring recycling, and one epoch of `Trainer.train()` from either loader."""
-import re
 from collections import OrderedDict
 
 import numpy as np
@@ -9,7 +8,8 @@ import pytest
 import torch
 
 from guard_arena import GuardArena
-from test_trainer_surface_gpu import make
+from data_support import write_outdoor_records
+from model_support import loss_lines, make
 
 pytestmark = pytest.mark.gpu
 
@@ -109,33 +109,12 @@ def test_batch_gather_acoustic_sizes(device, N, elems):
 
 
 # ---- the loader --------------------------------------------------------------------------------------------------------
-def _write_records(tmp, count=3):
-    from acimg import tfio
-    rng = np.random.RandomState(11)
-    paths = []
-    for r in range(count):
-        ai = rng.rand(12, 36, 48, 12).astype(np.float32) * 5 - 1
-        sa = (rng.randn(12, 1024) * 800).astype(np.int32)
-        vi = rng.randint(0, 256, size=(12, 224, 298, 3)).astype(np.uint8)
-        ctx = OrderedDict([("classes", np.array([2 + 3 * r])), ("location", np.array([7 + r])),
-                           ("audio_image/height", np.array([36])), ("audio_image/width", np.array([48])),
-                           ("audio_image/depth", np.array([12])), ("audio_data/mics", np.array([1])),
-                           ("audio_data/samples", np.array([1024])), ("video/height", np.array([224])),
-                           ("video/width", np.array([298])), ("video/depth", np.array([3]))])
-        lists = OrderedDict([("audio/image", [a.tobytes() for a in ai]), ("audio/data", [s.tobytes() for s in sa]),
-                             ("video/image", [v.tobytes() for v in vi])])
-        p = str(tmp / ("part%d.tfrecord" % r))
-        tfio.write_tfrecord(p, [tfio.build_sequence_example(ctx, lists)], compression="GZIP")
-        paths.append(p)
-    return paths
-
-
 @pytest.fixture(scope="module")
 def records(device, tmp_path_factory):
     """three GZIP files of one 12-frame record each, and the 36 frames `TFRecordDataLoader` makes of them (host tensors,
     computed once, never written to)"""
     from acimg.data import TFRecordDataLoader
-    paths = _write_records(tmp_path_factory.mktemp("records"))
+    paths = write_outdoor_records(tmp_path_factory.mktemp("records"), 11, [(2 + 3 * r, 7 + r) for r in range(3)], wide=True)
     (frames,) = list(TFRecordDataLoader(paths, 64, device=device).data)
     assert frames[0].shape[0] == 36
     return paths, frames
@@ -244,11 +223,6 @@ def test_loader_recycles_pages_and_ring(device, records, repeat):
     dl.close()
 
 
-def _lines(log):
-    return [re.search(r"Iteration: \[ *\d+\]\t Training_mse_Loss: [0-9.]+\t Training_Loss: [0-9.]+", ln).group(0)
-            for ln in log if "Training_mse_Loss" in ln]
-
-
 def test_loader_feeds_the_trainer(device, records):
     """one epoch of `Trainer.train()` from each loader: the inputs are bit-equal and the step is deterministic, so the log
     lines and the validation loss are the same; then an epoch from the shuffled loader"""
@@ -265,11 +239,11 @@ def test_loader_feeds_the_trainer(device, records):
         tr.log = log.append
         best = tr.train(kind(paths, 8, device=device), kind(paths[:1], 8, device=device))
         assert tr.global_step == 5 and np.isfinite(best) and 0 < best < 1
-        runs.append((_lines(log), [ln.split("Validation_mse_Loss:")[1] for ln in log if "- Epoch:" in ln], best))
+        runs.append((loss_lines(log, validation=False), [ln.split("Validation_mse_Loss:")[1] for ln in log if "- Epoch:" in ln], best))
     assert len(runs[0][0]) == 5 and runs[0][0] == runs[1][0]
     assert len(runs[0][1]) == 1 and runs[0][1] == runs[1][1] and runs[0][2] == runs[1][2]
     log = []
     tr.log = log.append
     best = tr.train(DeviceDataLoader(paths, 8, shuffle=True, buffer_size=5, seed=2, device=device),
                     DeviceDataLoader(paths[:1], 8, device=device))
-    assert tr.global_step == 10 and np.isfinite(best) and len(_lines(log)) == 5
+    assert tr.global_step == 10 and np.isfinite(best) and len(loss_lines(log, validation=False)) == 5

@@ -18,6 +18,8 @@ from acimg import _lib, localize, tfio  # noqa: E402
 from acimg.data import BoxRecordLoader, box_mfcc  # noqa: E402
 from acimg.evaluate import THRESHOLDS, accuracy_curve, area_under_curve, mean_iou  # noqa: E402
 import localize_ref as ref  # noqa: E402
+from data_support import box_record  # noqa: E402
+from localize_ref import boxes_of  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "box_golden.npz")
 
@@ -25,25 +27,6 @@ GOLDEN = os.path.join(HERE, "golden", "box_golden.npz")
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def box_record(boxes, scene, audio, video, drop=None, override=None):
-    """one SequenceExample in the layout convert_data2.py:264-305 writes"""
-    ctx = {"audio_data/mics": np.array([1]), "audio_data/samples": np.array([audio.shape[-1]]),
-           "video/height": np.array([video.shape[-3]]), "video/width": np.array([video.shape[-2]]),
-           "video/depth": np.array([video.shape[-1]])}
-    b = np.asarray(boxes, np.int32).reshape(-1, 4, 3)
-    fl = {"xmin": [r[0].tobytes() for r in b], "xmax": [r[1].tobytes() for r in b],
-          "ymin": [r[2].tobytes() for r in b], "ymax": [r[3].tobytes() for r in b],
-          "typescene": [np.asarray(s, np.int32).tobytes() for s in np.asarray(scene).reshape(-1, 3)],
-          "audio/data": [np.asarray(audio, np.int32).reshape(-1).tobytes()],
-          "video/image": [f.tobytes() for f in np.asarray(video, np.uint8).reshape(-1, *video.shape[-3:])]}
-    for k, v in (override or {}).items():
-        (ctx if k in ctx else fl)[k] = v
-    for k in drop or ():
-        ctx.pop(k, None)
-        fl.pop(k, None)
-    return tfio.build_sequence_example(ctx, fl)
 
 
 def sample(rng, length=12288, h=224, w=298):
@@ -162,13 +145,6 @@ def test_box_loader_tuples(lib, tmp_path):
 NOBOX = np.zeros((4, 3), np.int32)
 FULL = np.ones((224, 298), bool)
 EMPTY = np.zeros((224, 298), bool)
-
-
-def boxes_of(*rects):
-    b = np.zeros((4, 3), np.int32)
-    for k, (x0, x1, y0, y1) in enumerate(rects):
-        b[:, k] = (x0, x1, y0, y1)
-    return b
 
 
 def test_metric_box_over_the_whole_frame():

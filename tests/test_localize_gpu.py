@@ -16,6 +16,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import localize_ref as ref  # noqa: E402
+from data_support import outdoor_record, random_box_record  # noqa: E402
+from localize_ref import random_boxes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -50,16 +52,6 @@ def check_against_restatement(device, logen, boxes):
     return iou, counts, mask
 
 
-def random_boxes(rng, N):
-    b = rng.randint(-30, 330, size=(N, 4, 3)).astype(np.int32)
-    b[:, 2:] = rng.randint(-30, 250, size=(N, 2, 3))
-    rev = rng.rand(N, 3) < 0.2                           # reversed corners
-    b[:, 0][rev], b[:, 1][rev] = b[:, 1][rev], b[:, 0][rev].copy()
-    off = rng.rand(N, 3) < 0.25
-    b[:, 1][off] = 0                                     # xmax == 0: that annotator is absent
-    return b
-
-
 @pytest.mark.parametrize("N", [1, 7, 64])
 def test_box_iou_matches_restatement_random(device, N):
     rng = np.random.RandomState(N)
@@ -92,36 +84,6 @@ def test_box_iou_tie_columns_and_nan(device):
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------
-def box_record(rng, length):
-    from acimg import tfio
-    b = random_boxes(rng, 1)[0]
-    b[1, 0] = 150                                        # at least one annotator
-    ctx = OrderedDict([("audio_data/mics", np.array([1])), ("audio_data/samples", np.array([length])),
-                       ("video/height", np.array([224])), ("video/width", np.array([298])), ("video/depth", np.array([3]))])
-    fl = OrderedDict([(k, [b[i].tobytes()]) for i, k in enumerate(("xmin", "xmax", "ymin", "ymax"))])
-    fl["typescene"] = [np.array([1, 0, 0], np.int32).tobytes()]
-    t = np.arange(length) / 12288.0
-    fl["audio/data"] = [(rng.randn(length) * 500 + 2000 * np.sin(2 * np.pi * rng.uniform(100, 3000) * t))
-                        .astype(np.int32).tobytes()]
-    fl["video/image"] = [rng.randint(0, 256, size=(224, 298, 3)).astype(np.uint8).tobytes()]
-    return tfio.build_sequence_example(ctx, fl)
-
-
-def outdoor_record(rng, cls):
-    from acimg import tfio
-    ai = rng.rand(12, 36, 48, 12).astype(np.float32)
-    sa = (rng.randn(12, 1024) * 800).astype(np.int32)
-    vi = rng.randint(0, 256, size=(12, 224, 298, 3)).astype(np.uint8)
-    ctx = OrderedDict([("classes", np.array([cls])), ("location", np.array([7])),
-                       ("audio_image/height", np.array([36])), ("audio_image/width", np.array([48])),
-                       ("audio_image/depth", np.array([12])), ("audio_data/mics", np.array([1])),
-                       ("audio_data/samples", np.array([1024])), ("video/height", np.array([224])),
-                       ("video/width", np.array([298])), ("video/depth", np.array([3]))])
-    lists = OrderedDict([("audio/image", [a.tobytes() for a in ai]), ("audio/data", [s.tobytes() for s in sa]),
-                         ("video/image", [v.tobytes() for v in vi])])
-    return tfio.build_sequence_example(ctx, lists)
-
-
 def test_generate_and_localize_end_to_end(device, tmp_path):
     from acimg import localize, tfio
     from acimg.data import BoxRecordLoader, TFRecordDataLoader
@@ -153,8 +115,8 @@ def test_generate_and_localize_end_to_end(device, tmp_path):
     tfio.write_checkpoint(ckpt, state)
 
     files = [str(tmp_path / "f0.tfrecord"), str(tmp_path / "f1.tfrecord")]
-    tfio.write_tfrecord(files[0], [box_record(rng, 12288), box_record(rng, 24576)], compression="GZIP")
-    tfio.write_tfrecord(files[1], [box_record(rng, 15001)], compression="GZIP")
+    tfio.write_tfrecord(files[0], [random_box_record(rng, 12288), random_box_record(rng, 24576)], compression="GZIP")
+    tfio.write_tfrecord(files[1], [random_box_record(rng, 15001)], compression="GZIP")
     listing = tmp_path / "flickr_test.txt"
     listing.write_text("\n".join(files) + "\n")
 
@@ -192,8 +154,8 @@ def test_generate_and_localize_end_to_end(device, tmp_path):
 
     # the energy path on TFRecordDataLoader records: the same curve as EnergyIoU applied batch by batch
     ofiles = [str(tmp_path / "o0.tfrecord"), str(tmp_path / "o1.tfrecord")]
-    tfio.write_tfrecord(ofiles[0], [outdoor_record(rng, 2)], compression="GZIP")
-    tfio.write_tfrecord(ofiles[1], [outdoor_record(rng, 4)], compression="GZIP")
+    tfio.write_tfrecord(ofiles[0], [outdoor_record(rng, 2, 7, wide=False)], compression="GZIP")
+    tfio.write_tfrecord(ofiles[1], [outdoor_record(rng, 4, 7, wide=False)], compression="GZIP")
     olist = tmp_path / "testing.txt"
     olist.write_text("\n".join(ofiles) + "\n")
     oargs = localize.parse_args(["--train_file", str(olist), "--init_checkpoint", ckpt, "--batch_size", "2",

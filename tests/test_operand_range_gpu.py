@@ -18,7 +18,8 @@ import torch
 import torch.nn.functional as F
 
 import split_format_ref as sf
-from test_ops_gpu import plane_bytes, unsplit
+from op_support import trunk_forms
+from split_format_ref import plane_bytes, unsplit
 
 pytestmark = pytest.mark.gpu
 
@@ -132,8 +133,7 @@ def test_few_channel_mfma_conv(device):
 # the trunk's kernel forms as tests/test_split_planes_gpu.py forces them, and the kernel each must reach
 # (acimg_conv2d_fwd_split3_tiling()[2]); 128x128 tiles also where the shipped rule would pick 64-row tiles (< 200 tiles)
 TILE128 = dict(split3_tile_bm=128, split3_tile_bn=128)
-TRUNK_FORMS = (("one-tile", dict(trunk_persistent=0, trunk_ring=0), 0), ("persistent", dict(trunk_persistent=2, trunk_ring=0), 1),
-               ("ring128", dict(trunk_ring=2, trunk_ring_bm=128), 2), ("halo", dict(trunk_halo=2), 3))
+TRUNK_FORMS = trunk_forms("one-tile", "persistent", "ring128", "halo")
 
 
 def presplit_input(ops, plan, o, rows, Cc, device):

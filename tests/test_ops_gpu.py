@@ -2,65 +2,17 @@
 same TensorFlow op.  Tolerance: the kernels compute in fp32 (exact-f32 MFMA, fp32 accumulate), so
 results must agree with the fp64 reference to 2e-5 relative to the tensor's max magnitude.
 """
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from op_support import TRUNK_FORMS, close_at, conv_geom, dev, pad_last, pad_w, rnd, same_pads, tf_conv_ref, up4
+from split_format_ref import POISONS, make_planes, plane_bytes, repack, unsplit
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 2e-5
-
-
-def up4(v):
-    return (v + 3) & ~3
-
-
-def close(got, ref, tol=RTOL, what=""):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    scale = max(ref.abs().max().item(), 1e-12)
-    err = (got - ref).abs().max().item() / scale
-    assert np.isfinite(err) and err <= tol, "%s: rel err %.3e > %.1e" % (what, err, tol)
-
-
-def tf_conv_ref(x, w, stride, pads, bias=None):
-    """x NHWC fp64, w HWIO; pads = (pt, pb, pl, pr)"""
-    xt = x.permute(0, 3, 1, 2)
-    xt = F.pad(xt, (pads[2], pads[3], pads[0], pads[1]))
-    y = F.conv2d(xt, w.permute(3, 2, 0, 1), bias, stride=stride)
-    return y.permute(0, 2, 3, 1)
-
-
-def same_pads(size, k, s):
-    out = -(-size // s)
-    tot = max((out - 1) * s + k - size, 0)
-    return out, tot // 2, tot - tot // 2
-
-
-def rnd(gen, *shape):
-    return torch.randn(*shape, generator=gen, dtype=torch.float64)
-
-
-def dev(t, device):
-    return t.float().contiguous().to(device)
-
-
-def pad_last(t, n):
-    if t.shape[-1] == n:
-        return t
-    out = torch.zeros(*t.shape[:-1], n, dtype=t.dtype)
-    out[..., : t.shape[-1]] = t
-    return out
-
-
-def pad_w(w, cp, kp):
-    """HWIO -> zero padded [R,S,cp,kp]"""
-    R, S, Cc, K = w.shape
-    out = torch.zeros(R, S, cp, kp, dtype=w.dtype)
-    out[:, :, :Cc, :K] = w
-    return out
+close = close_at(RTOL)
 
 
 CONV_CASES = [
@@ -78,20 +30,6 @@ CONV_CASES = [
 ]
 
 
-def _conv_geom(H, W, R, S, stride, padding):
-    if padding == "SAME":
-        OH, pt, pb = same_pads(H, R, stride)
-        OW, pl, pr = same_pads(W, S, stride)
-    elif padding == "VALID":
-        OH, OW = (H - R) // stride + 1, (W - S) // stride + 1
-        pt = pb = pl = pr = 0
-    else:
-        p = padding
-        OH, OW = (H + 2 * p - R) // stride + 1, (W + 2 * p - S) // stride + 1
-        pt = pb = pl = pr = p
-    return OH, OW, (pt, pb, pl, pr)
-
-
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv2d_fwd(device, case):
     from acimg import ops
@@ -101,7 +39,7 @@ def test_conv2d_fwd(device, case):
     x = rnd(g, N, H, W, Cc)
     w = rnd(g, R, S, Cc, K) * 0.1
     b = rnd(g, K)
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     ref = torch.relu(tf_conv_ref(x, w, stride, pads, b))
     cp, kp = up4(Cc), up4(K)
     xd = dev(pad_last(x, cp), device)
@@ -195,7 +133,7 @@ def test_conv2d_fwd_f16x3(device, case):
     x = rnd(g, N, H, W, Cc)
     sc, sh = rnd(g, Cc).abs() + 0.5, rnd(g, Cc)
     w = rnd(g, R, S, Cc, K) * (2.0 / (R * S * Cc)) ** 0.5
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     ref = tf_conv_ref(torch.relu(x * sc + sh), w, stride, pads)
     d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding)
     wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
@@ -228,7 +166,7 @@ def test_split3_generator_convs(device, case):
     x = rnd(g, N, H, W, Cc).requires_grad_(True)
     w = (rnd(g, R, S, Cc, K) * (2.0 / (R * S * Cc)) ** 0.5).requires_grad_(True)
     b = rnd(g, K).requires_grad_(True)
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     pre = tf_conv_ref(x, w, stride, pads, b)
     d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldy=2 * K, act=ops.ACT_RELU)
     plan = ops.Plan(device, eager=True)
@@ -273,7 +211,7 @@ def test_wgrad_split3_geometries(device, case):
     x = rnd(g, N, H, W, Cc).requires_grad_(True)
     w = (rnd(g, R, S, Cc, K) * 0.05).requires_grad_(True)
     b = rnd(g, K).requires_grad_(True)
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     y = tf_conv_ref(x, w, stride, pads, b)
     gywide = rnd(g, N, OH, OW, 2 * K) * 1e-6
     y.backward(gywide[..., K:])
@@ -285,47 +223,6 @@ def test_wgrad_split3_geometries(device, case):
     torch.cuda.synchronize()
     close(dw, w.grad, tol=3e-5, what="bf16x3 wgrad %s" % (case,))
     close(db, b.grad, tol=3e-5, what="bf16x3 bgrad %s" % (case,))
-
-
-def plane_bytes(rows, Cc):
-    """bytes of one split-format plane: whole 16-pixel x 32-channel bricks (include/acimg.h)"""
-    return -(-rows // 16) * 16 * Cc * 2
-
-
-def brick_index(rows, Cc):
-    """fp16 element index inside a split-format plane of every element of a [rows, C] tensor, row-major: brick (row >> 4,
-    c >> 5) of 1 KiB, inside it row & 15 at 64 bytes and 16-byte group (c >> 3) & 3 at group ((c >> 3) ^ -(row >> 2)) & 3"""
-    r = torch.arange(rows).view(-1, 1)
-    c = torch.arange(Cc).view(1, -1)
-    off = ((r >> 4) * (Cc // 32) + (c >> 5)) * 1024 + (r & 15) * 64 + ((((c >> 3) ^ (-(r >> 2))) & 3) << 4) + (c & 7) * 2
-    return (off // 2).reshape(-1)
-
-
-def unsplit(planes, lo_off, rows, Cc):
-    """two fp16 planes in LDS-tile order (uint8 buffer) -> float64 [rows, C] (undoing the 2^-2 scale)"""
-    idx = brick_index(rows, Cc).to(planes.device)
-    n = plane_bytes(rows, Cc)
-    hi = planes[:n].view(torch.float16)[idx].double()
-    lo = planes[lo_off: lo_off + n].view(torch.float16)[idx].double()
-    return ((hi + lo) * 4.0).reshape(rows, Cc).cpu()
-
-
-# what the bytes of split planes outside the valid rows' elements may hold (include/acimg.h: unspecified): fp16 NaN, and a
-# large finite value (0x7b7b = 6.2e4 per half, 2.5e5 after the x4 scale) that a ReLU or a max cannot hide; (fill byte, gap
-# between the hi plane's end and lo_off)
-POISONS = ((0xFF, 0), (0x7B, 4096))
-
-
-def repack(planes, lo_off, rows, Cc, fill, gap=0, slack=4096):
-    """a copy of split-format planes that keeps only the valid rows' elements: every other byte - the pad rows of the last
-    brick row, a `gap`-byte hole between the planes, `slack` bytes after the lo plane - holds `fill`.  -> (buffer, lo_off)"""
-    n = plane_bytes(rows, Cc)
-    lo2 = n + gap
-    out = torch.full((lo2 + n + slack,), fill, dtype=torch.uint8, device=planes.device)
-    idx = brick_index(rows, Cc).to(planes.device)
-    for src, dst in ((0, 0), (lo_off, lo2)):
-        out[dst:dst + n].view(torch.float16)[idx] = planes[src:src + n].view(torch.float16)[idx]
-    return out, lo2
 
 
 @pytest.mark.parametrize("tail", [False, True])
@@ -340,7 +237,7 @@ def test_presplit_activation_path(device, case, tail):
     x = rnd(g, N, H, W, Cc)
     sc, sh = rnd(g, Cc).abs() + 0.5, rnd(g, Cc)
     w = rnd(g, R, S, Cc, K) * (2.0 / (R * S * Cc)) ** 0.5
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     xa = torch.relu(x * sc + sh)
     ref = tf_conv_ref(xa, w, stride, pads)
     d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding)
@@ -446,7 +343,7 @@ def test_conv2d_dgrad_wgrad(device, case):
     x = rnd(g, N, H, W, Cc).requires_grad_(True)
     w = (rnd(g, R, S, Cc, K) * 0.1).requires_grad_(True)
     b = rnd(g, K).requires_grad_(True)
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     y = tf_conv_ref(x, w, stride, pads, b)
     gy = rnd(g, N, OH, OW, K)
     y.backward(gy)
@@ -776,7 +673,7 @@ def test_few_channel_direct_conv(device, case):
     x = rnd(g, N, H, W, Cc).requires_grad_(True)
     w = (rnd(g, R, S, Cc, K) * 0.2).requires_grad_(True)
     b = rnd(g, K)
-    OH, OW, pads = _conv_geom(H, W, R, S, stride, padding)
+    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
     raw = tf_conv_ref(x, w, stride, pads, b)
     d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, act=1)
     plan = ops.Plan(device, eager=True)
@@ -1050,32 +947,14 @@ def test_trunk_kernel_variants_agree(device, case):
     w = torch.randn(R, S, Cc, K, generator=g) * (2.0 / (R * S * Cc)) ** 0.5
     d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding)
     rows = N * H * W
-    lo_off = plane_bytes(rows, Cc)
-    planes = torch.zeros(lo_off * 2, dtype=torch.uint8, device=device)
     plan = ops.Plan(device, eager=True)
-    one, zero = torch.ones(Cc, device=device), torch.zeros(Cc, device=device)
-    ops.bn_relu_split(plan, x.to(device), one, zero, 1, planes, lo_off, rows, Cc)
+    planes, lo_off = make_planes(plan, device, x, rows, Cc, relu=1)
     wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
     ops.conv2d_split3_prepare(plan, d, w.to(device), wsplit)
     tws = torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8, device=device)
     outs = {}
     try:
-        for name, cfg in (("one-tile whole", dict(trunk_persistent=0, tail_split=0, trunk_ring=0)),
-                          ("persistent whole", dict(trunk_persistent=2, tail_split=0, trunk_ring=0)),
-                          ("one-tile", dict(trunk_persistent=0, trunk_ring=0)),
-                          ("persistent", dict(trunk_persistent=2, trunk_ring=0)),
-                          ("staggered", dict(trunk_persistent=2, trunk_stagger=50, trunk_ring=0)),
-                          ("spread", dict(trunk_persistent=2, trunk_dma_pos=1, trunk_ring=0)),
-                          ("auto no ring", dict(trunk_ring=0)), ("auto", dict()),
-                          ("ring256 whole", dict(trunk_ring=2, trunk_ring_bm=256, tail_split=0)),
-                          ("ring128 whole", dict(trunk_ring=2, trunk_ring_bm=128, tail_split=0)),
-                          ("ring256", dict(trunk_ring=2, trunk_ring_bm=256)),
-                          ("ring128", dict(trunk_ring=2, trunk_ring_bm=128)),
-                          ("ring256 s3", dict(trunk_ring=2, trunk_ring_bm=256, tail_s=3)),
-                          ("ring", dict(trunk_ring=2)),
-                          # the halo kernel takes the 3x3 cases only (the others stay on the shipped choice)
-                          ("halo whole", dict(trunk_halo=2, tail_split=0)), ("halo", dict(trunk_halo=2)),
-                          ("halo s3", dict(trunk_halo=2, tail_s=3))):
+        for name, (cfg, _) in TRUNK_FORMS.items():
             _lib.configure(**cfg)
             srows = ops.conv2d_fwd_split3p_stats_rows(d)     # depends on the kernel the configuration picks
             y = torch.full((N, d.OH, d.OW, K), float("nan"), device=device)
@@ -1131,12 +1010,9 @@ def test_two_pass_conv3_equals_conv_then_bn_pass(device, case):
     shift = (torch.rand(K, generator=g) - 0.7).to(device)
     d = ops.conv_desc(N, H, W, Cc, K, 1, 1, 1, "SAME")
     rows = N * H * W
-    lo_x, lo_y = plane_bytes(rows, Cc), plane_bytes(rows, K)
     plan = ops.Plan(device, eager=True)
-    xp = torch.zeros(lo_x * 2, dtype=torch.uint8, device=device)
-    ops.bn_relu_split(plan, x.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device), 1, xp, lo_x, rows, Cc)
-    sp = torch.zeros(lo_y * 2, dtype=torch.uint8, device=device)
-    ops.bn_relu_split(plan, short.to(device), torch.ones(K, device=device), torch.zeros(K, device=device), 1, sp, lo_y, rows, K)
+    xp, lo_x = make_planes(plan, device, x, rows, Cc, relu=1)
+    sp, lo_y = make_planes(plan, device, short, rows, K, relu=1)
     wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
     ops.conv2d_split3_prepare(plan, d, w.to(device), wsplit)
     tws = torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8, device=device)
@@ -1448,10 +1324,8 @@ def test_gram_statistics_match_fp64(device, case):
     w[:, :K] = torch.randn(Cc, K, generator=g) * (2.6 / Cc) ** 0.5
     gamma, beta = torch.rand(K, generator=g) + 0.5, torch.rand(K, generator=g) - 0.5
     mm0, mv0 = torch.randn(K, generator=g) * 0.1, torch.rand(K, generator=g) + 0.5
-    lo = plane_bytes(rows, Cc)
     plan = ops.Plan(device, eager=True)
-    xp = torch.zeros(lo * 2, dtype=torch.uint8, device=device)
-    ops.bn_relu_split(plan, x.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device), 1, xp, lo, rows, Cc)
+    xp, lo = make_planes(plan, device, x, rows, Cc, relu=1)
     need = ops.gram_stats_workspace(rows, Cc)
     assert need > 0
     # fp64 reference on the values the planes hold (hi + lo: x to 2^-22)
@@ -1525,11 +1399,8 @@ def test_halo_kernel_edges(device, case):
     w = torch.randn(3, 3, Cc, K, generator=g) * (2.0 / (9 * Cc)) ** 0.5
     d = ops.conv_desc(N, H, W, Cc, K, 3, 3, 1, "SAME")
     rows = N * H * W
-    lo_off = plane_bytes(rows, Cc)
-    planes = torch.zeros(lo_off * 2, dtype=torch.uint8, device=device)
     plan = ops.Plan(device, eager=True)
-    ops.bn_relu_split(plan, x.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device), 0, planes, lo_off,
-                      rows, Cc)
+    planes, lo_off = make_planes(plan, device, x, rows, Cc, relu=0)
     wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
     ops.conv2d_split3_prepare(plan, d, w.to(device), wsplit)
     tws = torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8, device=device)
@@ -1579,11 +1450,8 @@ def test_fp16_operand_storage_conv(device, case):
     w = torch.randn(R, S, Cc, K, generator=g) * (2.0 / (R * S * Cc)) ** 0.5
     d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding)
     rows = N * H * W
-    lo_off = plane_bytes(rows, Cc)
-    planes = torch.zeros(lo_off * 2, dtype=torch.uint8, device=device)
     plan = ops.Plan(device, eager=True)
-    ops.bn_relu_split(plan, x.to(device), torch.ones(Cc, device=device), torch.zeros(Cc, device=device), 1, planes,
-                      lo_off, rows, Cc)
+    planes, lo_off = make_planes(plan, device, x, rows, Cc, relu=1)
     wsplit = torch.zeros(ops.conv2d_split3_weight_bytes(d), dtype=torch.uint8, device=device)
     ops.conv2d_split3_prepare(plan, d, w.to(device), wsplit)
     tws = torch.zeros(ops.conv2d_fwd_split3p_workspace(d), dtype=torch.uint8, device=device)

@@ -17,21 +17,11 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import retrieval_ref as ref  # noqa: E402
+from data_support import outdoor_record  # noqa: E402
+from retrieval_ref import int_features  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(HERE, "golden", "retrieval_golden.npz")
-
-
-def int_features(rng, Q, G, D):
-    q = rng.randint(-8, 9, size=(Q, D)).astype(np.float64)
-    g = rng.randint(-8, 9, size=(G, D)).astype(np.float64)
-    if G > 1:
-        dup = rng.randint(0, G, size=(G // 3, 2))     # duplicated gallery rows: exact ties broken by index
-        g[dup[:, 0]] = g[dup[:, 1]]
-    if G > 2 and Q > 0:
-        g[-1] = q[0]                                  # a zero distance
-        g[G // 2] = q[0]
-    return q, g
 
 
 def run_topk(device, q, g, K, ldq=None, ldg=None):
@@ -207,21 +197,6 @@ def test_trainer_features_match_the_oracle(device):
         assert torch.equal(tr._graph_for(n).modelac.zbuf[:, :150].double().cpu(), z)
 
 
-def outdoor_record(rng, cls, loc):
-    from acimg import tfio
-    ai = rng.rand(12, 36, 48, 12).astype(np.float32)
-    sa = (rng.randn(12, 1024) * 800).astype(np.int32)
-    vi = rng.randint(0, 256, size=(12, 224, 298, 3)).astype(np.uint8)
-    ctx = OrderedDict([("classes", np.array([cls])), ("location", np.array([loc])),
-                       ("audio_image/height", np.array([36])), ("audio_image/width", np.array([48])),
-                       ("audio_image/depth", np.array([12])), ("audio_data/mics", np.array([1])),
-                       ("audio_data/samples", np.array([1024])), ("video/height", np.array([224])),
-                       ("video/width", np.array([298])), ("video/depth", np.array([3]))])
-    lists = OrderedDict([("audio/image", [a.tobytes() for a in ai]), ("audio/data", [s.tobytes() for s in sa]),
-                         ("video/image", [v.tobytes() for v in vi])])
-    return tfio.build_sequence_example(ctx, lists)
-
-
 def test_extract_knn_retrieve_end_to_end(device, tmp_path):
     from acimg import features, localize, retrieval, tfio
     rng = np.random.RandomState(23)
@@ -234,7 +209,7 @@ def test_extract_knn_retrieve_end_to_end(device, tmp_path):
         paths = []
         for i, (cls, loc) in enumerate(rr):
             p = str(tmp_path / ("%s%d.tfrecord" % (name, i)))
-            tfio.write_tfrecord(p, [outdoor_record(rng, cls, loc)], compression="GZIP")
+            tfio.write_tfrecord(p, [outdoor_record(rng, cls, loc, wide=False)], compression="GZIP")
             paths.append(p)
         (tmp_path / ("%s.txt" % name)).write_text("\n".join(paths) + "\n")
     quiet = dict(log=lambda *a: None)

@@ -4,9 +4,7 @@ as `render_ref` restates it, the PNG writer read back by a reader written here, 
 directories, file names and `show.json`, and the refusals of `acimg_overlay_render`, which come before any launch."""
 import json
 import os
-import struct
 import sys
-import zlib
 
 import numpy as np
 import pytest
@@ -16,6 +14,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import render_ref as ref  # noqa: E402
+from localize_ref import boxes_of  # noqa: E402
+from render_ref import read_png  # noqa: E402
 
 GOLD = np.load(os.path.join(HERE, "golden", "render_golden.npz"))
 GOLD_INPUTS = sorted(k[3:] for k in GOLD.files if k.startswith("in_"))
@@ -118,14 +118,6 @@ def test_two_valued_map_extremes_on_border_columns():
     assert (out[:, 0] == JET[0]).all() and (out[:, 297] == JET[255]).all() and (out[:, 150] == JET[96]).all()
 
 
-def boxes_of(*quads):
-    """(xmin, xmax, ymin, ymax) per annotator -> [4,3] int32"""
-    b = np.zeros((4, 3), np.int32)
-    for k, q in enumerate(quads):
-        b[:, k] = q
-    return b
-
-
 def test_outline_rule():
     m = ref.outline_mask(boxes_of((10, 20, 30, 40)))
     # outer 13 x 13 (9..21, 29..41) minus inner 7 x 7 (12..18, 32..38)
@@ -162,28 +154,6 @@ def test_outline_pixels_take_the_top_grey_entry():
 
 
 # ---- PNG -------------------------------------------------------------------------------------------------------------
-def read_png(data):
-    """a reader for what write_png promises: signature, chunk CRCs, IHDR 8-bit RGB, one IDAT, filter 0 on every line"""
-    assert data[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, chunks = 8, []
-    while pos < len(data):
-        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
-        body = data[pos + 8:pos + 8 + n]
-        (crc,) = struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])
-        assert crc == zlib.crc32(kind + body) & 0xFFFFFFFF, kind
-        chunks.append((kind, body))
-        pos += 12 + n
-    assert pos == len(data)
-    assert [k for k, _ in chunks] == [b"IHDR", b"IDAT", b"IEND"] and chunks[2][1] == b""
-    w, h, depth, ctype, comp, flt, lace = struct.unpack(">IIBBBBB", chunks[0][1])
-    assert (depth, ctype, comp, flt, lace) == (8, 2, 0, 0, 0)
-    raw = zlib.decompress(chunks[1][1])
-    assert len(raw) == h * (1 + 3 * w)
-    rows = np.frombuffer(raw, np.uint8).reshape(h, 1 + 3 * w)
-    assert not rows[:, 0].any()
-    return rows[:, 1:].reshape(h, w, 3)
-
-
 @pytest.mark.parametrize("shape", [(1, 1), (224, 298), (5, 7), (224, 604)])
 def test_write_png_round_trip(tmp_path, shape):
     from acimg.png import write_png

@@ -17,8 +17,9 @@ if HERE not in sys.path:
 
 import render_ref as ref  # noqa: E402
 from guard_arena import GuardArena  # noqa: E402
-from test_localize_gpu import box_record, outdoor_record, random_boxes  # noqa: E402
-from test_show_cpu import read_png  # noqa: E402
+from data_support import outdoor_record, random_box_record  # noqa: E402
+from localize_ref import random_boxes  # noqa: E402
+from render_ref import read_png  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -227,8 +228,8 @@ def test_show_end_to_end(device, tmp_path):
     vdir = tmp_path / "class_1" / "video_4"
     vdir.mkdir(parents=True)
     ofiles = [str(vdir / "o0.tfrecord"), str(vdir / "o1.tfrecord")]
-    tfio.write_tfrecord(ofiles[0], [outdoor_record(rng, 2)], compression="GZIP")
-    tfio.write_tfrecord(ofiles[1], [outdoor_record(rng, 4)], compression="GZIP")
+    tfio.write_tfrecord(ofiles[0], [outdoor_record(rng, 2, 7, wide=False)], compression="GZIP")
+    tfio.write_tfrecord(ofiles[1], [outdoor_record(rng, 4, 7, wide=False)], compression="GZIP")
     olist = vdir / "testing.txt"
     olist.write_text("\n".join(ofiles) + "\n")
     common = ["--init_checkpoint", ckpt, "--batch_size", "3", "--num_skip_conn", "1", "--ae", "0", "--png_level", "1"]
@@ -270,7 +271,7 @@ def test_show_end_to_end(device, tmp_path):
         assert_same_bytes(img[:, W + show.GAP:], ref.render(frames[i], energy[i], GRAY, JET), "generated %d" % i)
 
     bfiles = [str(tmp_path / "f0.tfrecord")]
-    tfio.write_tfrecord(bfiles[0], [box_record(rng, 12288), box_record(rng, 24576), box_record(rng, 15001)],
+    tfio.write_tfrecord(bfiles[0], [random_box_record(rng, 12288), random_box_record(rng, 24576), random_box_record(rng, 15001)],
                         compression="GZIP")
     blist = tmp_path / "flickr_test.txt"
     blist.write_text("\n".join(bfiles) + "\n")

@@ -7,109 +7,30 @@ fp64 reference bit for bit: a dropped row, a skipped tail, a doubled block or a 
 instead of hiding inside a tolerance.  Each bound is asserted on the host.  One case per op uses ordinary randn data and
 checks the non-reduction arithmetic at the module tolerance (2e-5 relative to max|ref|, looser only where stated).
 """
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
 
-from test_ops_gpu import close, dev, rnd
+import op_support
+from op_support import (SENTINEL, assert_exact_sum, assert_f32, bits_equal, bn_bwd_dyadic_inputs, bn_bwd_ref, close_at, dev, dyadic,
+                        exact, pads_untouched, rnd, widen)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 7.0
-EXACT_LIMIT = 2.0 ** 24
-
-
-def dyadic(g, shape, res, maxabs, lo=None):
-    """multiples of `res` in [lo, maxabs] (lo defaults to -maxabs), fp64"""
-    lo_k = int(round((-maxabs if lo is None else lo) / res))
-    hi_k = int(round(maxabs / res))
-    return torch.randint(lo_k, hi_k + 1, shape, generator=g).double() * res
-
-
-def assert_f32(t, what):
-    """every value is exactly representable in fp32"""
-    assert torch.equal(t.float().double(), t), "%s is not exactly representable in fp32" % what
-
-
-def assert_exact_sum(terms, res, what, dim=None):
-    """sum |term| / res < 2^24: every partial sum of these terms is exact in fp32, in any order"""
-    s = terms.abs().sum() if dim is None else terms.abs().sum(dim).max()
-    assert float(s) / res < EXACT_LIMIT, "%s: magnitude bound violated (%.3g / %g >= 2^24)" % (what, float(s), res)
-
-
-def exact(got, ref, what):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    bad = (got != ref).nonzero()
-    assert bad.numel() == 0, "%s: %d values differ, first at %s: %r != %r" % (
-        what, bad.shape[0], tuple(bad[0].tolist()), got[tuple(bad[0])].item(), ref[tuple(bad[0])].item())
-
-
-def rel_err(got, ref):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    return (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-12)
-
-
-def strided(t, ld, fill):
-    """[..., C] fp64 -> fp32 device tensor [..., ld] with the pad columns set to `fill`"""
-    out = torch.full((*t.shape[:-1], ld), fill, dtype=torch.float64)
-    out[..., : t.shape[-1]] = t
-    return out.float()
-
-
-def pads_untouched(t, C, what):
-    assert (t[..., C:] == SENTINEL).all(), "%s: pad columns written" % what
-
-
-def bits_equal(a, b, what):
-    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), "%s differs between two identical calls" % what
+close = close_at(2e-5)           # tests/test_ops_gpu.py RTOL
+rel_err = functools.partial(op_support.rel_err, floor=1e-12)
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # acimg_bn_bwd
 # ------------------------------------------------------------------------------------------------------------------
-def bn_bwd_ref(xhat, gm, gamma, invstd):
-    """fp64 statement of the comment above bn_bwd_reduce_kernel; gm = gy already masked by the ReLU"""
-    n = xhat.shape[0]
-    dbeta = gm.sum(0)
-    dgamma = (gm * xhat).sum(0)
-    gx = gamma * invstd * (gm - dbeta / n - xhat * (dgamma / n))
-    return gx, dgamma, dbeta
-
-
-def bn_bwd_dyadic_inputs(g, rows, C):
-    """xhat in {+-0.5, +-1}, power-of-two invstd, dyadic mean: x - mean and (x - mean) * invstd are exact in fp32;
-    dyadic gamma / beta with beta an odd multiple of 1/8 keep the pre-activation gamma*xhat + beta away from 0, so the
-    recomputed ReLU mask cannot flip (FMA contraction included)"""
-    xhat = torch.tensor([-1.0, -0.5, 0.5, 1.0], dtype=torch.float64)[torch.randint(0, 4, (rows, C), generator=g)]
-    gy = torch.randint(-1, 2, (rows, C), generator=g).double()
-    mean = torch.randint(-8, 9, (C,), generator=g).double() / 4
-    invstd = 2.0 ** torch.randint(-1, 3, (C,), generator=g).double()
-    sign = torch.randint(0, 2, (C,), generator=g).double() * 2 - 1
-    gamma = sign * torch.randint(1, 5, (C,), generator=g).double() / 2
-    beta = (2 * torch.randint(-4, 4, (C,), generator=g).double() + 1) / 8
-    x = mean + xhat / invstd
-    scale = gamma * invstd
-    shift = beta - mean * scale
-    pre = x * scale + shift
-    assert (pre != 0).all(), "a pre-activation is exactly 0"
-    for t, name in ((x, "x"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (scale, "scale"),
-                    (shift, "shift"), (pre, "pre-activation")):
-        assert_f32(t, name)
-    gm = gy * (pre > 0)
-    del pre
-    assert_exact_sum(gm, 1.0, "dbeta", dim=0)
-    assert_exact_sum(gm * xhat, 0.5, "dgamma", dim=0)
-    return x, gy, gm, xhat, mean, invstd, gamma, scale, shift
-
-
 def run_bn_bwd(device, x, ldx, gy, ldgy, mean, invstd, gamma, scale, shift, rows, C, ldgx, inplace):
     from acimg import ops
 
-    xd = strided(x, ldx, float("nan")).to(device)          # pad columns are never read: NaN there would show up
-    gyd = strided(gy, ldgy, SENTINEL if inplace else float("nan")).to(device)
+    xd = widen(x, ldx, fill=float("nan")).to(device)          # pad columns are never read: NaN there would show up
+    gyd = widen(gy, ldgy, fill=SENTINEL if inplace else float("nan")).to(device)
     gxd = gyd if inplace else torch.full((rows, ldgx), SENTINEL, device=device)
     dgamma = torch.full((C,), SENTINEL, device=device)
     dbeta = torch.full((C,), SENTINEL, device=device)
@@ -398,11 +319,11 @@ def test_maxpool(device, case, data):
         x = torch.relu(rnd(g, N, H, W, C)).float().double()
     gy = rnd(g, N, OH, OW, C).float().double()
     y_ref, gx_ref = maxpool_ref(x, gy, k)
-    xd = strided(x, ldx, float("nan")).to(device)
+    xd = widen(x, ldx, fill=float("nan")).to(device)
     yd = torch.full((N, OH, OW, ldy), SENTINEL, device=device)
     plan = ops.Plan(device, eager=True)
     ops.maxpool_fwd(plan, xd, ldx, yd, ldy, N, H, W, C, k)
-    gyd = strided(gy, ldy, float("nan")).to(device)
+    gyd = widen(gy, ldy, fill=float("nan")).to(device)
     gxd = torch.full((N, H, W, ldgx), SENTINEL, device=device)
     ops.maxpool_relu_bwd(plan, xd, ldx, gyd, ldy, gxd, ldgx, N, H, W, C, k)
     torch.cuda.synchronize()
@@ -429,7 +350,7 @@ def test_spatial_sum(device, case):
     x = dyadic(g, (N, P, C), 1 / 8, 4)
     assert_exact_sum(x, 1 / 8, "spatial sum", dim=1)
     gy = rnd(g, N, C).float().double()
-    xd = strided(x, ldx, float("nan")).to(device)
+    xd = widen(x, ldx, fill=float("nan")).to(device)
     y = torch.full((N, C + 4), SENTINEL, device=device)
     gxd = torch.full((N, P, ldx), SENTINEL, device=device)
     plan = ops.Plan(device, eager=True)
@@ -490,7 +411,7 @@ def test_clip_softmax_ce(device, case, data):
         labels[2] = (int(lv[2].mean(0).argmax()) + 1) % K
     ldl, ldg = K + 3, K + 5
     loss_r, acc_r, g_r = clip_ce_ref(logits, labels, F_)
-    ld = strided(logits, ldl, float("nan")).to(device)
+    ld = widen(logits, ldl, fill=float("nan")).to(device)
     lab = labels.to(torch.int32).to(device)
     out = torch.zeros(2, device=device)
     gd = torch.full((clips * F_, ldg), SENTINEL, device=device)
@@ -529,12 +450,12 @@ def test_softplus(device):
     gy = rnd(g, rows, C).float().double()
     y_ref = F.softplus(x)
     gx_ref = gy * torch.sigmoid(x)
-    xd = strided(x, ldx, float("nan")).to(device)
+    xd = widen(x, ldx, fill=float("nan")).to(device)
     yd = torch.full((rows, ldy), SENTINEL, device=device)
     gxd = torch.full((rows, ldg), SENTINEL, device=device)
     plan = ops.Plan(device, eager=True)
     ops.softplus_fwd(plan, xd, ldx, yd, ldy, rows, C)
-    ops.softplus_bwd(plan, xd, ldx, strided(gy, ldx, float("nan")).to(device), ldx, gxd, ldg, rows, C)
+    ops.softplus_bwd(plan, xd, ldx, widen(gy, ldx, fill=float("nan")).to(device), ldx, gxd, ldg, rows, C)
     torch.cuda.synchronize()
     pads_untouched(yd, C, "y")
     pads_untouched(gxd, C, "gx")
@@ -579,7 +500,7 @@ def test_latent_linear(device, Z):
     gh = torch.full((N, 2 * Z), SENTINEL, device=device)
     plan = ops.Plan(device, eager=True)
     ops.latent_linear_fwd(plan, hd, ed, zd, ldz, kld, N, Z)
-    ops.latent_linear_bwd(plan, hd, ed, strided(gz, ldgz, float("nan")).to(device), ldgz, klw, gh, N, Z)
+    ops.latent_linear_bwd(plan, hd, ed, widen(gz, ldgz, fill=float("nan")).to(device), ldgz, klw, gh, N, Z)
     torch.cuda.synchronize()
     close(zd[:, :Z], z, what="z")
     pads_untouched(zd, Z, "z")
@@ -617,7 +538,7 @@ def test_latent_softplus(device, Z):
     gh = torch.empty(N, 2 * Z, device=device)
     plan = ops.Plan(device, eager=True)
     ops.latent_fwd(plan, hd, ed, zd, ldz, sd, kld, N, Z)
-    ops.latent_bwd(plan, hd, ed, sd, strided(gz, ldz, float("nan")).to(device), ldz, klw, gh, N, Z)
+    ops.latent_bwd(plan, hd, ed, sd, widen(gz, ldz, fill=float("nan")).to(device), ldz, klw, gh, N, Z)
     torch.cuda.synchronize()
     close(sd, s, what="sigma")
     close(zd[:, :Z], z, what="z")

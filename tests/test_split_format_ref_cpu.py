@@ -252,3 +252,43 @@ def test_split_planes_hold_what_plane_bound_says():
             over = (err > torch.maximum(v.double().abs() * 2.0 ** -24, torch.full_like(err, 2.0 ** -23)))
             assert float(over.double().mean()) >= 0.02, (name, float(over.double().mean()))
     assert worst_rel > 2.0 ** -15                                # the floor: quiet activations keep ~14 bits
+
+
+# ---- the activation-plane layout ---------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+
+    ge.build()
+    from acimg import _lib
+
+    return _lib.load()
+
+
+# rows, C; 5320 x 256 is a trunk row count that is 8 mod 16 (the Gram statistics read such planes)
+PLANE_SHAPES = [(1, 32), (5, 32), (16, 64), (17, 96), (40, 128), (5320, 256)]
+
+
+@pytest.mark.parametrize("rows,Cc", PLANE_SHAPES)
+def test_brick_index_is_a_layout_of_the_plane(lib, rows, Cc):
+    """every element of a [rows, C] tensor has its own fp16 slot inside the plane, the slots fill the plane when there are no
+    pad rows, and the plane is as large as the library says"""
+    idx = sf.brick_index(rows, Cc)
+    n = sf.plane_bytes(rows, Cc)
+    assert n == lib.acimg_split_plane_bytes(rows, Cc)
+    assert idx.numel() == rows * Cc and idx.unique().numel() == rows * Cc
+    assert int(idx.min()) >= 0 and int(idx.max()) < n // 2
+    if rows % 16 == 0:
+        assert torch.equal(idx.sort().values, torch.arange(n // 2))
+
+
+def test_brick_index_matches_the_header_by_hand():
+    """byte = ((row >> 4) * C / 32 + (c >> 5)) * 1024 + (row & 15) * 64 + (((c >> 3) ^ -(row >> 2)) & 3) * 16 + (c & 7) * 2
+    (include/acimg.h, "Pre-split activation format"), worked out by hand"""
+    for rows, Cc, row, c, byte in ((1, 32, 0, 0, 0),
+                                   (1, 32, 0, 9, 16 + 2),                       # group 1 stays group 1 in rows 0 .. 3
+                                   (16, 32, 5, 0, 5 * 64 + 3 * 16),             # rows 4 .. 7: group g at g ^ 3
+                                   (16, 32, 5, 17, 5 * 64 + 1 * 16 + 2),        # group 2 at 2 ^ 3 = 1
+                                   (40, 64, 17, 40, 3 * 1024 + 64 + 16),        # brick (1, 1) of 2 per row; group 5 & 3 = 1 at 1 ^ 0
+                                   (5320, 256, 5319, 255, (332 * 8 + 7) * 1024 + 7 * 64 + 0 * 16 + 14)):    # group 3 at 3 ^ 3 = 0
+        assert int(sf.brick_index(rows, Cc)[row * Cc + c]) * 2 == byte, (rows, Cc, row, c)

@@ -9,34 +9,13 @@ counts are 8 mod 16, on poisoned arenas."""
 import pytest
 import torch
 
-from test_ops_gpu import POISONS, brick_index, close, plane_bytes, repack, same_pads, unsplit
+from op_support import close_at, same_bits, same_pads, trunk_forms
+from split_format_ref import POISONS, make_planes, plane_bytes, repack, unsplit, valid_halves
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0xA5
-
-
-def make_planes(plan, device, x, rows, Cc):
-    """split planes of x [.., C] (identity affine, no ReLU) in a zeroed buffer: (planes, lo_off)"""
-    from acimg import ops
-
-    lo = plane_bytes(rows, Cc)
-    planes = torch.zeros(2 * lo, dtype=torch.uint8, device=device)
-    ops.bn_relu_split(plan, x.reshape(rows, Cc).float().contiguous().to(device), torch.ones(Cc, device=device),
-                      torch.zeros(Cc, device=device), 0, planes, lo, rows, Cc)
-    return planes, lo
-
-
-def same_bits(a, b):
-    """bit-identical (NaN included) fp32 tensors"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def valid_halves(buf, lo_off, rows, Cc):
-    """the valid rows' fp16 elements of both planes as int16 (bit patterns), row-major"""
-    idx = brick_index(rows, Cc).to(buf.device)
-    n = plane_bytes(rows, Cc)
-    return torch.cat([buf[o:o + n].view(torch.int16)[idx] for o in (0, lo_off)])
+close = close_at(2e-5)           # tests/test_ops_gpu.py RTOL
 
 
 def sentinel_out(rows, Cc, device, gap=4096, slack=4096):
@@ -64,14 +43,8 @@ def conv_ref(x, w, R):
 # (acimg_conv2d_fwd_split3_tiling()[2]: 0 one tile per workgroup, 1 persistent, 2 ring, 3 halo); "auto" is the shipped
 # choice.  The forced forms take 128x128 tiles also where the shipped rule would pick 64-row tiles (< 200 tiles).
 TILE128 = dict(split3_tile_bm=128, split3_tile_bn=128)
-FORMS = (("one-tile whole", dict(trunk_persistent=0, tail_split=0, trunk_ring=0), 0),
-         ("persistent whole", dict(trunk_persistent=2, tail_split=0, trunk_ring=0), 1),
-         ("one-tile", dict(trunk_persistent=0, trunk_ring=0), 0),
-         ("persistent", dict(trunk_persistent=2, trunk_ring=0), 1),
-         ("ring256", dict(trunk_ring=2, trunk_ring_bm=256), 2),
-         ("ring128", dict(trunk_ring=2, trunk_ring_bm=128), 2),
-         ("halo", dict(trunk_halo=2), 3),
-         ("auto", None, None))
+FORMS = trunk_forms("one-tile whole", "persistent whole", "one-tile", "persistent", "ring256", "ring128", "halo") + (
+    ("auto", None, None),)
 
 
 def _halo_fits(W):

@@ -9,18 +9,13 @@ import torch
 
 import summary_ref as sref
 from guard_arena import GuardArena
+from op_support import raw_lib
 
 pytestmark = pytest.mark.gpu
 
 CHUNK, GRID = 8192, 512          # csrc/summary.hip: elements per chunk, workgroups of the partial launch at most
 
 
-def _lib():
-    from acimg import _lib as m
-    return m, m.load()
-
-
-# ---- images -------------------------------------------------------------------------------------------------------------
 def _below(k):
     """the largest fp32 below k"""
     return np.nextafter(np.float32(k), np.float32(-np.inf))
@@ -67,7 +62,7 @@ def _strided_case():
 @pytest.mark.parametrize("case", [_frame_case, _strided_case])
 def test_summary_images_bit_equal(device, case):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     x, c0, G, n_images = case()
     N, H, W, ldc = x.shape
     want = sref.summary_images(x, c0, G, n_images)
@@ -165,7 +160,7 @@ def hist_case():
 
 def _run_hist(device, base, table, limits, total, arena=None, regions=None, ws_bytes=None):
     from acimg import ops
-    m, L = _lib()
+    m, L = raw_lib()
     V, nl = table.shape[0], len(limits)
     bd = torch.from_numpy(base).to(device)
     td = torch.from_numpy(table).to(device)
@@ -179,7 +174,7 @@ def _run_hist(device, base, table, limits, total, arena=None, regions=None, ws_b
 
 
 def test_histogram_segments(device, hist_case):
-    m, L = _lib()
+    m, L = raw_lib()
     base, table, limits, total, want, specs = hist_case
     V, nl = table.shape[0], len(limits)
     q = int(L.acimg_histogram_segments_workspace(V, nl, total))

@@ -5,46 +5,16 @@ one-stream run write the same events, and that a run without a logger computes t
 import glob
 import io
 import os
-import re
 from collections import OrderedDict
 
 import numpy as np
 import pytest
 
 import summary_ref as sref
+from data_support import write_outdoor_records
+from model_support import loss_lines
 
 pytestmark = pytest.mark.gpu
-
-
-def _write_records(tmp):
-    from acimg import tfio
-    rng = np.random.RandomState(23)
-    paths = []
-    for r in range(2):
-        ai = rng.rand(12, 36, 48, 12).astype(np.float32) * 5 - 1
-        sa = (rng.randn(12, 1024) * 800).astype(np.int32)
-        vi = rng.randint(0, 256, size=(12, 224, 298, 3)).astype(np.uint8)
-        ctx = OrderedDict([("classes", np.array([3 + r])), ("location", np.array([5 + r])),
-                           ("audio_image/height", np.array([36])), ("audio_image/width", np.array([48])),
-                           ("audio_image/depth", np.array([12])), ("audio_data/mics", np.array([1])),
-                           ("audio_data/samples", np.array([1024])), ("video/height", np.array([224])),
-                           ("video/width", np.array([298])), ("video/depth", np.array([3]))])
-        lists = OrderedDict([("audio/image", [a.tobytes() for a in ai]), ("audio/data", [s.tobytes() for s in sa]),
-                             ("video/image", [v.tobytes() for v in vi])])
-        p = str(tmp / ("part%d.tfrecord" % r))
-        tfio.write_tfrecord(p, [tfio.build_sequence_example(ctx, lists)], compression="GZIP")
-        paths.append(p)
-    train, valid = str(tmp / "train.txt"), str(tmp / "valid.txt")
-    with open(train, "w") as f:
-        f.write("\n".join(paths) + "\n")
-    with open(valid, "w") as f:
-        f.write(paths[0] + "\n")
-    return train, valid
-
-
-def _lines(log):
-    return [re.search(r"Iteration: \[ *\d+\]\t Training_mse_Loss: [0-9.]+\t Training_Loss: [0-9.]+", ln).group(0)
-            for ln in log if "Training_mse_Loss" in ln] + [ln.split("Validation_mse_Loss:")[1] for ln in log if "- Epoch:" in ln]
 
 
 @pytest.fixture(scope="module")
@@ -54,7 +24,12 @@ def runs(device, tmp_path_factory):
     histograms on one stream, the same pipelined"""
     from acimg.main import run_main
     tmp = tmp_path_factory.mktemp("cli")
-    train, valid = _write_records(tmp)
+    paths = write_outdoor_records(tmp, 23, [(3 + r, 5 + r) for r in range(2)], wide=True)
+    train, valid = str(tmp / "train.txt"), str(tmp / "valid.txt")
+    with open(train, "w") as f:
+        f.write("\n".join(paths) + "\n")
+    with open(valid, "w") as f:
+        f.write(paths[0] + "\n")
     out = {}
     for name, pipeline, logged in (("off", 0, False), ("p0", 0, True), ("p1", 1, True)):
         log, seen, box = [], [], {}
@@ -153,7 +128,7 @@ def test_pipeline_is_a_pure_schedule(runs):
     for x, y in zip(a, b):
         assert x["step"] == y["step"]
         assert x.get("summary") == y.get("summary")          # tags, order, scalars, PNG bytes, histograms
-    assert _lines(runs["p0"]["log"]) == _lines(runs["p1"]["log"])
+    assert loss_lines(runs["p0"]["log"], validation=True) == loss_lines(runs["p1"]["log"], validation=True)
 
 
 def test_histograms(runs):
@@ -183,7 +158,8 @@ def test_histograms(runs):
 
 def test_logger_off_changes_nothing(runs):
     off, on = runs["off"], runs["p0"]
-    assert len(_lines(off["log"])) == 3 and _lines(off["log"]) == _lines(on["log"])
+    lines = loss_lines(off["log"], validation=True)
+    assert len(lines) == 3 and lines == loss_lines(on["log"], validation=True)
     assert off["best"] == on["best"] and off["steps"] == on["steps"] == 2
     assert not glob.glob(off["ckpt"] + "/events*")
     a = off["state"]

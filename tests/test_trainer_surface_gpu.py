@@ -10,22 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from data_support import outdoor_arrays, outdoor_example
+from model_support import make
+
 pytestmark = pytest.mark.gpu
-
-
-def make(device, lr=1e-3, epochs=1):
-    from acimg.flags import FLAGS
-    from acimg.session import Session
-    from acimg.trainer import Trainer
-    from acimg.unet_acresnet import UNetAc
-    from acimg.vision import ResNet50Model
-
-    FLAGS.model, FLAGS.ae, FLAGS.latent_loss = "UNet", 0, 1e-6
-    sess = Session(device)
-    tr = Trainer(UNetAc(input_shape=[36, 48, 12], embedding=False, num_skip=1),
-                 ResNet50Model(input_shape=[224, 298, 3], num_classes=None), display_freq=1, learning_rate=lr,
-                 num_epochs=epochs, session=sess)
-    return tr, sess
 
 
 def test_train_checkpoint_restore_test(device, tmp_path):
@@ -157,8 +145,6 @@ def test_tfrecord_loader_feeds_the_trainer(device, tmp_path):
     -> device low-pass + MFCC with `_normalize_mfcc` (:558-575, :696-703, :796-876) -> per-frame maps (:634-679) ->
     frames re-batched (:99-104) -> `Trainer.train()`.  Every tensor of every batch against the pinned CPU oracle of the
     front end and a NumPy restatement of the maps; then one epoch of training + validation straight from the files."""
-    from collections import OrderedDict
-
     from acimg import tfio
     from acimg.data import TFRecordDataLoader
     from acimg.flags import FLAGS
@@ -167,17 +153,8 @@ def test_tfrecord_loader_feeds_the_trainer(device, tmp_path):
     rng = np.random.RandomState(3)
     recs, truth = [], []
     for r in range(2):
-        ai = rng.rand(12, 36, 48, 12).astype(np.float32) * 5 - 1
-        sa = (rng.randn(12, 1024) * 800).astype(np.int32)
-        vi = rng.randint(0, 256, size=(12, 224, 298, 3)).astype(np.uint8)
-        ctx = OrderedDict([("classes", np.array([3 + r])), ("location", np.array([7])),
-                           ("audio_image/height", np.array([36])), ("audio_image/width", np.array([48])),
-                           ("audio_image/depth", np.array([12])), ("audio_data/mics", np.array([1])),
-                           ("audio_data/samples", np.array([1024])), ("video/height", np.array([224])),
-                           ("video/width", np.array([298])), ("video/depth", np.array([3]))])
-        lists = OrderedDict([("audio/image", [a.tobytes() for a in ai]), ("audio/data", [s.tobytes() for s in sa]),
-                             ("video/image", [v.tobytes() for v in vi])])
-        recs.append(tfio.build_sequence_example(ctx, lists))
+        ai, sa, vi = outdoor_arrays(rng, wide=True)
+        recs.append(outdoor_example(ai, sa, vi, 3 + r, 7))
         truth.append((ai, sa, vi, 3 + r))
     paths = []
     for i, rec in enumerate(recs):

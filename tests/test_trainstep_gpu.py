@@ -10,9 +10,14 @@ different but equally valid subgradient, so for the BACKWARD comparison the orac
 patterns from the HIP run (both sides then differentiate the same piecewise-linear function); forward
 values are compared independently and the number of such flips is printed.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
+
+import op_support
+from model_support import MASK_PAIRS, build, saved_activations
 
 pytestmark = pytest.mark.gpu
 
@@ -24,63 +29,10 @@ TOL = 1e-3
 FLIP_RATE = 3.2e-6
 
 
-def rel_err(got, ref):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    return float((got - ref).abs().max() / max(float(ref.abs().max()), 1e-12))
-
-
-def l2_err(got, ref):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    return float((got - ref).norm() / max(float(ref.norm()), 1e-30))
-
-
-def build(device, num_skip, embedding, batch, lr=1e-3, precision="f16x3", bench_defaults=False, side_lane=True, stages=None):
-    from acimg.flags import FLAGS
-    from acimg.session import Session
-    from acimg.trainer import Trainer
-    from acimg.unet_acresnet import UNetAc
-    from acimg.vision import ResNet50Model
-    from oracle import trainer as otr
-
-    FLAGS.model = "UNet"
-    FLAGS.ae = int(embedding)
-    # larger than the default 1e-6 so the KL path is visible in the gradients (bench_defaults: the bench's own 1e-6)
-    FLAGS.latent_loss = 1e-6 if bench_defaults else 1e-3
-    orc = otr.Oracle(num_skip=num_skip, embedding=embedding, learning_rate=lr, latent_loss=FLAGS.latent_loss,
-                     randomize=True)
-    sess = Session(device)
-    mi = ResNet50Model(input_shape=[224, 298, 3], num_classes=None, precision=precision, stages=stages, side_lane=side_lane)
-    ma = UNetAc(input_shape=[36, 48, 12], embedding=embedding, num_skip=num_skip,
-                precision="split" if precision == "f16x3" else "f32", side_lane=side_lane)
-    if not bench_defaults:
-        ma.split_min_rows = 0   # exercise the split-MFMA generator convs even at the tiny test batch
-    tr = Trainer(ma, mi, learning_rate=lr, session=sess)
-    tr._build_functions(batch_size=batch)
-    loaded = sess.store.load_state(orc.state_dict(), strict=True)
-    assert len(loaded) == len(orc.state_dict())
-    return tr, orc, sess
-
-
-MASK_PAIRS = [("c11", "layer1/conv_1"), ("conv1", "layer1/conv_2"), ("pool1", "layer1/pool_2"),
-              ("c21", "layer2/conv_1"), ("conv2_0", "layer2/conv_2"), ("dns", "dense"), ("net", "conv2d"),
-              ("c41", "layer4/conv_1"), ("conv4", "layer4/conv_2"), ("c51", "layer5/conv_1"),
-              ("conv5", "layer5/conv_2"), ("c61", "layer6/conv_1"), ("conv6", "layer6/conv_2"),
-              ("c71", "layer7/conv_1"), ("conv7", "layer7/conv_2")]
+rel_err = functools.partial(op_support.rel_err, floor=1e-12)
+l2_err = functools.partial(op_support.l2_err, floor=1e-30)
 EP_KEYS = {"layer1/conv_2": "conv1", "layer1/pool_2": "pool1", "layer2/conv_2": "conv2_0", "layer4/conv_2": "conv4",
            "layer5/conv_2": "conv5", "layer6/conv_2": "conv6", "layer7/conv_2": "conv7"}
-
-
-def saved_activations(g):
-    """{oracle layer name: post-ReLU activation saved by the HIP forward} (+ the ResNet feature)"""
-    out = {}
-    for attr, key in MASK_PAIRS:
-        a = getattr(g.modelac, attr)
-        out[key] = a.t.cpu().reshape(a.N, a.H, a.W, -1)[..., a.off:a.off + a.C]
-    out["conv_map"] = g.modelimages.output.cpu()
-    return out
 
 
 def tf_adam_fp64(p, g, m, v, step, lr):

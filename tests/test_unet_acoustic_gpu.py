@@ -1,6 +1,7 @@
 """The acoustic-image VAE `UNetAc` (scope 'UNetAcoustic'; SURVEY A.3 last row, §8 a9): models/unet_noconc.py as a
 stand-alone VAE train step (trainer/trainer.py, encoder_type 'Ac') and models/unet_z.py as the decoder driven by
 external (mean2, std2) — outputs, losses, every gradient (incl. d loss / d (mean2, std2)) vs the fp64 oracle."""
+import functools
 import os
 import sys
 
@@ -12,21 +13,13 @@ for p in (ROOT, os.path.join(ROOT, "acoustic-image-generation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from model_support import noconc_masks  # noqa: E402
+from op_support import rel_err  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def _masks(m):
-    acts = {"layer1/conv_1": m.c11, "layer1/conv_2": m.conv1, "layer1/pool_2": m.pool1, "layer3/conv_1": m.c31,
-            "layer3/conv_2": m.conv2, "conv2d": m.net, "layer4/conv_1": m.c41, "layer4/conv_2": m.conv4,
-            "layer5/conv_1": m.c51, "layer5/conv_2": m.conv5}
-    out = {k: (a.t[..., :a.C] > 0).cpu() for k, a in acts.items()}
-    out["dense"] = (m.dns.t > 0).cpu()
-    return out
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 
 @pytest.mark.parametrize("precision", ["split", "f32"])
@@ -50,7 +43,7 @@ def test_unet_noconc_vae_step(precision):
     torch.cuda.synchronize()
     m = tr.model
     p = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    fw = oa.forward(p, x, eps, relu_masks=_masks(m))
+    fw = oa.forward(p, x, eps, relu_masks=noconc_masks(m))
     ls = oa.vae_losses(x, fw)
     grads = dict(zip(p.keys(), torch.autograd.grad(ls["loss"], list(p.values()))))
     assert rel(m.output, fw["output"].detach()) < 1e-4 and rel(m.mean, fw["mean"].detach()) < 1e-4
@@ -93,7 +86,7 @@ def test_unet_z_external_latent():
     m.initialize(state={k: v.float() for k, v in params.items()})
     plan.run()
     torch.cuda.synchronize()
-    masks = _masks(m)
+    masks = noconc_masks(m)
     p = {k: v.clone().requires_grad_(True) for k, v in params.items()}
     m2, s2 = mean2.clone().requires_grad_(True), std2.clone().requires_grad_(True)
     fw = oa.forward(p, x, eps, m2, s2, relu_masks=masks)

@@ -1,6 +1,7 @@
 """Parity of the RGB / spectrogram U-Net VAE train step (BASELINE configs[0]/[1]) against the CPU
 oracle (fp64): outputs, loss terms, every gradient, BN moving statistics and one TF-1 Adam update, through the C ABI.
 Tolerance: 1e-3 relative (north_star), observed ~1e-5."""
+import functools
 import os
 import sys
 
@@ -12,12 +13,12 @@ for p in (ROOT, os.path.join(ROOT, "acoustic-image-generation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from op_support import l2_err, rel_err  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 
 def _hip_masks(m):
@@ -236,9 +237,7 @@ def test_bf16_operand_convs(case):
     assert rel(y, y32) > 2e-4
 
 
-def l2rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+l2rel = functools.partial(l2_err, floor=1e-30)
 
 
 def test_unet_vae_bf16_train_step():

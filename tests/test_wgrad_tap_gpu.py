@@ -8,36 +8,26 @@ column blocks of 128 or 64 with ragged columns, leading dimensions wider than th
 splits than there are row tiles, so no split is left without a tile; `test_more_splits_granted_than_tiles` is the shape where
 that cap binds.  Shapes just outside the predicate must still match fp64 on the per-tap kernel."""
 import ctypes as C
+import functools
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import op_support
+from op_support import up4, widen
 
 pytestmark = pytest.mark.gpu
 
 TOL = 3e-5             # tests/test_ops_gpu.py::test_split3_generator_convs: bf16x3 weight / bias gradient against fp64
 GSCALE = 1e-7
-
-
-def close(got, ref, tol, what=""):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    scale = max(ref.abs().max().item(), 1e-12)
-    err = (got - ref).abs().max().item() / scale
-    print("%s: rel err %.3e (tol %.1e)" % (what, err, tol))
-    assert np.isfinite(err) and err <= tol, "%s: rel err %.3e > %.1e" % (what, err, tol)
-
-
-def up4(v):
-    return (v + 3) & ~3
+close = functools.partial(op_support.close, show=True)
 
 
 _REF = {}
 
 
-def reference(N, H, W, Cc, K):
+def wgrad_reference(N, H, W, Cc, K):
     """x, gy (float32 values held as float64) and the fp64 autograd dW, db of the 3x3 SAME convolution; computed once"""
     key = (N, H, W, Cc, K)
     if key not in _REF:
@@ -52,18 +42,11 @@ def reference(N, H, W, Cc, K):
     return _REF[key]
 
 
-def widen(t, ld, off=0, fill=float("nan")):
-    """[..., n] -> [..., ld] with t at columns off .. off + n and `fill` elsewhere"""
-    out = torch.full(tuple(t.shape[:-1]) + (ld,), fill, dtype=torch.float32)
-    out[..., off:off + t.shape[-1]] = t.float()
-    return out
-
-
 def run_ops(device, case, ldx=None, gy_wide=False, with_db=True):
     from acimg import ops
 
     N, H, W, Cc, K = case
-    x, gy, gw, gb = reference(*case)
+    x, gy, gw, gb = wgrad_reference(*case)
     kp = up4(K)
     d = ops.conv_desc(N, H, W, Cc, K, 3, 3, 1, "SAME", ldx=ldx)
     xd = (x.float() if ldx is None else widen(x, ldx)).contiguous().to(device)
@@ -130,7 +113,7 @@ def test_caller_memory_replay_and_old_kernel(device):
     L = m.load()
     case = (2, 36, 48, 128, 64)
     N, H, W, Cc, K = case
-    x, gy, gw, gb = reference(*case)
+    x, gy, gw, gb = wgrad_reference(*case)
     ldw, tail = K + 8, 1024
     d = ops.conv_desc(N, H, W, Cc, K, 3, 3, 1, "SAME", ldw=ldw)
     xd, gyd = x.float().to(device), gy.float().to(device)

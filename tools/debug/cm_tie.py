@@ -1,10 +1,12 @@
 """debug: train-step parity case (2 skips, f16x3): per step, the per-sample top-2 of the conv_map feature in the HIP run
 and in the oracle, and the worst conv_map gradients"""
-import os, sys
+import functools, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "acoustic-image-generation_amd"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "acoustic-image-generation_amd"), os.path.join(ROOT, "tests")]
 import torch
-from tests.test_trainstep_gpu import build, saved_activations, rel_err
+import op_support
+from model_support import build, saved_activations
+rel_err = functools.partial(op_support.rel_err, floor=1e-12)
 from oracle import trainer as otr
 dev = torch.device("cuda:0")
 tr, orc, sess = build(dev, 2, False, 2, 1e-3, "f16x3")

@@ -1,14 +1,16 @@
 """diagnostics of the joint-latent step against its oracle: relative errors stage by stage"""
-import os, sys
+import functools, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "acoustic-image-generation_amd"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "acoustic-image-generation_amd"), os.path.join(ROOT, "tests")]
 import torch
 from acimg.multimodal import Jointmvae
 from acimg.session import Session
 from acimg.trainer_multi import TrainerMulti
 from acimg.unet_joint import UNetAc2, UNetSound22, Unet2
 from oracle import joint
-from tests.test_joint_gpu import rel
+from op_support import rel_err
+
+rel = functools.partial(rel_err, floor=1e-30, same_shape=False)
 
 dev = torch.device("cuda:0")
 N = 2
