@@ -167,6 +167,10 @@ PROTOTYPES = {
     "acimg_knn_topk": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "acimg_knn_topk_workspace": (_SZ, [_I, _I, _I, _I]),
     "acimg_knn_vote": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "acimg_tsne_affinities": (_I, [_P, _I, _I, _I, _D, _P, _I, _P, _P, _P]),
+    "acimg_tsne_symmetrize": (_I, [_P, _I, _I, _P]),
+    "acimg_tsne_gradient": (_I, [_P, _I, _I, _P, _I, _P, _P]),
+    "acimg_tsne_update": (_I, [_P, _I, _D, _D, _D, _P, _P, _P, _P, _P]),
     "acimg_batch_gather": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "acimg_batch_gather_workspace": (_SZ, [_I, _I]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),

@@ -905,6 +905,31 @@ def knn_vote(plan, idx, ldidx, Q, K, gallery_labels, query_labels, num_classes, 
              int(num_classes), pred, first_hit)
 
 
+def tsne_affinities(plan, x, ldx, N, D, perplexity, P, ldp, beta, steps):
+    """conditional t-SNE affinities p_{j|i} of the rows of fp64 x [N,ldx] -> P [N,ldp] (diagonal 0, columns >= N
+    untouched), the precision beta [N] the search of every row ended at and its step count int32 [N]"""
+    plan.add("tsne_affinities", _L().acimg_tsne_affinities, x, int(ldx), int(N), int(D), float(perplexity), P, int(ldp),
+             beta, steps)
+
+
+def tsne_symmetrize(plan, P, ldp, N):
+    """in place: P[i][j] = P[j][i] = (P[i][j] + P[j][i]) / (2N), diagonal 0"""
+    plan.add("tsne_symmetrize", _L().acimg_tsne_symmetrize, P, int(ldp), int(N))
+
+
+def tsne_gradient(plan, P, ldp, N, Y, want_kl, rows):
+    """per row of Y [N,2]: attractive sums (x, y), repulsive sums (x, y), sum of w, KL part (0 unless want_kl) ->
+    rows float64 [N,6]"""
+    plan.add("tsne_gradient", _L().acimg_tsne_gradient, P, int(ldp), int(N), Y, int(bool(want_kl)), rows)
+
+
+def tsne_update(plan, rows, N, e, momentum, learning_rate, Y, V, G, kl=None):
+    """gains, velocity and position rule of one t-SNE iteration from the row sums (exaggeration e); kl [1] receives
+    the divergence at the Y the rows were formed from"""
+    plan.add("tsne_update", _L().acimg_tsne_update, rows, int(N), float(e), float(momentum), float(learning_rate), Y, V,
+             G, kl)
+
+
 def batch_gather(plan, pool_video, video_stride, pool_acoustic, pool_mfcc, pool_mfcc_low, pool_labels, slots, N, pixels,
                  elems, video, acoustic, mfcc, mfcc_low, action, num_actions, location, num_locations):
     """frames slots[0..N) (int32 on the device, every one inside the pool) of a pool of decoded records -> one batch:

@@ -753,6 +753,46 @@ size_t acimg_knn_topk_workspace(int Q, int G, int D, int K);
 int acimg_knn_vote(const int32_t* idx, int ldidx, int Q, int K, const int32_t* gallery_labels,
                    const int32_t* query_labels, int num_classes, int32_t* pred, int32_t* first_hit, void* stream);
 
+/* Exact two-component t-SNE of a latent dump, fp64 throughout (what knn.py:67-90 asks of sklearn.manifold.TSNE; the
+ * algorithm is van der Maaten & Hinton's, the precision search sklearn's _binary_search_perplexity).  Four entries; an
+ * iteration of the descent is acimg_tsne_gradient followed by acimg_tsne_update.  All are stream-ordered, take no
+ * workspace, use no atomics and reduce in fixed trees: two runs give the same bits.  Inputs must be finite.
+ *
+ * acimg_tsne_affinities: conditional affinities of the rows of x [N][ldx].  For every row i, with
+ *   d_ij = sum_d (x[i][d] - x[j][d])^2 (direct-difference form, summed in feature order),
+ *   the search starts at beta = 1 with the bracket (-inf, +inf) and runs at most 100 steps.  A step forms, over j != i,
+ *   p_j = exp(-d_ij * beta), S = sum p_j (S == 0 -> 1e-8), H = log S + beta * (sum d_ij p_j) / S and
+ *   diff = H - log(perplexity); it stops when |diff| <= 1e-5; otherwise diff > 0 raises the lower end of the bracket to
+ *   beta (beta doubles while the upper end is +inf, else moves to the bracket's middle) and diff <= 0 lowers the upper
+ *   end (beta halves while the lower end is -inf, else moves to the middle).
+ *   P[i][j] = p_j / S of the last step evaluated, P[i][i] = 0; beta[i] = the beta of that step; steps[i] = the number of
+ *   steps evaluated (1..100; 100 without |diff| <= 1e-5 means the search ran out).  Columns j >= N of P are never
+ *   written (nor read).  Row i of P also serves as the scratch of row i's distances while the call runs.
+ *   N >= 4, D >= 1, ldx >= D, ldp >= N, 1 < perplexity < N - 1 (else ACIMG_EINVAL).
+ *
+ * acimg_tsne_symmetrize: in place, P[i][j] = P[j][i] = (P[i][j] + P[j][i]) / (2N) - one addition, one true division,
+ *   formed once per unordered pair, so the result is symmetric bit for bit - and P[i][i] = 0.  Columns j >= N untouched.
+ *
+ * acimg_tsne_gradient: with w_ij = 1 / (1 + |Y[i] - Y[j]|^2) (Y [N][2], j != i), rows [N][6] receives
+ *   rows[i][0..1] = sum_j P[i][j] w_ij (Y[i] - Y[j])   (x, y: the attractive sums, NOT exaggerated),
+ *   rows[i][2..3] = sum_j w_ij^2 (Y[i] - Y[j])         (x, y: the repulsive sums, NOT divided by Z),
+ *   rows[i][4]    = sum_j w_ij,
+ *   rows[i][5]    = sum_{j: P[i][j] > 0} P[i][j] (log P[i][j] - log w_ij) when want_kl != 0, else 0 (the logarithms
+ *                   cost about as much as the rest of the pass).
+ *
+ * acimg_tsne_update: Z = sum_i rows[i][4]; per element (c = 0, 1) g = 4 (e * rows[i][c] - rows[i][2 + c] / Z), then
+ *   G = (g * V < 0) ? G + 0.2 : G * 0.8, G = max(G, 0.01); V = momentum * V - learning_rate * G * g; Y += V
+ *   (Y, V, G [N][2], updated in place).  kl, when not NULL, receives kl[0] = sum_i rows[i][5] + log Z: the
+ *   Kullback-Leibler divergence at the Y the rows were formed from, provided they were formed with want_kl and P sums
+ *   to 1.  Y, V and G may be NULL together (kl not): then only kl[0] is formed, e.g. at the final Y.
+ *   e, learning_rate > 0, momentum >= 0, all finite; N >= 1 (else ACIMG_EINVAL). */
+int acimg_tsne_affinities(const double* x, int ldx, int N, int D, double perplexity, double* P, int ldp, double* beta,
+                          int32_t* steps, void* stream);
+int acimg_tsne_symmetrize(double* P, int ldp, int N, void* stream);
+int acimg_tsne_gradient(const double* P, int ldp, int N, const double* Y, int want_kl, double* rows, void* stream);
+int acimg_tsne_update(const double* rows, int N, double e, double momentum, double learning_rate, double* Y, double* V,
+                      double* G, double* kl, void* stream);
+
 /* Batch assembly out of a device-resident pool of decoded frames (acimg/data.py: DeviceDataLoader): the per-frame maps
  * of dataloader/outdoor_data_mfcc.py:634-703 applied while the N frames slots[0..N) of a batch are gathered.  (Added
  * without raising ACIMG_VERSION: nothing existing changed, and the number is pinned by the host tests.)
