@@ -29,6 +29,15 @@ inline int check_launch(const char* what) {
 }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// workgroups of 256 threads for `work` items: ceil(work / 256), clamped to [1, cap]
+inline int clamped_blocks(long work, long cap) {
+    long b = (work + 255) / 256;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+// grid of the grid-stride elementwise kernels
+inline int ew_grid(long work_items) { return clamped_blocks(work_items, 4096); }
 
 // ---- device helpers ---------------------------------------------------------------------
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -66,9 +75,24 @@ __device__ __forceinline__ float block_sum(float v, float* smem /* >= 17 floats 
     return r;
 }
 
+// per-component float4 arithmetic of the 16-byte elementwise passes
+__device__ __forceinline__ float4 affine4(const float4 v, const float4 s, const float4 t) {
+    return make_float4(v.x * s.x + t.x, v.y * s.y + t.y, v.z * s.z + t.z, v.w * s.w + t.w);
+}
+__device__ __forceinline__ float4 relu4(const float4 v) {
+    return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+}
+__device__ __forceinline__ float4 scale4(const float4 v, const float k) {
+    return make_float4(v.x * k, v.y * k, v.z * k, v.w * k);
+}
+__device__ __forceinline__ float4 max4(const float4 a, const float4 b) {
+    return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+}
+
 // ---- split-fp16 ("f16x3") operand format ------------------------------------------------------
 // A value v is kept as hi = f16(v*SCALE), lo = f16(v*SCALE - hi): 22 mantissa bits in 4 bytes.  The
 // power-of-two scales keep fp16 in range: activations x2^-2 (finite up to 2.6e5), weights x2^10.
+// (Where the halves of a pre-split activation tensor lie in memory - the brick planes - is split_planes.hpp's.)
 constexpr float SPLIT3_WSCALE = 1024.f;
 constexpr float SPLIT3_ASCALE = 0.25f;
 constexpr float SPLIT3_OUTSCALE = 1.f / 256.f;   // undoes both on the fp32 accumulators

@@ -293,12 +293,7 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
 }
 
 // column sums; workspace: parts*ncols floats
-static int colsum_parts(long rows) {
-    int parts = (int)((rows + 255) / 256);
-    if (parts > 256) parts = 256;
-    if (parts < 1) parts = 1;
-    return parts;
-}
+static int colsum_parts(long rows) { return clamped_blocks(rows, 256); }
 static int launch_colsum(const float* G, long rows, int ncols, int ld, float* out, void* ws,
                          size_t ws_bytes, hipStream_t st) {
     const int parts = colsum_parts(rows);

@@ -29,16 +29,15 @@
 // fp32 accuracy is enough here (tests/test_ops_gpu.py::test_gram_statistics_match_fp64: mean and variance to 1e-6
 // relative against fp64 statistics of the conv output; a numpy experiment at C = 512 put the fp32 quadratic form at 1e-6 of
 // the variance, 10 x that of an fp64 one, three orders under the 1e-3 bar).
-#include "common.hpp"
+#include "split_planes.hpp"      // the brick layout this file reads (swz)
 
 namespace acimg {
 
-// (the few helpers shared with the trunk kernels are restated here: their headers define non-template kernels, which
+// (the few other helpers shared with the trunk kernels are restated here: their headers define non-template kernels, which
 //  may live in one translation unit only)
 namespace {
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 constexpr unsigned OOB = 0x80000000u;      // >= num_records of every descriptor (tensors < 2 GiB): the DMA writes zeros
-__device__ __forceinline__ int swz(int row) { return (0 - (row >> 2)) & 3; }   // brick chunk swizzle (igemm_split3_kernel.hpp)
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");

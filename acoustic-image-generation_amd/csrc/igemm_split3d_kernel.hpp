@@ -1,7 +1,7 @@
 // f16x3 forward convolution on PRE-SPLIT activations with LDS-DMA operand staging (gfx950): the trunk kernel.
 //
 // A is stored in HBM as two fp16 planes of 16-pixel x 32-channel bricks (hi at p.A, lo p.a_lo_off bytes further; values
-// already carry the 2^-2 scale and any BN affine + ReLU, written by the elementwise producers in elementwise.hip), B is
+// already carry the 2^-2 scale and any BN affine + ReLU, written by the producers in batchnorm.hip; layout: split_planes.hpp), B is
 // the tile-ordered weight image behind the row-major planes of `split3_prepare_kernel` (see "bricks" below).  Same GEMM core, LDS image (64-byte rows,
 // chunk ^ swz(row)) and epilogue as `igemm_split3_kernel`, but neither operand tile passes through VGPRs:
 // every wave copies 1-KiB pieces (16 tile rows of one fp16 plane) global -> LDS with
@@ -41,10 +41,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 //     128-byte lines); a shifted (3x3 tap) or strided piece is still a per-lane gather, now out of one or two bricks;
 //   * weights: behind the row-major planes, for every (128-column tile n >> 7, K step q) the two 8 KiB plane images
 //     [row n & 127][64 B] with the same chunk swizzle (acimg_conv2d_split3_prepare writes both forms).
-__device__ __forceinline__ unsigned brick_a_off(unsigned f, unsigned c32, unsigned kc) {
-    // byte offset of logical chunk kc of pixel f's row in channel chunk 0; c32 = C * 32 = bytes of one pixel block
-    return (f >> 4) * c32 + ((f & 15u) << 6) + (((kc ^ (0u - (f >> 2))) & 3u) << 4);
-}
+// (the activation side, brick_a_off, is stated with the rest of that layout in split_planes.hpp)
 __device__ __forceinline__ unsigned brick_b_off(unsigned n, unsigned ksteps, unsigned pch) {
     // byte offset (hi plane, K step 0) of physical chunk pch of weight row n; + 16384 per K step, + 8192 for the lo plane
     return (n >> 7) * ksteps * 16384u + ((n & 127u) << 6) + (pch << 4);

@@ -1,4 +1,4 @@
-"""Plain numpy restatement of randn_kernel (csrc/elementwise.hip): Philox4x32-10 + Box-Muller, four samples per counter.
+"""Plain numpy restatement of randn_kernel (csrc/optim.hip): Philox4x32-10 + Box-Muller, four samples per counter.
 
 counter = (ctr_lo, ctr_hi, 0x9E3779B9, 0xBB67AE85) with ctr = quad + offset as a 64-bit sum, key = (seed_lo, seed_hi);
 words (0, 1) and (2, 3) of the output feed one Box-Muller draw each: sample 4q + {0, 1} = r0 * {cos, sin}(2 pi u1),

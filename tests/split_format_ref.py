@@ -489,7 +489,8 @@ def impulse_operands(case):
 
 # ----------------------------------------------------------------------------------------------------------------------
 # the activation-plane layout (include/acimg.h, "Pre-split activation format"): two fp16 planes, hi at byte 0 and lo at
-# lo_off, each of whole 16-pixel x 32-channel bricks of 1 KiB
+# lo_off, each of whole 16-pixel x 32-channel bricks of 1 KiB.  These functions mirror csrc/split_planes.hpp, the one C++
+# statement of the layout: plane_bytes its split_plane_bytes, brick_index its plane_off with swz.
 # ----------------------------------------------------------------------------------------------------------------------
 def plane_bytes(rows, Cc):
     """bytes of one split-format plane: whole 16-pixel x 32-channel bricks"""

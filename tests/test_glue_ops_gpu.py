@@ -1,4 +1,4 @@
-"""Direct fp64 parity of the glue, optimizer and RNG kernels of csrc/elementwise.hip at sizes past one grid sweep.
+"""Direct fp64 parity of the glue, optimizer and RNG kernels of csrc/glue.hip, optim.hip, loss.hip and batchnorm.hip at sizes past one grid sweep.
 
 Every launch here goes through ew_grid(), which caps the grid at 4096 workgroups of 256 threads: a call with more than
 SWEEP = 1,048,576 work items (float4s for adam_step / bn_add_relu / bn_relu_maxpool, pixels for pad_image, scalars
@@ -436,7 +436,7 @@ def test_bn_relu_bwd(device, rows):
 # acimg_minmax_fwd / _bwd
 # ------------------------------------------------------------------------------------------------------------------
 # P, C, ldx (= ldgx), ld of the buffer the output (and its gradient) is a slice of, first column of the slice, chunks.
-# The chunk counts are minmax_chunks(P, C) of elementwise.hip, worked out by hand and checked against the workspace size
+# The chunk counts are minmax_chunks(P, C) of glue.hip, worked out by hand and checked against the workspace size
 MINMAX_REGIMES = [
     (7, 12, 16, 20, 0, 1),
     (192, 133, 136, 148, 0, 13),
