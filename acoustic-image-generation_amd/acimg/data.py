@@ -70,10 +70,12 @@ class TFRecordDataLoader(object):
     reference's session.run results, and `Trainer._feed` copies them up.
     embedding=0 is the path without `unbatch` (:102-107): `batch_size` counts records (clips); the frame tensors come out
     as [B*12, ...] with each clip's frames consecutive and in record order, the two label tensors as ONE row per clip
-    ([B, num_actions], [B, num_locations]); `num_samples` / `total_batches` count clips."""
+    ([B, num_actions], [B, num_locations]); `num_samples` / `total_batches` count clips.
+    raw_audio=True: every batch carries a seventh tensor, the records' int32 [n,1024] audio samples as stored, batched
+    like the other frame tensors (the sound track of `python -m acimg.show video --avi 1`)."""
 
     def __init__(self, files, batch_size, num_actions=10, num_locations=61, device="cuda:0", frames_per_record=12,
-                 compression_verify=True, embedding=1):
+                 compression_verify=True, embedding=1, raw_audio=False):
         from .frontend import FrontEnd
         if isinstance(files, str):
             with open(files) as f:
@@ -84,6 +86,7 @@ class TFRecordDataLoader(object):
         self.frames = int(frames_per_record)
         self.verify = bool(compression_verify)
         self.embedding = _embedding(embedding)
+        self.tensors = 7 if raw_audio else 6
         self.device = torch.device(device)
         self.fe = FrontEnd(self.device)
         self.data = self
@@ -128,15 +131,18 @@ class TFRecordDataLoader(object):
         act[:, d["action"]] = 1.0
         loc = np.zeros((n, self.num_locations), np.float32)
         loc[:, d["location"]] = 1.0
-        return (torch.from_numpy(a), mfcc.cpu(), torch.from_numpy(np.ascontiguousarray(v)), torch.from_numpy(act),
-                torch.from_numpy(loc), mfcc_low.cpu())
+        out = (torch.from_numpy(a), mfcc.cpu(), torch.from_numpy(np.ascontiguousarray(v)), torch.from_numpy(act),
+               torch.from_numpy(loc), mfcc_low.cpu())
+        if self.tensors == 7:
+            out += (torch.from_numpy(np.ascontiguousarray(sa, dtype=np.int32)),)
+        return out
 
     def _clip_batch(self, pend):
         """whole records -> one clip batch: frames concatenated, the two label tensors cut to one row per record"""
         for p_ in pend:
             if p_[0].shape[0] != self.frames:
                 raise ValueError("clip mode wants records of %d frames, got one of %d" % (self.frames, p_[0].shape[0]))
-        return tuple(torch.cat([(p_[k][:1] if k in (3, 4) else p_[k]) for p_ in pend], 0) for k in range(6))
+        return tuple(torch.cat([(p_[k][:1] if k in (3, 4) else p_[k]) for p_ in pend], 0) for k in range(self.tensors))
 
     def _iter_clips(self):
         from . import tfio
@@ -166,13 +172,13 @@ class TFRecordDataLoader(object):
                 pend.append(self._record(rec))
                 have += pend[-1][0].shape[0]
                 while have >= self.batch_size:
-                    cat = [torch.cat([p_[k] for p_ in pend], 0) for k in range(6)]
+                    cat = [torch.cat([p_[k] for p_ in pend], 0) for k in range(self.tensors)]
                     yield tuple(c[:self.batch_size] for c in cat)
                     rest = tuple(c[self.batch_size:] for c in cat)
                     have = rest[0].shape[0]
                     pend = [rest] if have else []
         if have:
-            yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(6))
+            yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(self.tensors))
 
 
 # ---- the tf.data machinery of dataloader/outdoor_data_mfcc.py:99-105 -------------------------------------------------

@@ -3,7 +3,11 @@
 Stands where the reference's three plotting scripts stand, with their flags, directories and file names:
 * `video`: showvideo.py (records of `TFRecordDataLoader`): every frame's generated energy map over the grey frame,
   `<dir of train_file>/Generated_10s/I_%06d.png` (:63, :230).  No ffmpeg is run: `show.json` records the frame count, the
-  12 fps rate, the file pattern and the two ffmpeg command lines of :247 and :260 as strings;
+  12 fps rate, the file pattern and the two ffmpeg command lines of :247 and :260 as strings.  With `--avi 1` the merged
+  clip of :260 is written as well, by this package: `<dir of train_file>/video_<class>_<video>_<checkpoint>.avi`, the
+  frames as Motion-JPEG encoded on the device (`acimg.jpeg`: `acimg_jpeg_blocks`, `acimg_jpeg_scan`, `--quality`,
+  `--restart_mcus`) and the records' sound as 16-bit PCM normalised to the clip's peak (`acimg.avi`), 1024 samples per
+  frame at 12288 Hz; `show.json` then also names the file, its size, the quality, the restart interval and the rate;
 * `images`: showimages.py: the real acoustic image's map beside the generated one's (real on the left, :107),
   `<checkpoint dir>/<model>_<data set>_AcousticMapJet_<checkpoint number>/<data set>_images_<n>.png` (:32-39, :151);
 * `boxes`: showimages_bb.py with --plot 1 (box-annotated records, `BoxRecordLoader`): the generated map over the frame
@@ -22,6 +26,8 @@ from .localize import build_trainer
 
 RESULT_FILE = "show.json"
 FPS = 12
+SAMPLES_PER_FRAME = 1024
+SAMPLE_RATE = SAMPLES_PER_FRAME * FPS      # 12288: sound and picture stay in step
 GAP = 8      # white columns between the two panels of `images`
 
 # showvideo.py:126-132: class directory -> the name in the merged video's file name
@@ -52,6 +58,10 @@ def build_parser():
     v = sub.add_parser("video", help="showvideo.py: the frames of a demo video")
     common(v)
     v.add_argument("--data_type", type=str, default="outdoor", help="outdoor or old: the class names of the video's name")
+    v.add_argument("--avi", type=int, default=0, choices=(0, 1), help="1: also write the clip as MJPEG + PCM in an AVI file")
+    v.add_argument("--quality", type=int, default=90, help="JPEG quality of the clip's frames (1 - 100)")
+    v.add_argument("--restart_mcus", type=int, default=None,
+                   help="16x16-pixel MCUs per JPEG restart interval (default: one MCU row)")
     i = sub.add_parser("images", help="showimages.py: real beside generated")
     common(i)
     i.add_argument("--datatype", type=str, default="outdoor")
@@ -96,6 +106,20 @@ def frame_file(args, num):
     return os.path.join(output_dir(args), file_pattern(args).format(num))
 
 
+def merged_video_name(args):
+    """showvideo.py:126-132, :260: video_<class name>_<video directory>_<checkpoint number>.avi"""
+    parts = args.train_file.split("/")
+    classe = parts[-3] if len(parts) >= 3 else ""
+    videonum = parts[-2] if len(parts) >= 2 else ""
+    label = CLASS_NAMES.get(args.data_type, CLASS_NAMES["old"]).get(classe, classe)
+    return "video_{}_{}_{}.avi".format(label, videonum, checkpoint_number(args))
+
+
+def avi_file(args):
+    """the target of the merge command of `ffmpeg_commands`, unescaped: beside the train file, outside Generated_10s"""
+    return "/".join(args.train_file.split("/")[:-1] + [merged_video_name(args)])
+
+
 def ffmpeg_commands(args):
     """the two command lines showvideo.py:239-263 runs after the frames are saved (video track, then audio merge)"""
     parts = args.train_file.split("/")
@@ -104,13 +128,20 @@ def ffmpeg_commands(args):
     video_file = "{}/video_track.avi".format(data_dir)
     track = "ffmpeg -y -r {} -f image2 -s 640x480 -i {}/Generated_10s/I_%06d.png -vcodec libx264 -crf 25 -pix_fmt yuv420p {}".format(
         FPS, esc(data_dir), esc(video_file))
-    classe = parts[-3] if len(parts) >= 3 else ""
-    videonum = parts[-2] if len(parts) >= 2 else ""
-    label = CLASS_NAMES.get(args.data_type, CLASS_NAMES["old"]).get(classe, classe)
-    merge = "ffmpeg -y -i {} -i {} -codec copy -shortest {}/video_{}_{}_{}.avi".format(
-        esc(data_dir + "/audio/output_audio2.wav"), esc(video_file), esc(data_dir), label, videonum,
-        checkpoint_number(args))
+    merge = "ffmpeg -y -i {} -i {} -codec copy -shortest {}/{}".format(
+        esc(data_dir + "/audio/output_audio2.wav"), esc(video_file), esc(data_dir), merged_video_name(args))
     return [track, merge]
+
+
+def write_avi(args, jpegs, samples, width, height=224):
+    """the clip: one JPEG file and one [1024] row of `samples` (the clip's int32 audio) per frame -> summary entries"""
+    from .avi import AviWriter, normalize_pcm
+    pcm = normalize_pcm(samples).reshape(len(jpegs), SAMPLES_PER_FRAME)
+    path = avi_file(args)
+    with AviWriter(path, width, height, FPS, SAMPLE_RATE) as w:
+        for jpeg, row in zip(jpegs, pcm):
+            w.add_frame(jpeg, row)
+    return dict(avi=path, avi_bytes=int(w.close()), sample_rate=SAMPLE_RATE)
 
 
 def write_summary(args, num_frames, width, extra=None):
@@ -136,11 +167,15 @@ def run(args, trainer=None, keep_energy=False, log=print):
     from .png import write_png
     device = torch.device(args.device)
     tr = trainer if trainer is not None else build_trainer(args, device)
+    avi = args.command == "video" and bool(args.avi)
     if args.command == "boxes":
         data = BoxRecordLoader(args.train_file, args.batch_size)
     else:
-        data = TFRecordDataLoader(args.train_file, args.batch_size, device=device)
+        data = TFRecordDataLoader(args.train_file, args.batch_size, device=device, raw_audio=avi)
     rend = OverlayRenderer(device)
+    if avi:      # the whole clip is kept (the sound's peak is known only at its end): a few MB for ten seconds
+        from .jpeg import JpegEncoder
+        enc, jpegs, sound = JpegEncoder(device, args.quality, args.restart_mcus), [], []
     os.makedirs(output_dir(args), exist_ok=True)
     num, width, kept, kept_real = 0, 298, [], []
     for batch in data.data:
@@ -158,6 +193,9 @@ def run(args, trainer=None, keep_energy=False, log=print):
             img = rend.render(frames, energy)
         if keep_energy:
             kept.append(energy.cpu().numpy())
+        if avi:
+            jpegs.extend(enc.encode(img))
+            sound.append(batch[6].numpy())
         host = img.cpu().numpy()
         width = host.shape[2]
         for h in range(host.shape[0]):
@@ -166,7 +204,11 @@ def run(args, trainer=None, keep_energy=False, log=print):
         log("{} frames".format(num))
     if num == 0:
         raise ValueError("no samples in %s" % args.train_file)
-    res = write_summary(args, num, width)
+    extra = None
+    if avi:
+        extra = write_avi(args, jpegs, np.concatenate(sound), width)
+        extra.update(quality=enc.quality, restart_mcus=enc.restart_mcus(width))
+    res = write_summary(args, num, width, extra=extra)
     if keep_energy:
         res["energy"] = np.concatenate(kept)
         if kept_real:

@@ -824,6 +824,49 @@ int acimg_batch_gather(const uint8_t* pool_video, size_t video_stride, const flo
                        float* mfcc_low, float* action, float* location, void* ws, size_t ws_bytes, void* stream);
 size_t acimg_batch_gather_workspace(int N, int elems);
 
+/* Baseline JPEG of RGB8 frames, 4:2:0, integer arithmetic throughout (tests/jpeg_ref.py restates it bit for bit; the
+ * definition is DESIGN section 8).  Replaces: the `-vcodec libx264` ffmpeg run of showvideo.py:239-251 as the video track
+ * of the clip `python -m acimg.show video --avi 1` writes (Motion-JPEG; H.264 is not reproduced).  (Added without raising
+ * ACIMG_VERSION: nothing existing changed, and the number is pinned by the host tests.)
+ * Geometry: 16 x 16 MCUs in raster order, mcu_w = ceil(W / 16), mcu_h = ceil(H / 16), the frame extended by replicating
+ * its last column and row; per MCU six 8 x 8 blocks Y00 Y01 Y10 Y11 Cb Cr.  1 <= H, W <= 65535.
+ *
+ * acimg_jpeg_quant_tables (host only): out[128] = the Annex K luminance, then chrominance table in NATURAL order, scaled
+ *   by s = 5000 / quality (quality < 50) or 200 - 2 quality: (base * s + 50) / 100 clamped to 1..255.  quality 1..100.
+ * acimg_jpeg_blocks: rgb uint8 [n][H][W][3] dense, qtables uint8 [128] ON THE DEVICE (the layout above, entries >= 1)
+ *   -> coef int16 [n][mcus][6][64] (acimg_jpeg_coef_bytes), each block in zig-zag order.  Colour (JFIF, full range):
+ *   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = clamp(((-11059 R - 21709 G + 32768 B + 32767) >> 16) + 128),
+ *   Cr = clamp(((32768 R - 27439 G - 5329 B + 32767) >> 16) + 128); chroma = (a + b + c + d + 1 + (column & 1)) >> 2 over
+ *   2 x 2 pixels (`column` of the chroma sample); DCT on sample - 128 with T = rint(2^14 A): rows, (p + 256) >> 9,
+ *   columns; c = sign(q) (|q| + (d >> 1)) / d with d = Q << 19; AC clamped to +-1023.  1 <= n <= 65535.  ONE launch, one
+ *   workgroup per MCU.
+ * acimg_jpeg_scan: coef (as above, 16-byte aligned) -> per frame i the entropy-coded segment - everything between the
+ *   SOS header and EOI - at scan + i * frame_stride, and its length in scan_bytes[i] (int32 [n]); the bytes of a frame's
+ *   stride beyond its length are not written.  A restart interval is restart_mcus (1..65535) consecutive MCUs (the last
+ *   of a frame may be shorter); the DC predictors are 0 at its start, it is coded with the four typical Huffman tables of
+ *   Annex K.3 (ZRL, EOB, a negative value v as v + 2^size - 1), padded to a byte with 1-bits, a 0x00 stuffed after every
+ *   0xFF, and followed - but the last - by FF D0+m, m = 0, 1, ... modulo 8.  Coefficients are clamped as they are read (DC
+ *   difference +-2047, AC +-1023), so no input can exceed the capacity.
+ *   acimg_jpeg_scan_capacity: the most bytes a frame can take.  A block takes at most 22 bits of DC (11-bit code + 11
+ *   bits) and 63 x 26 bits of AC (16-bit code + 10 bits) = 1660 bits, an MCU 9960 bits = 1245 bytes, twice that with
+ *   every byte stuffed; an interval adds a stuffed pad byte and a marker: 2490 mcus + 4 intervals.  frame_stride below it,
+ *   or a capacity beyond INT32_MAX: ACIMG_EINVAL.
+ *   ws: 16-byte aligned, acimg_jpeg_scan_workspace bytes (two int32 per interval, one int32 and a 1248-byte slot per
+ *   MCU, then a worst-case slot of 2490 restart_mcus + 2 bytes per interval); short = ACIMG_EWORKSPACE.
+ *   THREE launches: one LANE per (frame, MCU) codes the MCU's unstuffed bits into its slot (its DC predictors are the
+ *   previous MCU's DC values); one wave per (frame, interval) joins its MCUs' bits into bytes, pads and stuffs; one
+ *   workgroup per frame forms the prefix of its interval lengths and copies intervals and markers densely.
+ * The three queries are pure host arithmetic and return 0 for an argument outside its range.  A null pointer or an
+ * argument outside its range: ACIMG_EINVAL; every refusal precedes the first launch.  No atomics, no floating point:
+ * bit-identical from run to run and equal to the restatement on any machine. */
+int acimg_jpeg_quant_tables(int quality, uint8_t* out);
+size_t acimg_jpeg_coef_bytes(int n, int H, int W);
+int acimg_jpeg_blocks(const uint8_t* rgb, int n, int H, int W, const uint8_t* qtables, int16_t* coef, void* stream);
+size_t acimg_jpeg_scan_capacity(int H, int W, int restart_mcus);
+size_t acimg_jpeg_scan_workspace(int n, int H, int W, int restart_mcus);
+int acimg_jpeg_scan(const int16_t* coef, int n, int H, int W, int restart_mcus, uint8_t* scan, size_t frame_stride,
+                    int32_t* scan_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
