@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void partial_stats_kernel(const float* y, int 
 // writes bias to the output positions of a kernel<stride transposed conv that no patch covers
 __global__ __launch_bounds__(256) void deconv_gap_fill_kernel(float* y, int ldy, const float* bias,
                                                               long pixels, int OH, int OW, int K,
-                                                              int R, int S, int stride) {
+                                                              int R, int S, int stride, int vec) {
     const int k4 = K / 4;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= pixels * k4) return;
@@ -200,9 +200,14 @@ __global__ __launch_bounds__(256) void deconv_gap_fill_kernel(float* y, int ldy,
     const int ox = (int)(pix % OW);
     const int oy = (int)((pix / OW) % OH);
     if ((oy % stride) < R && (ox % stride) < S) return;
-    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (bias) b = *reinterpret_cast<const float4*>(bias + c);
-    *reinterpret_cast<float4*>(y + pix * ldy + c) = b;
+    if (vec) {      // y, ldy and bias allow 16-byte accesses (epi_vec_flag, as the GEMM's epilogue before this kernel)
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (bias) b = *reinterpret_cast<const float4*>(bias + c);
+        *reinterpret_cast<float4*>(y + pix * ldy + c) = b;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[pix * ldy + c + k] = bias ? bias[c + k] : 0.f;
+    }
 }
 
 // zero insertion: out[n, h*s, w*s, :] = in[n, h, w, :], zeros elsewhere; out is [N][(H-1)s+1][(W-1)s+1][C].

@@ -120,6 +120,7 @@ static int launch_igemm(IgemmParams p, bool nt, void* ws, size_t ws_bytes, void*
         if (handoff) need = (size_t)p.splits * tiles * c.bm * c.bn * sizeof(float);
         if (ws == nullptr || ws_bytes < need)
             return fail(ACIMG_EWORKSPACE, "igemm: workspace %zu < %zu", ws_bytes, need);
+        if (int wrc = check_ws_aligned("igemm", ws)) return wrc;       // the K ranges are stored in 16-byte pieces
         p.slab = static_cast<float*>(ws);
         if (handoff) p.ts_counters = static_cast<int*>(tickets);
     }
@@ -174,6 +175,7 @@ static int launch_direct(const DirectParams& q, void* ws, size_t ws_bytes, hipSt
     if (!aligned16(q.x) || (q.ldx & 3)) return fail(ACIMG_EINVAL, "direct conv: input must be 16-byte aligned");
     const int total = q.R * q.S * q.C * ((q.K + 7) & ~7);
     if (!ws || ws_bytes < (size_t)total * sizeof(float)) return fail(ACIMG_EWORKSPACE, "direct conv: workspace too small");
+    if (int wrc = check_ws_aligned("direct conv", ws)) return wrc;     // the kernel reads the prepared weights in 16-byte pieces
     float* wprep = static_cast<float*>(ws);
     hipLaunchKernelGGL(direct_prepare_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, q, wprep, total);
     const long units = (long)cdiv(q.M, 256) * cdiv(q.K, 8);
@@ -435,9 +437,11 @@ int acimg_conv2d_fwd(const AcimgConvDesc* d, const float* x, const float* w, con
     int rc = check_desc(d, "conv2d_fwd");
     if (rc) return rc;
     if (d->ldw < d->K) return fail(ACIMG_EINVAL, "conv2d_fwd: ldw < K");
-    if (skinny_shape(d) && !in_scale && !in_shift && !in_relu && !stats && ws && ws_bytes >= skinny_fwd_ws_bytes(d) && aligned16(x) &&
-        aligned16(w) && aligned16(y) && aligned16(ws) && (!bias || aligned16(bias)) && (d->ldw & 3) == 0 && (d->ldx & 3) == 0 &&
-        (d->ldy & 3) == 0) {
+    if ((rc = check_wide("conv2d_fwd", {{"x", x}, {"w", w}, {"in_scale", in_scale}, {"in_shift", in_shift}, {"tickets", tickets}})) ||
+        (rc = check_ws_aligned("conv2d_fwd", ws)))
+        return rc;
+    if (skinny_shape(d) && !in_scale && !in_shift && !in_relu && !stats && ws && ws_bytes >= skinny_fwd_ws_bytes(d) &&
+        aligned16(y) && (!bias || aligned16(bias)) && (d->ldy & 3) == 0) {
         // the VAE heads' dense layer: weight rows read once in whole lines, K slabs combined in slab order
         SkinnyParams q{};
         q.W = w; q.X = x; q.out = y; q.bias = bias; q.act = d->act; q.part = static_cast<float*>(ws);
@@ -452,9 +456,9 @@ int acimg_conv2d_fwd(const AcimgConvDesc* d, const float* x, const float* w, con
     }
     if (few16_fwd_shape(d)) {
         // acimg_conv2d_stats_rows(d) promised one statistics row per workgroup of this kernel: no silent fallback
-        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || !aligned16(x) || !aligned16(y) || (d->ldy & 3) ||
-            d->ldy < d->K || (bias && !aligned16(bias)) || (in_scale && (!aligned16(in_scale) || !aligned16(in_shift))))
-            return fail(ACIMG_EINVAL, "conv2d_fwd: few-channel MFMA shape with half an input affine or unaligned operands");
+        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || d->ldy < d->K)
+            return fail(ACIMG_EINVAL, "conv2d_fwd: few-channel MFMA shape with half an input affine or ldy < K");
+        if ((rc = check_route("conv2d_fwd", "few-channel MFMA forward", {{"y", y, d->ldy}, {"bias", bias, 0}}))) return rc;
         FewParams q{};
         q.a_scale = in_scale; q.a_shift = in_shift; q.a_relu = in_relu;
         q.X = x; q.H = d->H; q.W = d->W; q.ldx = d->ldx; q.Y = y; q.ldy = d->ldy; q.nout = d->K; q.bias = bias;
@@ -489,7 +493,8 @@ int acimg_conv2d_fwd(const AcimgConvDesc* d, const float* x, const float* w, con
     return launch_igemm(p, false, ws, ws_bytes, tickets, (hipStream_t)stream);
 }
 
-// (under-reports when the narrow halo route falls through to a route below; a behaviour change, left to a later pull request)
+// (the narrow halo route's answer is for that kernel alone: acimg_conv2d_dgrad refuses, by name, a dx / residual / mask that
+// would take the shape to a route below, which needs more)
 size_t acimg_conv2d_dgrad_workspace(const AcimgConvDesc* d) {
     if (dgrad_halo16_narrow_shape(d)) return DGRAD_HALO16_NARROW_WS + 256;
     if (dgrad_is_patch(d)) return igemm_ws_bytes(d->N * d->OH * d->OW, d->R * d->S * d->C, cdiv(up4(d->K), 32));
@@ -511,7 +516,9 @@ int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const 
     if (rc) return rc;
     const int ca = up4(d->K);
     if (ca > ldgy || ca > d->ldw || (ldgy & 3)) return fail(ACIMG_EINVAL, "conv2d_dgrad: padded K=%d exceeds ldgy=%d/ldw=%d", ca, ldgy, d->ldw);
-    if (skinny_shape(d) && aligned16(gy) && aligned16(w) && (d->ldw & 3) == 0) {
+    if ((rc = check_wide("conv2d_dgrad", {{"gy", gy}, {"w", w}, {"tickets", tickets}})) || (rc = check_ws_aligned("conv2d_dgrad", ws)))
+        return rc;
+    if (skinny_shape(d)) {
         // a dense layer over a few batch rows (the 28 416 -> 300 VAE heads): the weight matrix is read once, in rows
         SkinnyParams q{};
         q.W = w; q.G = gy; q.out = dx; q.res = residual; q.mask = mask;
@@ -529,9 +536,13 @@ int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const 
         return launch_subpixel(gy, d->N, d->OH, d->OW, ca, ldgy, w, d->R, d->S, d->ldw, d->C, dx, lddx, d->H, d->W, -d->pad_t,
                                -d->pad_l, nullptr, residual, ldres, mask, ldmask, ACIMG_ACT_NONE, ws, ws_bytes, tickets,
                                (hipStream_t)stream, "conv2d_dgrad");
-    if (dgrad_halo16_narrow_shape(d) && aligned16(gy) && aligned16(dx) && (lddx & 3) == 0 && ws && aligned16(ws) &&
-        ws_bytes >= DGRAD_HALO16_NARROW_WS && (!residual || ((ldres & 3) == 0 && aligned16(residual))) &&
-        (!mask || ((ldmask & 3) == 0 && aligned16(mask)))) {
+    if (dgrad_halo16_narrow_shape(d)) {
+        // acimg_conv2d_dgrad_workspace(d) answered for this kernel alone: no silent fall-through to a route that needs more
+        if (!ws || ws_bytes < DGRAD_HALO16_NARROW_WS)
+            return fail(ACIMG_EWORKSPACE, "conv2d_dgrad: workspace %zu < %zu", ws_bytes, DGRAD_HALO16_NARROW_WS);
+        if ((rc = check_route("conv2d_dgrad", "narrow-halo data gradient",
+                              {{"dx", dx, lddx}, {"residual", residual, ldres}, {"mask", mask, ldmask}})))
+            return rc;
         // the flipped / transposed image [16 rows = input channels, zero beyond C][k = tap * 32 + gy channel], bf16 hi / lo
         FewParams f{};
         f.w = w; f.ldw = d->ldw; f.wrows = d->C; f.cin = d->K; f.mode = 1; f.nout = d->C;
@@ -539,8 +550,8 @@ int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const 
                            static_cast<__bf16*>(ws));
         return launch_dgrad_halo16_narrow(d, gy, ldgy, ws, dx, lddx, residual, ldres, mask, ldmask, (hipStream_t)stream);
     }
-    if (few16_dgrad_shape(d) && !subpixel_ok(d->stride, d->C, ca) && !mask && aligned16(gy) && aligned16(dx) && (lddx & 3) == 0 &&
-        ws && aligned16(ws) && ws_bytes >= few16_ws_bytes(ca, d->C) && (!residual || ((ldres & 3) == 0 && aligned16(residual)))) {
+    if (few16_dgrad_shape(d) && !subpixel_ok(d->stride, d->C, ca) && !mask && aligned16(dx) && (lddx & 3) == 0 &&
+        ws && ws_bytes >= few16_ws_bytes(ca, d->C) && (!residual || ((ldres & 3) == 0 && aligned16(residual)))) {
         // dx[h][w][c] = sum gy1[h - (2 - pad_t) + r'][w - (2 - pad_l) + s'][k] W[2 - r'][2 - s'][c][k], gy1 = gy (stride 1) or
         // its zero-inserted view (stride 2), zero outside
         FewParams q{};
@@ -627,6 +638,8 @@ int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, con
     int rc = check_desc(d, "deconv_fwd");
     if (rc) return rc;
     if (d->ldw < d->C || (d->K & 3)) return fail(ACIMG_EINVAL, "deconv_fwd: ldw<C or K%%4");
+    if ((rc = check_wide("deconv_fwd", {{"x", x}, {"w", w}, {"tickets", tickets}})) || (rc = check_ws_aligned("deconv_fwd", ws)))
+        return rc;
     if (d->R > d->stride || d->S > d->stride) {
         // overlapping patches (tf conv2d_transpose VALID: OH = (H-1)*stride + R): y = stride-1 "full" correlation
         // of the zero-inserted x with the flipped kernel = the data gradient of the stride-1 VALID conv
@@ -653,8 +666,7 @@ int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, con
     }
     if (d->OH != d->H * d->stride || d->OW != d->W * d->stride)
         return fail(ACIMG_EINVAL, "deconv_fwd: kernel<=stride needs OH=H*stride");
-    if (patch2_shape(d) && aligned16(x) && aligned16(y) && aligned16(w) && (d->ldx & 3) == 0 && (d->ldy & 3) == 0 && (d->ldw & 3) == 0 &&
-        (!bias || aligned16(bias))) {
+    if (patch2_shape(d) && aligned16(y) && (d->ldy & 3) == 0 && (!bias || aligned16(bias))) {
         Patch2Params q{};
         q.X = x; q.ldx = d->ldx; q.Y = y; q.ldy = d->ldy; q.w = w; q.ldw = d->ldw; q.bias = bias; q.act = d->act;
         q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;
@@ -667,12 +679,13 @@ int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, con
     p.e.Y = y; p.e.ldy = d->ldy; p.e.M = p.M; p.e.Nstore = p.Ngemm; p.e.bias = bias; p.e.act = d->act;
     p.e.scatter = 1; p.e.Ko = d->K; p.e.Sq = d->S; p.e.sc = d->stride;
     p.e.YH = d->OH; p.e.YW = d->OW; p.e.AH = d->H; p.e.AW = d->W;
+    epi_vec_flag(p.e);      // (launch_igemm decides the same for its epilogue; the gap fill below follows it)
     rc = launch_igemm(p, true, ws, ws_bytes, tickets, (hipStream_t)stream);
     if (rc) return rc;
     if (d->R < d->stride || d->S < d->stride) {
         const long pixels = (long)d->N * d->OH * d->OW;
         hipLaunchKernelGGL(deconv_gap_fill_kernel, dim3(cdiv(pixels * (d->K / 4), 256)), dim3(256), 0,
-                           (hipStream_t)stream, y, d->ldy, bias, pixels, d->OH, d->OW, d->K, d->R, d->S, d->stride);
+                           (hipStream_t)stream, y, d->ldy, bias, pixels, d->OH, d->OW, d->K, d->R, d->S, d->stride, p.e.vec);
         rc = check_launch("deconv_gap_fill");
     }
     return rc;
@@ -685,9 +698,10 @@ int acimg_deconv_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const 
     if (rc) return rc;
     const int ca = up4(d->K);
     if (ca > ldgy || (ldgy & 3) || ca != d->K) return fail(ACIMG_EINVAL, "deconv_dgrad: K must be a multiple of 4 and <= ldgy");
+    if ((rc = check_wide("deconv_dgrad", {{"gy", gy}, {"w", w}, {"tickets", tickets}})) || (rc = check_ws_aligned("deconv_dgrad", ws)))
+        return rc;
     // dx[n,h,w,c] = sum_{r,s,k} gy[n, h*stride+r, w*stride+s, k] * W[r][s][k][c]  (a strided conv)
-    if (patch2_shape(d) && aligned16(gy) && aligned16(dx) && aligned16(w) && (d->ldx & 3) == 0 && (d->ldw & 3) == 0 &&
-        (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
+    if (patch2_shape(d) && aligned16(dx) && (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
         Patch2Params q{};
         q.X = gy; q.ldx = ldgy; q.Y = dx; q.ldy = d->ldx; q.w = w; q.ldw = d->ldw; q.mask = mask; q.ldmask = ldmask;
         q.H = d->H; q.W = d->W; q.pixels = (long)d->N * d->H * d->W;

@@ -7,6 +7,7 @@
 // lists: into conv_tiles.o).
 #pragma once
 #include "igemm.hpp"
+#include <initializer_list>
 
 namespace acimg {
 
@@ -16,6 +17,38 @@ extern AcimgConfig g_cfg;
 
 int check_desc(const AcimgConvDesc* d, const char* who, bool row_run = false);
 static inline int up4(int v) { return (v + 3) & ~3; }
+
+// ---- operand forms (include/acimg.h, "Operand forms of the convolution family"): ONE rule, applied by every entry point
+// before its first launch.  Operands the kernels touch with 16-byte accesses whatever the route (x, gy, w and weight images,
+// split planes, in_scale / in_shift, dw, tickets) are refused by name; outputs and epilogue operands take any float* and
+// only choose the epilogue (epi_vec_flag) or, on the shapes the header lists, are refused by the route that was promised.
+struct WideOperand { const char* name; const void* ptr; };
+static inline int check_wide(const char* who, std::initializer_list<WideOperand> ops) {
+    for (const WideOperand& o : ops)
+        if (!aligned16(o.ptr)) return fail(ACIMG_EINVAL, "%s: %s must be 16-byte aligned", who, o.name);
+    return ACIMG_OK;
+}
+struct WideLd { const char* name; int ld; };
+static inline int check_wide_ld(const char* who, std::initializer_list<WideLd> lds) {
+    for (const WideLd& l : lds)
+        if (l.ld & 3) return fail(ACIMG_EINVAL, "%s: %s=%d must be a multiple of 4 floats", who, l.name, l.ld);
+    return ACIMG_OK;
+}
+// the workspace is written in 16-byte pieces (split-K slabs, weight-gradient slabs, prepared weights): code and wording of
+// launch_subpixel's refusal
+static inline int check_ws_aligned(const char* who, const void* ws) {
+    return aligned16(ws) ? ACIMG_OK : fail(ACIMG_EWORKSPACE, "%s: workspace too small or not 16-byte aligned", who);
+}
+// a route that the sizing / statistics-rows query promised and that takes 16-byte accesses to its outputs: no silent
+// fall-through to a kernel the reported workspace does not cover
+struct RouteOperand { const char* name; const void* ptr; int ld; };
+static inline int check_route(const char* who, const char* route, std::initializer_list<RouteOperand> ops) {
+    for (const RouteOperand& o : ops)
+        if (!aligned16(o.ptr) || (o.ptr && (o.ld & 3)))
+            return fail(ACIMG_EINVAL, "%s: %s of the %s must be 16-byte aligned with a leading dimension in multiples of 4",
+                        who, o.name, route);
+    return ACIMG_OK;
+}
 // 16-byte epilogue accesses: every operand the epilogue touches allows them
 static inline void epi_vec_flag(EpiParams& e) {
     e.vec = aligned16(e.Y) && (e.ldy & 3) == 0 && (!e.bias || aligned16(e.bias)) &&

@@ -125,14 +125,13 @@ static int fwd_split_onthefly(const AcimgConvDesc* d, const float* x, const void
     int rc = check_desc(d, "conv2d_fwd_split3", true);
     if (rc) return rc;
     if (d->C % 32) return fail(ACIMG_EINVAL, "conv2d_fwd_split3: C=%d must be a multiple of 32", d->C);
-    if (d->ldw < d->K || !aligned16(x) || !aligned16(wsplit))
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3: ldw<K or unaligned operands");
+    if (d->ldw < d->K) return fail(ACIMG_EINVAL, "conv2d_fwd_split3: ldw<K");
+    if ((rc = check_wide("conv2d_fwd_split3", {{"x", x}, {"wsplit", wsplit}, {"in_scale", in_scale}, {"in_shift", in_shift}}))) return rc;
     if (conv_halo16_fwd_shape(d)) {
         // (acimg_conv2d_fwd_split3_stats_rows already told the caller this shape leaves CONV_HALO16_WGS rows: no fallback)
-        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale) || !aligned16(y) || (d->ldy & 3) || (d->ldx & 3) ||
-            (bias && !aligned16(bias)) || (in_scale && (!aligned16(in_scale) || !aligned16(in_shift))))
-            return fail(ACIMG_EINVAL, "conv2d_fwd_split3: the halo form of this shape needs scale AND shift of an input affine, "
-                                      "16-byte aligned y / bias / affine and ldx, ldy multiples of 4");
+        if ((in_scale != nullptr) != (in_shift != nullptr) || (in_relu && !in_scale))
+            return fail(ACIMG_EINVAL, "conv2d_fwd_split3: the halo form of this shape needs scale AND shift of an input affine");
+        if ((rc = check_route("conv2d_fwd_split3", "halo-16 forward", {{"y", y, d->ldy}, {"bias", bias, 0}}))) return rc;
         ConvHaloParams q{};
         q.a_scale = in_scale; q.a_shift = in_shift; q.a_relu = in_relu;
         q.X = x; q.H = d->H; q.W = d->W; q.ldx = d->ldx; q.Wimg = static_cast<const char*>(wsplit);
@@ -164,10 +163,14 @@ static int dgrad_split_onthefly(const AcimgConvDesc* d, const float* gy, int ldg
                                 void* stream, int terms) {
     int rc = check_desc(d, "conv2d_dgrad_split3");
     if (rc) return rc;
-    if (d->stride != 1 || d->K % 32 || d->K > ldgy || (ldgy & 3))
-        return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: needs stride 1 and K %% 32 == 0 (K=%d)", d->K);
+    if (d->stride != 1 || d->K % 32 || d->K > ldgy)
+        return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: needs stride 1 and K %% 32 == 0 (K=%d) <= ldgy", d->K);
+    if ((rc = check_wide_ld("conv2d_dgrad_split3", {{"ldgy", ldgy}})) ||
+        (rc = check_wide("conv2d_dgrad_split3", {{"gy", gy}, {"wsplit_t", wsplit_t}})))
+        return rc;
     if (lddx <= 0) lddx = d->ldx;
-    if (conv_halo16_dgrad_shape(d) && aligned16(gy) && aligned16(wsplit_t) && aligned16(dx) && (lddx & 3) == 0 &&
+    if (lddx < d->C) return fail(ACIMG_EINVAL, "conv2d_dgrad_split3: lddx < C");
+    if (conv_halo16_dgrad_shape(d) && aligned16(dx) && (lddx & 3) == 0 &&
         (!residual || (aligned16(residual) && (ldres & 3) == 0)) && (!mask || (aligned16(mask) && (ldmask & 3) == 0))) {
         // a forward SAME conv of gy (32 channels) with the flipped / transposed image: rows = the layer's input channels
         ConvHaloParams q{};
@@ -212,7 +215,7 @@ size_t acimg_conv2d_split3_weight_bytes(const AcimgConvDesc* d) {
 
 int acimg_conv2d_split3_prepare(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream) {
     int rc = check_desc(d, "conv2d_split3_prepare", true);
-    if (rc) return rc;
+    if (rc || (rc = check_wide("conv2d_split3_prepare", {{"w", w}, {"wsplit", wsplit}}))) return rc;
     const int Ktot = d->R * d->S * d->C;
     hipLaunchKernelGGL((split3_prepare_kernel<SplitF16, false>), dim3(cdiv(Ktot, 32), cdiv(d->ldw, 32)), dim3(256), 0,
                        (hipStream_t)stream, w, d->R * d->S, d->C, d->K, d->ldw, d->ldw, static_cast<_Float16*>(wsplit));
@@ -227,7 +230,7 @@ int acimg_conv2d_split3_prepare(const AcimgConvDesc* d, const float* w, void* ws
 
 int acimg_conv2d_bf16_prepare(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream) {
     int rc = check_desc(d, "conv2d_bf16_prepare", true);
-    if (rc) return rc;
+    if (rc || (rc = check_wide("conv2d_bf16_prepare", {{"w", w}, {"wsplit", wsplit}}))) return rc;
     const int Ktot = d->R * d->S * d->C;
     hipLaunchKernelGGL((split3_prepare_kernel<SplitBF16, false>), dim3(cdiv(Ktot, 32), cdiv(d->ldw, 32)), dim3(256), 0,
                        (hipStream_t)stream, w, d->R * d->S, d->C, d->K, d->ldw, d->ldw, static_cast<__bf16*>(wsplit));
@@ -240,7 +243,7 @@ size_t acimg_conv2d_split3_dgrad_weight_bytes(const AcimgConvDesc* d) {
 
 int acimg_conv2d_split3_prepare_dgrad(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream) {
     int rc = check_desc(d, "conv2d_split3_prepare_dgrad");
-    if (rc) return rc;
+    if (rc || (rc = check_wide("conv2d_split3_prepare_dgrad", {{"w", w}, {"wsplit", wsplit}}))) return rc;
     if (d->K % 32 || d->K > d->ldw) return fail(ACIMG_EINVAL, "conv2d_split3_prepare_dgrad: K must be a multiple of 32");
     const int Ktot = d->R * d->S * d->K;
     hipLaunchKernelGGL((split3_prepare_kernel<SplitBF16, true>), dim3(cdiv(Ktot, 32), cdiv(d->C, 32)), dim3(256), 0,
@@ -263,6 +266,7 @@ int acimg_conv2d_split3_prepare_multi(int n, const AcimgConvDesc* const* descs, 
         int rc = check_desc(d, "conv2d_split3_prepare_multi", true);
         if (rc) return rc;
         if (!w[i] || !out[i]) return fail(ACIMG_EINVAL, "conv2d_split3_prepare_multi: null pointer in job %d", i);
+        if ((rc = check_wide("conv2d_split3_prepare_multi", {{"w", w[i]}, {"wsplit", out[i]}}))) return rc;
         PrepJob& J = jobs.j[i];
         J.w = w[i]; J.out = out[i]; J.ntaps = d->R * d->S; J.C = d->C; J.K = d->K; J.ldw = d->ldw;
         if (mode[i] < 0 || mode[i] > 2) return fail(ACIMG_EINVAL, "conv2d_split3_prepare_multi: job %d: mode is 0, 1 or 2", i);

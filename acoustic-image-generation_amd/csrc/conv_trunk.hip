@@ -216,9 +216,12 @@ static int fwd_presplit(const AcimgConvDesc* d, const void* x_planes, size_t x_l
     int rc = check_desc(d, "conv2d_fwd_split3p");
     if (rc) return rc;
     if (d->C % 32) return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: C=%d must be a multiple of 32", d->C);
-    if (d->ldw < d->K || !aligned16(x_planes) || !aligned16(wsplit) || !aligned16(y) || (d->ldy & 3) || d->ldx != d->C ||
-        (x_lo_off & 15))
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: ldw<K, ldx != C (split-format tensors are dense) or unaligned operands");
+    // (y here is a wide-access operand: the trunk kernels store whole 16-byte pieces, include/acimg.h)
+    if ((rc = check_wide("conv2d_fwd_split3p", {{"x_planes", x_planes}, {"wsplit", wsplit}, {"y", y}})) ||
+        (rc = check_wide_ld("conv2d_fwd_split3p", {{"ldy", d->ldy}})) || (rc = check_ws_aligned("conv2d_fwd_split3p", ws)))
+        return rc;
+    if (d->ldw < d->K || d->ldx != d->C || (x_lo_off & 15))
+        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p: ldw<K, ldx != C (split-format tensors are dense) or x_lo_off not a multiple of 16");
     IgemmParams p = fwd_view(d);
     split_ksteps(p);
     p.A = static_cast<const float*>(x_planes); p.B = static_cast<const float*>(wsplit);
@@ -252,7 +255,8 @@ static int fwd_presplit(const AcimgConvDesc* d, const void* x_planes, size_t x_l
         e.Y = nullptr;
         if (tail->mode != 1) {
             const long oplane = (long)acimg_split_plane_bytes((long)p.M, d->K);
-            if (!aligned16(tail->sc_planes) || !aligned16(tail->out_planes) || (tail->out_lo_off & 15) ||
+            if ((rc = check_wide("conv2d_fwd_split3p_tail", {{"shortcut", tail->sc_planes}, {"out_planes", tail->out_planes}}))) return rc;
+            if ((tail->out_lo_off & 15) ||
                 (long)tail->out_lo_off < oplane || (long)tail->out_lo_off + oplane >= (1L << 31))
                 return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: unaligned / overlapping / >= 2 GiB split-format operands");
             e.stats = nullptr;
@@ -368,8 +372,9 @@ int acimg_conv2d_fwd_split3p_stats(const AcimgConvDesc* d, const void* x_planes,
 int acimg_conv2d_fwd_split3p_tail(const AcimgConvDesc* d, const void* x_planes, size_t x_lo_off, const void* wsplit,
                                   const float* scale, const float* shift, const void* sc_planes, size_t sc_lo_off,
                                   void* out_planes, size_t out_lo_off, void* ws, size_t ws_bytes, void* stream) {
-    if (!scale || !shift || !sc_planes || !out_planes || !aligned16(scale) || !aligned16(shift))
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: null / unaligned scale, shift, shortcut or output");
+    if (!scale || !shift || !sc_planes || !out_planes)
+        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail: null scale, shift, shortcut or output");
+    if (int rc = check_wide("conv2d_fwd_split3p_tail", {{"scale", scale}, {"shift", shift}})) return rc;
     const Split3pTail t{2, scale, shift, sc_planes, sc_lo_off, out_planes, out_lo_off, nullptr, nullptr};
     return fwd_presplit(d, x_planes, x_lo_off, wsplit, nullptr, nullptr, ws, ws_bytes, stream, 3, &t);
 }
@@ -378,9 +383,10 @@ int acimg_conv2d_fwd_split3p_tail_proj(const AcimgConvDesc* d, const void* x_pla
                                        const float* scale, const float* shift, const float* sc32, const float* sc_scale,
                                        const float* sc_shift, void* out_planes, size_t out_lo_off, void* ws, size_t ws_bytes,
                                        void* stream) {
-    if (!scale || !shift || !sc32 || !sc_scale || !sc_shift || !out_planes || !aligned16(scale) || !aligned16(shift) ||
-        !aligned16(sc_scale) || !aligned16(sc_shift))
-        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail_proj: null / unaligned scale, shift, shortcut or output");
+    if (!scale || !shift || !sc32 || !sc_scale || !sc_shift || !out_planes)
+        return fail(ACIMG_EINVAL, "conv2d_fwd_split3p_tail_proj: null scale, shift, shortcut or output");
+    if (int rc = check_wide("conv2d_fwd_split3p_tail_proj", {{"scale", scale}, {"shift", shift}, {"sc_scale", sc_scale}, {"sc_shift", sc_shift}}))
+        return rc;
     const Split3pTail t{3, scale, shift, sc32, 0, out_planes, out_lo_off, sc_scale, sc_shift};
     return fwd_presplit(d, x_planes, x_lo_off, wsplit, nullptr, nullptr, ws, ws_bytes, stream, 3, &t);
 }

@@ -136,6 +136,9 @@ static int wgrad_reduce(const WgradSlabs& s, int n, const WgradParams& p, float*
     return check_launch("wgrad_reduce");
 }
 
+static int colsum_parts(long rows);
+static int launch_colsum(const float* G, long rows, int ncols, int ld, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+
 // db (optional): fused bias gradient, db[n] = sum_m G[m][n] for n < Ngemm
 static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t st,
                         bool split3 = false, int terms = 3) {
@@ -143,6 +146,7 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         return fail(ACIMG_EINVAL, "wgrad: C=%d ldx=%d ldg=%d ldo=%d must be multiples of 4", p.C, p.ldx, p.ldg, p.ldo);
     if (!aligned16(p.X) || !aligned16(p.G) || !aligned16(dw))
         return fail(ACIMG_EINVAL, "wgrad: operands must be 16-byte aligned");
+    if (int wrc = check_ws_aligned("wgrad", ws)) return wrc;       // (wgrad_slabs: the kernels store slab rows in 16-byte pieces)
     if (p.a_scale && !wgrad_halo16_ok(p, split3))
         return fail(ACIMG_EINVAL, "wgrad: an input affine is only taken by the halo form (3x3 / stride 1 / SAME, <= 32 columns, >= 65536 pixels)");
     if (p.a_scale && (!p.a_shift || !aligned16(p.a_scale) || !aligned16(p.a_shift)))
@@ -229,6 +233,12 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         return rc ? rc : wgrad_reduce(sl, nb, p, dw, db, true, st);
     }
     if (split3) bn = wgrad_split3_bn(p.Ngemm);
+    // An unsplit launch writes dW and db themselves, and the split-MFMA kernels store a row in 16-byte pieces: right for dw and
+    // the slabs, not for a db that is only float-aligned (include/acimg.h: any float*).  Such a db is left to the column sums
+    // of G, whose partials the sizing query reserves; refused here, before dW is written, when they do not fit.
+    const bool db_colsum = split3 && db && !aligned16(db);
+    const auto colsum_fits = [&]() { return ws && ws_bytes >= (size_t)colsum_parts(p.M) * p.Ngemm * sizeof(float); };
+    const auto colsum_short = [&]() { return fail(ACIMG_EWORKSPACE, "wgrad: workspace %zu too small for the bias gradient's column sums", ws_bytes); };
     if (split3 && terms == 3 && wgrad_tap_ok(p)) {
         WgradTapParams q{};
         q.X = p.X; q.H = p.H; q.W = p.W; q.C = p.C; q.ldx = p.ldx; q.G = p.G; q.ldg = p.ldg;
@@ -244,8 +254,9 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
             q.out = sl.out;
             q.db_out = sl.db_out;
         } else {                // one slab: the kernel writes dW / db themselves, no reduce
+            if (db_colsum && !colsum_fits()) return colsum_short();
             q.out = dw;
-            q.db_out = db;
+            q.db_out = db_colsum ? nullptr : db;
         }
         const size_t lds = wgrad_tap_lds(p.W);
         static bool attr_set = false;
@@ -260,7 +271,8 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         if (bn == 128) hipLaunchKernelGGL((wgrad_tap_kernel<128>), grid, dim3(512), lds, st, q);
         else hipLaunchKernelGGL((wgrad_tap_kernel<64>), grid, dim3(512), lds, st, q);
         int rc = check_launch("wgrad_tap");
-        return (rc || ns == 1) ? rc : wgrad_reduce(sl, ns, p, dw, db, false, st);
+        if (rc || ns > 1) return rc ? rc : wgrad_reduce(sl, ns, p, dw, db, false, st);
+        return db_colsum ? launch_colsum(p.G, p.M, p.Ngemm, p.ldg, db, ws, ws_bytes, st) : rc;
     }
     p.splits = pick_wgrad_splits(p.M, p.KK, p.Ngemm, bmo, bn);
     int rps = cdiv(p.M, p.splits);
@@ -273,10 +285,11 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
         p.out = sl.out;
         p.db_out = sl.db_out;
     } else {
+        if (db_colsum && !colsum_fits()) return colsum_short();
         p.out = dw;
-        p.db_out = db;
+        p.db_out = db_colsum ? nullptr : db;
     }
-    const int rows = p.KK + (db ? 1 : 0);
+    const int rows = p.KK + (p.db_out ? 1 : 0);
     dim3 grid(cdiv(rows, bmo), cdiv(p.Ngemm, bn), p.splits);
     if (split3 && terms == 1 && bn == 128) hipLaunchKernelGGL((wgrad_split3_kernel<128, 1, 512>), grid, dim3(512), 65536, st, p);
     else if (split3 && terms == 1 && bn == 64) hipLaunchKernelGGL((wgrad_split3_kernel<64, 1, 512>), grid, dim3(512), 65536, st, p);
@@ -289,17 +302,18 @@ static int launch_wgrad(WgradParams p, float* dw, float* db, void* ws, size_t ws
     else if (bn == 32) hipLaunchKernelGGL((wgrad_f32_kernel<128, 32>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((wgrad_f32_kernel<128, 16, 4>), grid, dim3(256), 0, st, p);
     int rc = check_launch("wgrad");
-    return (rc || p.splits <= 1) ? rc : wgrad_reduce(sl, p.splits, p, dw, db, false, st);
+    if (rc || p.splits > 1) return rc ? rc : wgrad_reduce(sl, p.splits, p, dw, db, false, st);
+    return db_colsum ? launch_colsum(p.G, p.M, p.Ngemm, p.ldg, db, ws, ws_bytes, st) : rc;
 }
 
 // column sums; workspace: parts*ncols floats
 static int colsum_parts(long rows) { return clamped_blocks(rows, 256); }
-static int launch_colsum(const float* G, long rows, int ncols, int ld, float* out, void* ws,
-                         size_t ws_bytes, hipStream_t st) {
+static int launch_colsum(const float* G, long rows, int ncols, int ld, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
     const int parts = colsum_parts(rows);
     const long rpb = (rows + parts - 1) / parts;
     const size_t need = (size_t)parts * ncols * sizeof(float);
     if (ws == nullptr || ws_bytes < need) return fail(ACIMG_EWORKSPACE, "colsum: workspace %zu < %zu", ws_bytes, need);
+    if (int wrc = check_ws_aligned("colsum", ws)) return wrc;
     float* partial = static_cast<float*>(ws);
     if (ncols <= 64 && (ncols & 3) == 0 && (ld & 3) == 0 && aligned16(G))
         hipLaunchKernelGGL(colsum_narrow_kernel, dim3(parts), dim3(256), 0, st, G, rows, ncols, ld, rpb, partial);
@@ -329,8 +343,11 @@ static int wgrad_entry(const AcimgConvDesc* d, const char* who, const float* x, 
     int rc = check_desc(d, who);
     if (rc) return rc;
     if (up4(d->K) > ldgy || up4(d->K) > d->ldw) return fail(ACIMG_EINVAL, "%s: padded K exceeds ldgy/ldw", who);
-    if (!split3 && !in_scale && skinny_shape(d) && aligned16(x) && aligned16(gy) && aligned16(dw) && (!db || aligned16(db)) &&
-        (d->ldw & 3) == 0 && (ldgy & 3) == 0 && (d->ldx & 3) == 0)     // (acimg_conv2d_wgrad alone: the VAE heads' dense layer)
+    if ((rc = check_wide_ld(who, {{"ldgy", ldgy}})) ||
+        (rc = check_wide(who, {{"x", x}, {"gy", gy}, {"dw", dw}, {"in_scale", in_scale}, {"in_shift", in_shift}})) ||
+        (rc = check_ws_aligned(who, ws)))
+        return rc;
+    if (!split3 && !in_scale && skinny_shape(d) && (!db || aligned16(db)))     // (acimg_conv2d_wgrad alone: the VAE heads' dense layer)
         return launch_skinny_wgrad(d, x, gy, ldgy, dw, db, (hipStream_t)stream);
     WgradParams p = wgrad_view(d, x, gy, ldgy);
     p.a_scale = in_scale; p.a_shift = in_shift; p.a_relu = in_relu;
@@ -358,9 +375,9 @@ int acimg_deconv_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, 
     if (rc) return rc;
     const int ca = up4(d->K);
     if (ca > ldgy || (ldgy & 3) || ca != d->K) return fail(ACIMG_EINVAL, "deconv_wgrad: K must be a multiple of 4 and <= ldgy");
+    if ((rc = check_wide("deconv_wgrad", {{"x", x}, {"gy", gy}, {"dw", dw}})) || (rc = check_ws_aligned("deconv_wgrad", ws))) return rc;
     // dW[(r,s,k)][c] = sum_{n,h,w} gy[n,h*stride+r,w*stride+s,k] * x[n,h,w,c]
-    if (patch2_shape(d) && aligned16(dw) && (d->ldw & 3) == 0 && ws && aligned16(ws) &&
-        ws_bytes >= patch2_wgrad_ws_bytes(d->ldw) && (!db || aligned16(db))) {
+    if (patch2_shape(d) && ws && ws_bytes >= patch2_wgrad_ws_bytes(d->ldw) && (!db || aligned16(db))) {
         float* slabs = static_cast<float*>(ws);
         float* db_part = db ? slabs + (size_t)PATCH2_WGRAD_WGS * 32 * d->ldw : nullptr;
         rc = launch_patch2_wgrad(d, x, gy, ldgy, slabs, db_part, (hipStream_t)stream);

@@ -20,6 +20,22 @@
  *     of a concat buffer (tf.concat never materialises).  Channel counts seen by the GEMM
  *     kernels are multiples of 4 (the host pads 3->4, 133->136, 145->148, 150->152, 266->268
  *     with zeros; padded weights rows/cols are zero and provably stay zero under Adam).
+ *   - OPERAND FORMS of the convolution family (every acimg_conv2d_* / acimg_deconv_* entry point, the prepare calls
+ *     included); each refusal below precedes the first launch and leaves every output byte untouched:
+ *       operands read with 16-byte accesses - x, gy, w, every prepared weight image, split planes, in_scale / in_shift
+ *         (and the per-channel scale / shift vectors of the _tail entries), the ticket words - must be 16-byte aligned with
+ *         leading dimensions (ldx, ldw, ldgy) in multiples of 4 floats: anything else is ACIMG_EINVAL with text that names
+ *         the operand.  dw is written that way and counts among them.  So does the workspace, with its own code: a
+ *         workspace that is NULL, short or not 16-byte aligned is ACIMG_EWORKSPACE;
+ *       outputs and epilogue operands - y / dx, bias, residual, mask, db, stats - may be ANY 4-byte-aligned float* with
+ *         any leading dimension at or above the channel count: the call succeeds with the same documented result on a
+ *         general kernel, and the workspace the query reported is enough for it.  EXCEPT where the query already promised
+ *         one kernel, which are refused with ACIMG_EINVAL naming the operand: the few-channel MFMA forward of
+ *         acimg_conv2d_fwd (it promised FEW16 statistics rows: y, ldy, bias), the halo-16 forward of
+ *         acimg_conv2d_fwd_split3 / _bf16 (3x3 / stride 1 / SAME, C = 32 or 64 into K = 32 from 65536 pixels on: y, ldy,
+ *         bias), the narrow-halo data gradient of acimg_conv2d_dgrad (3x3 / stride 1 / SAME, K = 32 into C <= 16 from
+ *         65536 pixels on, whose workspace query answers for that kernel alone: dx, lddx, residual, ldres, mask, ldmask),
+ *         and the pre-split trunk entries (acimg_conv2d_fwd_split3p and siblings: y is dense and 16-byte aligned).
  *   - weights use TensorFlow's own layouts, padded as above:
  *       conv2d            HWIO  [R][S][Cin_p][Cout_p]
  *       conv2d_transpose        [R][S][Cout_p][Cin_p]
@@ -70,6 +86,9 @@ typedef struct AcimgConvDesc {
  * stats (optional, [grid_m][2][ldw] floats, grid_m = acimg_conv2d_stats_rows(d)) receives per
  * row-block partial sums / sums of squares of conv + bias BEFORE the activation for batch-norm statistics (the
  * few-channel direct kernel with an activation sums the stored, activated y instead; batch-norm layers use ACT_NONE).
+ * With an activation the meaning of `stats` therefore follows the KERNEL THAT RUNS, not the shape alone: a y / bias that is
+ * not 16-byte aligned, or an ldy that is no multiple of 4, moves a direct-kernel shape onto the implicit GEMM and its
+ * pre-activation sums (operand forms, above).  Nothing in this project asks for statistics of an activated layer.
  * The row count belongs to THIS descriptor, `act` included (the few-channel 3x3 / stride-1 layers from 65536
  * pixels on run on an MFMA kernel that leaves one row per workgroup - 512 - when act is ACIMG_ACT_NONE, and on
  * the direct kernel with one row per 256 pixels otherwise): size the buffer from the descriptor that is launched.
@@ -162,6 +181,9 @@ size_t acimg_conv2d_fwd_workspace(const AcimgConvDesc* d);
  * ARITHMETIC: on the 3x3 / stride 1 / SAME layers with image rows of 32 or 48 pixels, C >= 64 and K > 32 (no in_scale, no
  * stats; wgrad_halo = 1) the same format with K summed chunk-major - 32 channels at a time, the nine taps inside - instead
  * of tap-major: the same products in another order.
+ * OPERAND FORMS (this entry, _bf16 and the data gradients below): x / gy, the weight image and in_scale / in_shift 16-byte
+ * aligned, ldgy % 4 == 0; y / dx, bias, residual and mask any float* with any leading dimension at or above the channel count
+ * (per-tap kernel with scalar stores) EXCEPT the halo-16 forward shape, whose statistics rows were promised: ACIMG_EINVAL.
  * Replaces: slim layers.conv2d / conv2d_same in the trunk, models/resnet50.py:109-121. */
 size_t acimg_conv2d_split3_weight_bytes(const AcimgConvDesc* d);
 int acimg_conv2d_split3_prepare(const AcimgConvDesc* d, const float* w, void* wsplit, void* stream);
@@ -305,6 +327,9 @@ int acimg_bn_relu_maxpool_split(const float* x, const float* scale, const float*
  * no floor while gy stays fp32-normal; per product up to 2^-15 of |gy w|, acimg_conv2d_dgrad_split3 above): stride 1 or 2
  * without a mask, up4(K) = 8 or 16 gy channels into C % 4 == 0, C <= 32 (<= 16 unless up4(K) = 8; stride 2: C = 4, 8 or 12, read
  * from the zero-inserted VIEW of gy, no copy), and stride 1 / SAME with K = 32 into C <= 16 (mask and residual allowed).
+ * OPERAND FORMS: gy, w, workspace and tickets 16-byte aligned, ldgy % 4 == 0; dx / residual / mask any float* and any
+ * lddx / ldres / ldmask >= C (general kernel, same result) EXCEPT on the narrow-halo shape (the last one above), where a
+ * dx / residual / mask off a 16-byte boundary or an lddx / ldres / ldmask that is no multiple of 4 is ACIMG_EINVAL.
  * Replaces: the Conv2DBackpropInput ops tf.gradients emits for the calls above
  *           (trainer/mfcctrainer.py:72-79). */
 int acimg_conv2d_dgrad(const AcimgConvDesc* d, const float* gy, int ldgy, const float* w,
@@ -316,6 +341,10 @@ size_t acimg_conv2d_dgrad_workspace(const AcimgConvDesc* d);
  * ARITHMETIC: exact fp32 products EXCEPT, from 65536 pixels on (wgrad_halo = 1), the 3x3 / stride 1 / SAME layers with
  * C < 32 (a multiple of 4) and K <= 32, which run bf16x3 - dw AND db - as acimg_conv2d_wgrad_split3 below does: per product
  * up to 2^-15 of |x gy|, no operand range and no floor while x and gy stay fp32-normal.
+ * OPERAND FORMS (this entry, _split3, _bf16, _affine and acimg_deconv_wgrad): x, gy, dw, in_scale / in_shift and the workspace
+ * 16-byte aligned, ldgy % 4 == 0; db any float*.  One value depends on that pointer: where acimg_conv2d_wgrad_bf16 needs no
+ * slabs (at most wgrad_minpix pixels: the kernel writes dw and db itself, in 16-byte pieces), an aligned db is the sum of the
+ * bf16-ROUNDED gy, and a db off a 16-byte boundary is the fp32 column sum of gy as given (its partials: the workspace).
  * Replaces: Conv2DBackpropFilter / BiasAddGrad (trainer/mfcctrainer.py:72-79). */
 int acimg_conv2d_wgrad(const AcimgConvDesc* d, const float* x, const float* gy, int ldgy,
                        float* dw, float* db, void* ws, size_t ws_bytes, void* stream);
@@ -353,6 +382,8 @@ int acimg_conv2d_wgrad_affine(const AcimgConvDesc* d, int precision, const float
  * operand range |w| < 63, |x| < 2.6e5 and the floors 2^-23 per activation / 2^-35 per weight of acimg_conv2d_fwd_split3 apply,
  * the bias is added in fp32 - and acimg_deconv_dgrad / acimg_deconv_wgrad run bf16x3 (per product up to 2^-15 of |gy w| /
  * |gy x|; no range, no floor); the bias gradient of that route is an fp32 sum of gy and never meets the split.
+ * OPERAND FORMS: x / gy, w, workspace and tickets 16-byte aligned; y / dx, bias and mask any float*, ldy / ldmask any value
+ * at or above the channel count (the gap fill follows the scatter's epilogue onto scalar stores).
  * Replaces: tf.layers.conv2d_transpose  models/unet_acresnet.py:210-217 (call :86). */
 int acimg_deconv_fwd(const AcimgConvDesc* d, const float* x, const float* w, const float* bias,
                      float* y, void* ws, size_t ws_bytes, void* tickets, void* stream);

@@ -40,6 +40,8 @@ DGRAD_CASES = OrderedDict([
     ("dilated_3x2_valid", ((2, 15, 18, 8, 16, 3, 2, 2, "VALID"), True, True, False, RTOL)),
     # >= 65536 pixels: the few-channel MFMA form reads the zero-inserted view itself (no mask): test_few_channel_direct_conv, 3e-5
     ("few_channel_stride2", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), True, False, False, 3e-5)),
+    # ... and its stride-1 form on gy itself (the shape of FWD_CASES / WGRAD_CASES "few_channel_*"; 3e-5 as above)
+    ("few_channel_stride1", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), True, False, False, 3e-5)),
     # ... and with a ReLU mask neither MFMA nor direct form applies: dilated copy, then the implicit GEMM (exact f32)
     ("dilated_then_igemm_65536", ((3, 224, 298, 8, 8, 3, 3, 2, "SAME"), True, True, True, 3e-5)),
     # 112x149 8 -> 32: the 16-row instance of the halo kernel (test_few_channel_mfma_conv_matches_fp64 (3,147,161,8,32), 3e-5)
@@ -70,6 +72,11 @@ WGRAD_CASES = OrderedDict([
     ("halo16_affine_split3", ((4, 112, 149, 32, 32, 3, 3, 1, "SAME"), "affine1", 2e-5)),
     ("few_channel_affine", ((3, 150, 160, 8, 8, 3, 3, 1, "SAME"), "affine0", 2e-5)),
     ("skinny", ((32, 1, 1, 28416, 300, 1, 1, 1, "VALID"), "f32", 2e-6)),
+    # 128 pixels: one slab, so the split-MFMA kernels write dW and db themselves, no reduce (3e-5 as the split cases above) -
+    # the per-tap kernel (16-pixel rows) and the tap-sharing kernel (32-pixel rows).  A db off a 16-byte boundary cannot take
+    # their 16-byte row stores: tests/test_operand_forms_gpu.py
+    ("unsplit_split3", ((1, 8, 16, 64, 64, 3, 3, 1, "SAME"), "split3", 3e-5)),
+    ("unsplit_tap", ((1, 4, 32, 64, 64, 3, 3, 1, "SAME"), "split3", 3e-5)),
 ])
 
 

@@ -21,290 +21,24 @@ from collections import OrderedDict
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from caller_memory_cases import DECONV_CASES, DGRAD_CASES, FWD_CASES, RTOL, WGRAD_CASES
-from guard_arena import CANARY, GuardArena
+from caller_memory_cases import DECONV_CASES, DGRAD_CASES, FWD_CASES, WGRAD_CASES
+from caller_memory_support import (STATS_TOL, Case, Out, close, deconv_cases, dgrad_case, f32, first_lt, fwd_case, last_lt, run_case,
+                                   wgrad_case)
 from localize_ref import random_boxes
-from op_support import close_at, conv_geom, raw_lib, tf_conv_ref, up4, widen
+from op_support import raw_lib, tf_conv_ref, up4, widen
 from retrieval_ref import int_features
 from split_format_ref import brick_index, make_planes, plane_bytes, unsplit
 
 pytestmark = pytest.mark.gpu
 
-STATS_TOL = 2e-4       # ... and its batch-norm partial sums (fp32 sums of many signed terms)
-SENT = 0x7B            # 0x7B7B7B7B = 1.3e36 as a float, 2071690107 as an int: finite, never a result
-WS_FILL = 0xFF         # NaN in every float format
-close = close_at(RTOL, show=True)
-
-
-def f32(g, *shape, scale=1.0):
-    return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).float()
-
-
-def last_lt(shape, n):
-    """mask of the documented elements of a [..., ld] buffer: the first n of every row"""
-    return (torch.arange(shape[-1]) < n).expand(*shape)
-
-
-def first_lt(shape, n):
-    m = torch.zeros(*shape, dtype=torch.bool)
-    m[:n] = True
-    return m
-
-
-class Out(object):
-    """an output buffer: dtype, full shape of the memory handed over (pads included), mask of the documented elements
-    (None: all), init = a sentinel byte, or a tensor for in/out buffers the caller must initialise (accumulators)"""
-
-    def __init__(self, dtype, shape, mask=None, init=SENT):
-        self.dtype, self.shape, self.mask, self.init = dtype, tuple(int(s) for s in shape), mask, init
-        self.nbytes = int(np.prod(self.shape)) * torch.empty((), dtype=dtype).element_size() if self.shape else 0
-
-    def paint(self, u8):
-        if isinstance(self.init, torch.Tensor):
-            u8.copy_(self.init.contiguous().view(-1).view(torch.uint8).to(u8.device))
-        else:
-            u8.fill_(self.init)
-
-    def typed(self, u8):
-        return u8.cpu().view(self.dtype).view(*self.shape)
-
-
-class Case(object):
-    """calls: [fn(ws_ptr, ws_bytes, ptr, tickets_ptr) -> rc], run in order (state carried through the workspace:
-    triplet fwd + bwd); verify(outs): the fp64 check; zero_head: leading workspace bytes the header wants zero before
-    the first call; zero_exit: leading bytes (ticket words) it promises to leave zero after every call; short_code: the
-    code a short workspace must be refused with (None: any negative code, or a legal fallback), null_code: the same for
-    ws = NULL where the entry point names that another way; fallback: the entry point documents another kernel (another
-    summation order) for a short or missing workspace - only then may a short run that returns 0 differ in bits from the
-    reference run, and it must pass the fp64 check instead"""
-
-    def __init__(self, query, outs, calls, verify, tickets=False, zero_head=0, zero_exit=0, short_code=None, null_code=None,
-                 fallback=False, keep=None):
-        self.query, self.outs, self.verify = int(query), outs, verify
-        self.calls = calls if isinstance(calls, (list, tuple)) else [calls]
-        self.tickets, self.zero_head, self.zero_exit, self.keep = tickets, int(zero_head), int(zero_exit), keep
-        self.short_code, self.null_code = short_code, short_code if null_code is None else null_code
-        self.fallback = fallback
-
-
-def _bits(t):
-    return t.contiguous().view(-1).view(torch.uint8)
-
-
-def run_case(device, case, what):
-    from acimg import ops
-    m, L = raw_lib()
-    st = ops.current_stream_handle(device)
-    q = case.query
-    tbytes = 4 * ops.TICKET_WORDS
-
-    def launch(ws_ptr, ws_bytes, ptr, tick, arena=None, stage=""):
-        """every call of the case; one synchronize + arena check per call; stops at the first refusal"""
-        for i, fn in enumerate(case.calls):
-            rc = fn(ws_ptr, ws_bytes, ptr, tick)
-            torch.cuda.synchronize()
-            if arena is not None:
-                arena.check("%s, %s, call %d" % (what, stage, i))
-            if rc != 0:
-                return rc
-        return 0
-
-    # ---- reference run: roomy, zeroed workspace; plain tensors ---------------------------------------------------------
-    ws = torch.zeros(4 * q + (1 << 20), dtype=torch.uint8, device=device)
-    bufs = OrderedDict((n, torch.empty(max(o.nbytes, 16), dtype=torch.uint8, device=device)) for n, o in case.outs.items())
-    for n, o in case.outs.items():
-        o.paint(bufs[n][:o.nbytes])
-    tick = torch.zeros(ops.TICKET_WORDS, dtype=torch.int32, device=device) if case.tickets else None
-    rc = launch(ws.data_ptr(), ws.numel(), {n: b.data_ptr() for n, b in bufs.items()}, tick.data_ptr() if case.tickets else None)
-    assert rc == 0, "%s: reference run rc=%d: %s" % (what, rc, m.last_error())
-    ref = OrderedDict((n, o.typed(bufs[n][:o.nbytes])) for n, o in case.outs.items())
-    case.verify(ref)
-    if case.tickets:
-        assert int(tick.abs().max()) == 0, "%s: reference run left tickets non-zero" % what
-    del ws, bufs
-
-    # ---- guarded run: exactly the queried bytes, poisoned; outputs between guard bands ---------------------------------
-    sizes = [q] + [o.nbytes for o in case.outs.values()] + ([tbytes] if case.tickets else [])
-    arena = GuardArena.for_sizes(device, sizes)
-    wsr = arena.region(q, name="workspace")
-    regs = OrderedDict((n, arena.region(o.nbytes, name=n)) for n, o in case.outs.items())
-    tr = arena.region(tbytes, fill=0, name="tickets") if case.tickets else None
-    ptr = {n: r.ptr for n, r in regs.items()}
-
-    def paint(short=False):
-        wsr.fill(WS_FILL)
-        if case.zero_head:
-            wsr.u8[:case.zero_head].zero_()
-        if short:
-            wsr.u8[q - 16:].fill_(CANARY)
-        for n, o in case.outs.items():
-            o.paint(regs[n].u8)
-        if tr is not None:
-            tr.fill(0)
-
-    def outputs():
-        return OrderedDict((n, o.typed(regs[n].u8)) for n, o in case.outs.items())
-
-    def untouched(got, stage, everything):
-        """sentinel bytes: outside the documented elements, or (a refused call) everywhere"""
-        for n, o in case.outs.items():
-            if isinstance(o.init, torch.Tensor):
-                if everything:
-                    assert torch.equal(_bits(got[n]), _bits(o.init)), "%s, %s: %s changed by a refused call" % (what, stage, n)
-                continue
-            if everything or o.mask is not None:
-                sel = got[n] if everything else got[n][~o.mask]
-                bad = _bits(sel).ne(o.init)
-                assert not bool(bad.any()), "%s, %s: output %r written outside its documented extent (%d bytes)" % (
-                    what, stage, n, int(bad.sum()))
-
-    def same_as_reference(got, stage):
-        for n, o in case.outs.items():
-            a = got[n] if o.mask is None else got[n][o.mask]
-            b = ref[n] if o.mask is None else ref[n][o.mask]
-            if not torch.equal(_bits(a), _bits(b)):
-                return False, n
-        return True, None
-
-    paint()
-    rc = launch(wsr.ptr, q, ptr, tr.ptr if tr is not None else None, arena, "guarded run")
-    assert rc == 0, "%s: guarded run (ws = the query, %d bytes) rc=%d: %s" % (what, q, rc, m.last_error())
-    got = outputs()
-    ok, n = same_as_reference(got, "guarded run")
-    assert ok, "%s: output %r differs between a zeroed roomy workspace and a poisoned exact one" % (what, n)
-    untouched(got, "guarded run", False)
-    if tr is not None:
-        assert not bool(tr.u8.any()), "%s: tickets left non-zero" % what
-    if case.zero_exit:
-        assert not bool(wsr.u8[:case.zero_exit].any()), "%s: zero-on-exit words of the workspace left non-zero" % what
-
-    # ---- short runs: query - 16 bytes, then no workspace at all -------------------------------------------------------
-    if q > 0:
-        assert q >= 16, "%s: a query of %d bytes leaves no 16 bytes to cut" % (what, q)
-        for stage, p, nb in (("short run (query - 16)", wsr.ptr, q - 16), ("NULL workspace", None, 0)):
-            paint(short=True)
-            rc = launch(p, nb, ptr, tr.ptr if tr is not None else None, arena, stage)
-            assert bool((wsr.u8[q - 16:] == CANARY).all()), "%s, %s: the 16 bytes past ws_bytes were written" % (what, stage)
-            got = outputs()
-            if rc < 0:
-                print("%s, %s: refused rc=%d (%s)" % (what, stage, rc, m.last_error()))
-                want = case.short_code if p is not None else case.null_code
-                if want is not None:
-                    assert rc == want, (what, stage, rc, want)
-                untouched(got, stage, True)
-            else:
-                assert rc == 0 and case.short_code is None, (what, stage, rc)
-                ok, n = same_as_reference(got, stage)
-                assert ok or case.fallback, "%s, %s: rc == 0 but output %r differs from the reference run" % (what, stage, n)
-                if not ok:       # a declared fallback kernel (for the loss sums the float atomics the header documents for a
-                    # call without scratch): the reference run's own fp64 check at the op's existing tolerance
-                    print("%s, %s: fallback path, %r not bit-identical; fp64 check" % (what, stage, n))
-                    case.verify(got)
-                untouched(got, stage, False)
-            if tr is not None:
-                assert not bool(tr.u8.any()), "%s, %s: tickets left non-zero" % (what, stage)
-            if case.zero_exit and p is not None:        # "left zero by every call": accepted or refused
-                assert not bool(wsr.u8[:min(case.zero_exit, nb)].any()), "%s, %s: zero-on-exit words left non-zero" % (what, stage)
-    return ref
-
 
 # =====================================================================================================================
-# convolution family
+# convolution family (the case builders: tests/caller_memory_support.py)
 # =====================================================================================================================
-def conv_inputs(case, seed, wscale=0.1):
-    N, H, W, Cc, K, R, S, stride, padding = case
-    g = torch.Generator().manual_seed(seed)
-    OH, OW, pads = conv_geom(H, W, R, S, stride, padding)
-    x, w, b = f32(g, N, H, W, Cc), f32(g, R, S, Cc, K, scale=wscale), f32(g, K)
-    gy, res, mask = f32(g, N, OH, OW, K), f32(g, N, H, W, Cc), f32(g, N, H, W, Cc)
-    return g, OH, OW, pads, x, w, b, gy, res, mask
-
-
-def fwd_case(device, name, configure=None):
-    from acimg import ops
-    m, L = raw_lib()
-    shape, act, with_stats, branch, tol = FWD_CASES[name]
-    N, H, W, Cc, K, R, S, stride, padding = shape
-    g, OH, OW, pads, x, w, b, _, _, _ = conv_inputs(shape, 11 + sum(v for v in shape if isinstance(v, int)),
-                                                    wscale=0.05 if branch == "skinny" else (2.0 / (R * S * Cc)) ** 0.5)
-    ldy = K + 4
-    d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldy=ldy, act=act)
-    til = ops.conv2d_fwd_tiling(d)
-    q = int(L.acimg_conv2d_fwd_workspace(C.byref(d)))
-    if branch.startswith("splitk"):
-        assert til[2] > 1 and q > 0
-    elif branch == "unsplit":
-        assert til[2] == 1 and q == 0
-    elif branch == "256x16":
-        assert til[:2] == (256, 16) and til[2] > 1
-    elif branch == "few16":
-        assert ops.conv2d_stats_rows(d) == 512 and ops.conv2d_affine_input_ok(d, 0)
-    elif branch == "direct":
-        assert ops.conv2d_stats_rows(d) == -(-N * OH * OW // 256) and not ops.conv2d_affine_input_ok(d, 0)
-    raw = tf_conv_ref(x.double(), w.double(), stride, pads, b.double())
-    yref = torch.relu(raw) if act else raw
-    xd, wd, bd = x.to(device), w.to(device), b.to(device)
-    rows = ops.conv2d_stats_rows(d)
-    outs = OrderedDict(y=Out(torch.float32, (N, OH, OW, ldy), last_lt((N, OH, OW, ldy), K)))
-    if with_stats:
-        outs["stats"] = Out(torch.float32, (rows + 3, 2, d.ldw), first_lt((rows + 3, 2, d.ldw), rows))
-
-    def call(ws, nb, p, tick):
-        return L.acimg_conv2d_fwd(C.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), p["y"], None, None, 0,
-                                  p.get("stats"), ws, nb, tick if branch.endswith("tickets") else None,
-                                  ops.current_stream_handle(device))
-
-    def verify(o):
-        close(o["y"][..., :K], yref, tol=tol, what="conv2d_fwd %s" % name)
-        if with_stats:
-            # the implicit-GEMM epilogue sums conv + bias BEFORE the activation; the few-channel direct kernel with an
-            # activation leaves its statistics to a pass over the stored (activated) tensor (include/acimg.h; the same
-            # thing with ACIMG_ACT_NONE, which every batch-norm layer uses)
-            flat = (yref if act and branch == "direct" else raw).reshape(-1, K)
-            close(o["stats"][:rows, 0, :K].sum(0), flat.sum(0), tol=STATS_TOL, what="conv2d_fwd %s stats sum" % name)
-            close(o["stats"][:rows, 1, :K].sum(0), (flat * flat).sum(0), tol=STATS_TOL, what="conv2d_fwd %s stats sumsq" % name)
-    # skinny: without its full workspace the dense layer runs as a split-K implicit GEMM (another summation order)
-    return Case(q, outs, call, verify, tickets=branch.endswith("tickets"), fallback=branch == "skinny", keep=(xd, wd, bd, d))
-
-
 @pytest.mark.parametrize("name", list(FWD_CASES))
 def test_conv2d_fwd_caller_memory(device, name):
     run_case(device, fwd_case(device, name), "conv2d_fwd[%s]" % name)
-
-
-def dgrad_case(device, name):
-    from acimg import ops
-    m, L = raw_lib()
-    shape, with_res, with_mask, tickets, tol = DGRAD_CASES[name]
-    N, H, W, Cc, K, R, S, stride, padding = shape
-    small = name in ("halo16_narrow", "few_channel_stride2", "dilated_then_igemm_65536")
-    g, OH, OW, pads, x, w, b, gy, res, mask = conv_inputs(shape, 5 + sum(v for v in shape if isinstance(v, int)),
-                                                          wscale=0.05 if name == "skinny" else 0.1)
-    if small:
-        gy, res = gy * 1e-3, res * 1e-3          # gradients of the size the bf16x3 forms were made for (fp16 would lose them)
-    lddx, ldgy = Cc + 4, K + 4
-    d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldw=K)
-    q = int(L.acimg_conv2d_dgrad_workspace(C.byref(d)))
-    xr = x.double().requires_grad_(True)
-    y = tf_conv_ref(xr, w.double(), stride, pads)
-    (gx,) = torch.autograd.grad(y, (xr,), gy.double())
-    ref = gx + (res.double() if with_res else 0)
-    if with_mask:
-        ref = ref * (mask > 0).double()
-    gyd, wd = widen(gy, ldgy).to(device), w.to(device)
-    resd, maskd = widen(res, Cc + 8).to(device), widen(mask, Cc + 4).to(device)
-    outs = OrderedDict(dx=Out(torch.float32, (N, H, W, lddx), last_lt((N, H, W, lddx), Cc)))
-
-    def call(ws, nb, p, tick):
-        return L.acimg_conv2d_dgrad(C.byref(d), gyd.data_ptr(), ldgy, wd.data_ptr(), p["dx"], lddx,
-                                    resd.data_ptr() if with_res else None, Cc + 8, maskd.data_ptr() if with_mask else None,
-                                    Cc + 4, ws, nb, tick if tickets else None, ops.current_stream_handle(device))
-
-    def verify(o):
-        close(o["dx"][..., :Cc], ref, tol=tol, what="conv2d_dgrad %s" % name)
-    return Case(q, outs, call, verify, tickets=tickets, keep=(gyd, wd, resd, maskd, d))
 
 
 @pytest.mark.parametrize("name", list(DGRAD_CASES))
@@ -312,116 +46,9 @@ def test_conv2d_dgrad_caller_memory(device, name):
     run_case(device, dgrad_case(device, name), "conv2d_dgrad[%s]" % name)
 
 
-def wgrad_case(device, name):
-    from acimg import ops
-    m, L = raw_lib()
-    shape, entry, tol = WGRAD_CASES[name]
-    N, H, W, Cc, K, R, S, stride, padding = shape
-    g, OH, OW, pads, x, w, b, gy, _, _ = conv_inputs(shape, 3 + sum(v for v in shape if isinstance(v, int)))
-    if name != "skinny":
-        gy = gy * 1e-2
-    kp = up4(K)
-    ldw, ldgy = kp + 4, kp + 4
-    d = ops.conv_desc(N, H, W, Cc, K, R, S, stride, padding, ldw=ldw)
-    q = int(L.acimg_conv2d_wgrad_workspace(C.byref(d)))
-    affine = entry.startswith("affine")
-    prec = int(entry[-1]) if affine else 0
-    if affine:
-        assert ops.conv2d_affine_input_ok(d, prec)
-        scale, shift = (torch.rand(Cc, generator=g) + 0.5).float(), f32(g, Cc, scale=0.5)
-        scd, shd = scale.to(device), shift.to(device)
-    rnd_ = (lambda t: t.to(torch.bfloat16).double()) if entry == "bf16" else (lambda t: t.double())   # bf16: fp64 of the ROUNDED operands
-    xd = x.to(device)
-    gyd = widen(gy, ldgy, fill=0.0).to(device)           # columns K .. kp are operands (zero); beyond kp never read
-    gyd[..., kp:] = float("nan")
-    st = ops.current_stream_handle(device)
-    if affine:
-        # the reference of the existing test: the SAME entry family on the materialised tensor (roomy zeroed workspace)
-        xmat = torch.relu(xd * scd + shd)
-        rws = torch.zeros(4 * q + (1 << 20), dtype=torch.uint8, device=device)
-        rdw = torch.zeros(R, S, Cc, ldw, device=device)
-        rdb = torch.zeros(ldw, device=device)
-        fn = L.acimg_conv2d_wgrad_split3 if prec == 1 else L.acimg_conv2d_wgrad
-        m.check(fn(C.byref(d), xmat.data_ptr(), gyd.data_ptr(), ldgy, rdw.data_ptr(), rdb.data_ptr(), rws.data_ptr(),
-                   rws.numel(), st), "reference wgrad")
-        torch.cuda.synchronize()
-        gw, gb = rdw[..., :K].cpu().double(), rdb[:K].cpu().double()
-        del rws, xmat
-        # ... and, independent of the library, fp64 of the same product at the tolerance of the non-affine case on the same
-        # kernel (halo16_split3: 4e-5, few_channel_halo: 2e-5)
-        wz = torch.zeros(R, S, Cc, K, dtype=torch.float64, requires_grad=True)
-        yr = tf_conv_ref(torch.relu(x.double() * scale.double() + shift.double()), wz, stride, pads)
-        (gw64,) = torch.autograd.grad(yr, (wz,), gy.double())
-        gb64, tol64 = gy.double().sum((0, 1, 2)), 4e-5 if prec == 1 else 2e-5
-    else:
-        wz = torch.zeros(R, S, Cc, K, dtype=torch.float64, requires_grad=True)
-        yr = tf_conv_ref(rnd_(x), wz, stride, pads)
-        (gw,) = torch.autograd.grad(yr, (wz,), rnd_(gy))
-        gb = rnd_(gy).sum((0, 1, 2))
-    # columns [K, kp) are the zero padding of the GEMM (written, zero); [kp, ldw) is outside the layer: untouched
-    outs = OrderedDict(dw=Out(torch.float32, (R, S, Cc, ldw), last_lt((R, S, Cc, ldw), kp)),
-                       db=Out(torch.float32, (ldw,), last_lt((ldw,), kp)))
-
-    def call(ws, nb, p, tick):
-        if affine:
-            return L.acimg_conv2d_wgrad_affine(C.byref(d), prec, xd.data_ptr(), scd.data_ptr(), shd.data_ptr(), 1, gyd.data_ptr(),
-                                               ldgy, p["dw"], p["db"], ws, nb, st)
-        fn = {"f32": L.acimg_conv2d_wgrad, "split3": L.acimg_conv2d_wgrad_split3, "bf16": L.acimg_conv2d_wgrad_bf16}[entry]
-        return fn(C.byref(d), xd.data_ptr(), gyd.data_ptr(), ldgy, p["dw"], p["db"], ws, nb, st)
-
-    def verify(o):
-        close(o["dw"][..., :K], gw, tol=tol, what="conv2d_wgrad %s" % name)
-        close(o["db"][:K], gb, tol=tol, what="conv2d_wgrad %s bias gradient" % name)
-        if affine:
-            close(o["dw"][..., :K], gw64, tol=tol64, what="conv2d_wgrad %s against fp64" % name)
-            close(o["db"][:K], gb64, tol=tol64, what="conv2d_wgrad %s bias gradient against fp64" % name)
-        assert float(o["dw"][..., K:kp].abs().max() if kp > K else 0.0) == 0.0
-    return Case(q, outs, call, verify, keep=(xd, gyd, d))
-
-
 @pytest.mark.parametrize("name", list(WGRAD_CASES))
 def test_conv2d_wgrad_caller_memory(device, name):
     run_case(device, wgrad_case(device, name), "conv2d_wgrad[%s]" % name)
-
-
-def deconv_cases(device, name):
-    from acimg import ops
-    m, L = raw_lib()
-    shape, tol_f, tol_d, tol_w = DECONV_CASES[name]
-    N, H, W, Cc, K, R, S, s = shape
-    g = torch.Generator().manual_seed(77 + N + Cc)
-    x, w, b = f32(g, N, H, W, Cc), f32(g, R, S, K, Cc, scale=0.1), f32(g, K)
-    xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
-    y = F.conv_transpose2d(xr.permute(0, 3, 1, 2), wr.permute(3, 2, 0, 1), b.double(), stride=s,
-                           output_padding=(max(s - R, 0), max(s - S, 0))).permute(0, 2, 3, 1)
-    ldy = 2 * K
-    d = ops.deconv_desc(N, H, W, Cc, K, R, S, s, ldy=ldy)
-    OH, OW = d.OH, d.OW
-    assert tuple(y.shape[1:3]) == (OH, OW)
-    gy = f32(g, N, OH, OW, K)
-    gxr, gwr = torch.autograd.grad(y, (xr, wr), gy.double())
-    mask = f32(g, N, H, W, Cc)
-    with_mask = name != "direct_dgrad"
-    q = int(L.acimg_deconv_workspace(C.byref(d)))
-    xd, wd, bd, gyd, maskd = x.to(device), w.to(device), b.to(device), widen(gy, ldy).to(device), mask.to(device)
-    st = ops.current_stream_handle(device)
-    keep = (xd, wd, bd, gyd, maskd, d)
-    fwd = Case(q, OrderedDict(y=Out(torch.float32, (N, OH, OW, ldy), last_lt((N, OH, OW, ldy), K))),
-               lambda ws, nb, p, tick: L.acimg_deconv_fwd(C.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), p["y"], ws, nb, tick, st),
-               lambda o: close(o["y"][..., :K], y.detach(), tol=tol_f, what="deconv_fwd %s" % name), tickets=True, keep=keep)
-    dref = gxr * (mask > 0).double() if with_mask else gxr
-    dgr = Case(q, OrderedDict(dx=Out(torch.float32, (N, H, W, Cc))),
-               lambda ws, nb, p, tick: L.acimg_deconv_dgrad(C.byref(d), gyd.data_ptr(), ldy, wd.data_ptr(), p["dx"],
-                                                            maskd.data_ptr() if with_mask else None, Cc, ws, nb, tick, st),
-               lambda o: close(o["dx"], dref, tol=tol_d, what="deconv_dgrad %s" % name), tickets=True, keep=keep)
-
-    def verify_w(o):
-        close(o["dw"], gwr, tol=tol_w, what="deconv_wgrad %s" % name)
-        close(o["db"], gy.double().sum((0, 1, 2)), tol=tol_w, what="deconv_wgrad %s bias gradient" % name)
-    wgr = Case(q, OrderedDict(dw=Out(torch.float32, (R, S, K, Cc)), db=Out(torch.float32, (K,))),
-               lambda ws, nb, p, tick: L.acimg_deconv_wgrad(C.byref(d), xd.data_ptr(), gyd.data_ptr(), ldy, p["dw"], p["db"], ws, nb, st),
-               verify_w, keep=keep)
-    return fwd, dgr, wgr
 
 
 @pytest.mark.parametrize("name", list(DECONV_CASES))
