@@ -114,6 +114,36 @@ __device__ __forceinline__ float4 unsplit4(const uint2 hi, const uint2 lo, float
                        ((float)h[2] + (float)l[2]) * inv_scale, ((float)h[3] + (float)l[3]) * inv_scale);
 }
 
+// ---- what every LDS-DMA / MFMA kernel needs (trunk and weight-gradient kernel headers, gram.hip) ------------------
+using u32x4 = __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int;    // a buffer store's 16 bytes
+typedef __attribute__((address_space(3))) void* lds_ptr_t;                                // an LDS-DMA destination
+// a buffer offset >= num_records of every descriptor (tensors < 2 GiB): the load returns zeros, an LDS-DMA writes zeros
+constexpr unsigned OOB = 0x80000000u;
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+
+// `s_waitcnt vmcnt(N)` with a compile-time N.  An `asm volatile` with a memory clobber: nothing moves across it, and the
+// compiler's own counter bookkeeping does not see it (where that matters - a pipelined loop whose fragment registers were
+// loaded one iteration earlier - igemm_split3r_kernel.hpp waits through the builtin instead).
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    static_assert(N >= 0 && N < 64, "vmcnt immediate");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// The transposing fragment read of gfx950: `ds_read_b64_tr_b16` returns, per 16-lane group and column-major, a
+// 4 (k) x 16 (column) block of 16-bit elements out of a tile kept [k][column] in LDS - exactly the layout of a 16x16x32
+// MFMA operand, whose lane group g owns k = 8 g .. 8 g + 7.  So a fragment is TWO reads, of the k rows 8 g + (0 .. 3) at
+// r0 and 8 g + (4 .. 7) at r1 (the caller's tile image decides the two addresses), packed into one operand V8 (h16x8 or
+// b16x8).
+template <typename V8>
+__device__ __forceinline__ V8 tr16_frag(const char* r0, const char* r1) {
+    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)r0);
+    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)r1);
+    const s16x8 v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    return __builtin_bit_cast(V8, v);
+}
+
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == ACIMG_ACT_RELU) return fmaxf(v, 0.f);
     if (act == ACIMG_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));

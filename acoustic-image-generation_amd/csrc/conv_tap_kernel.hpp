@@ -159,20 +159,8 @@ __global__ __launch_bounds__(512, 4) void conv_tap_kernel(const IgemmParams p) {
             bh[j] = *reinterpret_cast<const V8*>(wb + b_off + j * 16 * 64);
             bl[j] = *reinterpret_cast<const V8*>(wb + B_BYTES + b_off + j * 16 * 64);
         }
-        // small terms first; the three terms of a product are a whole sweep apart (per-accumulator order as the per-tap kernel)
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = TR::mfma(bl[j], ah[i], acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = TR::mfma(bh[j], al[i], acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = TR::mfma(bh[j], ah[i], acc[i][j]);
+        split_sweep<TR, 3>(acc, ah, al, bh, bl);
     };
 
     int tp = 0;                                        // tap of the step being multiplied

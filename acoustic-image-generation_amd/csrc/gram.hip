@@ -33,22 +33,6 @@
 
 namespace acimg {
 
-// (the few other helpers shared with the trunk kernels are restated here: their headers define non-template kernels, which
-//  may live in one translation unit only)
-namespace {
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-constexpr unsigned OOB = 0x80000000u;      // >= num_records of every descriptor (tensors < 2 GiB): the DMA writes zeros
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else static_assert(N == 2, "add the immediate");
-}
-}  // namespace
-
 struct GramParams {
     const char* X;       // split-format planes (hi at X, lo at X + lo_off)
     unsigned x_bytes;    // extent for the buffer resource
@@ -62,9 +46,6 @@ struct GramParams {
     float* sxpart;       // [S][C]
 };
 
-typedef short g_s16x4 __attribute__((ext_vector_type(4)));
-typedef short g_s16x8 __attribute__((ext_vector_type(8)));
-
 // fragment of 16 channels (tile ct of the block side) x 32 pixels (half h of the 64-pixel K step) out of a region
 // [4 pixel blocks][NCC bricks]: lane (li, g) gets channel 16 ct + li, pixels 32 h + 8 g .. + 7 (two transposing reads of 4
 // pixel rows each)
@@ -76,10 +57,7 @@ __device__ __forceinline__ h16x8 gram_frag(const char* region, int ct, int h, in
     const int row0 = 8 * (g & 1) + q, row1 = row0 + 4;
     const int a0 = brick + row0 * 64 + ((kc ^ swz(row0)) << 4) + 8 * (p & 1);
     const int a1 = brick + row1 * 64 + ((kc ^ swz(row1)) << 4) + 8 * (p & 1);
-    const g_s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) g_s16x4*)(region + a0));
-    const g_s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) g_s16x4*)(region + a1));
-    const g_s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(h16x8, v);
+    return tr16_frag<h16x8>(region + a0, region + a1);
 }
 
 template <int BC>

@@ -15,12 +15,74 @@
 
 namespace acimg {
 
-using u32x4 = __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int;
-
+// (u32x4 and OOB, the out-of-range buffer offset: common.hpp)
 __device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
 }
-constexpr unsigned OOB = 0x80000000u;  // >= num_records of every descriptor (tensors < 2 GiB)
+
+// ---- K-range hand-off: the library's only synchronisation between workgroups ---------------------------------------
+// `nranges` workgroups each hold the partial sums of one K range of the same output tile of TILE elements (split-K of
+// igemm_f32_kernel, tail split of the trunk kernels); the ranges of a tile meet in `nranges` slots of TILE floats at slot0
+// (element order = accumulator order: the slots are only ever read back here).  Nobody waits for anybody.
+//
+// krange_park: range `mine` PARKS its accumulators in its slot and takes a ticket; -> nonzero in the workgroup that came last.
+//   * The stores are write-through (sc1) and every thread waits for its own (vmcnt(0)): an sc1 store has completed only
+//     when it is past this XCD's L2, where every other XCD sees it.  Behind the barrier that follows, the WHOLE slot is
+//     there.  That is why no release fence (an L2 write-back) is needed and the ticket can be a RELAXED atomic: the data
+//     is globally visible before thread 0 touches the counter.
+//   * Thread 0 takes the ticket from the tile's agent-scope counter.  The last ticket proves that every other range was
+//     parked before it was drawn; that workgroup ACQUIRES (whatever stale lines it might hold are dropped), waits, puts the
+//     counter back to zero for the next launch, and tells its threads through an LDS flag (the first word of `smem`).
+//   * Everybody else returns: a range that is not last has nothing more to do.
+// `mine` keeps the caller's type (an int range index, or the unsigned blockIdx.z): its widening is part of the address code.
+template <int TILE, int NTHR, int TM, int TN, typename Index>
+__device__ __forceinline__ int krange_park(f32x4 (&acc)[TM][TN], float* const slot0, const Index mine, const int nranges,
+                                           int* const counter, float* smem, const int tid) {
+    const __amdgpu_buffer_rsrc_t rsP =
+        __builtin_amdgcn_make_buffer_rsrc(slot0 + (long)mine * TILE, 0, TILE * 4, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rsP,
+                                                   ((i * TN + j) * NTHR + tid) * 16, 0, 16);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    int* const flag = reinterpret_cast<int*>(smem);
+    if (tid == 0) {
+        const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = ticket == nranges - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        *flag = last;
+    }
+    __syncthreads();
+    return *flag;
+}
+// krange_sum: the last arriver adds the ranges FROM MEMORY, IN RANGE ORDER, its own included: fp32 addition is not
+// associative, and this way the tile's bits do not depend on which range happened to come last (sc1 loads: never a stale
+// L1 / L2 copy).  The barrier in front: every thread has read krange_park's flag before the LDS is used again - by this
+// kernel's epilogue, which stages through it.
+template <int TILE, int NTHR, int TM, int TN>
+__device__ __forceinline__ void krange_sum(f32x4 (&acc)[TM][TN], float* const slot0, const int nranges, const int tid) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < nranges; ++c) {
+        const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(slot0 + (long)c * TILE, 0, TILE * 4, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                           rsQ, ((i * TN + j) * NTHR + tid) * 16, 0, 16));
+    }
+}
 
 // ---- epilogue -------------------------------------------------------------------------------
 // row m -> linear output pixel; (oh, ow): where tap (0, 0) of the row lands (scatter modes)
@@ -489,37 +551,12 @@ __global__ __launch_bounds__(NTHR) void igemm_f32_kernel(const IgemmParams p) {
     }
 
     if (p.splits > 1 && p.ts_counters != nullptr) {
-        // split-K without a reduce launch (same hand-off as the trunk kernel's tail split): every K range parks its
-        // partial tile (write-through sc1 stores: visible to the other XCDs), takes a ticket; the last arriver adds
-        // the ranges IN RANGE ORDER (its own included, from memory: the result does not depend on who came last)
-        // and runs the ordinary epilogue.  Nobody waits.
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        // split-K without a reduce launch: the K ranges of a tile meet in the slab (krange_handoff), the last arriver runs
+        // the ordinary epilogue
         const int tl = blockIdx.y * gridDim.x + blockIdx.x;
         float* const slot0 = p.slab + (long)tl * p.splits * (BM * BN);
-        const __amdgpu_buffer_rsrc_t rsP =
-            __builtin_amdgcn_make_buffer_rsrc(slot0 + (long)blockIdx.z * (BM * BN), 0, BM * BN * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rsP,
-                                                       ((i * TN + j) * NTHR + tid) * 16, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* const flag = reinterpret_cast<int*>(smem);
-        if (tid == 0) {
-            const int ticket = __hip_atomic_fetch_add(p.ts_counters + tl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = ticket == p.splits - 1;
-            if (last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(p.ts_counters + tl, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            *flag = last;
-        }
-        __syncthreads();
-        if (!*flag) return;
-        __syncthreads();                           // everyone has read the flag before the epilogue reuses the LDS
+        if (!krange_park<BM * BN, NTHR>(acc, slot0, blockIdx.z, p.splits, p.ts_counters + tl, smem, tid)) return;
+        __syncthreads();                           // (krange_sum, kept in place: the shared form changes this kernel's code)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -530,7 +567,7 @@ __global__ __launch_bounds__(NTHR) void igemm_f32_kernel(const IgemmParams p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j)     // sc1 loads: never a stale L1 / L2 copy
+                for (int j = 0; j < TN; ++j)
                     acc[i][j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                                                rsQ, ((i * TN + j) * NTHR + tid) * 16, 0, 16));
         }

@@ -18,7 +18,7 @@
 //   MFMA roles swapped as in the fp32 kernel (weights in the A slot): a lane's 4 accumulators are 4 consecutive
 //      output channels of one pixel -> shared 16-byte epilogue incl. the batch-norm statistics partials.
 #pragma once
-#include "igemm_kernel.hpp"
+#include "split_gemm_core.hpp"      // (includes igemm_kernel.hpp)
 #include "split_planes.hpp"
 
 namespace acimg {
@@ -234,24 +234,8 @@ __global__ __launch_bounds__(NTHR) void igemm_split3_kernel(const IgemmParams p)
             bh[j] = *reinterpret_cast<const V8*>(st + off);
             if (TERMS == 3) bl[j] = *reinterpret_cast<const V8*>(st + B_BYTES + off);
         }
-        // rows of D = output channels (weights in the A slot), columns = pixels; small terms first.  All fragment
-        // reads are issued before the first MFMA and the three terms of a product are a whole sweep apart, so no
-        // MFMA waits on its predecessor's accumulator (per-accumulator order unchanged).
-        __builtin_amdgcn_sched_barrier(0);
-        if (TERMS == 3) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = TR::mfma(bl[j], ah[i], acc[i][j]);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = TR::mfma(bh[j], al[i], acc[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = TR::mfma(bh[j], ah[i], acc[i][j]);
+        __builtin_amdgcn_sched_barrier(0);          // all fragment reads are issued before the first MFMA
+        split_sweep<TR, TERMS>(acc, ah, al, bh, bl);
     };
 
     if (it_end > 0) {

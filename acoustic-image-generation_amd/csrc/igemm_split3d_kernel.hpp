@@ -27,8 +27,6 @@
 
 namespace acimg {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 // ---- operands in LDS-TILE ORDER ("bricks") --------------------------------------------------------------------------
 // A request of the LDS-DMA path is 64 lanes x 16 bytes = 16 tile rows of 64 bytes.  With row-major operands those are
 // sixteen 64-byte pieces of sixteen different rows (half a cache line each, a row pitch apart), and the K loop waits at
@@ -45,22 +43,6 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 __device__ __forceinline__ unsigned brick_b_off(unsigned n, unsigned ksteps, unsigned pch) {
     // byte offset (hi plane, K step 0) of physical chunk pch of weight row n; + 16384 per K step, + 8192 for the lo plane
     return (n >> 7) * ksteps * 16384u + ((n & 127u) << 6) + (pch << 4);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else static_assert(N == 0, "add the immediate");
 }
 
 // linear workgroup id -> (row tile, column tile), see IgemmParams::ras_*
@@ -130,10 +112,10 @@ __global__ __launch_bounds__(NTHR) void igemm_split3d_kernel(const IgemmParams p
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.B), 0, p.b_bytes, 0x00020000);
 
     int it_begin = 0, it_end = p.kiters;
-    if (split) {                                   // balanced K ranges: the first (kiters % s) get one step more
-        const int base = p.kiters / p.ts_s, extra = p.kiters - base * p.ts_s;
-        it_begin = chunk * base + min(chunk, extra);
-        it_end = it_begin + base + (chunk < extra ? 1 : 0);
+    if (split) {
+        const KRange k = balanced_krange(p.kiters, p.ts_s, chunk);
+        it_begin = k.begin;
+        it_end = k.end;
     }
     const int Ktot = p.ntaps * p.C;
 
@@ -246,27 +228,8 @@ __global__ __launch_bounds__(NTHR) void igemm_split3d_kernel(const IgemmParams p
             bh[j] = *reinterpret_cast<const h16x8*>(stb + off);
             if (TERMS == 3) bl[j] = *reinterpret_cast<const h16x8*>(stb + B_BYTES + off);
         }
-        // all 12 fragment reads are in flight before the first MFMA (one exposed LDS latency per step instead
-        // of one per fragment pair), and the three terms of a product are issued a whole sweep apart so that no
-        // MFMA waits on its predecessor's accumulator (the per-accumulator order lo*hi, hi*lo, hi*hi is kept)
-        __builtin_amdgcn_sched_barrier(0);
-        if (TERMS == 3) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);          // all 12 fragment reads are in flight before the first MFMA
+        split_sweep<SplitF16, TERMS>(acc, ah, al, bh, bl);
     };
 
     // prologue = the requests the steps -(NSA-1) .. -1 would have made, in the same order (B before A)
@@ -297,49 +260,11 @@ __global__ __launch_bounds__(NTHR) void igemm_split3d_kernel(const IgemmParams p
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] *= SPLIT3_OUTSCALE;
     if (split) {
-        // every range parks its partial sums (write-through sc1 stores: visible to the other XCDs without an L2
-        // write-back fence) and takes a ticket; the last arriver adds the ts_s partials IN RANGE ORDER (its own
-        // included, from memory: the result does not depend on who came last) and runs the epilogue.  Nobody waits.
+        // the ranges of one tile meet in the workspace; the last arriver holds their sum and runs the epilogue
         const int tl = vt - p.ts_whole;
         float* const slot0 = p.ts_partial + (long)tl * p.ts_s * (BM * BN);
-        const __amdgpu_buffer_rsrc_t rsP =
-            __builtin_amdgcn_make_buffer_rsrc(slot0 + (long)chunk * (BM * BN), 0, BM * BN * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rsP,
-                                                       ((i * TN + j) * NTHR + tid) * 16, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* const flag = reinterpret_cast<int*>(smem);
-        if (tid == 0) {
-            const int ticket = __hip_atomic_fetch_add(p.ts_counters + tl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = ticket == p.ts_s - 1;
-            if (last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(p.ts_counters + tl, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            *flag = last;
-        }
-        __syncthreads();
-        if (!*flag) return;
-        __syncthreads();                           // everyone has read the flag before the LDS is reused below
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int c = 0; c < p.ts_s; ++c) {
-            const __amdgpu_buffer_rsrc_t rsQ =
-                __builtin_amdgcn_make_buffer_rsrc(slot0 + (long)c * (BM * BN), 0, BM * BN * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)     // sc1 loads: never a stale L1 / L2 copy
-                    acc[i][j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                               rsQ, ((i * TN + j) * NTHR + tid) * 16, 0, 16));
-        }
+        if (!krange_park<BM * BN, NTHR>(acc, slot0, chunk, p.ts_s, p.ts_counters + tl, smem, tid)) return;
+        krange_sum<BM * BN, NTHR>(acc, slot0, p.ts_s, tid);
     }
     const EpiParams& e = p.e;
     if (e.vec && !e.bias && !e.res && !e.mask && !e.scatter && e.act == ACIMG_ACT_NONE) {

@@ -265,37 +265,21 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void igemm_split3dp_kernel(c
 #else
             constexpr bool lo_terms = true;
 #endif
-            if (TERMS == 3 && lo_terms) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
-            }
+            if (TERMS == 3 && lo_terms) split_term<SplitF16, 0>(acc, ah, al, bh, bl);
             if (DPOS == 1 && kh == 0) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (req == 1) issue_b(ta, slot ^ 1);
                 else if (req == 2) issue_b(tb, slot ^ 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (TERMS == 3 && lo_terms) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
-            }
+            if (TERMS == 3 && lo_terms) split_term<SplitF16, 1>(acc, ah, al, bh, bl);
             if (DPOS == 1 && kh == 0) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (req == 1) issue_a(ta, slot ^ 1);
                 else if (req == 2) issue_a(tb, slot ^ 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
+            split_term<SplitF16, 2>(acc, ah, al, bh, bl);
             ACIMG_STAMP_AT(4);
         }
     };
@@ -588,9 +572,8 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void igemm_split3dp_kernel(c
         const int u = unit - p.ts_whole;
         const int vt = p.ts_whole + u / p.ts_s;
         const int chunk = u - (u / p.ts_s) * p.ts_s;
-        const int base = p.kiters / p.ts_s, extra = p.kiters - base * p.ts_s;
-        const int it_begin = chunk * base + min(chunk, extra);
-        const int it_end = it_begin + base + (chunk < extra ? 1 : 0);
+        const KRange kr = balanced_krange(p.kiters, p.ts_s, chunk);
+        const int it_begin = kr.begin, it_end = kr.end;
         const Tile cur = setup(vt);
         __builtin_amdgcn_s_barrier();               // nobody still reads LDS from the previous unit
         cursor_set(it_begin);
@@ -605,6 +588,8 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void igemm_split3dp_kernel(c
             __builtin_amdgcn_s_setprio(0);
             slot ^= 1;
         }
+        // the hand-off of igemm_kernel.hpp (krange_park / krange_sum: protocol and memory ordering are stated there), with
+        // this kernel's barrier idiom and `continue` for `return`
         const int tl = vt - p.ts_whole;
         float* const slot0 = p.ts_partial + (long)tl * p.ts_s * (BM * BN);
         const __amdgpu_buffer_rsrc_t rsP =
@@ -641,7 +626,7 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void igemm_split3dp_kernel(c
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j)     // sc1 loads: never a stale L1 / L2 copy
+                for (int j = 0; j < TN; ++j)
                     acc[i][j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                                                rsQ, ((i * TN + j) * NTHR + tid) * 16, 0, 16));
         }

@@ -70,9 +70,9 @@ __global__ __launch_bounds__(512, 4) void igemm_split3h_kernel(const IgemmParams
 
     int it_begin = 0, it_end = p.kiters;          // K steps in (chunk, tap) order: step = chunk * 9 + tap
     if (split) {
-        const int base = p.kiters / p.ts_s, extra = p.kiters - base * p.ts_s;
-        it_begin = krange * base + min(krange, extra);
-        it_end = it_begin + base + (krange < extra ? 1 : 0);
+        const KRange k = balanced_krange(p.kiters, p.ts_s, krange);
+        it_begin = k.begin;
+        it_end = k.end;
     }
     const int cpk = p.C >> 5;                     // channel chunks; the weight image's K step of (chunk, tap) is tap * cpk + chunk
     const unsigned c32 = (unsigned)p.C * 32u;
@@ -186,6 +186,7 @@ __global__ __launch_bounds__(512, 4) void igemm_split3h_kernel(const IgemmParams
                 issue_patch(nchunk);
                 __builtin_amdgcn_sched_barrier(0);
             }
+            // split_sweep<SplitF16, 3> (split_gemm_core.hpp: term order), kept in place: the shared form changes this kernel's code
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -212,33 +213,11 @@ __global__ __launch_bounds__(512, 4) void igemm_split3h_kernel(const IgemmParams
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] *= SPLIT3_OUTSCALE;
-    if (split) {                                  // K ranges of a tail tile meet in the workspace (igemm_split3d_kernel)
+    if (split) {                                  // K ranges of a tail tile meet in the workspace, as in igemm_split3d_kernel
         const int tl = vt - p.ts_whole;
         float* const slot0 = p.ts_partial + (long)tl * p.ts_s * (BM * BN);
-        const __amdgpu_buffer_rsrc_t rsP =
-            __builtin_amdgcn_make_buffer_rsrc(slot0 + (long)krange * (BM * BN), 0, BM * BN * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rsP,
-                                                       ((i * TN + j) * NTHR + tid) * 16, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* const flag = reinterpret_cast<int*>(smem);
-        if (tid == 0) {
-            const int ticket = __hip_atomic_fetch_add(p.ts_counters + tl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = ticket == p.ts_s - 1;
-            if (last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(p.ts_counters + tl, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            *flag = last;
-        }
-        __syncthreads();
-        if (!*flag) return;
-        __syncthreads();
+        if (!krange_park<BM * BN, NTHR>(acc, slot0, krange, p.ts_s, p.ts_counters + tl, smem, tid)) return;
+        __syncthreads();                          // (krange_sum, kept in place: the shared form changes this kernel's code)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll

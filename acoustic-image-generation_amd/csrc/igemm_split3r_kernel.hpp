@@ -37,8 +37,8 @@ struct TileAddrR {
     unsigned b_goff;                       // this lane's row of the wave's B piece, byte offset at K step 0
 };
 
-// s_waitcnt through the builtin, so that the compiler's own counter bookkeeping sees it (an `asm volatile` wait is opaque:
-// behind it the compiler still protects every fragment register loaded one loop iteration earlier with a conservative
+// s_waitcnt through the builtin, so that the compiler's own counter bookkeeping sees it (the `asm volatile` wait every other
+// kernel uses - wait_vmcnt, common.hpp - is opaque: behind it the compiler still protects every fragment register loaded one loop iteration earlier with a conservative
 // lgkmcnt wait in front of its first use - which, in a pipelined loop, waits for the reads issued just before)
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 template <int N>
@@ -95,9 +95,9 @@ __global__ __launch_bounds__(512, 2) void igemm_split3r_kernel(const IgemmParams
             const int t = uu / p.ts_s;
             chunk = uu - t * p.ts_s;
             vt = p.ts_whole + t;
-            const int base = p.kiters / p.ts_s, extra = p.kiters - base * p.ts_s;
-            kb = chunk * base + min(chunk, extra);
-            ke = kb + base + (chunk < extra ? 1 : 0);
+            const KRange k = balanced_krange(p.kiters, p.ts_s, chunk);
+            kb = k.begin;
+            ke = k.end;
         } else {
             vt = u;
             chunk = -1;
@@ -340,8 +340,8 @@ __global__ __launch_bounds__(512, 2) void igemm_split3r_kernel(const IgemmParams
         }
     };
 
-    // K range of a tail tile: park the partial sums (sc1), take a ticket; the last arriver adds all ranges in range
-    // order (-> true: the caller runs the epilogue)
+    // K range of a tail tile: the hand-off of igemm_kernel.hpp (krange_park / krange_sum: protocol and memory ordering are
+    // stated there) with this kernel's barrier idiom and a two-ranges-in-flight sum (-> true: the caller runs the epilogue)
     auto handoff = [&](int vt, int chunk) __attribute__((always_inline)) -> bool {
         const int tl = vt - p.ts_whole;
         float* const slot0 = p.ts_partial + (long)tl * p.ts_s * (BM * BN);
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(512, 2) void igemm_split3r_kernel(const IgemmParams
             for (int i = 0; i < TM; ++i) {
                 f32x4 v0[TN], v1[TN];
 #pragma unroll
-                for (int j = 0; j < TN; ++j)     // sc1 loads: never a stale L1 / L2 copy
+                for (int j = 0; j < TN; ++j)
                     v0[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                                           rsQ0, tid * 16, (i * TN + j) * NTHR * 16, 16));
 #pragma unroll
@@ -456,15 +456,7 @@ __global__ __launch_bounds__(512, 2) void igemm_split3r_kernel(const IgemmParams
             if constexpr ((G) == 0) {                                                                                 \
                 if (late_half) decide();                                                                              \
             }                                                                                                         \
-            if (T_ == 2 || lo_terms)                                                                                  \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                          \
-                if constexpr (T_ == 0)                                                                                \
-                    acc[i_][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbl[j], fah[P][i_], acc[i_][j], 0, 0, 0);     \
-                else if constexpr (T_ == 1)                                                                           \
-                    acc[i_][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[P][j], fal[i_], acc[i_][j], 0, 0, 0);     \
-                else                                                                                                  \
-                    acc[i_][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[P][j], fah[P][i_], acc[i_][j], 0, 0, 0);  \
-            }                                                                                                         \
+            if (T_ == 2 || lo_terms) split_term_row<SplitF16, T_>(acc[i_], fah[P][i_], fal[i_], fbh[P], fbl);         \
             __builtin_amdgcn_sched_barrier(0);                                                                        \
             if constexpr ((G) == 0) {                                                                                 \
                 if (!late_half) decide();                                                                             \

@@ -339,14 +339,6 @@ __global__ __launch_bounds__(512, C == 16 ? 4 : 1) void wgrad_halo16_kernel(cons
             if (TERMS == 3) *reinterpret_cast<uint2*>(gl + GPL + off) = lo;
         }
     };
-    typedef short s16x4_ __attribute__((ext_vector_type(4)));
-    typedef short s16x8_ __attribute__((ext_vector_type(8)));
-    auto frag = [&](const char* base, int a0, int a1) -> b16x8 {
-        const s16x4_ v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(base + a0));
-        const s16x4_ v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(base + a1));
-        const s16x8_ v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        return __builtin_bit_cast(b16x8, v);
-    };
 
     f32x4 acc[9], accb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -364,17 +356,17 @@ __global__ __launch_bounds__(512, C == 16 ? 4 : 1) void wgrad_halo16_kernel(cons
 #pragma unroll
         for (int jj = 0; jj < TH / NJ; ++jj) {
             const int j = jj * NJ;                     // (+ jh: in the lane bases)
-            const b16x8 gh = frag(gl + j * TW * 64, gb[0], gb[1]);
+            const b16x8 gh = tr16_frag<b16x8>(gl + j * TW * 64 + gb[0], gl + j * TW * 64 + gb[1]);
             b16x8 glo;
-            if (TERMS == 3) glo = frag(gl + GPL + j * TW * 64, gb[0], gb[1]);
+            if (TERMS == 3) glo = tr16_frag<b16x8>(gl + GPL + j * TW * 64 + gb[0], gl + GPL + j * TW * 64 + gb[1]);
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int s_ = 0; s_ < 3; ++s_) {
                     const char* xrow = lds + (j + r) * XW * PITCH;
-                    const b16x8 xh = frag(xrow, xb[s_][0], xb[s_][1]);
+                    const b16x8 xh = tr16_frag<b16x8>(xrow + xb[s_][0], xrow + xb[s_][1]);
                     if (TERMS == 3) {
-                        const b16x8 xl = frag(xrow + XPL, xb[s_][0], xb[s_][1]);
+                        const b16x8 xl = tr16_frag<b16x8>(xrow + XPL + xb[s_][0], xrow + XPL + xb[s_][1]);
                         acc[r * 3 + s_] = SplitBF16::mfma(glo, xh, acc[r * 3 + s_]);
                         acc[r * 3 + s_] = SplitBF16::mfma(gh, xl, acc[r * 3 + s_]);
                     }

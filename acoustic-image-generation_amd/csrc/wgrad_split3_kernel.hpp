@@ -18,21 +18,14 @@
 
 namespace acimg {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
+// tr16_frag (common.hpp) on this file's tile image
 __device__ __forceinline__ b16x8 tr_frag(const char* tile, int row0, int colbyte, int lane) {
     // block rows row0..row0+3 and row0+4..row0+7 (row0 = 8g), 16 columns starting at byte `colbyte` of the row
     const int t = lane & 15, q = t >> 2, p = t & 3, g = lane >> 4;
     const int f = q | ((g & 1) << 2);
     const int c32 = colbyte >> 5;
     const int off = ((c32 ^ f) << 5) + p * 8;
-    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(tile + (row0 + q) * 256 + off));
-    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(tile + (row0 + 4 + q) * 256 + off));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(b16x8, v);
+    return tr16_frag<b16x8>(tile + (row0 + q) * 256 + off, tile + (row0 + 4 + q) * 256 + off);
 }
 
 // BN = 128 or 64 output columns per block; 128 dW rows per block; 32 pixels per K step

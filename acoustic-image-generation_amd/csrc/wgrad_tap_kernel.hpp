@@ -131,13 +131,6 @@ __global__ __launch_bounds__(512) void wgrad_tap_kernel(const WgradTapParams p) 
             }
         }
     };
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    auto xfrag = [&](const char* base, int a0, int a1) -> b16x8 {
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a0));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a1));
-        const s16x8 v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        return __builtin_bit_cast(b16x8, v);
-    };
 
     f32x4 acc[9][TNW], accb[TNW];
 #pragma unroll
@@ -183,8 +176,8 @@ __global__ __launch_bounds__(512) void wgrad_tap_kernel(const WgradTapParams p) 
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int s_ = 0; s_ < 3; ++s_) {
-                    const b16x8 xh = xfrag(xh_pl + r * rowb, xa[s_][0], xa[s_][1]);
-                    const b16x8 xl = xfrag(xl_pl + r * rowb, xa[s_][0], xa[s_][1]);
+                    const b16x8 xh = tr16_frag<b16x8>(xh_pl + r * rowb + xa[s_][0], xh_pl + r * rowb + xa[s_][1]);
+                    const b16x8 xl = tr16_frag<b16x8>(xl_pl + r * rowb + xa[s_][0], xl_pl + r * rowb + xa[s_][1]);
 #pragma unroll
                     for (int i = 0; i < TNW; ++i) {
                         acc[r * 3 + s_][i] = SplitBF16::mfma(gl[i], xh, acc[r * 3 + s_][i]);

@@ -5,7 +5,8 @@
     tools/codeobj_diff.py --parent PARENT.o [...] --new NEW1.o NEW2.o [...]      (one file split into several, or the reverse)
 
 With several objects on a side their symbols are taken together, and a kernel (a symbol with a kernel descriptor) that
-occurs in more than one object of a side is reported: it would exist twice on the device.
+occurs in more than one object of a side is reported: it would exist twice on the device.  An object without device code
+(a host-only source) is named and adds nothing, so all of csrc/Makefile's objects can be given.
 Unbundles the device code object of each file (llvm-objdump --offloading), disassembles it, cuts the listing at every
 `<symbol>:` line, drops the trailing `// address: encoding` column and the padding behind a symbol's last instruction, and compares the instruction streams per symbol;
 then compares each kernel's metadata from the code object's notes (register counts, segment sizes, kernarg size, maximum
@@ -40,8 +41,8 @@ def unbundle(obj, arch, work):
     shutil.copy(obj, local)
     run(os.path.join(LLVM, "llvm-objdump"), "--offloading", "obj.o", cwd=d)
     found = [f for f in glob.glob(os.path.join(d, "*")) if f != local and arch in os.path.basename(f)]
-    assert len(found) == 1, "expected one %s code object in %s, found %s" % (arch, obj, found)
-    return found[0]
+    assert len(found) <= 1, "expected one %s code object in %s, found %s" % (arch, obj, found)
+    return found[0] if found else None      # a host-only source (no kernel) has none
 
 
 def streams(elf):
@@ -87,6 +88,9 @@ def side(name, objs, arch, work):
     sa, order, ma, bad = {}, [], {}, 0
     for i, obj in enumerate(objs):
         elf = unbundle(obj, arch, os.path.join(work, name, str(i)))
+        if elf is None:
+            print("  no %s device code in %s: %s" % (arch, name, os.path.basename(obj)))
+            continue
         s, o = streams(elf)
         m = metadata(elf)
         for k in sorted(set(m) & set(ma)):
