@@ -179,6 +179,8 @@ PROTOTYPES = {
     "acimg_jpeg_scan_capacity": (_SZ, [_I, _I, _I]),
     "acimg_jpeg_scan_workspace": (_SZ, [_I, _I, _I, _I]),
     "acimg_jpeg_scan": (_I, [_P, _I, _I, _I, _I, _P, _SZ, _P, _P, _SZ, _P]),
+    "acimg_resize_cubic_tables": (_I, [_I, _I, _I, _I, _P, _P]),
+    "acimg_resize_cubic_u8": (_I, [_P, _SZ, _SZ, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

@@ -72,10 +72,21 @@ class TFRecordDataLoader(object):
     as [B*12, ...] with each clip's frames consecutive and in record order, the two label tensors as ONE row per clip
     ([B, num_actions], [B, num_locations]); `num_samples` / `total_batches` count clips.
     raw_audio=True: every batch carries a seventh tensor, the records' int32 [n,1024] audio samples as stored, batched
-    like the other frame tensors (the sound track of `python -m acimg.show video --avi 1`)."""
+    like the other frame tensors (the sound track of `python -m acimg.show video --avi 1`).
+    modalities: None = all three, every record must carry `audio/image`.  (1, 2) = audio data + video, the reference's
+    `modalities=[1, 2]` (showvideo.py:72-75, outdoor_data_mfcc.py:35-37,316-317): records with or without `audio/image`
+    - `python -m acimg.convert` writes none - are read, and the acoustic slot holds zeros [n,36,48,12] as :316 builds
+    them; the other tensors are unchanged.  Other subsets are refused.  (Given by keyword, like `raw_audio`, which stays
+    the last parameter.)"""
 
     def __init__(self, files, batch_size, num_actions=10, num_locations=61, device="cuda:0", frames_per_record=12,
-                 compression_verify=True, embedding=1, raw_audio=False):
+                 compression_verify=True, embedding=1, modalities=None, raw_audio=False):
+        if modalities is not None:
+            if sorted(modalities) != [1, 2]:
+                raise ValueError("modalities is None (acoustic image, audio, video) or (1, 2) (audio, video), got %r"
+                                 % (modalities,))
+            modalities = (1, 2)
+        self.modalities = modalities
         from .frontend import FrontEnd
         if isinstance(files, str):
             with open(files) as f:
@@ -113,6 +124,8 @@ class TFRecordDataLoader(object):
         d = tfio.decode_sequence_example_native(rec)
         ai, sa, vi = d["audio_images"], d["audio_samples"], d["video_images"]
         n = vi.shape[0]
+        if self.modalities is not None:      # audio + video: the acoustic image, if the record has one, is not read
+            ai = np.zeros((n, 36, 48, 12), np.float32)
         if not (ai.shape[0] == n and sa.shape[0] == n and sa.shape[1] == 1024):
             raise ValueError("record with %d video / %d acoustic / %d audio steps" % (n, ai.shape[0], sa.shape[0]))
         # audio: raw frames -> device; low-passed copy (`filtered_wav`, :562) and the two MFCC vectors, each min-max
@@ -123,8 +136,9 @@ class TFRecordDataLoader(object):
         mfcc_low = self.fe._build_spectrograms_function(low, normalize=True)
         # acoustic images: per-frame min-max (`_normalize_acoustic_images_rescaled`, :672-679)
         a = ai.astype(np.float32)
-        a = a - a.min(axis=(1, 2, 3), keepdims=True)
-        a = a / a.max(axis=(1, 2, 3), keepdims=True)
+        if self.modalities is None:
+            a = a - a.min(axis=(1, 2, 3), keepdims=True)
+            a = a / a.max(axis=(1, 2, 3), keepdims=True)
         # video: float, channel order reversed, 1/255 (`_normalize_images_rescaled`, :649-655)
         v = vi[..., ::-1].astype(np.float32) * np.float32(1.0 / 255.0)
         act = np.zeros((n, self.num_actions), np.float32)

@@ -171,7 +171,9 @@ def run(args, trainer=None, keep_energy=False, log=print):
     if args.command == "boxes":
         data = BoxRecordLoader(args.train_file, args.batch_size)
     else:
-        data = TFRecordDataLoader(args.train_file, args.batch_size, device=device, raw_audio=avi)
+        # the video command reads audio + video alone (showvideo.py:72-75), so it plays converted recordings too
+        data = TFRecordDataLoader(args.train_file, args.batch_size, device=device, raw_audio=avi,
+                                  modalities=(1, 2) if args.command == "video" else None)
     rend = OverlayRenderer(device)
     if avi:      # the whole clip is kept (the sound's peak is known only at its end): a few MB for ten seconds
         from .jpeg import JpegEncoder

@@ -898,6 +898,38 @@ size_t acimg_jpeg_scan_workspace(int n, int H, int W, int restart_mcus);
 int acimg_jpeg_scan(const int16_t* coef, int n, int H, int W, int restart_mcus, uint8_t* scan, size_t frame_stride,
                     int32_t* scan_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* cv2.resize(frame, (new_w, new_h), interpolation=cv2.INTER_CUBIC) of 8-bit 3-channel frames with a crop window fused
+ * in.  Replaces: `_aspect_preserving_resize` + `_central_crop` of convert_data.py:53-67,120-138 (the frames of
+ * `python -m acimg.convert`).  tests/convert_ref.py restates it bit for bit; the definition - OpenCV's scalar fixed-point
+ * path - is DESIGN section 8.  (Added without raising ACIMG_VERSION: nothing existing changed, and the number is pinned
+ * by the host tests.)
+ *
+ * acimg_resize_cubic_tables (host only, pure arithmetic): for the output coordinates d = first .. first + count - 1 of
+ *   a resize of n_in to n_out samples, idx int32 [count][4] and coef int16 [count][4]:
+ *     scale = 1.0 / ((double)n_out / n_in);  f = (float)((d + 0.5) * scale - 0.5);  s = floor(f);  f -= s  (no clamp of
+ *     s or f at the border);  float32, A = -0.75f:  c0 = ((A (f+1) - 5A)(f+1) + 8A)(f+1) - 4A,
+ *     c1 = ((A+2) f - (A+3)) f f + 1,  c2 = ((A+2)(1-f) - (A+3))(1-f)(1-f) + 1,  c3 = 1 - c0 - c1 - c2;
+ *     coef[k] = saturate_int16(rint(c[k] * 2048.0f)), half to even, the sum NOT fixed up (2047 and 2049 occur);
+ *     idx[k] = clamp(s - 1 + k, 0, n_in - 1).
+ *   1 <= n_in, n_out <= 65535, 0 <= first, 1 <= count <= n_out - first, no null pointer: otherwise ACIMG_EINVAL.
+ * acimg_resize_cubic_u8: n frames of H x W pixels of 3 bytes; frame i's top row starts at src + i * frame_stride +
+ *   pixel_offset and row y lies y * row_stride bytes from it.  row_stride is SIGNED: negative for a bottom-up BMP, whose
+ *   pixel_offset then points at the last stored row.  Nothing about src need be aligned (a BMP's pixels start at byte
+ *   54 and its rows are padded to 4 bytes): the kernel loads bytes.  idx_y / coef_y [OH][4] and idx_x / coef_x [OW][4]
+ *   ON THE DEVICE, the layout above, indices in PIXELS; they cover the crop window only.  An index outside the frame is
+ *   clamped to it as it is read.  out: uint8 [n][OH][OW][3] dense, channel order as in src.
+ *     horizontal pass first, per channel, int32, no shift:  h = sum_k src[row][idx_x[k]] * coef_x[k];
+ *     vertical pass:  v = sum_k h[idx_y[k]] * coef_y[k];  out = clamp((v + (1 << 21)) >> 22, 0, 255).
+ *   ONE launch per 65535 frames, one workgroup per (8 output rows, <= 320 output columns, frame); the horizontal pass
+ *   of the source rows a band needs is held in LDS.  No workspace, no atomics, integer arithmetic: bit-identical from
+ *   run to run and equal to the restatement on any machine.
+ *   A null pointer, a size outside 1..65535 (n: any positive), |row_stride| < 3 W, or a frame whose rows do not lie
+ *   inside [0, frame_stride) of its start: ACIMG_EINVAL; every refusal precedes the launch. */
+int acimg_resize_cubic_tables(int n_in, int n_out, int first, int count, int32_t* idx, int16_t* coef);
+int acimg_resize_cubic_u8(const uint8_t* src, size_t frame_stride, size_t pixel_offset, long row_stride, int n, int H, int W,
+                          const int32_t* idx_y, const int16_t* coef_y, const int32_t* idx_x, const int16_t* coef_x, int OH,
+                          int OW, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
