@@ -173,6 +173,9 @@ PROTOTYPES = {
     "acimg_tsne_update": (_I, [_P, _I, _D, _D, _D, _P, _P, _P, _P, _P]),
     "acimg_batch_gather": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "acimg_batch_gather_workspace": (_SZ, [_I, _I]),
+    "acimg_batch_gather_pairs": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                      _P]),
+    "acimg_batch_gather_pairs_workspace": (_SZ, [_I, _I]),
     "acimg_jpeg_quant_tables": (_I, [_I, _P]),
     "acimg_jpeg_coef_bytes": (_SZ, [_I, _I, _I]),
     "acimg_jpeg_blocks": (_I, [_P, _I, _I, _I, _P, _P, _P]),

@@ -15,6 +15,10 @@ audio [n,12])), `.num_samples`, `.total_batches` (:117,214,973-976).
   buffer_size=FLAGS.buffer_size`, main.py:112-116) with `reshuffle_each_iteration`.  Decoded frames stay on the device
   in their raw form (video as bytes); a batch is assembled by `acimg_batch_gather`, which applies the per-frame maps
   while it gathers, and is handed out as device tensors.
+* `correspondence=1` on either of the two (the published training recipe, `--correspondence 1`): the pair map of
+  :108-113, 888-928 - every frame a second time with the MFCC of the low-passed sound, tiled, as its acoustic image -
+  and, for a shuffling `DeviceDataLoader`, the second shuffle stage; the sixth tensor is then the one-hot
+  correspondence label [n,2].
 * `BoxRecordLoader`: the box-annotated Flickr-SoundNet records of dataloader/frames.py (`ActionsDataLoader(...,
   embedding=1, nr_frames=1, sample_length=1, shuffle=False)`, written by convert_data2.py:200-307): 8-tuples (acoustic
   zeros [n,36,48,12], mfcc [n,12], video [n,224,298,3], xmin, xmax, ymin, ymax, typescene [n,3] int32) that
@@ -77,10 +81,17 @@ class TFRecordDataLoader(object):
     `modalities=[1, 2]` (showvideo.py:72-75, outdoor_data_mfcc.py:35-37,316-317): records with or without `audio/image`
     - `python -m acimg.convert` writes none - are read, and the acoustic slot holds zeros [n,36,48,12] as :316 builds
     them; the other tensors are unchanged.  Other subsets are refused.  (Given by keyword, like `raw_audio`, which stays
-    the last parameter.)"""
+    the last parameter.)
+    correspondence=1 (given by keyword as well): the pair map of :108-109, 888-928 on every batch, in the form of a
+    loader that does not shuffle (this one never does): a batch of n frames becomes 2n rows, the n real rows followed by the n silent
+    rows of the same frames - acoustic image = the low-passed MFCC row tiled over the pixels (not normalised), mfcc =
+    that row, video and labels (and raw audio) the frame's - and the sixth tensor is the one-hot correspondence label
+    [2n, 2], [0, 1] real / [1, 0] silent.  `num_samples` / `total_batches` keep the reference's formulas (:973-976),
+    which know nothing of the doubling; `num_rows` / `num_batches` are the counts of a pass.  Refused with
+    embedding=0."""
 
     def __init__(self, files, batch_size, num_actions=10, num_locations=61, device="cuda:0", frames_per_record=12,
-                 compression_verify=True, embedding=1, modalities=None, raw_audio=False):
+                 compression_verify=True, embedding=1, modalities=None, correspondence=0, raw_audio=False):
         if modalities is not None:
             if sorted(modalities) != [1, 2]:
                 raise ValueError("modalities is None (acoustic image, audio, video) or (1, 2) (audio, video), got %r"
@@ -97,6 +108,7 @@ class TFRecordDataLoader(object):
         self.frames = int(frames_per_record)
         self.verify = bool(compression_verify)
         self.embedding = _embedding(embedding)
+        self.correspondence = _correspondence(correspondence, self.embedding)
         self.tensors = 7 if raw_audio else 6
         self.device = torch.device(device)
         self.fe = FrontEnd(self.device)
@@ -117,6 +129,16 @@ class TFRecordDataLoader(object):
     @property
     def total_batches(self):
         return -(-self.num_samples // self.batch_size)
+
+    @property
+    def num_rows(self):
+        """rows (embedding=0: clips) of one pass: `num_samples`, twice that with correspondence=1"""
+        return self.num_samples * (2 if self.correspondence else 1)
+
+    @property
+    def num_batches(self):
+        """batches of one pass (the pair map doubles the rows of a batch, not the batches)"""
+        return self.total_batches
 
     # ---- one record -> 12 frames (:263-343, :434-476, :558-575, :634-703) ---------------------------------------------
     def _record(self, rec):
@@ -172,12 +194,25 @@ class TFRecordDataLoader(object):
         if pend:
             yield self._clip_batch(pend)
 
+    def _pairs(self, b):
+        """`_map_func_correspondence` (:888-928) on one batch"""
+        ac, mfcc, video, act, loc, low = b[:6]
+        n = ac.shape[0]
+        silent = low.reshape((n,) + (1,) * (ac.dim() - 2) + (12,)).expand_as(ac)
+        label = torch.zeros(2 * n, 2)
+        label[:n, 1] = 1.0
+        label[n:, 0] = 1.0
+        out = (torch.cat([ac, silent]), torch.cat([mfcc, low]), torch.cat([video, video]), torch.cat([act, act]),
+               torch.cat([loc, loc]), label)
+        return out + tuple(torch.cat([t, t]) for t in b[6:])
+
     def __iter__(self):
+        batches = self._iter_clips() if not self.embedding else self._iter_frames()
+        for b in batches:
+            yield self._pairs(b) if self.correspondence else b
+
+    def _iter_frames(self):
         from . import tfio
-        if not self.embedding:
-            for b in self._iter_clips():
-                yield b
-            return
         pend, have = [], 0
         for path in self.files:
             for rec in tfio.read_tfrecord_native(path, verify=self.verify):
@@ -206,9 +241,25 @@ def _embedding(embedding):
     return int(embedding)
 
 
+def _correspondence(correspondence, embedding):
+    """the reference's `correspondence` argument: 1 adds the pair map of :108-113 (frames only)"""
+    if correspondence not in (0, 1, False, True):
+        raise ValueError("correspondence is 0 or 1, got %r" % (correspondence,))
+    if correspondence and not embedding:
+        raise ValueError("correspondence=1 needs embedding=1: the pair map's reshape(-1, 1, 12) of a clip batch has no defined "
+                         "meaning in main.py's dispatch")
+    return int(correspondence)
+
+
 def epoch_rng(seed, epoch):
     """the generator of one pass over the data: `reshuffle_each_iteration` is a new `epoch`"""
     return np.random.Generator(np.random.PCG64([int(seed), int(epoch)]))
+
+
+def pair_rng(seed, epoch):
+    """the generator of a pass's SECOND shuffle stage (the one behind the pair map): one of its own, so that stage 1 draws
+    from `epoch_rng(seed, epoch)` exactly what it draws in a loader without the pair map"""
+    return np.random.Generator(np.random.PCG64([int(seed), int(epoch), 1]))
 
 
 def shuffle_stream(inputs, buffer_size, rng):
@@ -241,6 +292,39 @@ def shuffle_order(n_frames, buffer_size, rng):
     return list(shuffle_stream(range(int(n_frames)), int(buffer_size), rng))
 
 
+def pair_batches(inputs, batch_size, buffer_size, rng1):
+    """stage 1 and the pair map of :104-109 over an iterator of non-negative ints: shuffle buffer, batches of
+    `batch_size` (the last may be short), and every batch [x0 .. xn-1] expanded to the ROW CODES [x0 .. xn-1, ~x0 ..
+    ~xn-1]: x is the real row of x, ~x (negative) its silent row.  A batch is expanded once stage 1 has completed it."""
+    batch = []
+    for x in shuffle_stream(inputs, buffer_size, rng1):
+        batch.append(x)
+        if len(batch) == batch_size:
+            yield batch + [~v for v in batch]
+            batch = []
+    if batch:
+        yield batch + [~v for v in batch]
+
+
+def pair_stream(inputs, batch_size, buffer_size, rng1, rng2):
+    """stage 2 (:110-112): the rows of the pair batches, in order, through a second shuffle buffer of `buffer_size` rows
+    drawing from `rng2`"""
+    return shuffle_stream((code for b in pair_batches(inputs, batch_size, buffer_size, rng1) for code in b), buffer_size,
+                          rng2)
+
+
+def pair_order(n_frames, batch_size, buffer_size, rng1, rng2=None):
+    """row codes, in frame numbering, of one pass over `n_frames` frames with the pair map: the pair batches one after
+    the other (rng2 None: a loader that does not shuffle; cut them at the batches of `shuffle_order` to get its batches),
+    or those rows through stage 2 (a shuffling loader, which re-batches them to `batch_size` rows)"""
+    if batch_size < 1 or buffer_size < 1:
+        raise ValueError("batch_size and buffer_size must be at least 1, got %r, %r" % (batch_size, buffer_size))
+    frames = range(int(n_frames))
+    if rng2 is None:
+        return [code for b in pair_batches(frames, int(batch_size), int(buffer_size), rng1) for code in b]
+    return list(pair_stream(frames, int(batch_size), int(buffer_size), rng1, rng2))
+
+
 def epoch_files(files, shuffle, shard, rng):
     """the record files of one pass: permuted with the pass's generator when shuffling (`_shuffle_and_repeat_lists`,
     :218-225), then entries i % world == rank of that list for shard = (rank, world)"""
@@ -264,13 +348,28 @@ def pool_pages(buffer_size, prefetch):
     return int(buffer_size) + int(prefetch) + 2
 
 
+def pair_pages(buffer_size, batch_size, prefetch):
+    """pages that always suffice with the pair map (`BatchFeeder(..., pairs=True)`), where a frame pins its page until
+    BOTH of its rows are emitted.  When a record is admitted, the frames with a row to come are: at most `buffer_size`
+    in the stage-1 buffer (the one just drawn included), at most `batch_size - 1` in the pair batch that stage 1 is
+    completing (stage 1 is only asked for more once stage 2 has taken every row of the batch before), and at most
+    `buffer_size` with a row in the stage-2 buffer (the row just drawn included): 2 * buffer_size + batch_size - 1
+    frames, one page each at the worst, and one page to upload into.  That is 2 * buffer_size + batch_size, reached by
+    records of one frame; `prefetch` more let records be uploaded ahead at that moment too (uploading ahead only ever
+    takes a free page, so it adds nothing to the need).  Without stage 2 (a loader that does not shuffle) the third term
+    is absent and the bound, kept as it is, is `buffer_size` pages loose."""
+    return 2 * int(buffer_size) + int(batch_size) + int(prefetch)
+
+
 class FramePages(object):
     """Bookkeeping of the frame pool, no device in sight: pages of `frames` slots; a page is taken for one record, counts
     that record's un-emitted frames, and comes back once its last frame's gather has been enqueued (`release`).  The pool
-    starts with `size` pages and may grow to `limit`."""
+    starts with `size` pages and may grow to `limit`.  uses: how often every frame is emitted before it is done with (2 with
+    the pair map: its real and its silent row)."""
 
-    def __init__(self, size, limit, frames):
+    def __init__(self, size, limit, frames, uses=1):
         self.frames, self.limit, self.size = int(frames), int(limit), min(int(size), int(limit))
+        self.uses = int(uses)
         self.live = [0] * self.size
         self.free = list(range(self.size - 1, -1, -1))
         self.pending = []
@@ -285,7 +384,7 @@ class FramePages(object):
 
     def fill(self, page, n):
         assert 0 < n <= self.frames and self.live[page] == 0
-        self.live[page] = n
+        self.live[page] = n * self.uses
 
     def emit(self, slot):
         page = slot // self.frames
@@ -319,13 +418,21 @@ class BatchFeeder(object):
     A batch is gathered in one call unless a page is wanted while the only candidates are pages emptied by THIS batch:
     then the rows chosen so far are gathered first, which frees them.
     units="records" (the loaders' embedding=0): the shuffle buffer holds whole records and `batch_size` counts them; a
-    record's slots enter the batch together, in record order."""
+    record's slots enter the batch together, in record order.
+    pairs=True (the loaders' correspondence=1; `pages` must count two uses per frame): what `gather` receives are ROW
+    CODES, slot or ~slot (`pair_batches`).  rng2 None: a batch is one pair batch, up to 2 * batch_size rows; its rows are
+    chosen only once stage 1 has completed it, so its size is known at its first row, no record is admitted between its
+    rows, and it is gathered in one call at offset 0.  With rng2 the rows pass stage 2 (`pair_stream`) and leave in
+    batches of `batch_size` rows.  `pair_pages` is the page bound."""
 
     def __init__(self, records, pages, batch_size, buffer_size, prefetch, rng, upload, gather, grow=None, ready=None,
-                 units="frames"):
+                 units="frames", pairs=False, rng2=None):
         if units not in ("frames", "records"):
             raise ValueError("units is 'frames' or 'records', got %r" % (units,))
         self.by_record = units == "records"
+        self.pairs, self.rng2 = bool(pairs), rng2
+        if self.pairs and (self.by_record or pages.uses != 2):
+            raise ValueError("the pair map wants frames as the units and pages that count two uses per frame")
         self.records, self.pages = iter(records), pages
         self.batch_size, self.buffer_size, self.prefetch, self.rng = int(batch_size), int(buffer_size), int(prefetch), rng
         self.upload, self.gather, self.grow_cb, self.ready = upload, gather, grow, ready or (lambda: True)
@@ -347,9 +454,11 @@ class BatchFeeder(object):
             if self.grow_cb is not None:
                 self.grow_cb(size)
             page = self.pages.acquire()
-        assert page is not None, "frame pool exhausted: %d pages (buffer_size + prefetch + 2) must suffice" % self.pages.limit
-        self.pages.fill(page, self.upload(page, rec))
-        self.ahead.append((page, self.pages.live[page]))
+        assert page is not None, "frame pool exhausted: %d pages (%s) must suffice" % (
+            self.pages.limit, "2 * buffer_size + batch_size + prefetch" if self.pairs else "buffer_size + prefetch + 2")
+        n = self.upload(page, rec)
+        self.pages.fill(page, n)
+        self.ahead.append((page, n))
         return True
 
     def _slots(self):
@@ -373,19 +482,31 @@ class BatchFeeder(object):
                and (self.pages.free or self.pages.size < self.pages.limit)):
             self._admit()
 
+    def _rows(self):
+        """(rows, last): the rows that enter the batch together, and whether they complete it"""
+        if self.pairs and self.rng2 is None:
+            for b in pair_batches(self._slots(), self.batch_size, self.buffer_size, self.rng):
+                for k, code in enumerate(b):
+                    yield (code,), k == len(b) - 1
+            return
+        if self.pairs:
+            stream = pair_stream(self._slots(), self.batch_size, self.buffer_size, self.rng, self.rng2)
+        else:
+            stream = shuffle_stream(self._slots(), self.buffer_size, self.rng)
+        for k, unit in enumerate(stream):
+            yield (unit if self.by_record else (unit,)), (k + 1) % self.batch_size == 0
+
     def __iter__(self):
         """yields the size of each batch once its gather is enqueued"""
-        units = 0
-        for unit in shuffle_stream(self._slots(), self.buffer_size, self.rng):
-            for slot in (unit if self.by_record else (unit,)):
-                self.batch.append(slot)
-                self.pages.emit(slot)
-            units += 1
-            if units == self.batch_size:
+        for rows, last in self._rows():
+            for row in rows:
+                self.batch.append(row)
+                self.pages.emit(~row if row < 0 else row)
+            if last:
                 self._flush()
                 self._top_up()
                 yield len(self.batch)
-                self.batch, self.flushed, units = [], 0, 0
+                self.batch, self.flushed = [], 0
         if self.batch:
             self._flush()
             yield len(self.batch)
@@ -493,6 +614,24 @@ class DeviceDataLoader(object):
       order; the label tensors are the strided view of the gathered rows that keeps one row per clip ([B, num_actions],
       [B, num_locations]).  `num_samples` / `total_batches` count clips; every record must hold `frames_per_record`
       frames.  `pool_pages` states why the page bound is the same with records as the units.
+    * correspondence=1 (`--correspondence 1`, the published recipe; :108-113, 888-928; embedding=1 only): stage 1 is all of
+      the above, unchanged.  A stage-1 batch of n frames becomes a pair batch of 2n rows: the n real rows - today's
+      tensors - then the n silent rows of the same frames in the same order: acoustic image = the frame's low-passed
+      MFCC row tiled over the pixels (not normalised), mfcc = that row, video and labels the frame's.  The sixth tensor
+      is no longer `mfcc_low` but the one-hot correspondence label [rows, 2], [0, 1] real / [1, 0] silent.
+      STAGE 2 RUNS ONLY FOR A SHUFFLING LOADER: the reference un-batches, shuffles again and re-batches under `mode ==
+      'training'` (:110), and `acimg.main` passes shuffle=True exactly for that mode.  Then the rows of the pair batches,
+      in order, pass a second shuffle buffer of `buffer_size` rows that draws from `pair_rng(seed, epoch)` - a generator
+      of its own, so stage 1 emits the order the plain loader emits under the same seed - and leave in batches of
+      `batch_size` rows: 2 * num_samples rows in ceil(2 * num_samples / batch_size) batches.  As with `shuffle_stream`,
+      the procedure is tf.data's, the random stream is not.  A loader that does not shuffle yields the pair batches
+      themselves: ceil(num_samples / batch_size) batches of up to 2 * batch_size rows, for which the output ring is
+      sized.  The silent half of such a batch starts at the batch's final size: the rows of a pair batch are chosen only
+      once stage 1 has completed it (`BatchFeeder`), so that size is known at the first row and the batch is one gather.
+      A frame stays resident until both of its rows are gathered (`FramePages(uses=2)`); `pair_pages` is the page bound
+      (asserted).  A batch is one `acimg_batch_gather_pairs` over row codes, still one int32 list uploaded per gather.
+      `num_samples` / `total_batches` keep the reference's formulas (:973-976), which know nothing of the doubling;
+      `num_rows` / `num_batches` are the true counts of a pass.
     `times` accumulates the host seconds of the stages (inflate, index, decode in the workers; upload, wait on the
     consuming thread)."""
 
@@ -501,7 +640,7 @@ class DeviceDataLoader(object):
 
     def __init__(self, files, batch_size, shuffle=False, buffer_size=None, seed=0, workers=4, prefetch=2, ring=4,
                  shard=None, num_actions=10, num_locations=61, device="cuda:0", compression_verify=True,
-                 frames_per_record=12, embedding=1):
+                 frames_per_record=12, embedding=1, correspondence=0):
         from . import ops
         from .flags import FLAGS
         from .frontend import FrontEnd
@@ -521,7 +660,10 @@ class DeviceDataLoader(object):
         self.num_actions, self.num_locations = int(num_actions), int(num_locations)
         self.frames = int(frames_per_record)
         self.embedding = _embedding(embedding)
-        self._rows = self.batch_size * (1 if self.embedding else self.frames)      # frame rows of a full batch
+        self.correspondence = _correspondence(correspondence, self.embedding)
+        frames = self.batch_size * (1 if self.embedding else self.frames)      # frames behind a full batch
+        # rows of a full batch: its frames, or a whole pair batch where stage 2 does not re-batch
+        self._rows = frames * (2 if self.correspondence and not self.shuffle else 1)
         self.verify = bool(compression_verify)
         self.device = torch.device(device)
         self.fe = FrontEnd(self.device)
@@ -530,7 +672,7 @@ class DeviceDataLoader(object):
         self.data = self
         self.times = dict(inflate=0.0, index=0.0, decode=0.0, upload=0.0, wait=0.0)
         # decode window: enough records in the workers' hands to cover a batch while the consumer is away
-        self._window = max(self.workers + self.prefetch, -(-self._rows // self.frames) + self.workers)
+        self._window = max(self.workers + self.prefetch, -(-frames // self.frames) + self.workers)
         self._num_samples = None
         self._epoch = 0
         self._pass = 0            # the pass whose iterator may touch the pool
@@ -558,6 +700,18 @@ class DeviceDataLoader(object):
     @property
     def total_batches(self):
         return -(-self.num_samples // self.batch_size)
+
+    @property
+    def num_rows(self):
+        """rows (embedding=0: clips) of one pass: `num_samples`, twice that with correspondence=1"""
+        return self.num_samples * (2 if self.correspondence else 1)
+
+    @property
+    def num_batches(self):
+        """batches of one pass: stage 2 re-batches the doubled rows; without it the pair map doubles the rows of a batch"""
+        if self.correspondence and self.shuffle:
+            return -(-self.num_rows // self.batch_size)
+        return self.total_batches
 
     def _executor(self):
         if self._exec is None:
@@ -591,7 +745,8 @@ class DeviceDataLoader(object):
         with torch.cuda.stream(self.stream):     # every device buffer of the loader belongs to its stream
             self._outs = [(torch.empty(bs, ah, aw, ad, device=dev), torch.empty(bs, 12, device=dev),
                            torch.empty(bs, vh, vw, 3, device=dev), torch.empty(bs, self.num_actions, device=dev),
-                           torch.empty(bs, self.num_locations, device=dev), torch.empty(bs, 12, device=dev))
+                           torch.empty(bs, self.num_locations, device=dev),
+                           torch.empty(bs, 2 if self.correspondence else 12, device=dev))
                           for _ in range(self.ring)]
             self._slots_dev = torch.empty(self._slot_rows, bs, dtype=torch.int32, device=dev)
         self._staging = collections.deque(_Staging(self.frames, self.pixels * 3, self.elems)
@@ -726,9 +881,10 @@ class DeviceDataLoader(object):
             if wait is not None:
                 self.stream.wait_event(wait)
             ac, mf, vid, act, loc, mfl = (t[offset:offset + n] for t in out)
-            ops.batch_gather(self.plan, pool["video"], self.vstride, pool["acoustic"], pool["mfcc"], pool["mfcc_low"],
-                             pool["labels"], self._slots_dev[row], n, self.pixels, self.elems, vid, ac, mf, mfl, act,
-                             self.num_actions, loc, self.num_locations)
+            gather = ops.batch_gather_pairs if self.correspondence else ops.batch_gather      # mfl: then the pair rows
+            gather(self.plan, pool["video"], self.vstride, pool["acoustic"], pool["mfcc"], pool["mfcc_low"], pool["labels"],
+                   self._slots_dev[row], n, self.pixels, self.elems, vid, ac, mf, mfl, act, self.num_actions, loc,
+                   self.num_locations)
 
     def __iter__(self):
         epoch, self._epoch = self._epoch, self._epoch + 1
@@ -736,9 +892,10 @@ class DeviceDataLoader(object):
         me = self._pass
         rng = epoch_rng(self.seed, epoch)
         files = epoch_files(self.files, self.shuffle, self.shard, rng)
-        return self._iterate(files, rng, me)
+        rng2 = pair_rng(self.seed, epoch) if self.correspondence and self.shuffle else None
+        return self._iterate(files, rng, me, rng2)
 
-    def _iterate(self, files, rng, me):
+    def _iterate(self, files, rng, me, rng2=None):
         def alive():
             if self._pass != me:
                 raise RuntimeError("DeviceDataLoader: this iterator was ended by a later pass over the same loader")
@@ -748,9 +905,11 @@ class DeviceDataLoader(object):
         first = next(records, None)          # sizes the buffers on the first pass
         if first is None:
             return
-        limit = pool_pages(self.buffer_size, self.prefetch)
+        pairs = bool(self.correspondence)
+        limit = (pair_pages(self.buffer_size, self.batch_size, self.prefetch) if pairs
+                 else pool_pages(self.buffer_size, self.prefetch))
         # (a pool grown by an earlier pass is kept)
-        pages = FramePages(min(limit, max(self.FIRST_PAGES, self._pool_pages)), limit, self.frames)
+        pages = FramePages(min(limit, max(self.FIRST_PAGES, self._pool_pages)), limit, self.frames, uses=2 if pairs else 1)
         if self._pool_pages < pages.size:
             self._alloc_pool(pages.size)
 
@@ -766,7 +925,8 @@ class DeviceDataLoader(object):
             state["wait"] = None
 
         feeder = BatchFeeder(chain(), pages, self.batch_size, self.buffer_size, self.prefetch, rng, self._upload, gather,
-                             grow=self._alloc_pool, ready=self._ready, units="frames" if self.embedding else "records")
+                             grow=self._alloc_pool, ready=self._ready, units="frames" if self.embedding else "records",
+                             pairs=pairs, rng2=rng2)
         try:
             for n in feeder:
                 done = torch.cuda.Event()

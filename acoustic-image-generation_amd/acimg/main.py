@@ -9,6 +9,11 @@ trainer/mfcctrainer.py), writes `configuration.txt` (main.py:247-276, the embedd
 the reference logs: scalars and the eight image summaries on every displayed step, `valid_loss` per epoch
 (`--histograms 1`: also one histogram per trainable variable).  `--mode test` scores `--test_file`.
 
+`--correspondence 1` (the published recipe, scripts/scriptacresn.bash) reaches the three loaders: every frame a second
+time with the MFCC of its low-passed sound, tiled, as the target (dataloader/outdoor_data_mfcc.py:108-113); the
+training loader, the one that shuffles, also runs the second shuffle stage, validation and test see batches of
+2 * batch_size rows.
+
 `--embedding 0 --model DualCamNet` is the classification experiment: `classify.run_main`.  Every other branch of
 main.py's dispatch names a trainer whose step this project has as a class without main.py's loop around it, or does not
 have: they are refused with that name.  Extras beside main.py's flags: `--device`, `--seed` (the eps draws),
@@ -46,6 +51,9 @@ def dispatch(flags):
         raise ValueError("--embedding 0 --model UNet is the single-modality VAE: its step is acimg.trainer_vae.TrainerVAE, a "
                          "class without main.py's loop; there is no command line for it")
     if f.model == "DualCamNet":
+        if f.correspondence:
+            raise ValueError("--correspondence 1 with --embedding 0: the pair map tiles reshape(-1, 1, 12) of a clip batch, "
+                             "which has no defined meaning for the classification experiment's clips")
         return "classify"
     raise ValueError("Unknown model type %r" % (f.model,))
 
@@ -126,7 +134,8 @@ def run_main(argv, log=print, hooks=None):
         if files is None:
             return None
         return DeviceDataLoader(files, FLAGS.batch_size, shuffle=shuffle, buffer_size=FLAGS.buffer_size if shuffle else None,
-                                embedding=FLAGS.embedding, num_actions=NUM_CLASSES, device=device)
+                                embedding=FLAGS.embedding, num_actions=NUM_CLASSES, device=device,
+                                correspondence=FLAGS.correspondence)
 
     log('{}: {} - Building model'.format(datetime.now(), FLAGS.exp_name))
     log('{}: {} - Building trainer'.format(datetime.now(), FLAGS.exp_name))

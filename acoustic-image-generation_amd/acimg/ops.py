@@ -940,6 +940,17 @@ def batch_gather(plan, pool_video, video_stride, pool_acoustic, pool_mfcc, pool_
              mfcc_low, action, location, _WsPtr(plan.ws), _WsBytes(plan.ws))
 
 
+def batch_gather_pairs(plan, pool_video, video_stride, pool_acoustic, pool_mfcc, pool_mfcc_low, pool_labels, rows, N, pixels,
+                       elems, video, acoustic, mfcc, pair, action, num_actions, location, num_locations):
+    """`batch_gather` over row codes rows[0..N) (int32 on the device): code >= 0 is the real row of slot code, code < 0 the
+    silent row of slot ~code (the low-passed MFCC row as MFCC and, tiled, as the acoustic image); pair [N,2] receives the
+    one-hot correspondence label, [0, 1] real / [1, 0] silent"""
+    plan.ws.require(_L().acimg_batch_gather_pairs_workspace(int(N), int(elems)))
+    plan.add("batch_gather_pairs", _L().acimg_batch_gather_pairs, pool_video, int(video_stride), pool_acoustic, pool_mfcc,
+             pool_mfcc_low, pool_labels, rows, int(N), int(pixels), int(elems), int(num_actions), int(num_locations), video,
+             acoustic, mfcc, pair, action, location, _WsPtr(plan.ws), _WsBytes(plan.ws))
+
+
 def adam_lr_t(lr, step, beta1=0.9, beta2=0.999):
     """TF-1 Adam effective step size for 1-based step t."""
     return lr * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step)

@@ -855,6 +855,31 @@ int acimg_batch_gather(const uint8_t* pool_video, size_t video_stride, const flo
                        float* mfcc_low, float* action, float* location, void* ws, size_t ws_bytes, void* stream);
 size_t acimg_batch_gather_workspace(int N, int elems);
 
+/* The correspondence pairs of dataloader/outdoor_data_mfcc.py:888-928 (`--correspondence 1`) out of the same pool: every
+ * frame once as it is and once as "this frame, near-silence -> a flat map".  (Added without raising ACIMG_VERSION:
+ * acimg_batch_gather is unchanged, and the number is pinned by the host tests.)
+ * Pool arguments, sizes, alignment and `stream` exactly as acimg_batch_gather.  rows: int32 [N] ON THE DEVICE, ROW CODES:
+ *   code >= 0  the REAL row of slot code;  code < 0  the SILENT row of slot ~code (= -code - 1).
+ * Repeats, any order and both kinds of one slot are allowed.  PRECONDITION: the decoded slot lies inside the pool.
+ * Outputs, dense, row n < N, s = the decoded slot:
+ *   video, action, location  as acimg_batch_gather gives them for slot s, whatever the row's kind
+ *   acoustic [N][elems]      real: as acimg_batch_gather, bit for bit.  silent: acoustic[n][i] = pool_mfcc_low[s][i % 12],
+ *            the row tiled over elems / 12 pixels, NOT normalised.  elems % 12 != 0: ACIMG_EINVAL
+ *   mfcc [N][12]             pool_mfcc[s] for a real row, pool_mfcc_low[s] for a silent one
+ *   pair [N][2]              the one-hot correspondence label: {0, 1} real, {1, 0} silent (tf.one_hot(1 | 0, 2))
+ * There is no mfcc_low output.  ws: acimg_batch_gather_pairs_workspace(N, elems) bytes, 16-byte aligned (short =
+ * ACIMG_EWORKSPACE): receives [N][4] floats, {min(a), max(a - min(a)), 0, 0} for a real row, four zeros for a silent one.
+ * Refusals: everything acimg_batch_gather refuses, and elems % 12 != 0; every one precedes the first launch.
+ * TWO launches on `stream`: the video launch of acimg_batch_gather on the decoded slots, then one workgroup per row (the
+ * branch on the kind is uniform in it): a silent row reads its 48 bytes and stores float4 when `acoustic` is 16-byte
+ * aligned (with pool_acoustic, as for the real rows), else float by float.  No atomics: bit-identical from run to run. */
+int acimg_batch_gather_pairs(const uint8_t* pool_video, size_t video_stride, const float* pool_acoustic,
+                             const float* pool_mfcc, const float* pool_mfcc_low, const int32_t* pool_labels,
+                             const int32_t* rows, int N, int pixels, int elems, int num_actions, int num_locations,
+                             float* video, float* acoustic, float* mfcc, float* pair, float* action, float* location, void* ws,
+                             size_t ws_bytes, void* stream);
+size_t acimg_batch_gather_pairs_workspace(int N, int elems);
+
 /* Baseline JPEG of RGB8 frames, 4:2:0, integer arithmetic throughout (tests/jpeg_ref.py restates it bit for bit; the
  * definition is DESIGN section 8).  Replaces: the `-vcodec libx264` ffmpeg run of showvideo.py:239-251 as the video track
  * of the clip `python -m acimg.show video --avi 1` writes (Motion-JPEG; H.264 is not reproduced).  (Added without raising

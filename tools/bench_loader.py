@@ -9,7 +9,10 @@ one-file validation pass included, the same for both).  One JSON line per pass, 
 spread of each loader and whether the device loader's slowest pass beats the host loader's fastest by more than the two
 spreads together, and the device loader's host seconds per stage.
 
-    python tools/bench_loader.py --files 16 --records 4 --batch 32 --repeats 3 [--train] [--shuffle]
+    python tools/bench_loader.py --files 16 --records 4 --batch 32 --repeats 3 [--train] [--shuffle] [--correspondence 1]
+
+--correspondence 1: both loaders apply the pair map (every frame a second time as its silent row), the shuffling device
+loader also its second shuffle stage; the rates then count ROWS, two per frame.
 """
 import argparse
 import concurrent.futures
@@ -63,8 +66,9 @@ def write_file(path, content, records, seed):
 def make_loader(kind, files, a, dev, shuffle=False):
     from acimg.data import DeviceDataLoader, TFRecordDataLoader
     if kind == "host":
-        return TFRecordDataLoader(files, a.batch, device=dev)
-    return DeviceDataLoader(files, a.batch, shuffle=shuffle, seed=1, workers=a.workers, prefetch=a.prefetch, device=dev)
+        return TFRecordDataLoader(files, a.batch, device=dev, correspondence=a.correspondence)
+    return DeviceDataLoader(files, a.batch, shuffle=shuffle, seed=1, workers=a.workers, prefetch=a.prefetch, device=dev,
+                            correspondence=a.correspondence)
 
 
 def loader_pass(loader, dev):
@@ -89,6 +93,7 @@ def main():
     ap.add_argument("--prefetch", type=int, default=2)
     ap.add_argument("--shuffle", action="store_true", help="also time the device loader with shuffle=True")
     ap.add_argument("--train", action="store_true", help="time an epoch of Trainer.train() through each loader")
+    ap.add_argument("--correspondence", type=int, default=0, choices=[0, 1], help="1: the pair map; rates count rows")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     tr = None
@@ -115,6 +120,7 @@ def main():
                                                          a.records, i), range(a.files)))
             size = sum(os.path.getsize(p) for p in files)
             frames = a.files * a.records * 12
+            rows = frames * (2 if a.correspondence else 1)
             print(json.dumps(dict(content=content, files=a.files, frames=frames, gzip_mb=round(size / 1e6, 1),
                                   written_s=round(time.perf_counter() - t0, 1))), flush=True)
             loaders = {k: make_loader("host" if k == "host" else "device", files, a, dev, shuffle=k == "device_shuffle")
@@ -136,13 +142,13 @@ def main():
                         t0 = time.perf_counter()
                         tr.train(loaders[k], valid)
                         torch.cuda.synchronize(dev)
-                        n, dt = frames, time.perf_counter() - t0
+                        n, dt = rows, time.perf_counter() - t0
                         getattr(valid, "close", lambda: None)()
                     rates[k].append(n / dt)
                     print(json.dumps(dict(content=content, loader=k, mode="train" if tr else "loader", repeat=rep,
                                           frames=n, seconds=round(dt, 4), images_per_s=round(n / dt, 1))), flush=True)
             summary = dict(content=content, mode="train" if tr else "loader", batch=a.batch, workers=a.workers,
-                           prefetch=a.prefetch)
+                           prefetch=a.prefetch, correspondence=a.correspondence)
             for k in kinds:
                 summary[k] = dict(min=round(min(rates[k]), 1), max=round(max(rates[k]), 1))
             if "host" in rates and "device" in rates:
