@@ -354,6 +354,8 @@ def wgrad_counts(case, slabs):
 #   few     3x3 / 1 / SAME, 4 - 16 channels convolved: conv_few16_kernel (f16x3 forward, bf16x3 data gradient); the data
 #           gradient of 8 -> 32 is the 16-row instance of the halo kernel; weight gradient wgrad_halo16_kernel<16, 3> (bf16x3)
 #   few/2   3x3 / 2 / SAME data gradient: conv_few16_kernel over the zero-inserted view of gy
+#   few/bwd 3x3 / 1 / SAME data gradient of a 32 -> 8 layer: 8 gy channels into 32, the 32-row instance of conv_few16_kernel
+#           (the layer's forward and weight gradient convolve 32 channels: not few-channel routes)
 #   point   2x2 / 2 transposed conv 32 -> 8: patch2_32x8_kernel (f16x3 forward, bf16x3 data gradient), patch2_wgrad_32x8_kernel
 # Shapes: >= 65536 pixels, heights and widths off the 16 x 32 / 8 x 32 / 4 x 32 tile grids (150 x 160 has whole tile columns);
 # 3 x 149 x 147 = 65709 pixels is odd: the last 16-pixel group of the pointwise kernels has 3 dead lanes, the last 32-pixel
@@ -367,11 +369,12 @@ FP32_CASES = {
     "few 8->32": (3, 150, 161, 8, 32, "few", SETS, 114),         # its data gradient: the narrow halo instance
     "few/2 even": (3, 150, 160, 8, 8, "few/2", (), 115),         # leading pads 0, 0
     "few/2 odd": (3, 149, 147, 8, 8, "few/2", (), 116),          # leading pads 1, 1
+    "few 32->8": (3, 147, 150, 32, 8, "few/bwd", (), 118),       # data gradient only: 8 gy channels into 32 columns
     "pointwise": (3, 149, 147, 32, 8, "point", ("channels", "quiet", "loud"), 117),
 }
 FP32_FWD = [(case, name) for case, rec in FP32_CASES.items() for name in rec[6]]
 FP32_BWD = list(FP32_CASES)
-FP32_WGRAD = [case for case, rec in FP32_CASES.items() if rec[5] != "few/2"]
+FP32_WGRAD = [case for case, rec in FP32_CASES.items() if rec[5] not in ("few/2", "few/bwd")]
 IMPULSE_CASES = FP32_WGRAD + ["halo 64"]
 
 
@@ -391,6 +394,8 @@ def fp32_products(case):
         return dict(fwd=(deconv_fwd, 1), dgrad=(deconv_dgrad, 1), wgrad=deconv_wgrad)
     if kind == "few/2":
         return dict(dgrad=(conv_dgrad_s2(H, W), few16_ksteps(K)))
+    if kind == "few/bwd":
+        return dict(dgrad=(conv_dgrad, few16_ksteps(K)))
     return dict(fwd=(conv_fwd, few16_ksteps(Cc)), dgrad=(conv_dgrad, few16_ksteps(K) if K <= 16 else fwd_ksteps(3, 3, K)),
                 wgrad=conv_wgrad(3))
 

@@ -183,7 +183,7 @@ def test_presplit_conv_caller_memory(device, shape, entry):
     run_case(device, Case(q, outs, call, verify, zero_head=4096, zero_exit=4096), "%s[%s]" % (entry, shape))
 
 
-@pytest.mark.parametrize("shape", [(20011, 128, 512), (37, 64, 100)])
+@pytest.mark.parametrize("shape", [(20011, 128, 512), (37, 64, 100), (4111, 384, 136)])
 def test_gram_stats_caller_memory(device, shape):
     """acimg_gram_stats: scale / shift at 3e-6, moving averages at 2e-6 (test_gram_statistics_match_fp64); a short
     workspace is refused (tests/test_host_cpu.py::test_gram_stats_host_side: ACIMG_EINVAL)"""

@@ -130,18 +130,20 @@ def test_production_planes_dgrad(device, case, fused):
 
 
 # chunk parity and ragged edges: width 32 with three chunks (an odd count exercises the prefetch's hand-over), a height the
-# two-row tiles do not divide (the last tile holds one image row), 72 output columns / 72 dx columns
-RAGGED = [(3, 7, 32, 96, 128), (1, 5, 48, 64, 64), (2, 4, 32, 96, 72), (2, 4, 48, 72 + 24, 72), (2, 4, 32, 72, 96)]
+# two-row tiles do not divide (the last tile holds one image row), 72 output columns / 72 dx columns; width 32 with ONE 64-column
+# block, 40 of its columns live (conv_tap_kernel<SplitF16 / SplitBF16, 32, 64>: forward 96 -> 40, data gradient of 40 -> 96)
+RAGGED = [(3, 7, 32, 96, 128), (1, 5, 48, 64, 64), (2, 4, 32, 96, 72), (2, 4, 48, 72 + 24, 72), (2, 4, 32, 72, 96),
+          (2, 5, 32, 96, 40), (2, 5, 32, 40, 96)]
 
 
-@pytest.mark.parametrize("case", RAGGED[:4])
+@pytest.mark.parametrize("case", RAGGED[:4] + [RAGGED[5]])
 def test_ragged_forward(device, case):
     run_fwd(device, case, ldx=case[3] + 4)
 
 
-@pytest.mark.parametrize("case", [RAGGED[0], RAGGED[1], RAGGED[4]])
+@pytest.mark.parametrize("case", [RAGGED[0], RAGGED[1], RAGGED[4], RAGGED[6]])
 def test_ragged_dgrad(device, case):
-    """(2, 4, 32, 72->96): 72 columns of dx from three chunks of gy"""
+    """(2, 4, 32, 72->96): 72 columns of dx from three chunks of gy; (2, 5, 32, 40->96): 40 columns in one 64-column block"""
     run_dgrad(device, case, ldg=case[4] + 4)
 
 

@@ -52,8 +52,9 @@ def check_against_restatement(device, logen, boxes):
     return iou, counts, mask
 
 
-@pytest.mark.parametrize("N", [1, 7, 64])
+@pytest.mark.parametrize("N", [1, 7, 64, 257])
 def test_box_iou_matches_restatement_random(device, N):
+    """N = 257: box_iou_finish_kernel takes one workgroup per 256 samples, so a second workgroup with one sample"""
     rng = np.random.RandomState(N)
     logen = (rng.rand(N, 36, 48) * rng.rand(N, 1, 1) * 3).astype(np.float32)
     check_against_restatement(device, logen, random_boxes(rng, N))

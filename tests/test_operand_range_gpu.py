@@ -510,11 +510,13 @@ def test_few_channel_forward_route(device, case, name):
 @pytest.mark.parametrize("case", FEW_BWD)
 def test_few_channel_data_gradient_routes(device, case):
     """acimg_conv2d_dgrad on conv_few16_kernel MODE 1 (bf16x3): stride 1, and stride 2 over the zero-inserted view of gy with
-    leading pads 0 (even sizes) and 1 (odd); the 8 -> 32 layer on the 16-row halo instance.  gy channels at 2^-30 .. 2^-10,
+    leading pads 0 (even sizes) and 1 (odd); the 8 -> 32 layer on the 16-row halo instance; the 32 -> 8 layer on the few-channel
+    kernel's 32-row instance (conv_few16_kernel<SplitBF16, 8, 32, 1, 8>: 8 gy channels into 32).  gy channels at 2^-30 .. 2^-10,
     dx into a wider pixel stride with the pad channels and the memory behind it untouched.  Route: the workspace query's
     own size for the narrow halo instance; for the few-channel kernel the shape rule of the conv it is - gy's K channels
     into C (acimg_conv2d_stats_rows of that conv: 512) - and the workspace's footprint: the kernel's weight image
-    (2 x 16 rows x 96 or 160 bf16) and not a byte more, where the zero-inserted copy or the direct kernel would differ."""
+    (2 x 16 rows, or 32 for more than 16 channels of dx, x 96 or 160 bf16) and not a byte more, where the zero-inserted copy
+    or the direct kernel would differ."""
     import ctypes as C
 
     from acimg import _lib, ops
@@ -535,7 +537,7 @@ def test_few_channel_data_gradient_routes(device, case):
     dx[..., :Cc] = float("nan")
     ops.conv2d_dgrad(plan, d, o.gy.to(device), K, o.w.to(device), dx, lddx=Cc + 4)
     torch.cuda.synchronize()
-    image = 2 * 16 * (288 if narrow else (96 if K <= 8 else 160)) * 2
+    image = 2 * (16 if narrow or Cc <= 16 else 32) * (288 if narrow else (96 if K <= 8 else 160)) * 2
     assert int(ws[image - 1]) != WS_BYTE and bool((ws[image:] == WS_BYTE).all()), "the workspace's footprint is another route's"
     held("fp32 entry, " + case, "dx", dx[..., :Cc], ref, bound)
     untouched(case + " dx", flat, dx, Cc, Cc + 4)

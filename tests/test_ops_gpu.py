@@ -1304,13 +1304,16 @@ def test_batch_norm_affine_applied_while_staging(device, case):
 
 
 @pytest.mark.parametrize("case", [(134400, 64, 256), (34048, 256, 1024), (20011, 128, 512), (8512, 512, 2048), (37, 64, 100),
-                                  (4099, 128, 136), (50, 256, 256), (4111, 128, 256), (15, 512, 136), (4111, 512, 512)])
+                                  (4099, 128, 136), (50, 256, 256), (4111, 128, 256), (15, 512, 136), (4111, 512, 512),
+                                  (37, 384, 100), (4111, 384, 384)])
 def test_gram_statistics_match_fp64(device, case):
     """acimg_gram_stats (round 4, csrc/gram.hip): the batch-norm statistics of a 1x1 conv's output from the column sums and
     the Gram matrix of its INPUT (split planes in brick order), finalised into scale / shift and the moving averages -
     against fp64 statistics of y = x w over the values the planes actually hold, against acimg_bn_finalize fed with those
     fp64 sums (the same finalisation arithmetic), and against the statistics pass it replaces; row counts that are not
-    multiples of 16 / 32, one row, K not a multiple of 16; deterministic (two runs, the same bits).  The planes are
+    multiples of 16 / 32, one row, K not a multiple of 16; C = 384, the one width whose 24 row tiles do not divide over the
+    16 waves of gram_quadfin_kernel (waves 0..7 take two, 8..15 one) and whose partials form an odd 3 x 3 block grid;
+    deterministic (two runs, the same bits).  The planes are
     poisoned outside the valid rows (pad rows of the last brick row, a gap before lo_off, slack after the lo plane) with
     fp16 NaN and with a large finite pattern: the pad rows are unspecified (include/acimg.h), and a consumer that sums
     them gives NaN or statistics that are off by orders of magnitude"""

@@ -15,22 +15,30 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
+SENTINEL = -12345.0
+
+
 def _run(e0, e1, labels, scenario, margin, hard, weight=1.0, ld=None):
+    """ld: one leading dimension for all four matrices, or (lde0, lde1, ldg0, ldg1).  The pad columns hold NaN in the
+    embeddings and SENTINEL in the gradients: nothing may read the former, and the latter must survive"""
     from acimg import ops
     B, D = e0.shape
-    ld = ld or D
-    a = torch.zeros(B, ld, device=DEV)
-    b = torch.zeros(B, ld, device=DEV)
+    lde0, lde1, ldg0, ldg1 = ld if isinstance(ld, tuple) else (ld or D,) * 4
+    a = torch.full((B, lde0), float("nan"), device=DEV)
+    b = torch.full((B, lde1), float("nan"), device=DEV)
     a[:, :D] = e0.float().to(DEV)
     b[:, :D] = e1.float().to(DEV)
     lab, sc = labels.int().to(DEV), scenario.int().to(DEV)
     ws = torch.zeros(ops.triplet_loss_workspace(B), dtype=torch.uint8, device=DEV)
     out = torch.zeros(4, device=DEV)
-    g0, g1 = torch.zeros(B, ld, device=DEV), torch.zeros(B, ld, device=DEV)
+    g0, g1 = torch.full((B, ldg0), SENTINEL, device=DEV), torch.full((B, ldg1), SENTINEL, device=DEV)
+    g0[:, :D] = 0
+    g1[:, :D] = 0
     plan = ops.Plan(DEV, eager=True)
-    ops.triplet_loss_fwd(plan, a, ld, b, ld, lab, sc, B, D, margin, hard, ws, out)
-    ops.triplet_loss_bwd(plan, a, ld, b, ld, B, D, weight, ws, g0, ld, g1, ld)
+    ops.triplet_loss_fwd(plan, a, lde0, b, lde1, lab, sc, B, D, margin, hard, ws, out)
+    ops.triplet_loss_bwd(plan, a, lde0, b, lde1, B, D, weight, ws, g0, ldg0, g1, ldg1)
     torch.cuda.synchronize()
+    assert bool((g0[:, D:] == SENTINEL).all()) and bool((g1[:, D:] == SENTINEL).all()), "gradient pad columns written"
     return out.cpu(), g0[:, :D].cpu().double(), g1[:, :D].cpu().double(), (a, b, ws, plan)
 
 
@@ -50,8 +58,10 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("hard", [0, 1])
-@pytest.mark.parametrize("B,D,ld", [(48, 150, 152), (7, 12, 12), (300, 64, 64)])
+@pytest.mark.parametrize("B,D,ld", [(48, 150, 152), (7, 12, 12), (300, 64, 64), (9, 300, (300, 304, 308, 312))])
 def test_triplet_random(hard, B, D, ld):
+    """(9, 300): triplet_grad_kernel walks D in strides of 256, so a second pass of 44 columns; four different leading
+    dimensions, so an ld taken from the wrong matrix shows"""
     g = torch.Generator().manual_seed(100 + B)
     e0 = 0.05 * torch.randn(B, D, generator=g, dtype=torch.float64)
     e1 = 0.05 * torch.randn(B, D, generator=g, dtype=torch.float64)

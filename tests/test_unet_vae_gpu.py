@@ -187,12 +187,14 @@ def _bf16(t):
 
 
 @pytest.mark.parametrize("case", [(2, 56, 75, 64, 64, 3), (4, 28, 38, 128, 96, 3), (2, 112, 149, 32, 32, 3),
-                                  (3, 40, 52, 64, 128, 1)])
+                                  (3, 40, 52, 64, 128, 1), (1, 159, 161, 32, 128, 1)])
 def test_bf16_operand_convs(case):
     """BASELINE configs[1] "bf16": acimg_conv2d_fwd_bf16 / _dgrad_bf16 / _wgrad_bf16 are EXACTLY the convolutions of
     the bf16-rounded operands accumulated in fp32 (one v_mfma_f32_16x16x32_bf16 per product): compared with fp64
     convolutions of the same rounded operands (2e-5: fp32 accumulation order), incl. the fused bias gradient and the
-    batch-norm statistics of the forward."""
+    batch-norm statistics of the forward.  (1, 159, 161, 32 -> 128): 25599 pixels are 200 row tiles of 128, from which on the
+    forward takes the 128 x 128 tile (igemm_split3_kernel<128, 128, 2, 4, 512, SplitBF16, 1>; csrc/conv_split.hip pick_split3),
+    the last tile one row short; the other shapes with more than 64 columns stay on 64 x 128."""
     from acimg import ops
 
     dev = torch.device("cuda:0")
@@ -209,6 +211,10 @@ def test_bf16_operand_convs(case):
     ops.conv2d_split3_prepare(plan, d, wd, wimg, bf16=True)
     y = torch.full((N, H, W, K), float("nan"), device=dev)
     rows = ops.conv2d_fwd_split3_stats_rows(d)
+    if K > 64:         # one statistics row per row tile: 128 rows from 200 tiles of 128 x 128 on, 64 below
+        M = N * H * W
+        assert rows == -(-M // (128 if -(-M // 128) * -(-K // 128) >= 200 else 64)), rows
+        assert rows == (200 if M == 25599 else -(-M // 64))
     st = torch.zeros(rows, 2, K, device=dev)
     ops.conv2d_fwd_split3(plan, d, xd, wimg, y, stats=st, bias=bd, bf16=True)
     wt = torch.zeros(ops.conv2d_split3_dgrad_weight_bytes(d), dtype=torch.uint8, device=dev)

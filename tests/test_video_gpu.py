@@ -129,13 +129,16 @@ def device_scan(device, coef, H, W, restart, slack=5):
     return cnt.view(torch.int32, n).cpu().numpy(), out.u8.cpu().numpy().reshape(n, stride), cap
 
 
-@pytest.mark.parametrize("n,H,W", [(2, 17, 33), (1, 32, 144)])
+@pytest.mark.parametrize("n,H,W", [(2, 17, 33), (1, 32, 144), (1, 48, 368), (1, 224, 298)])
 @pytest.mark.parametrize("full", [False, True])
 def test_scan_equals_restatement(device, n, H, W, full):
+    """(1, 48, 368): 69 MCUs, so the merge kernel's 64-MCU scan takes a second pass - restart 69 is 64 + 5 MCUs, restart
+    65 is 64 + 1 and then an interval of 4.  (1, 224, 298): 266 MCUs - restart 1 is 266 intervals, two for some pack
+    threads and one for others, the RSTm index wrapping 33 times; restart 266 is one interval of five scan passes"""
     mh, mw = J.mcu_grid(H, W)
     mcus = mh * mw
     coef = synthetic_coefficients(n, mcus, full)
-    for restart in (1, mw, 7, mcus):
+    for restart in (1, mw, 7, mcus) + ((65,) if mcus == 69 else ()):
         counts, region, cap = device_scan(device, coef, H, W, restart)
         for i in range(n):
             want = J.scan(coef[i], restart)
@@ -151,6 +154,10 @@ def test_scan_equals_restatement(device, n, H, W, full):
         assert np.array_equal(again, counts) and np.array_equal(region2, region)  # bit-identical from run to run
     if (H, W) == (32, 144):
         assert J.num_intervals(H, W, 1) == 18 and J.num_intervals(H, W, 7) == 3   # the index wraps; a short last interval
+    if (H, W) == (48, 368):
+        assert mcus == 69 and J.num_intervals(H, W, 65) == 2
+    if (H, W) == (224, 298):
+        assert mcus == 266 and J.num_intervals(H, W, 1) == 266 and J.num_intervals(H, W, 266) == 1
 
 
 # ---- the encoder ------------------------------------------------------------------------------------------------------
