@@ -184,6 +184,14 @@ PROTOTYPES = {
     "acimg_jpeg_scan": (_I, [_P, _I, _I, _I, _I, _P, _SZ, _P, _P, _SZ, _P]),
     "acimg_resize_cubic_tables": (_I, [_I, _I, _I, _I, _P, _P]),
     "acimg_resize_cubic_u8": (_I, [_P, _SZ, _SZ, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "acimg_jpeg_decode_coef_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "acimg_jpeg_decode_plane_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "acimg_jpeg_decode_pixel_bytes": (_SZ, [_I, _I, _I]),
+    "acimg_jpeg_decode_entropy": (_I, [_P, _SZ, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
+    "acimg_jpeg_decode_idct": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "acimg_jpeg_decode_colour": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "acimg_resample_length": (_L, [_L, _I, _I, C.POINTER(_L)]),
+    "acimg_resample_sinc": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _L, _P]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

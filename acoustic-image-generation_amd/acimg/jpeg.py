@@ -1,7 +1,13 @@
 """Baseline JPEG files (JFIF, 4:2:0) of RGB8 device tensors: the two kernels of csrc/jpeg.hip (`acimg_jpeg_blocks`,
 `acimg_jpeg_scan`) produce each frame's entropy-coded segment on the device; the header segments, which depend on the
 size, the quality and the restart interval alone, are built here once per encoder and size.  Per `encode` call two
-transfers come back: the frames' byte counts and their packed bytes.  No imaging library is involved."""
+transfers come back: the frames' byte counts and their packed bytes.  No imaging library is involved.
+
+The other direction - baseline files to B, G, R pixels, the `cv2.imread` of convert_data2.py:157 - is `parse_jpeg` (the
+markers, on the host: geometry, tables in the device's layout, where the scan and its restart intervals lie; everything
+outside the decoder's scope is refused by name before any launch) and `JpegDecoder` (the three kernels of
+csrc/jpeg_decode.hip: entropy decode, dequantise + inverse DCT, upsample + colour)."""
+import collections
 import ctypes as C
 import struct
 
@@ -9,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .convert import ConvertError
 
 # zig-zag position -> natural (row-major) index: the order a DQT segment stores a table in
 ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -132,3 +139,261 @@ def write_jpeg(path, rgb_uint8, quality=90, restart_mcus=None, device="cuda:0"):
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
+
+
+# ---- decoding -------------------------------------------------------------------------------------------------------------
+HUFF_BYTES = 904                      # ACIMG_JPEG_HUFF_BYTES: look uint16[256], maxcode int32[17], valoff int32[17], vals uint8[256]
+STATUS_TEXT = {0: "ok", 1: "a code that is in no Huffman table", 2: "a run past coefficient 63", 3: "the data ends early",
+               4: "a bad interval descriptor"}
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+              0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic-coded sequential",
+              0xCA: "arithmetic-coded progressive", 0xCB: "arithmetic-coded lossless", 0xCD: "arithmetic-coded differential",
+              0xCE: "arithmetic-coded differential progressive", 0xCF: "arithmetic-coded differential lossless"}
+
+JpegInfo = collections.namedtuple(
+    "JpegInfo", "height width comps hs vs mcu_w mcu_h mcus blocks quant huff scan_begin scan_end restart_mcus intervals")
+JpegInfo.__doc__ = """what `parse_jpeg` finds: quant uint8 [3][64] natural order, per component; huff uint8 [6][HUFF_BYTES],
+DC and AC table per component in the device layout; [scan_begin, scan_end) the entropy-coded segment in the file;
+restart_mcus (0: none); intervals int32 [count][2]: first and end byte of each restart interval relative to scan_begin,
+count = ceil(mcus / restart_mcus) whatever the file holds (an interval the file lacks is empty)"""
+
+
+def derive_huffman(counts, vals, name="<jpeg>"):
+    """BITS (codes per length 1..16) and HUFFVAL of a DHT segment -> uint8 [HUFF_BYTES], the layout csrc/jpeg_decode.hip
+    reads (Annex C codes; an over-full code space is refused)"""
+    out = np.zeros(HUFF_BYTES, np.uint8)
+    look = out[:512].view(np.uint16)
+    maxcode = out[512:580].view(np.int32)
+    valoff = out[580:648].view(np.int32)
+    maxcode[:] = -1
+    out[648:648 + len(vals)] = np.frombuffer(bytes(vals), np.uint8)
+    code = k = 0
+    for length in range(1, 17):
+        n = counts[length - 1]
+        if code + n > (1 << length):
+            raise ConvertError("%s: a Huffman table with more codes of %d bits than there are" % (name, length))
+        if n:
+            valoff[length] = k - code
+            maxcode[length] = code + n - 1
+            if length <= 8:
+                for i in range(n):
+                    look[(code + i) << (8 - length):(code + i + 1) << (8 - length)] = (length << 8) | vals[k + i]
+            code += n
+            k += n
+        code <<= 1
+    return out
+
+
+def parse_jpeg(data, name="<jpeg>"):
+    """the markers of one file -> JpegInfo.  Taken: SOF0 of 8 bits, one or three components in one interleaved scan, luma
+    1x1 / 2x1 / 2x2 over 1x1 chroma, any 8-bit DQT and any DHT, DRI / RSTn; APPn and COM are skipped.  Everything else is
+    a ConvertError that names the file and the reason.  A scan that ends early is NOT refused here: the device reports it."""
+    buf = bytes(data)
+    size = len(buf)
+
+    def cut(what):
+        return ConvertError("%s: truncated JPEG file: %d bytes end inside %s" % (name, size, what))
+
+    if size < 4 or buf[:2] != b"\xFF\xD8":
+        raise ConvertError("%s: not a JPEG file (no SOI marker)" % name)
+    qt, huff, frame, restart, pos = {}, {}, None, 0, 2
+    while True:
+        if pos + 4 > size:
+            raise cut("the header segments")
+        if buf[pos] != 0xFF:
+            raise ConvertError("%s: byte %d is no marker" % (name, pos))
+        marker = buf[pos + 1]
+        if marker == 0xFF:                                # fill byte
+            pos += 1
+            continue
+        length = struct.unpack_from(">H", buf, pos + 2)[0]
+        if length < 2 or pos + 2 + length > size:
+            raise cut("segment FF %02X" % marker)
+        body = buf[pos + 4:pos + 2 + length]
+        if marker in _SOF_NAMES:
+            raise ConvertError("%s: %s JPEG (SOF%d): only baseline sequential Huffman files (SOF0) are decoded"
+                               % (name, _SOF_NAMES[marker], marker - 0xC0))
+        if marker == 0xC0:
+            if frame is not None or len(body) < 6:
+                raise ConvertError("%s: a second or short frame header" % name)
+            precision, height, width, comps = struct.unpack_from(">BHHB", body)
+            if precision != 8:
+                raise ConvertError("%s: %d-bit samples: only 8-bit files are decoded" % (name, precision))
+            if comps not in (1, 3):
+                raise ConvertError("%s: %d components: only one (grey) or three (Y Cb Cr) are decoded" % (name, comps))
+            if len(body) < 6 + 3 * comps or height < 1 or width < 1:
+                raise ConvertError("%s: frame header of %d bytes for %d x %d pixels" % (name, len(body), width, height))
+            frame = (height, width, [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i])
+                                     for i in range(comps)])
+        elif marker == 0xDB:
+            at = 0
+            while at < len(body):
+                if body[at] >> 4:
+                    raise ConvertError("%s: 16-bit DQT entries: only 8-bit quantisation tables are decoded" % name)
+                if at + 65 > len(body):
+                    raise cut("a DQT segment")
+                t = np.zeros(64, np.uint8)
+                t[list(ZIGZAG)] = np.frombuffer(body[at + 1:at + 65], np.uint8)
+                qt[body[at] & 15] = t
+                at += 65
+        elif marker == 0xC4:
+            at = 0
+            while at < len(body):
+                if at + 17 > len(body):
+                    raise cut("a DHT segment")
+                counts = list(body[at + 1:at + 17])
+                n = sum(counts)
+                if n > 256 or at + 17 + n > len(body):
+                    raise cut("a DHT segment")
+                vals = body[at + 17:at + 17 + n]
+                if body[at] >> 4 == 0 and any(v > 15 for v in vals):
+                    raise ConvertError("%s: a DC Huffman table with a category above 15" % name)
+                huff[body[at]] = derive_huffman(counts, vals, name)
+                at += 17 + n
+        elif marker == 0xDD:
+            if len(body) < 2:
+                raise cut("the DRI segment")
+            restart = struct.unpack_from(">H", body)[0]
+        elif marker == 0xDA:
+            break
+        elif not (0xE0 <= marker <= 0xEF or marker == 0xFE):
+            raise ConvertError("%s: marker FF %02X is not decoded" % (name, marker))
+        pos += 2 + length
+    if frame is None:
+        raise ConvertError("%s: a scan without a frame header" % name)
+    height, width, comp = frame
+    comps = len(comp)
+    if len(body) < 4 + 2 * body[0] or body[0] != comps:
+        raise ConvertError("%s: a scan of %d of the %d components: only one interleaved scan is decoded (multiple scans)"
+                           % (name, body[0], comps))
+    ss, se, ahal = body[1 + 2 * comps:4 + 2 * comps]
+    if (ss, se, ahal) != (0, 63, 0):
+        raise ConvertError("%s: a scan of coefficients %d..%d: only one full scan is decoded" % (name, ss, se))
+    if comps == 1:                                        # one component is never interleaved: 8 x 8 MCUs
+        comp = [(comp[0][0], 1, 1, comp[0][3])]
+    hs, vs = comp[0][1], comp[0][2]
+    if (hs, vs) not in ((1, 1), (2, 1), (2, 2)) or any(c[1:3] != (1, 1) for c in comp[1:]):
+        raise ConvertError("%s: sampling %s: only luma 1x1, 2x1 or 2x2 over 1x1 chroma is decoded"
+                           % (name, " ".join("%dx%d" % c[1:3] for c in comp)))
+    quant, tables = np.zeros((3, 64), np.uint8), np.zeros((6, HUFF_BYTES), np.uint8)
+    for i, (cid, _, _, tq) in enumerate(comp):
+        sel = [body[2 + 2 * j] for j in range(comps) if body[1 + 2 * j] == cid]
+        if len(sel) != 1:
+            raise ConvertError("%s: the scan does not name component %d once" % (name, cid))
+        if tq not in qt:
+            raise ConvertError("%s: no quantisation table %d" % (name, tq))
+        quant[i] = qt[tq]
+        for j, key in enumerate((sel[0] >> 4, 0x10 | (sel[0] & 15))):
+            if key not in huff:
+                raise ConvertError("%s: no Huffman table %d of class %d" % (name, key & 15, key >> 4))
+            tables[2 * i + j] = huff[key]
+    mcu_w, mcu_h = -(-width // (8 * hs)), -(-height // (8 * vs))
+    mcus = mcu_w * mcu_h
+    scan_begin = pos + 2 + length
+    # the segment ends at the first FF that neither stuffs (FF 00) nor restarts (FF D0..D7) nor fills (FF FF)
+    seg = np.frombuffer(buf, np.uint8, offset=scan_begin)
+    ff = np.flatnonzero(seg[:-1] == 0xFF) if seg.size > 1 else np.zeros(0, np.int64)
+    nxt = seg[ff + 1]
+    rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    other = np.flatnonzero(~rst & (nxt != 0) & (nxt != 0xFF))
+    scan_len = int(ff[other[0]]) if other.size else seg.size
+    if other.size:
+        after = int(nxt[other[0]])
+        if after != 0xD9:
+            raise ConvertError("%s: marker FF %02X follows the scan: only one scan is decoded (multiple scans)" % (name, after))
+    marks = ff[rst]
+    marks = marks[marks < scan_len]
+    per = restart if 0 < restart < mcus else mcus
+    count = -(-mcus // per)
+    intervals = np.full((count, 2), scan_len, np.int32)
+    starts = np.concatenate([[0], marks + 2])[:count]
+    ends = np.concatenate([marks, [scan_len]])[:count]
+    intervals[:len(starts), 0] = starts
+    intervals[:len(ends), 1] = ends
+    if scan_begin + scan_len >= 2 ** 31:
+        raise ConvertError("%s: a scan of %d bytes" % (name, scan_len))
+    return JpegInfo(height, width, comps, hs, vs, mcu_w, mcu_h, mcus, 1 if comps == 1 else hs * vs + 2, quant, tables,
+                    scan_begin, scan_begin + scan_len, restart if restart < mcus else 0, intervals)
+
+
+def pack_group(files, infos):
+    """what one launch reads, as host arrays: (data uint8: the entropy-coded segments back to back, desc int64 [n,4],
+    intervals int32 [total,2], huff uint8 [n,6,HUFF_BYTES], quant uint8 [n,3,64]) - the layout of include/acimg.h"""
+    n = len(files)
+    segs, desc, at, first = [], np.zeros((n, 4), np.int64), 0, 0
+    for i, (f, info) in enumerate(zip(files, infos)):
+        seg = np.frombuffer(f, np.uint8)[info.scan_begin:info.scan_end]
+        segs.append(seg)
+        desc[i] = (at, at + seg.size, info.restart_mcus, first)
+        at += seg.size
+        first += len(info.intervals)
+    data = np.concatenate(segs) if at else np.zeros(1, np.uint8)
+    arrays = (data, desc, np.concatenate([i.intervals for i in infos]), np.stack([i.huff for i in infos]),
+              np.stack([i.quant for i in infos]))
+    return tuple(np.ascontiguousarray(a) for a in arrays)
+
+
+class JpegDecoder(object):
+    """Baseline JPEG files -> B, G, R pixels on `device`.  `decode(files)` groups the files by geometry (height, width,
+    components, sampling), runs the three stages once per group and returns (pixels, status): per file a uint8 [H,W,3]
+    device tensor (a view of its group's tensor) and the int32 status the entropy stage gave it (0 = ok; the pixels of any
+    other are what its partly zero coefficients give)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.lib = _lib.load()
+
+    def upload(self, files, infos):
+        """the entropy-coded segments of one group, their descriptors and tables, on the device"""
+        return tuple(torch.from_numpy(a).to(self.device) for a in pack_group(files, infos))
+
+    def stages(self, files, infos, coef=None, planes=None, bgr=None, status=None):
+        """one group through the three kernels; buffers are allocated where the caller gives none ->
+        (coef int16 [n,mcus,blocks,64], planes uint8 [n, blocks * mcus * 64], bgr uint8 [n,H,W,3], status int32 [n])"""
+        L, g, n = self.lib, infos[0], len(files)
+        geo = (g.height, g.width, g.comps, g.hs, g.vs)
+        if any((i.height, i.width, i.comps, i.hs, i.vs) != geo for i in infos):
+            raise ValueError("the images of one launch share height, width, components and sampling")
+        data, desc, intervals, huff, quant = self.upload(files, infos)
+        dev = self.device
+        if coef is None:
+            coef = torch.empty(n, g.mcus, g.blocks, 64, dtype=torch.int16, device=dev)
+        if planes is None:
+            planes = torch.empty(n, g.blocks * g.mcus * 64, dtype=torch.uint8, device=dev)
+        if bgr is None:
+            bgr = torch.empty(n, g.height, g.width, 3, dtype=torch.uint8, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+        st = ops.current_stream_handle(dev)
+        _lib.check(L.acimg_jpeg_decode_entropy(data.data_ptr(), data.numel(), desc.data_ptr(), intervals.data_ptr(),
+                                               intervals.shape[0], huff.data_ptr(), n, *geo, coef.data_ptr(),
+                                               coef.numel() * 2, status.data_ptr(), st), "jpeg_decode_entropy")
+        _lib.check(L.acimg_jpeg_decode_idct(coef.data_ptr(), quant.data_ptr(), n, *geo, planes.data_ptr(), planes.numel(), st),
+                   "jpeg_decode_idct")
+        _lib.check(L.acimg_jpeg_decode_colour(planes.data_ptr(), n, *geo, bgr.data_ptr(), bgr.numel(), st), "jpeg_decode_colour")
+        return coef, planes, bgr, status
+
+    def decode(self, files, names=None, infos=None):
+        """files: a list of whole files (bytes) -> ([uint8 [H,W,3] device tensor per file], int32 [files] status on the host)"""
+        names = names or ["<jpeg %d>" % i for i in range(len(files))]
+        infos = infos or [parse_jpeg(f, nm) for f, nm in zip(files, names)]
+        groups = collections.OrderedDict()
+        for i, info in enumerate(infos):
+            groups.setdefault((info.height, info.width, info.comps, info.hs, info.vs), []).append(i)
+        pixels, status, parts = [None] * len(files), np.zeros(len(files), np.int32), []
+        for members in groups.values():
+            _, _, bgr, st = self.stages([files[i] for i in members], [infos[i] for i in members])
+            for k, i in enumerate(members):
+                pixels[i] = bgr[k]
+            parts.append((members, st))
+        for members, st in parts:                          # one read-back per group, after every launch is queued
+            status[members] = st.cpu().numpy()
+        return pixels, status
+
+
+def decode_jpeg(data, device="cuda:0", name="<jpeg>"):
+    """one baseline file -> uint8 [H,W,3] B, G, R on the host; a corrupt scan is a ConvertError"""
+    pixels, status = JpegDecoder(device).decode([data], [name])
+    if status[0]:
+        raise ConvertError("%s: corrupt JPEG scan: %s" % (name, STATUS_TEXT.get(int(status[0]), status[0])))
+    return pixels[0].cpu().numpy()

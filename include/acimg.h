@@ -955,6 +955,93 @@ int acimg_resize_cubic_u8(const uint8_t* src, size_t frame_stride, size_t pixel_
                           const int32_t* idx_y, const int16_t* coef_y, const int32_t* idx_x, const int16_t* coef_x, int OH,
                           int OW, uint8_t* out, void* stream);
 
+/* Baseline JPEG files (SOF0: sequential DCT, Huffman, 8 bit) to B, G, R pixels, integer arithmetic throughout: the decoder
+ * of `python -m acimg.convert_boxes`.  Replaces: the `cv2.imread` of convert_data2.py:157.  tests/jpeg_decode_ref.py
+ * restates every stage bit for bit, and the pixels equal libjpeg-turbo's (Pillow's) on the files of
+ * tests/golden/jpeg_decode_golden.npz; the definition is DESIGN section 8.  (Added without raising ACIMG_VERSION: nothing
+ * existing changed, and the number is pinned by the host tests.)
+ * Geometry: the images of one call share H, W (1..65535), comps (1 or 3) and the luma sampling hs x vs - 1x1, 2x1 or 2x2
+ * over 1x1 chroma; 1x1 for one component.  An MCU is 8 hs x 8 vs pixels, mcu_w = ceil(W / (8 hs)), mcu_h = ceil(H /
+ * (8 vs)), mcus = mcu_w mcu_h in raster order; it holds B = hs vs + 2 blocks (Y in raster order, Cb, Cr), B = 1 for one
+ * component.  The host (acimg/jpeg.py: parse_jpeg) reads the markers and refuses everything else by name.
+ *
+ * acimg_jpeg_decode_entropy: data uint8 [data_bytes]: the entropy-coded segments of the n files, anywhere in it;
+ *   desc int64 [n][4]: per image the first and the end byte of its segment in data, its restart interval in MCUs (0: none,
+ *   the image is one interval) and the index of its first interval in `intervals`; intervals int32 [total_intervals][2]:
+ *   first and end byte of a restart interval RELATIVE to the segment (the bytes between two RSTm markers; an image has
+ *   ceil(mcus / restart) of them, in order); huff uint8 [n][6][ACIMG_JPEG_HUFF_BYTES]: DC then AC table of component 0, 1,
+ *   2 (one component: the first two are read), each as
+ *     uint16 look[256]   the next 8 bits -> (length << 8) | symbol for a code of at most 8 bits, else 0
+ *     int32 maxcode[17]  [l], l = 1..16: the largest code of l bits, -1 where there is none ([0] unused)
+ *     int32 valoff[17]   [l]: index in vals of the first symbol of l bits minus the smallest code of l bits
+ *     uint8 vals[256]    HUFFVAL
+ *   -> coef int16 [n][mcus][B][64] (acimg_jpeg_decode_coef_bytes), each block in NATURAL (row-major) order, and status
+ *   int32 [n]: 0, or ACIMG_JPEG_STATUS_* of the image's first bad interval.  Per interval: DC predictors start at 0; bits
+ *   MSB first, FF 00 is the byte FF, any other FF ends the interval's data; a DC symbol s (0..15) is followed by s bits v,
+ *   the difference is v if v >= 2^(s-1), else v - 2^s + 1; an AC symbol (r, s): s > 0 skips r coefficients and stores the
+ *   next, (15, 0) skips 16, (r, 0) otherwise ends the block.  Errors: no code of up to 16 bits matches (a DC symbol above
+ *   15 counts as such), a coefficient would land past 63, more bits are used than the interval holds, a descriptor whose
+ *   intervals do not lie inside the table.  The blocks of an interval from the error on are zeros.
+ *   NOTHING IN data, desc OR intervals IS TRUSTED: every range is clamped to the range that holds it before it is used,
+ *   no read leaves [data, data + data_bytes), no write leaves the image's own coefficient slot, every loop is bounded by
+ *   the geometry; a corrupt image ends with a status and the other images of the call are unaffected.
+ *   ONE launch: one workgroup (one wave) per image with its tables in LDS, ONE LANE per restart interval - a file without
+ *   restart markers is decoded by a single lane, and the parallelism is the batch.
+ * acimg_jpeg_decode_idct: coef, quant uint8 [n][3][64] (the table of component 0, 1, 2 in NATURAL order) -> planes uint8,
+ *   per image B * mcus * 64 bytes (acimg_jpeg_decode_plane_bytes): the Y plane of (8 vs mcu_h) x (8 hs mcu_w) samples, then
+ *   Cb and Cr of (8 mcu_h) x (8 mcu_w).  libjpeg's jpeg_idct_islow in 32-bit integers that wrap: x = coef * quant,
+ *   CONST_BITS 13, PASS1_BITS 2, the constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172 in its
+ *   even / odd butterfly, columns first with (v + 2^10) >> 11, then rows with (v + 2^17) >> 18; + 128; clamp to 0..255.
+ *   ONE launch, eight threads per block.
+ * acimg_jpeg_decode_colour: planes -> bgr uint8 [n][H][W][3] dense, B G R (acimg_jpeg_decode_pixel_bytes).  Chroma is
+ *   upsampled as libjpeg's fancy upsampling does, on the component's true size cw = ceil(W / hs), ch = ceil(H / vs):
+ *     2x1: out[2i] = (3 a[i] + a[i-1] + 1) >> 2, out[2i+1] = (3 a[i] + a[i+1] + 2) >> 2; out[0] = a[0], out[2cw-1] = a[cw-1]
+ *     2x2: s[i] = 3 row[i] + neighbour[i], the neighbour being the row above for an even and below for an odd output
+ *          row (the first and last true row replicated); out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] +
+ *          s[i+1] + 7) >> 4, with s[-1] = s[0] and s[cw] = s[cw-1]
+ *   then, cb and cr less 128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16), G = Y + ((-22554
+ *   cb - 46802 cr + 32768) >> 16), clamped.  One component: B = G = R = Y.  ONE launch, one thread per pixel.
+ * The three size queries are pure host arithmetic and return 0 for an argument outside its range.  A null pointer, a
+ * geometry outside the above or a misaligned coef / huff / desc / intervals / planes (16 bytes): ACIMG_EINVAL; a buffer
+ * shorter than its query: ACIMG_EWORKSPACE; every refusal precedes the launch.  No atomics, no floating point, every
+ * output byte written by one thread: bit-identical from run to run and equal to the restatement on any machine. */
+#define ACIMG_JPEG_HUFF_BYTES 904
+#define ACIMG_JPEG_STATUS_BAD_CODE 1
+#define ACIMG_JPEG_STATUS_RUN 2
+#define ACIMG_JPEG_STATUS_EARLY_END 3
+#define ACIMG_JPEG_STATUS_DESCRIPTOR 4
+size_t acimg_jpeg_decode_coef_bytes(int n, int H, int W, int comps, int hs, int vs);
+size_t acimg_jpeg_decode_plane_bytes(int n, int H, int W, int comps, int hs, int vs);
+size_t acimg_jpeg_decode_pixel_bytes(int n, int H, int W);
+int acimg_jpeg_decode_entropy(const uint8_t* data, size_t data_bytes, const int64_t* desc, const int32_t* intervals,
+                              long total_intervals, const uint8_t* huff, int n, int H, int W, int comps, int hs, int vs,
+                              int16_t* coef, size_t coef_bytes, int32_t* status, void* stream);
+int acimg_jpeg_decode_idct(const int16_t* coef, const uint8_t* quant, int n, int H, int W, int comps, int hs, int vs,
+                           uint8_t* planes, size_t plane_bytes, void* stream);
+int acimg_jpeg_decode_colour(const uint8_t* planes, int n, int H, int W, int comps, int hs, int vs, uint8_t* bgr,
+                             size_t bgr_bytes, void* stream);
+
+/* Sample-rate conversion of one mono clip: `np.int32(librosa.core.resample(data * 1.0, fs, 12288))` of
+ * convert_data2.py:35,48 - resampy's windowed-sinc interpolation (`kaiser_best`).  tests/resample_ref.py restates it bit for
+ * bit; DESIGN section 8 has the definition and what of it is pinned.  (Added without raising ACIMG_VERSION.)
+ * acimg_resample_length (host only): ratio = (double)rate_out / rate_in; *computed = (long)(len * ratio), the samples
+ *   resampy forms; returns ceil(len * ratio), the length librosa pads them to with zeros.  0 for an argument below 1.
+ * acimg_resample_sinc: x int32 [len]; win, delta fp64 [nwin] ON THE DEVICE: the right half of the filter (times ratio
+ *   when ratio < 1) and its first differences with a 0 appended, num_table entries per zero crossing -> y fp64 [n_out]
+ *   and / or yi int32 [n_out] (either may be null), n_out = acimg_resample_length(...).  Per output sample t, fp64, every
+ *   product and every sum rounded on its own (nothing is contracted into a fused multiply-add):
+ *     time = t * (1 / ratio);  n = (long)time;  scale = min(1, ratio);  step = (int)(scale * num_table)
+ *     frac = scale * (time - n);  pos = frac * num_table;  o = (int)pos;  eta = pos - o
+ *     y  = sum over i < min(n + 1, (nwin - o) / step), in order, of (win[o + i step] + eta delta[o + i step]) * x[n - i]
+ *     frac = scale - frac;  pos, o, eta again
+ *     y += sum over k < min(len - n - 1, (nwin - o) / step), in order, of (...) * x[n + k + 1]
+ *   y[t] = 0 for t >= *computed.  yi[t] = y[t] truncated toward zero, clamped to the int32 range.  ONE launch, one thread
+ *   per output sample; no atomics.  A null pointer, an argument below 1, n_out other than the query's value or a ratio
+ *   below 1 / num_table: ACIMG_EINVAL before the launch. */
+long acimg_resample_length(long len, int rate_in, int rate_out, long* computed);
+int acimg_resample_sinc(const int32_t* x, long len, int rate_in, int rate_out, const double* win, const double* delta, int nwin,
+                        int num_table, double* y, int32_t* yi, long n_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Inventory of the kernel instantiations libacimg.so ships, against tests/golden/kernel_inventory.json.
+"""Inventory of the kernel instantiations libacimg.so ships, against tests/golden/kernel_inventory.json and the add-on files
+tests/golden/kernel_inventory_<feature>.json beside it (same record format; the kernels of later features).
 
 Every __global__ function the library can launch has one host stub (`__device_stub__<name>`), so the stub symbols of
 the built library are the list of instantiations.  Only symbol NAMES are read (llvm-nm -C of the ROCm tree, else
@@ -19,6 +20,7 @@ fixture's `tests` lists were filled ("Kernel inventory").
                                                         kernel, kept from the old fixture otherwise
 """
 import argparse
+import glob
 import json
 import os
 import shutil
@@ -81,9 +83,21 @@ def library_kernels(lib_path):
     return sorted(names)
 
 
+def addon_paths():
+    """tests/golden/kernel_inventory_<feature>.json, sorted: the records of kernels added after the fixture was filled from
+    a trace.  A change that adds kernels adds a file of its own beside the fixture and leaves the fixture as it is."""
+    return sorted(glob.glob(os.path.join(os.path.dirname(FIXTURE), "kernel_inventory_*.json")))
+
+
 def load_fixture(path=FIXTURE):
+    """the records of `path`; of the fixture itself (the default): followed by those of its add-on files"""
     with open(path) as f:
-        return json.load(f)
+        records = json.load(f)
+    if path == FIXTURE:
+        for extra in addon_paths():
+            with open(extra) as f:
+                records += json.load(f)
+    return records
 
 
 def write_fixture(records, path=FIXTURE):
@@ -117,8 +131,11 @@ def main(argv=None):
         with open(args.update) as f:
             found = json.load(f)
         old = {r["kernel"]: r for r in load_fixture()} if os.path.exists(FIXTURE) else {}
+        elsewhere = {r["kernel"] for extra in addon_paths() for r in load_fixture(extra)}
         records = []
         for k in built:
+            if k in elsewhere:                   # its record lives in an add-on file and stays there
+                continue
             rec = dict(old.get(k, {"kernel": k, "tests": [], "seen": "reading"}))
             if k in found:
                 rec["tests"], rec["seen"] = sorted(found[k]["tests"]), found[k]["seen"]
