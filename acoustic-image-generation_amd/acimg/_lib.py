@@ -192,6 +192,10 @@ PROTOTYPES = {
     "acimg_jpeg_decode_colour": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "acimg_resample_length": (_L, [_L, _I, _I, C.POINTER(_L)]),
     "acimg_resample_sinc": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _L, _P]),
+    "acimg_deflate_bound": (_SZ, [_L]),
+    "acimg_deflate_workspace": (_SZ, [_L, _I]),
+    "acimg_deflate": (_I, [_P, C.POINTER(_L), _I, _P, _SZ, _P, _P, _SZ, _P]),
+    "acimg_huffman_lengths": (_I, [_P, _I, _I, _I, _P, _P]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

@@ -1,4 +1,5 @@
-"""`python -m acimg.convert ROOT_RAW_DIR OUT_DIR [--modalities 1 2] [--list FILE] [--device cuda:0] [--workers N]`:
+"""`python -m acimg.convert ROOT_RAW_DIR OUT_DIR [--modalities 1 2] [--list FILE] [--device cuda:0] [--workers N]
+[--deflate zlib|device]`:
 convert_data.py of the reference - raw recordings (`I_%06d.bmp` frames, one mono WAV) to the GZIP TFRecords of
 one-second `SequenceExample`s that every loader of this package reads.
 
@@ -17,6 +18,8 @@ one-second `SequenceExample`s that every loader of this package reads.
   crop window only.  24-bit `BI_RGB` files only; a frame whose resized size is below 224 x 298 is refused (the
   reference slices with a negative offset there), as is a change of geometry inside a recording.
 * workers: reading files and building + deflating records run on `--workers` threads; the device does the resize.
+  `--deflate device` (default `zlib`): the workers build and frame the records, and the calling thread hands what has
+  gathered to ONE `acimg.deflate.DeviceDeflater.compress_many` - RFC 1951 on the device, read by the same loaders.
 * a recording with fewer than 12 * video_time frames is refused before anything of it is written.
 * `--list FILE`: the produced paths, sorted, one per line - what `--train_file` takes (the list step of framecount.py)."""
 import argparse
@@ -276,6 +279,15 @@ def _write_record(path, rec, audio_steps, video_steps):
     return time.perf_counter() - t0
 
 
+def _frame_record(path, rec, audio_steps, video_steps):
+    """worker of `--deflate device`: build and frame one record -> (path, the file's uncompressed bytes, seconds spent)"""
+    from . import tfio
+    t0 = time.perf_counter()
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    buf = tfio.frame_record(build_record(rec, audio_steps, video_steps))
+    return path, buf, time.perf_counter() - t0
+
+
 def _read_frame(path, row, layout):
     """worker: one BMP file as it is into `row` (a uint8 view of the pinned staging buffer); returns seconds spent"""
     t0 = time.perf_counter()
@@ -291,12 +303,49 @@ def _read_frame(path, row, layout):
     return time.perf_counter() - t0
 
 
+DEFLATE_CHOICES = ("zlib", "device")
+
+
+def make_deflater(deflate, device):
+    """'zlib' -> None (the workers write through gzip.open); 'device' -> a DeviceDeflater"""
+    if deflate not in DEFLATE_CHOICES:
+        raise ConvertError("--deflate is one of %s, got %r" % (", ".join(DEFLATE_CHOICES), deflate))
+    if deflate == "zlib":
+        return None
+    from .deflate import DeviceDeflater
+    return DeviceDeflater(device)
+
+
+def drain_writes(writes, keep, deflater):
+    """wait for the oldest futures of `writes` until `keep` are left -> seconds of deflate.  With a deflater the futures
+    hold framed records, not written files: they are taken once twice `keep` have gathered (all of them for keep = 0),
+    compressed in one `compress_many` and written here."""
+    if deflater is None:
+        seconds = 0.0
+        while len(writes) > keep:
+            seconds += writes.popleft().result()
+        return seconds
+    if keep and len(writes) <= 2 * keep:
+        return 0.0
+    ready = []
+    while len(writes) > keep:
+        ready.append(writes.popleft().result())
+    if not ready:
+        return 0.0
+    from .deflate import write_gzip_files
+    t0 = time.perf_counter()
+    write_gzip_files(deflater, [(path, buf) for path, buf, _ in ready])
+    return sum(r[2] for r in ready) + time.perf_counter() - t0
+
+
 class Converter(object):
     """The pipeline of one `convert` call: `workers` threads read frames into pinned buffers and deflate finished
     records; the calling thread uploads a record's files, launches the resize and brings the 12 frames back.
-    `times`: seconds in read and deflate (summed over the workers), and in upload + resize + download (wall)."""
+    `times`: seconds in read and deflate (summed over the workers), and in upload + resize + download (wall).
+    `deflate="device"`: the workers only build and frame the records; the calling thread compresses what is ready in one
+    `DeviceDeflater.compress_many` and writes the files (its seconds count as deflate too)."""
 
-    def __init__(self, out_dir, modalities=None, device="cuda:0", workers=4, log=None):
+    def __init__(self, out_dir, modalities=None, device="cuda:0", workers=4, log=None, deflate="zlib"):
         self.out_dir = out_dir
         self.audio = modalities is None or 1 in modalities
         self.video = modalities is None or 2 in modalities
@@ -307,14 +356,14 @@ class Converter(object):
         self.records = 0
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="acimg-convert")
         self._writes = collections.deque()
+        self._deflater = make_deflater(deflate, device)
 
     def close(self):
         self._drain(0)
         self._exec.shutdown(wait=True)
 
     def _drain(self, keep):
-        while len(self._writes) > keep:
-            self.times["deflate"] += self._writes.popleft().result()
+        self.times["deflate"] += drain_writes(self._writes, keep, self._deflater)
 
     def _check(self, rec):
         """everything that can be refused before a byte of the recording is written -> (audio, layout)"""
@@ -367,18 +416,19 @@ class Converter(object):
                 torch.cuda.current_stream(resizer.device).synchronize()
                 self.times["device"] += time.perf_counter() - t0
                 video_steps = host[k % 2].numpy().copy()
-            self._writes.append(self._exec.submit(_write_record, paths[k], rec, audio_steps, video_steps))
+            self._writes.append(self._exec.submit(_write_record if self._deflater is None else _frame_record, paths[k], rec,
+                                                  audio_steps, video_steps))
             self._drain(2 * self.workers)
             self.records += 1
             self.log("{} - Writing {}".format(time.strftime("%Y-%m-%d %H:%M:%S"), paths[k]))
         return paths
 
 
-def convert(root_raw_dir, out_dir, modalities=None, list_file=None, device="cuda:0", workers=4, log=None):
+def convert(root_raw_dir, out_dir, modalities=None, list_file=None, device="cuda:0", workers=4, log=None, deflate="zlib"):
     """the whole data set -> (sorted list of the files written, the Converter with its `times`)"""
     root_raw_dir = os.path.abspath(os.path.expanduser(root_raw_dir))
     out_dir = os.path.abspath(os.path.expanduser(out_dir))
-    conv = Converter(out_dir, modalities, device, workers, log)
+    conv = Converter(out_dir, modalities, device, workers, log, deflate)
     paths = []
     try:
         for rec in find_recordings(root_raw_dir):
@@ -407,13 +457,15 @@ def build_parser():
     p.add_argument("--list", dest="list_file", help="write the produced paths, sorted, one per line (a --train_file)")
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--workers", type=int, default=4, help="threads that read frames and deflate records (at most 16)")
+    p.add_argument("--deflate", default="zlib", choices=DEFLATE_CHOICES,
+                   help="zlib: the workers gzip the records (level 9); device: the GPU deflates them, batched")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     paths, conv = convert(args.root_raw_dir, args.out_dir, args.modalities, args.list_file, args.device, args.workers,
-                          log=print)
+                          log=print, deflate=args.deflate)
     print("{} records; seconds in read {:.2f}, upload + resize {:.2f}, deflate {:.2f}".format(
         len(paths), conv.times["read"], conv.times["device"], conv.times["deflate"]))
     return 0

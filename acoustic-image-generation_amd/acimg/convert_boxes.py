@@ -1,4 +1,5 @@
-"""`python -m acimg.convert_boxes ROOT_RAW_DIR OUT_DIR [--modalities 1 2] [--device cuda:0] [--workers N] [--list FILE]`:
+"""`python -m acimg.convert_boxes ROOT_RAW_DIR OUT_DIR [--modalities 1 2] [--device cuda:0] [--workers N] [--list FILE]
+[--deflate zlib|device]`:
 convert_data2.py of the reference - the annotated Flickr-SoundNet files (`<id>.jpg`, `<id>.wav`, `<id>.xml`) to the GZIP
 TFRecords of one box-annotated `SequenceExample` each that `acimg.data.BoxRecordLoader` reads and
 `python -m acimg.localize --datatype flickr` scores.
@@ -25,7 +26,9 @@ TFRecords of one box-annotated `SequenceExample` each that `acimg.data.BoxRecord
   Mono PCM of 16 or 32 bits (`convert.read_wav`); stereo is refused by name (`data * 1.0` of a two-column array resamples
   the wrong axis there).
 * workers: reading + parsing files and building + deflating records run on `--workers` threads (at most 16); the calling
-  thread runs the device, `BATCH` files per launch (a file without restart markers is decoded by one lane)."""
+  thread runs the device, `BATCH` files per launch (a file without restart markers is decoded by one lane).
+  `--deflate device` (default `zlib`): as in `acimg.convert`, the workers frame the records and the calling thread
+  compresses a batch of them in one `DeviceDeflater.compress_many`."""
 import argparse
 import collections
 import concurrent.futures
@@ -38,7 +41,8 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
-from .convert import CROP_H, CROP_W, MAX_WORKERS, SAMPLE_RATE, ConvertError, FrameResizer, _str2dir, read_wav
+from .convert import (CROP_H, CROP_W, DEFLATE_CHOICES, MAX_WORKERS, SAMPLE_RATE, ConvertError, FrameResizer, _str2dir,
+                      drain_writes, make_deflater, read_wav)
 
 BATCH = 256
 ANNOTATION_SIDE = 256                 # :225-228: the scale is 298 / 256 and 224 / 256 whatever the file's size
@@ -230,11 +234,20 @@ def _write(path, boxes, scene, audio, video):
     return time.perf_counter() - t0
 
 
+def _frame(path, boxes, scene, audio, video):
+    """worker of `--deflate device`: build and frame one record -> (path, the file's uncompressed bytes, seconds spent)"""
+    from . import tfio
+    t0 = time.perf_counter()
+    buf = tfio.frame_record(build_box_record(boxes, scene, audio, video))
+    return path, buf, time.perf_counter() - t0
+
+
 class BoxConverter(object):
     """The pipeline of one `convert` call.  `times`: seconds in read and parse (summed over the workers), on the device
-    (upload + decode + resize + resample + download, wall) and in deflate (summed over the workers)."""
+    (upload + decode + resize + resample + download, wall) and in deflate (summed over the workers).  `deflate="device"`:
+    as in acimg.convert, the workers frame the records and the calling thread compresses a batch in one call."""
 
-    def __init__(self, modalities=None, device="cuda:0", workers=4, log=None, batch=BATCH):
+    def __init__(self, modalities=None, device="cuda:0", workers=4, log=None, batch=BATCH, deflate="zlib"):
         self.audio = modalities is None or 1 in modalities
         self.video = modalities is None or 2 in modalities
         self.device = device
@@ -245,6 +258,7 @@ class BoxConverter(object):
         self.records = 0
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="acimg-boxes")
         self._writes = collections.deque()
+        self._deflater = make_deflater(deflate, device)
         self._decoder = self._resampler = None
         self._resizers = {}
 
@@ -253,8 +267,7 @@ class BoxConverter(object):
         self._exec.shutdown(wait=True)
 
     def _drain(self, keep):
-        while len(self._writes) > keep:
-            self.times["deflate"] += self._writes.popleft().result()
+        self.times["deflate"] += drain_writes(self._writes, keep, self._deflater)
 
     def _device_side(self, items, loaded):
         """-> (frames uint8 [n,224,298,3] on the host or None, [int32 clip per file] or None)"""
@@ -299,7 +312,8 @@ class BoxConverter(object):
         frames, clips = self._device_side(items, loaded)
         self.times["device"] += time.perf_counter() - t0
         for k, (it, l) in enumerate(zip(items, loaded)):
-            self._writes.append(self._exec.submit(_write, it.out, l.boxes, l.scene, None if clips is None else clips[k],
+            self._writes.append(self._exec.submit(_write if self._deflater is None else _frame, it.out, l.boxes, l.scene,
+                                                  None if clips is None else clips[k],
                                                   None if frames is None else frames[k]))
             self.records += 1
             self.log("{} - Writing {}".format(time.strftime("%Y-%m-%d %H:%M:%S"), it.out))
@@ -307,12 +321,13 @@ class BoxConverter(object):
         return [it.out for it in items]
 
 
-def convert(root_raw_dir, out_dir, modalities=None, list_file=None, device="cuda:0", workers=4, log=None, batch=BATCH):
+def convert(root_raw_dir, out_dir, modalities=None, list_file=None, device="cuda:0", workers=4, log=None, batch=BATCH,
+            deflate="zlib"):
     """the whole data set -> (the files written, in walk order; the BoxConverter with its `times`)"""
     root_raw_dir = os.path.abspath(os.path.expanduser(root_raw_dir))
     out_dir = os.path.abspath(os.path.expanduser(out_dir))
     items = find_files(root_raw_dir, out_dir)
-    conv = BoxConverter(modalities, device, workers, log, batch)
+    conv = BoxConverter(modalities, device, workers, log, batch, deflate)
     paths = []
     try:
         for at in range(0, len(items), conv.batch):
@@ -332,13 +347,15 @@ def build_parser():
     p.add_argument("--list", dest="list_file", help="write the produced paths here instead of ROOT_RAW_DIR/test.txt")
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--workers", type=int, default=4, help="threads that read, parse and deflate (at most 16)")
+    p.add_argument("--deflate", default="zlib", choices=DEFLATE_CHOICES,
+                   help="zlib: the workers gzip the records (level 9); device: the GPU deflates them, batched")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     paths, conv = convert(args.root_raw_dir, args.out_dir, args.modalities, args.list_file, args.device, args.workers,
-                          log=print)
+                          log=print, deflate=args.deflate)
     print("{} records; seconds in read {:.2f}, parse {:.2f}, device {:.2f}, deflate {:.2f}".format(
         len(paths), conv.times["read"], conv.times["parse"], conv.times["device"], conv.times["deflate"]))
     return 0

@@ -12,8 +12,9 @@ def _chunk(kind, data):
     return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
 
 
-def encode_png(rgb_uint8, level=6):
-    """[H,W,3] uint8 -> the bytes of a PNG file"""
+def encode_png(rgb_uint8, level=6, deflater=None):
+    """[H,W,3] uint8 -> the bytes of a PNG file; `deflater` (an acimg.deflate.DeviceDeflater) compresses the scanlines on
+    the device instead of zlib at `level`"""
     a = np.asarray(rgb_uint8)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError("write_png wants a [H,W,3] uint8 array, got %s %s" % (a.dtype, a.shape))
@@ -21,12 +22,12 @@ def encode_png(rgb_uint8, level=6):
     rows = np.zeros((h, 1 + 3 * w), np.uint8)            # filter byte 0 in front of every scanline
     rows[:, 1:] = a.reshape(h, 3 * w)
     ihdr = struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)
-    return (SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(rows.tobytes(), int(level)))
-            + _chunk(b"IEND", b""))
+    idat = deflater.zlib(rows.tobytes()) if deflater is not None else zlib.compress(rows.tobytes(), int(level))
+    return SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", idat) + _chunk(b"IEND", b"")
 
 
-def write_png(path, rgb_uint8, level=6):
-    data = encode_png(rgb_uint8, level)
+def write_png(path, rgb_uint8, level=6, deflater=None):
+    data = encode_png(rgb_uint8, level, deflater)
     with open(path, "wb") as f:
         f.write(data)
     return len(data)

@@ -54,6 +54,8 @@ def build_parser():
         p.add_argument("--ae", type=int, default=0, help="1: plain auto-encoder generator (no sampling)")
         p.add_argument("--device", type=str, default="cuda:0")
         p.add_argument("--png_level", type=int, default=6, help="zlib level of the PNG files (0 - 9)")
+        p.add_argument("--png_deflate", type=str, default="zlib", choices=("zlib", "device"),
+                       help="device: the GPU deflates the PNG files' scanlines (acimg.deflate); --png_level is then unused")
 
     v = sub.add_parser("video", help="showvideo.py: the frames of a demo video")
     common(v)
@@ -175,6 +177,10 @@ def run(args, trainer=None, keep_energy=False, log=print):
         data = TFRecordDataLoader(args.train_file, args.batch_size, device=device, raw_audio=avi,
                                   modalities=(1, 2) if args.command == "video" else None)
     rend = OverlayRenderer(device)
+    deflater = None
+    if args.png_deflate == "device":
+        from .deflate import DeviceDeflater
+        deflater = DeviceDeflater(device)
     if avi:      # the whole clip is kept (the sound's peak is known only at its end): a few MB for ten seconds
         from .jpeg import JpegEncoder
         enc, jpegs, sound = JpegEncoder(device, args.quality, args.restart_mcus), [], []
@@ -201,7 +207,7 @@ def run(args, trainer=None, keep_energy=False, log=print):
         host = img.cpu().numpy()
         width = host.shape[2]
         for h in range(host.shape[0]):
-            write_png(frame_file(args, num), host[h], level=args.png_level)
+            write_png(frame_file(args, num), host[h], level=args.png_level, deflater=deflater)
             num += 1
         log("{} frames".format(num))
     if num == 0:

@@ -347,12 +347,23 @@ def read_tfrecord(path, compression=None, verify=True):
             yield data
 
 
-def write_tfrecord(path, records, compression=None):
+def frame_record(r):
+    """one record in the TFRecord framing: [u64 len][u32 masked crc32c(len)][data][u32 masked crc32c(data)]"""
+    head = struct.pack("<Q", len(r))
+    return head + struct.pack("<I", mask_crc(crc32c(head))) + r + struct.pack("<I", mask_crc(crc32c(r)))
+
+
+def write_tfrecord(path, records, compression=None, deflater=None):
+    """`deflater` (an acimg.deflate.DeviceDeflater) with "GZIP": the framed records are one buffer that the device
+    compresses into one gzip member; without one the file is written through `gzip.open` as ever"""
+    if deflater is not None and compression == "GZIP":
+        with open(path, "wb") as f:
+            f.write(deflater.gzip(b"".join(frame_record(r) for r in records)))
+        return
     f = gzip.open(path, "wb") if compression == "GZIP" else open(path, "wb")
     with f:
         for r in records:
-            head = struct.pack("<Q", len(r))
-            f.write(head + struct.pack("<I", mask_crc(crc32c(head))) + r + struct.pack("<I", mask_crc(crc32c(r))))
+            f.write(frame_record(r))
 
 
 def _parse_feature(buf):

@@ -1043,6 +1043,39 @@ int acimg_resample_sinc(const int32_t* x, long len, int rate_in, int rate_out, c
                         int num_table, double* y, int32_t* yi, long n_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DEFLATE (RFC 1951) on the device: the compressor of the GZIP records and the PNG files the tools write
+ * (`--deflate device`, `--png_deflate device`; the default stays the host's zlib).  csrc/deflate.hip has the stream layout,
+ * the parse rule and the code construction, tests/deflate_ref.py restates them bit for bit, DESIGN section 8 has the
+ * measurements.  (Added without raising ACIMG_VERSION.)
+ * A payload is cut into blocks of ACIMG_DEFLATE_BLOCK bytes, coded independently (no match reaches before its block), each
+ * as one stored or dynamic-Huffman block, whichever is smaller; every block but the last is followed by an empty stored
+ * block (4 or 5 bytes, the sync-flush form), the last carries BFINAL.  The stream is the same from run to run.
+ * acimg_deflate_bound (host only): the most bytes the stream of an n-byte payload can have, n + 10 ceil(n / BLOCK) + 5
+ *   (a stored block costs 5 bytes, the marker behind it 5 more; the 5 cover the empty payload's stored block, which the
+ *   CALLER writes: 01 00 00 FF FF).  0 for n < 0 or n > 2^40.
+ * acimg_deflate_workspace (host only): bytes of `ws` for `count` payloads of `total_bytes` bytes together: per block a
+ *   24-byte record, a byte count, an offset and a slot of BLOCK + 16 bytes, for total_bytes / BLOCK + count blocks.  0 for
+ *   an argument below 1 or count > total_bytes.
+ * acimg_deflate: in uint8 [sum of lengths] ON THE DEVICE, the payloads one behind the other; lengths long [count] ON THE
+ *   HOST, each >= 1 -> out uint8 [out_bytes], the raw streams one behind the other with no gap, and out_sizes long [count]
+ *   (device), each stream's bytes.  out_bytes >= the sum of acimg_deflate_bound(lengths[i]); only the streams' bytes are
+ *   written.  ws 16-byte aligned, ws_bytes >= acimg_deflate_workspace(sum of lengths, count).  The block table is copied
+ *   to the device and the stream is waited for once BEFORE the launches (the table is memory of the call); then three
+ *   launches: one workgroup per block (match, histogram, codes, bits), one workgroup for the offsets, one per block for
+ *   the dense copy.  A null pointer, count < 1, a length < 1, out_bytes below the bounds or a misaligned ws: ACIMG_EINVAL;
+ *   ws_bytes too small: ACIMG_EWORKSPACE; all before anything is launched.
+ * acimg_huffman_lengths: the code construction of the three alphabets on its own.  freq int32 [n][nsym] (device) ->
+ *   lengths uint8 [n][nsym]: 0 for freq <= 0, 1 for a single used symbol, else a complete prefix code (Kraft sum exactly
+ *   1) of lengths 1..limit that costs what an unlimited Huffman code costs whenever that fits the limit.  nsym 1..288,
+ *   limit 1..15 with 2^limit >= nsym, n >= 1, else ACIMG_EINVAL.  One launch, one workgroup per histogram. */
+#define ACIMG_DEFLATE_BLOCK 16384
+size_t acimg_deflate_bound(long n);
+size_t acimg_deflate_workspace(long total_bytes, int count);
+int acimg_deflate(const uint8_t* in, const long* lengths, int count, uint8_t* out, size_t out_bytes, long* out_sizes, void* ws,
+                  size_t ws_bytes, void* stream);
+int acimg_huffman_lengths(const int32_t* freq, int n, int nsym, int limit, uint8_t* lengths, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
  * ---------------------------------------------------------------------------------------- */

@@ -7,7 +7,8 @@
   share of source rows that more than one band of 8 output rows reads (from the tap tables; the L2 serves the second).
 * the converter end to end (`acimg.convert.convert`) on a tree of --seconds one-second records written to --tmp: records/s
   of wall time, and where the time goes: `read` and `deflate` are summed over the --workers threads, `device` (upload +
-  resize + download) is wall time of the calling thread.
+  resize + download) is wall time of the calling thread.  `--deflate device` compresses the records on the GPU
+  (acimg.deflate) instead of gzip level 9 on the workers; tools/bench_deflate.py runs both alternately.
 * the NumPy restatement (tests/convert_ref.py) of one frame on the host, for scale.
 Prints one JSON line.
 
@@ -44,6 +45,13 @@ def video_like(rng, n):
     return np.clip(smooth + rng.normal(0, 3, size=smooth.shape), 0, 255).astype(np.uint8)
 
 
+def write_tree(raw, rng, seconds):
+    """one recording of `seconds` one-second records under `raw`"""
+    import convert_ref as ref
+    os.makedirs(raw)
+    ref.write_recording(raw, 1, 1, seconds, video_like(rng, 12 * seconds), rng.randint(-2 ** 15, 2 ** 15, size=12288 * seconds))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=int, default=10)
@@ -51,6 +59,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--tmp", type=str, default=None)
+    ap.add_argument("--deflate", default="zlib", choices=("zlib", "device"))
     a = ap.parse_args()
     import convert_ref as ref
 
@@ -105,22 +114,19 @@ def main():
     tmp = tempfile.mkdtemp(prefix="bench_convert_", dir=a.tmp)
     try:
         raw, outd = os.path.join(tmp, "raw"), os.path.join(tmp, "out")
-        os.makedirs(raw)
-        frames = video_like(rng, 12 * a.seconds)
-        sound = rng.randint(-2 ** 15, 2 ** 15, size=12288 * a.seconds)
-        ref.write_recording(raw, 1, 1, a.seconds, frames, sound)
+        write_tree(raw, rng, a.seconds)
         rates, shares = [], []
         for rep in range(a.repeats + 1):          # the first pass is the warm-up (page cache, code objects)
             shutil.rmtree(outd, ignore_errors=True)
             os.makedirs(outd)
             t0 = time.perf_counter()
-            paths, conv = convert.convert(raw, outd, device=str(dev), workers=a.workers)
+            paths, conv = convert.convert(raw, outd, device=str(dev), workers=a.workers, deflate=a.deflate)
             dt = time.perf_counter() - t0
             if rep:
                 rates.append(len(paths) / dt)
                 tot = sum(conv.times.values())
                 shares.append({k: v / tot for k, v in conv.times.items()})
-        res["convert"] = dict(records=a.seconds, workers=a.workers, records_per_s=spread(rates),
+        res["convert"] = dict(records=a.seconds, workers=a.workers, deflate=a.deflate, records_per_s=spread(rates),
                               frames_per_s=spread([12 * r for r in rates]),
                               share={k: statistics.median(s[k] for s in shares) for k in shares[0]},
                               record_file_bytes=os.path.getsize(paths[0]))

@@ -9,7 +9,8 @@
 * the resampler alone (`acimg_resample_sinc`) on one 10 s clip at 44100 Hz: clips/s and output samples/s.
 * the converter end to end (`acimg.convert_boxes.convert`) on a tree of --files files written to --tmp: files/s of wall
   time, and where the time goes: `read`, `parse` and `deflate` are summed over the --workers threads, `device` (upload +
-  decode + resize + resample + download) is wall time of the calling thread.
+  decode + resize + resample + download) is wall time of the calling thread.  `--deflate device` compresses the records
+  on the GPU (acimg.deflate) instead of gzip level 9 on the workers; tools/bench_deflate.py runs both alternately.
 * where Pillow is importable, its decode rate of the same files on one host thread, for scale.
 Prints one JSON line.
 
@@ -64,6 +65,28 @@ def timed(dev, call, launches, repeats):
     return out
 
 
+def write_tree(raw, jpegs, clip, rate):
+    """ROOT/test_list.txt, Dataset/Data/0/<id>.{jpg,wav}, Dataset/Annotations/<id>.xml: one file per JPEG, all with `clip`"""
+    import convert_boxes_support as support
+    import convert_ref
+    data_dir, ann_dir = os.path.join(raw, "Dataset", "Data", "0"), os.path.join(raw, "Dataset", "Annotations")
+    os.makedirs(data_dir)
+    os.makedirs(ann_dir)
+    names = []
+    wav = convert_ref.wav_bytes(clip, rate=rate)
+    for i, f in enumerate(jpegs):
+        ident = "%06d" % i
+        names.append(ident + ".jpg")
+        with open(os.path.join(data_dir, ident + ".jpg"), "wb") as fh:
+            fh.write(f)
+        with open(os.path.join(data_dir, ident + ".wav"), "wb") as fh:
+            fh.write(wav)
+        with open(os.path.join(ann_dir, ident + ".xml"), "wb") as fh:
+            fh.write(support.annotation_xml(ident, [("object", 40, 50, 200, 220)]))
+    with open(os.path.join(raw, "test_list.txt"), "w") as fh:
+        fh.write("".join(nm + "\n" for nm in names))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=256)
@@ -71,10 +94,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--tmp", type=str, default=None)
+    ap.add_argument("--deflate", default="zlib", choices=("zlib", "device"))
     a = ap.parse_args()
-    import convert_boxes_support as support
-    import convert_ref
-
     from acimg import _lib, convert_boxes, jpeg, ops
 
     dev = torch.device("cuda:0")
@@ -139,33 +160,19 @@ def main():
     tmp = tempfile.mkdtemp(prefix="bench_convert_boxes_", dir=a.tmp)
     try:
         raw, outd = os.path.join(tmp, "raw"), os.path.join(tmp, "out")
-        data_dir, ann_dir = os.path.join(raw, "Dataset", "Data", "0"), os.path.join(raw, "Dataset", "Annotations")
-        os.makedirs(data_dir)
-        os.makedirs(ann_dir)
-        names = []
-        for i, f in enumerate(encoded["no_restart"]):
-            ident = "%06d" % i
-            names.append(ident + ".jpg")
-            with open(os.path.join(data_dir, ident + ".jpg"), "wb") as fh:
-                fh.write(f)
-            with open(os.path.join(data_dir, ident + ".wav"), "wb") as fh:
-                fh.write(convert_ref.wav_bytes(clip, rate=rate))
-            with open(os.path.join(ann_dir, ident + ".xml"), "wb") as fh:
-                fh.write(support.annotation_xml(ident, [("object", 40, 50, 200, 220)]))
-        with open(os.path.join(raw, "test_list.txt"), "w") as fh:
-            fh.write("".join(nm + "\n" for nm in names))
+        write_tree(raw, encoded["no_restart"], clip, rate)
         rates, shares = [], []
         for rep in range(a.repeats + 1):          # the first pass is the warm-up (page cache, code objects)
             shutil.rmtree(outd, ignore_errors=True)
             os.makedirs(outd)
             t0 = time.perf_counter()
-            paths, conv = convert_boxes.convert(raw, outd, device=str(dev), workers=a.workers)
+            paths, conv = convert_boxes.convert(raw, outd, device=str(dev), workers=a.workers, deflate=a.deflate)
             dt = time.perf_counter() - t0
             if rep:
                 rates.append(len(paths) / dt)
                 tot = sum(conv.times.values())
                 shares.append({k: v / tot for k, v in conv.times.items()})
-        res["convert"] = dict(files=n, workers=a.workers, clip_seconds=seconds, clip_rate=rate, files_per_s=spread(rates),
+        res["convert"] = dict(files=n, workers=a.workers, deflate=a.deflate, clip_seconds=seconds, clip_rate=rate, files_per_s=spread(rates),
                               share={k: statistics.median(s[k] for s in shares) for k in shares[0]},
                               record_file_bytes=os.path.getsize(paths[0]))
     finally:
