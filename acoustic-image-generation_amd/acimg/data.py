@@ -541,6 +541,34 @@ def _inflate_file(path, verify):
     return buf, [int(off[i]) for i in keep], [int(ln[i]) for i in keep], t1 - t0, time.perf_counter() - t1
 
 
+def _read_file(path):
+    """worker stage 0 of the device path: file -> (file image, its gzip plan or None, seconds)"""
+    from . import inflate as _inflate
+    t0 = time.perf_counter()
+    raw = np.fromfile(path, dtype=np.uint8)
+    return raw, _inflate.gzip_plan(raw), time.perf_counter() - t0
+
+
+def _index_file(path, raw, plan, data, status, end_bits, verify):
+    """worker stage 1 of the device path: the device's result for a file is checked against its container (CRC-32, ISIZE,
+    where the stream ends; the host's reader takes the file otherwise), then indexed as `_inflate_file` does"""
+    from . import _lib
+    from . import inflate as _inflate
+    lib = _lib.load()
+    t0 = time.perf_counter()
+    buf = _inflate.gzip_verify(raw, plan, data, status, end_bits)
+    t1 = time.perf_counter()
+    n = buf.size
+    count = lib.acimg_tfrecord_index(buf.ctypes.data, n, None, None, 0, int(bool(verify)))
+    if count < 0:
+        raise IOError("%s: %s" % (path, _lib.last_error()))
+    off = np.zeros(max(count, 1), dtype=np.uint64)
+    ln = np.zeros(max(count, 1), dtype=np.uint64)
+    lib.acimg_tfrecord_index(buf.ctypes.data, n, off.ctypes.data, ln.ctypes.data, count, 0)
+    keep = [i for i in range(count) if ln[i]]
+    return buf, [int(off[i]) for i in keep], [int(ln[i]) for i in keep], t1 - t0, time.perf_counter() - t1
+
+
 def _record_dims(buf, off, ln):
     """AcimgSequenceDims of the serialized SequenceExample at buf[off:off + ln] (sizes only)"""
     from . import _lib
@@ -632,6 +660,13 @@ class DeviceDataLoader(object):
       (asserted).  A batch is one `acimg_batch_gather_pairs` over row codes, still one int32 list uploaded per gather.
       `num_samples` / `total_batches` keep the reference's formulas (:973-976), which know nothing of the doubling;
       `num_rows` / `num_batches` are the true counts of a pass.
+    * inflate="device" (default "zlib": the workers' `acimg_gzip_inflate`, nothing changes): the workers read the files and
+      parse the gzip headers; the files of the look-ahead, up to `workers` of them, are inflated in ONE
+      `acimg.inflate.DeviceInflater.gunzip_device` call on the loader's stream and copied to pinned host memory; the workers
+      check each against its container (end of the stream, ISIZE, CRC-32) and index it, and hand whatever the device path
+      does not take - a second member, a failed stream, a mismatch - to `acimg_gzip_inflate`, which raises what it always
+      raised.  Everything after the inflated image is the same code.  `times["inflate"]` is then the host's share and
+      `times["inflate_device"]` the consuming thread's seconds in the grouped calls.
     `times` accumulates the host seconds of the stages (inflate, index, decode in the workers; upload, wait on the
     consuming thread)."""
 
@@ -640,10 +675,13 @@ class DeviceDataLoader(object):
 
     def __init__(self, files, batch_size, shuffle=False, buffer_size=None, seed=0, workers=4, prefetch=2, ring=4,
                  shard=None, num_actions=10, num_locations=61, device="cuda:0", compression_verify=True,
-                 frames_per_record=12, embedding=1, correspondence=0):
+                 frames_per_record=12, embedding=1, correspondence=0, inflate="zlib"):
         from . import ops
         from .flags import FLAGS
         from .frontend import FrontEnd
+        if inflate not in ("zlib", "device"):
+            raise ValueError("inflate is 'zlib' or 'device', got %r" % (inflate,))
+        self.inflate = inflate
         if isinstance(files, str):
             with open(files) as f:
                 files = [ln.strip() for ln in f if ln.strip()]
@@ -671,6 +709,11 @@ class DeviceDataLoader(object):
         self.stream = torch.cuda.Stream(device=self.device)
         self.data = self
         self.times = dict(inflate=0.0, index=0.0, decode=0.0, upload=0.0, wait=0.0)
+        self._inflater = None
+        if self.inflate == "device":
+            from .inflate import DeviceInflater
+            self._inflater = DeviceInflater(self.device)
+            self.times["inflate_device"] = 0.0       # the consumer's seconds in the grouped device calls, copy back included
         # decode window: enough records in the workers' hands to cover a batch while the consumer is away
         self._window = max(self.workers + self.prefetch, -(-frames // self.frames) + self.workers)
         self._num_samples = None
@@ -780,7 +823,11 @@ class DeviceDataLoader(object):
         files = iter(files)
         state = dict(cur=None, files_done=False)
 
-        def more_files():
+        read_q = collections.deque()             # the device path: files being read, ahead of the group being inflated
+
+        def more_files(block=True, group=True):
+            if self._inflater is not None:
+                return more_files_device(block, group)
             while not state["files_done"] and len(file_q) < self.workers:
                 p = next(files, None)
                 if p is None:
@@ -788,10 +835,36 @@ class DeviceDataLoader(object):
                 else:
                     file_q.append(ex.submit(_inflate_file, p, self.verify))
 
+        def more_files_device(block, group):
+            """reads run up to two groups ahead; when a file is wanted and no inflated one is left, the files of the
+            look-ahead, up to `workers` of them, are inflated in ONE call on the loader's stream and handed back to the
+            workers (not block: only if their reads have finished)"""
+            while not state["files_done"] and len(read_q) + len(file_q) < 2 * self.workers:
+                p = next(files, None)
+                if p is None:
+                    state["files_done"] = True
+                else:
+                    read_q.append((p, ex.submit(_read_file, p)))
+            if not group or file_q or not read_q:
+                return
+            if not block and not all(f.done() for _, f in list(read_q)[:self.workers]):
+                return
+            group = [read_q.popleft() for _ in range(min(self.workers, len(read_q)))]
+            t0 = time.perf_counter()
+            read = [f.result() for _, f in group]
+            self.times["wait"] += time.perf_counter() - t0
+            self.times["inflate"] += sum(r[2] for r in read)
+            t0 = time.perf_counter()
+            with torch.cuda.stream(self.stream):
+                got = self._inflater.gunzip_device([r[0] for r in read], [r[1] for r in read])
+            self.times["inflate_device"] += time.perf_counter() - t0
+            for (p, _), (raw, plan, _), (data, status, end_bits) in zip(group, read, got):
+                file_q.append(ex.submit(_index_file, p, raw, plan, data, status, end_bits, self.verify))
+
         def more_records(block=True):
             while len(rec_q) < self._window:
                 if state["cur"] is None:
-                    more_files()
+                    more_files(block)
                     if not file_q or not (block or file_q[0].done()):
                         return
                     t0 = time.perf_counter()
@@ -799,7 +872,7 @@ class DeviceDataLoader(object):
                     self.times["wait"] += time.perf_counter() - t0
                     self.times["inflate"] += t_inf
                     self.times["index"] += t_idx
-                    more_files()
+                    more_files(group=False)
                     state["cur"] = (buf, collections.deque(zip(offs, lens)))
                 buf, todo = state["cur"]
                 if not todo:
@@ -832,9 +905,11 @@ class DeviceDataLoader(object):
         finally:
             for fut in file_q:
                 fut.cancel()
+            for _, fut in read_q:
+                fut.cancel()
             for st, fut in rec_q:
                 fut.cancel()
-            concurrent.futures.wait([f for f in file_q] + [f for _, f in rec_q])
+            concurrent.futures.wait([f for f in file_q] + [f for _, f in read_q] + [f for _, f in rec_q])
             for st, _ in rec_q:
                 self._staging.append(st)
 

@@ -82,6 +82,8 @@ def parse(argv):
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--histograms", type=int, default=0)
+    ap.add_argument("--inflate", choices=["zlib", "device"], default="zlib",
+                    help="who inflates the GZIP records: the loader's worker threads (zlib) or the device (acimg.inflate)")
     extra = ap.parse_args(rest)
     for name in ("mode", "exp_name"):          # flags.mark_flags_as_required(['mode', 'exp_name']), main.py:366
         if getattr(FLAGS, name) is None:
@@ -116,10 +118,10 @@ def run_main(argv, log=print, hooks=None):
     if route == "classify":
         from . import classify
         rest = [a for a in argv]
-        for i in range(len(rest) - 1, -1, -1):      # --histograms is this module's own
-            if rest[i] == "--histograms":
+        for i in range(len(rest) - 1, -1, -1):      # --histograms and --inflate are this module's own
+            if rest[i] in ("--histograms", "--inflate"):
                 del rest[i:i + 2]
-            elif rest[i].startswith("--histograms="):
+            elif rest[i].startswith(("--histograms=", "--inflate=")):
                 del rest[i]
         return classify.run_main(rest, log=log)
     import torch
@@ -135,7 +137,7 @@ def run_main(argv, log=print, hooks=None):
             return None
         return DeviceDataLoader(files, FLAGS.batch_size, shuffle=shuffle, buffer_size=FLAGS.buffer_size if shuffle else None,
                                 embedding=FLAGS.embedding, num_actions=NUM_CLASSES, device=device,
-                                correspondence=FLAGS.correspondence)
+                                correspondence=FLAGS.correspondence, inflate=extra.inflate)
 
     log('{}: {} - Building model'.format(datetime.now(), FLAGS.exp_name))
     log('{}: {} - Building trainer'.format(datetime.now(), FLAGS.exp_name))

@@ -1076,6 +1076,59 @@ int acimg_deflate(const uint8_t* in, const long* lengths, int count, uint8_t* ou
 int acimg_huffman_lengths(const int32_t* freq, int n, int nsym, int limit, uint8_t* lengths, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * INFLATE (RFC 1951) on the device: the reader of GZIP records (`DeviceDataLoader(inflate="device")`, `--inflate device`;
+ * the default stays the host's zlib).  A general decoder: stored, fixed and dynamic blocks, whatever zlib's inflate
+ * accepts, this library's own streams included; the output equals zlib's byte for byte.  csrc/inflate.hip has the plan,
+ * tests/inflate_ref.py restates it, DESIGN section 8 has the measurements.  (Added without raising ACIMG_VERSION.)
+ * Streams are RAW deflate (the caller strips gzip / zlib containers).  A stream of n bytes is cut into chunks of
+ * `chunk_bytes` compressed bytes (a power of two, 256 .. 2^24); one call decodes every chunk of every stream:
+ *   find     a workgroup per chunk j >= 1 looks for the lowest bit offset of the chunk that passes as the header of a
+ *            non-final dynamic block (chunk 0 starts at bit 0);
+ *   count    a wave per chunk with a start decodes without writing, up to the first block boundary that is a later
+ *            chunk's start (its link) or past the BFINAL block;
+ *   chain    the links are walked from chunk 0: the chunks on the chain are live and get their output offsets;
+ *   decode   the live chunks decode again, into 16-bit symbols: a byte, or 0x8000 + (32768 - k) for "the byte k before
+ *            this chunk's first";
+ *   resolve  a workgroup per stream replaces the markers of each live chunk's last 32768 symbols, in chain order;
+ *   finish   every symbol becomes its byte.
+ * A chunk whose start is missing or wrong is decoded by the chunk before it: correctness never rests on the search.
+ * acimg_inflate_workspace (host only): bytes of `ws` for `count` streams of `total_src` bytes that inflate to `total_out`
+ *   bytes together: an AcimgInflateChunk for each of total_src / chunk_bytes + count chunks, an int32 per stream and a
+ *   uint16 per output byte, each part rounded up to 16 bytes.  0 for an argument below 1, count > total_src or a bad
+ *   chunk_bytes.
+ * acimg_inflate: src uint8 ON THE DEVICE, the streams one behind the other; src_lengths and out_lengths long [count] ON
+ *   THE HOST, each >= 1, an out_length below 2^31: the expected inflated sizes -> out uint8 [sum of out_lengths] (device),
+ *   the outputs one behind the other; status int32 [count] (device): ACIMG_INFLATE_OK or the first failure of a live
+ *   chunk; end_bits long [count] (device): the bit after the BFINAL block, 0 when status != 0.  The bytes of a stream
+ *   whose status is not 0 are unspecified.  Nothing outside a stream's own output extent or outside ws is written,
+ *   whatever the input.  The chunk table is copied to the device and the stream is waited for once BEFORE the launches;
+ *   no read-back happens between them.  A null pointer, count < 1, a length < 1, an out_length >= 2^31, a bad chunk_bytes
+ *   or a misaligned ws: ACIMG_EINVAL; ws_bytes too small: ACIMG_EWORKSPACE; all before anything is launched.
+ * Debug view: after the call `ws` begins with the AcimgInflateChunk records of all chunks, stream after stream, chunk
+ *   after chunk (ceil(src_length / chunk_bytes) per stream). */
+#define ACIMG_INFLATE_OK 0
+#define ACIMG_INFLATE_CORRUPT 1   /* an invalid code, code set or block type, LEN != ~NLEN, a distance before the stream */
+#define ACIMG_INFLATE_SIZE 2      /* more or fewer bytes than out_length */
+#define ACIMG_INFLATE_TRUNCATED 3 /* the stream ends before its BFINAL block does */
+typedef struct AcimgInflateChunk {
+    int64_t src_off, src_len;     /* host: the chunk's STREAM in `src` */
+    int64_t out_off, out_len;     /* host: that stream's extent in `out` */
+    int32_t stream, index;        /* host: the stream and the chunk's number j within it */
+    int32_t first, nchunks;       /* host: the stream's first record and its number of chunks */
+    int64_t start;                /* find: the chunk's first bit in the stream, -1: none */
+    int64_t end;                  /* count: the bit where it stopped (the link, or the bit after the BFINAL block) */
+    int64_t length;               /* count: the bytes it produces */
+    int64_t offset;               /* chain: where they go in the stream's output (live chunks) */
+    int32_t next;                 /* count: the chunk (number within the stream) it links to, -1: none */
+    int32_t status;               /* count: ACIMG_INFLATE_* */
+    int32_t live;                 /* chain: 1 on the chain from chunk 0 */
+    int32_t reserved;
+} AcimgInflateChunk;
+size_t acimg_inflate_workspace(long total_src, long total_out, int count, int chunk_bytes);
+int acimg_inflate(const uint8_t* src, const long* src_lengths, const long* out_lengths, int count, int chunk_bytes, uint8_t* out,
+                  int32_t* status, long* end_bits, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
  * ---------------------------------------------------------------------------------------- */

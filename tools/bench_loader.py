@@ -10,6 +10,7 @@ spread of each loader and whether the device loader's slowest pass beats the hos
 spreads together, and the device loader's host seconds per stage.
 
     python tools/bench_loader.py --files 16 --records 4 --batch 32 --repeats 3 [--train] [--shuffle] [--correspondence 1]
+                                 [--inflate device | both]
 
 --correspondence 1: both loaders apply the pair map (every frame a second time as its silent row), the shuffling device
 loader also its second shuffle stage; the rates then count ROWS, two per frame.
@@ -64,11 +65,13 @@ def write_file(path, content, records, seed):
 
 
 def make_loader(kind, files, a, dev, shuffle=False):
+    """kind: host, device, device_shuffle, or device_inflate (the device loader with inflate="device", under --inflate both)"""
     from acimg.data import DeviceDataLoader, TFRecordDataLoader
     if kind == "host":
         return TFRecordDataLoader(files, a.batch, device=dev, correspondence=a.correspondence)
+    inflate = "device" if kind == "device_inflate" else "zlib" if a.inflate == "both" else a.inflate
     return DeviceDataLoader(files, a.batch, shuffle=shuffle, seed=1, workers=a.workers, prefetch=a.prefetch, device=dev,
-                            correspondence=a.correspondence)
+                            correspondence=a.correspondence, inflate=inflate)
 
 
 def loader_pass(loader, dev):
@@ -94,6 +97,9 @@ def main():
     ap.add_argument("--shuffle", action="store_true", help="also time the device loader with shuffle=True")
     ap.add_argument("--train", action="store_true", help="time an epoch of Trainer.train() through each loader")
     ap.add_argument("--correspondence", type=int, default=0, choices=[0, 1], help="1: the pair map; rates count rows")
+    ap.add_argument("--inflate", default="zlib", choices=["zlib", "device", "both"],
+                    help="who inflates for the device loader: its workers' zlib or acimg.inflate on the device; both: the "
+                         "two as loaders of their own (device, device_inflate), alternating pass by pass")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     tr = None
@@ -112,6 +118,7 @@ def main():
         tr.log = lambda line: None
         tr._build_functions(batch_size=a.batch)
     kinds = list(a.loaders) + (["device_shuffle"] if a.shuffle and "device" in a.loaders else [])
+    kinds += ["device_inflate"] if a.inflate == "both" and "device" in a.loaders else []
     with tempfile.TemporaryDirectory(prefix="acimg_loader_") as tmp:
         for content in a.content:
             t0 = time.perf_counter()
@@ -123,10 +130,9 @@ def main():
             rows = frames * (2 if a.correspondence else 1)
             print(json.dumps(dict(content=content, files=a.files, frames=frames, gzip_mb=round(size / 1e6, 1),
                                   written_s=round(time.perf_counter() - t0, 1))), flush=True)
-            loaders = {k: make_loader("host" if k == "host" else "device", files, a, dev, shuffle=k == "device_shuffle")
-                       for k in kinds}
+            loaders = {k: make_loader(k, files, a, dev, shuffle=k == "device_shuffle") for k in kinds}
             for k in kinds:                                                       # untimed: first-use costs of either
-                warm = make_loader("host" if k == "host" else "device", files[:1], a, dev)
+                warm = make_loader(k, files[:1], a, dev)
                 loader_pass(warm, dev)
                 getattr(warm, "close", lambda: None)()
             if tr is not None:
@@ -137,7 +143,7 @@ def main():
                     if tr is None:
                         n, dt = loader_pass(loaders[k], dev)
                     else:
-                        valid = make_loader("host" if k == "host" else "device", files[:1], a, dev)
+                        valid = make_loader(k, files[:1], a, dev)
                         torch.cuda.synchronize(dev)
                         t0 = time.perf_counter()
                         tr.train(loaders[k], valid)
@@ -154,6 +160,11 @@ def main():
             if "host" in rates and "device" in rates:
                 spread = (max(rates["host"]) - min(rates["host"])) + (max(rates["device"]) - min(rates["device"]))
                 summary["device_above_host_by_more_than_the_spreads"] = bool(min(rates["device"]) - max(rates["host"]) > spread)
+            if "device" in rates and "device_inflate" in rates:
+                spread = ((max(rates["device"]) - min(rates["device"]))
+                          + (max(rates["device_inflate"]) - min(rates["device_inflate"])))
+                summary["device_inflate_above_zlib_by_more_than_the_spreads"] = bool(
+                    min(rates["device_inflate"]) - max(rates["device"]) > spread)
             print(json.dumps(summary), flush=True)
             for k in kinds:
                 if k != "host":
