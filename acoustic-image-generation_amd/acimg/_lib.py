@@ -198,6 +198,10 @@ PROTOTYPES = {
     "acimg_huffman_lengths": (_I, [_P, _I, _I, _I, _P, _P]),
     "acimg_inflate_workspace": (_SZ, [_L, _L, _I, _I]),
     "acimg_inflate": (_I, [_P, C.POINTER(_L), C.POINTER(_L), _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "acimg_checksum_workspace": (_SZ, [_L, _I]),
+    "acimg_checksum": (_I, [_P, C.POINTER(_L), _I, _I, _P, _P, C.POINTER(_L), _P, _SZ, _P]),
+    "acimg_record_gather_workspace": (_SZ, [_I]),
+    "acimg_record_gather": (_I, [_P, _P, C.POINTER(_L), _I, _P, _SZ, _P, _SZ, _P]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

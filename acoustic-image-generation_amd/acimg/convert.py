@@ -1,5 +1,5 @@
 """`python -m acimg.convert ROOT_RAW_DIR OUT_DIR [--modalities 1 2] [--list FILE] [--device cuda:0] [--workers N]
-[--deflate zlib|device]`:
+[--deflate zlib|device] [--assemble host|device]`:
 convert_data.py of the reference - raw recordings (`I_%06d.bmp` frames, one mono WAV) to the GZIP TFRecords of
 one-second `SequenceExample`s that every loader of this package reads.
 
@@ -20,6 +20,9 @@ one-second `SequenceExample`s that every loader of this package reads.
 * workers: reading files and building + deflating records run on `--workers` threads; the device does the resize.
   `--deflate device` (default `zlib`): the workers build and frame the records, and the calling thread hands what has
   gathered to ONE `acimg.deflate.DeviceDeflater.compress_many` - RFC 1951 on the device, read by the same loaders.
+  `--assemble device` (default `host`; needs `--deflate device`): the resized frames stay in a device pool, the workers
+  build only the records' skeletons (`tfio.build_record_layout`), and the calling thread assembles, checksums and
+  deflates a batch on the device (`acimg_record_gather`, `acimg_checksum`, `acimg_deflate`): the files are the same bytes.
 * a recording with fewer than 12 * video_time frames is refused before anything of it is written.
 * `--list FILE`: the produced paths, sorted, one per line - what `--train_file` takes (the list step of framecount.py)."""
 import argparse
@@ -288,6 +291,33 @@ def _frame_record(path, rec, audio_steps, video_steps):
     return path, buf, time.perf_counter() - t0
 
 
+def build_record_layout(rec, audio_steps, frame_bytes, shape):
+    """`tfio.frame_record(build_record(...))` as a layout: the video frames (shape = (steps, H, W, depth), None: no video)
+    are external values of `frame_bytes` bytes each"""
+    from . import tfio
+    ctx = collections.OrderedDict((("classes", np.array([rec.classes])), ("location", np.array([rec.location]))))
+    lists = collections.OrderedDict()
+    if audio_steps is not None:
+        ctx["audio_data/mics"] = np.array([1])
+        ctx["audio_data/samples"] = np.array([NUMBER_OF_SAMPLES])
+        lists["audio/data"] = [np.ascontiguousarray(a, dtype="<i4").tobytes() for a in audio_steps]
+    if shape is not None:
+        ctx["video/height"] = np.array([shape[1]])
+        ctx["video/width"] = np.array([shape[2]])
+        ctx["video/depth"] = np.array([shape[3]])
+        lists["video/image"] = [tfio.External(frame_bytes) for _ in range(shape[0])]
+    return tfio.build_record_layout(ctx, lists)
+
+
+def _layout_record(path, rec, audio_steps, slot):
+    """worker of `--assemble device`: the record's skeleton -> (path, layout, pool slot or None, seconds spent)"""
+    t0 = time.perf_counter()
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    shape = None if slot is None else (FRAMES_PER_SECOND, CROP_H, CROP_W, 3)
+    layout = build_record_layout(rec, audio_steps, CROP_H * CROP_W * 3, shape)
+    return path, layout, slot, time.perf_counter() - t0
+
+
 def _read_frame(path, row, layout):
     """worker: one BMP file as it is into `row` (a uint8 view of the pinned staging buffer); returns seconds spent"""
     t0 = time.perf_counter()
@@ -304,6 +334,7 @@ def _read_frame(path, row, layout):
 
 
 DEFLATE_CHOICES = ("zlib", "device")
+ASSEMBLE_CHOICES = ("host", "device")
 
 
 def make_deflater(deflate, device):
@@ -338,14 +369,75 @@ def drain_writes(writes, keep, deflater):
     return sum(r[2] for r in ready) + time.perf_counter() - t0
 
 
+class DeviceAssembler(object):
+    """`--assemble device`: a pool of frame slots on the device and the batch step that turns skeletons + slots into gzip
+    files.  One stream carries, for the whole batch: one skeleton upload, one `acimg_record_gather`, one `acimg_checksum`
+    (masked CRC-32C of the data spans, stored into the trailers), one `acimg_checksum` (CRC-32 of the framed records), one
+    `acimg_deflate`; then byte counts and CRCs come back in one small transfer and the packed streams in another."""
+
+    SLOT_BYTES = FRAMES_PER_SECOND * CROP_H * CROP_W * 3
+
+    def __init__(self, deflater, slots):
+        import torch
+
+        from .checksum import DeviceChecksum
+        self.deflater, self.device = deflater, deflater.device
+        self.sums = DeviceChecksum(self.device)
+        self.pool = torch.empty(int(slots), self.SLOT_BYTES, dtype=torch.uint8, device=self.device)
+        self.free = collections.deque(range(int(slots)))
+
+    def slot_frames(self, slot):
+        return self.pool[slot].view(FRAMES_PER_SECOND, CROP_H, CROP_W, 3)
+
+    def write(self, ready):
+        """ready: [(path, RecordLayout, slot or None)] -> the files; the slots are free again on return"""
+        import torch
+
+        from .checksum import CRC32, CRC32C_MASKED
+        from .deflate import GZIP_HEADER
+        frame = CROP_H * CROP_W * 3
+        skeleton = b"".join(lay.skeleton for _, lay, _ in ready)
+        sizes = [len(lay.skeleton) for _, lay, _ in ready]
+        segments, spans, stores, base = [], [], [], 0
+        for _, lay, slot in ready:
+            for off, n in lay.pieces():
+                segments.append((base + off, base + off, n, 0))
+            for j, (off, n) in enumerate(lay.holes):
+                segments.append((base + off, slot * self.SLOT_BYTES + j * frame, n, 1))
+            if spans:                               # the trailer before this record and its 12-byte header: a payload of
+                spans.append(16)                    # no interest that keeps the data spans one behind the other
+                stores.append(-1)
+            spans.append(lay.data[1])
+            stores.append(base + lay.trailer)
+            base += len(lay.skeleton)
+        src0 = torch.from_numpy(np.frombuffer(skeleton, np.uint8).copy()).to(self.device, non_blocking=False)
+        framed = torch.empty(base, dtype=torch.uint8, device=self.device)
+        self.sums.gather(src0, self.pool.view(-1), segments, framed)
+        self.sums.packed(framed[12:], spans, CRC32C_MASKED, framed, stores)
+        crcs = self.sums.packed(framed, sizes, CRC32)
+        streams, values = self.deflater._download(*self.deflater._launch(framed, sizes), sums=crcs)
+        for _, _, slot in ready:
+            if slot is not None:
+                self.free.append(slot)
+        for (path, _, _), stream, crc, n in zip(ready, streams, values, sizes):
+            with open(path, "wb") as f:
+                f.write(GZIP_HEADER + stream + struct.pack("<II", crc, n & 0xFFFFFFFF))
+
+
 class Converter(object):
     """The pipeline of one `convert` call: `workers` threads read frames into pinned buffers and deflate finished
     records; the calling thread uploads a record's files, launches the resize and brings the 12 frames back.
     `times`: seconds in read and deflate (summed over the workers), and in upload + resize + download (wall).
     `deflate="device"`: the workers only build and frame the records; the calling thread compresses what is ready in one
-    `DeviceDeflater.compress_many` and writes the files (its seconds count as deflate too)."""
+    `DeviceDeflater.compress_many` and writes the files (its seconds count as deflate too).
+    `assemble="device"` (with `deflate="device"`): the frames stay in a `DeviceAssembler`'s pool, the workers build
+    skeletons, and the calling thread assembles, checksums and deflates what is ready on the device."""
 
-    def __init__(self, out_dir, modalities=None, device="cuda:0", workers=4, log=None, deflate="zlib"):
+    def __init__(self, out_dir, modalities=None, device="cuda:0", workers=4, log=None, deflate="zlib", assemble="host"):
+        if assemble not in ASSEMBLE_CHOICES:
+            raise ConvertError("--assemble is one of %s, got %r" % (", ".join(ASSEMBLE_CHOICES), assemble))
+        if assemble == "device" and deflate != "device":
+            raise ConvertError("--assemble device needs --deflate device (the host's zlib wants the record in host memory)")
         self.out_dir = out_dir
         self.audio = modalities is None or 1 in modalities
         self.video = modalities is None or 2 in modalities
@@ -357,13 +449,27 @@ class Converter(object):
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="acimg-convert")
         self._writes = collections.deque()
         self._deflater = make_deflater(deflate, device)
+        # a batch is taken once more than 4 * workers records have gathered (drain_writes' rule) and its slots are free
+        # again when it has been downloaded: 4 * workers + 2 slots always leave one for the record being resized
+        self._assembler = DeviceAssembler(self._deflater, 4 * self.workers + 2) if assemble == "device" else None
 
     def close(self):
         self._drain(0)
         self._exec.shutdown(wait=True)
 
     def _drain(self, keep):
-        self.times["deflate"] += drain_writes(self._writes, keep, self._deflater)
+        if self._assembler is None:
+            self.times["deflate"] += drain_writes(self._writes, keep, self._deflater)
+            return
+        if keep and len(self._writes) <= 2 * keep:
+            return
+        ready = []
+        while len(self._writes) > keep:
+            ready.append(self._writes.popleft().result())
+        if ready:
+            t0 = time.perf_counter()
+            self._assembler.write([r[:3] for r in ready])
+            self.times["deflate"] += sum(r[3] for r in ready) + time.perf_counter() - t0
 
     def _check(self, rec):
         """everything that can be refused before a byte of the recording is written -> (audio, layout)"""
@@ -392,7 +498,8 @@ class Converter(object):
             resizer = FrameResizer(self.device, layout.height, layout.width)
             stride = layout.file_bytes
             staging = [torch.empty(FRAMES_PER_SECOND, stride, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            host = [torch.empty(FRAMES_PER_SECOND, CROP_H, CROP_W, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            if self._assembler is None:
+                host = [torch.empty(FRAMES_PER_SECOND, CROP_H, CROP_W, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
             dev = torch.empty(FRAMES_PER_SECOND, stride, dtype=torch.uint8, device=resizer.device)
 
             def read(k):      # record k (from 0) into staging set k % 2
@@ -401,7 +508,7 @@ class Converter(object):
                         for j in range(FRAMES_PER_SECOND)]
             reads = read(0)
         for k in range(rec.video_time):
-            audio_steps = video_steps = None
+            audio_steps = video_steps = slot = None
             if self.audio:
                 lo = FRAMES_PER_SECOND * k * NUMBER_OF_SAMPLES
                 audio_steps = audio[lo:lo + FRAMES_PER_SECOND * NUMBER_OF_SAMPLES].reshape(FRAMES_PER_SECOND, NUMBER_OF_SAMPLES)
@@ -411,24 +518,34 @@ class Converter(object):
                     reads = read(k + 1)
                 t0 = time.perf_counter()
                 dev.copy_(staging[k % 2], non_blocking=True)
-                out = resizer.resize(dev.reshape(-1), stride, layout.pixel_offset, layout.row_stride, FRAMES_PER_SECOND)
-                host[k % 2].copy_(out, non_blocking=True)
+                if self._assembler is not None:     # the frames stay on the device, in a slot of the pool
+                    slot = self._assembler.free.popleft()
+                    resizer.resize(dev.reshape(-1), stride, layout.pixel_offset, layout.row_stride, FRAMES_PER_SECOND,
+                                   out=self._assembler.slot_frames(slot))
+                else:
+                    out = resizer.resize(dev.reshape(-1), stride, layout.pixel_offset, layout.row_stride, FRAMES_PER_SECOND)
+                    host[k % 2].copy_(out, non_blocking=True)
                 torch.cuda.current_stream(resizer.device).synchronize()
                 self.times["device"] += time.perf_counter() - t0
-                video_steps = host[k % 2].numpy().copy()
-            self._writes.append(self._exec.submit(_write_record if self._deflater is None else _frame_record, paths[k], rec,
-                                                  audio_steps, video_steps))
+                if self._assembler is None:
+                    video_steps = host[k % 2].numpy().copy()
+            if self._assembler is not None:
+                self._writes.append(self._exec.submit(_layout_record, paths[k], rec, audio_steps, slot))
+            else:
+                self._writes.append(self._exec.submit(_write_record if self._deflater is None else _frame_record, paths[k], rec,
+                                                      audio_steps, video_steps))
             self._drain(2 * self.workers)
             self.records += 1
             self.log("{} - Writing {}".format(time.strftime("%Y-%m-%d %H:%M:%S"), paths[k]))
         return paths
 
 
-def convert(root_raw_dir, out_dir, modalities=None, list_file=None, device="cuda:0", workers=4, log=None, deflate="zlib"):
+def convert(root_raw_dir, out_dir, modalities=None, list_file=None, device="cuda:0", workers=4, log=None, deflate="zlib",
+            assemble="host"):
     """the whole data set -> (sorted list of the files written, the Converter with its `times`)"""
     root_raw_dir = os.path.abspath(os.path.expanduser(root_raw_dir))
     out_dir = os.path.abspath(os.path.expanduser(out_dir))
-    conv = Converter(out_dir, modalities, device, workers, log, deflate)
+    conv = Converter(out_dir, modalities, device, workers, log, deflate, assemble)
     paths = []
     try:
         for rec in find_recordings(root_raw_dir):
@@ -459,13 +576,15 @@ def build_parser():
     p.add_argument("--workers", type=int, default=4, help="threads that read frames and deflate records (at most 16)")
     p.add_argument("--deflate", default="zlib", choices=DEFLATE_CHOICES,
                    help="zlib: the workers gzip the records (level 9); device: the GPU deflates them, batched")
+    p.add_argument("--assemble", default="host", choices=ASSEMBLE_CHOICES,
+                   help="device (needs --deflate device): records are assembled and checksummed on the GPU, the same bytes")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     paths, conv = convert(args.root_raw_dir, args.out_dir, args.modalities, args.list_file, args.device, args.workers,
-                          log=print, deflate=args.deflate)
+                          log=print, deflate=args.deflate, assemble=args.assemble)
     print("{} records; seconds in read {:.2f}, upload + resize {:.2f}, deflate {:.2f}".format(
         len(paths), conv.times["read"], conv.times["device"], conv.times["deflate"]))
     return 0

@@ -4,8 +4,9 @@ zlib containers around them - what `--deflate device` of `python -m acimg.conver
 
 A payload is cut into blocks of BLOCK bytes that are coded independently; `compress_many` codes all blocks of all its
 payloads in ONE `acimg_deflate` call and brings back two transfers: the streams' byte counts and their packed bytes.
-The containers' checksums (CRC-32, Adler-32) are the host's `zlib.crc32` / `zlib.adler32`: the payload is host memory
-where the tools call this.  tests/deflate_ref.py restates the streams bit for bit."""
+The containers' checksums (CRC-32, Adler-32) of `gzip` / `zlib` are the host's `zlib.crc32` / `zlib.adler32`: the payload
+is host memory there.  `gzip_many` / `zlib_many` take payloads that live on the device and get their checksums from
+`acimg_checksum` (acimg/checksum.py) in the same stream.  tests/deflate_ref.py restates the streams bit for bit."""
 import ctypes as C
 import struct
 import zlib
@@ -59,17 +60,11 @@ class DeviceDeflater(object):
         if int(self.lib.acimg_deflate_bound(BLOCK)) != bound(BLOCK):
             raise _lib.AcimgError("libacimg.so codes blocks of another size than acimg.deflate.BLOCK = %d" % BLOCK)
 
-    def compress_many(self, payloads):
-        """payloads (bytes-like or uint8 tensors, on the host or the device) -> their raw streams as bytes, in order"""
-        tensors = [_as_u8(p) for p in payloads]
-        out = [EMPTY_STREAM if t.numel() == 0 else None for t in tensors]
-        work = [i for i, t in enumerate(tensors) if t.numel()]
-        if not work:
-            return out
+    def _launch(self, data, lengths):
+        """ONE `acimg_deflate` on the current stream: data uint8 on the device, payloads of `lengths` (each >= 1) one behind
+        the other -> (packed streams, their int64 byte counts), both on the device"""
         L = self.lib
-        lengths = [int(tensors[i].numel()) for i in work]
-        total, count = sum(lengths), len(work)
-        data = torch.cat([tensors[i].to(self.device) for i in work]) if count > 1 else tensors[work[0]].to(self.device).contiguous()
+        total, count = sum(lengths), len(lengths)
         out_bytes = sum(int(L.acimg_deflate_bound(n)) for n in lengths)
         ws_bytes = int(L.acimg_deflate_workspace(total, count))
         if ws_bytes == 0:
@@ -79,13 +74,68 @@ class DeviceDeflater(object):
         sizes = torch.empty(count, dtype=torch.int64, device=self.device)
         _lib.check(L.acimg_deflate(data.data_ptr(), (C.c_long * count)(*lengths), count, packed.data_ptr(), out_bytes,
                                    sizes.data_ptr(), ws.data_ptr(), ws_bytes, ops.current_stream_handle(self.device)), "deflate")
-        sizes = sizes.cpu().tolist()
-        host = packed[:sum(sizes)].cpu().numpy()
-        at = 0
-        for i, n in zip(work, sizes):
-            out[i] = host[at:at + n].tobytes()
-            at += n
+        return packed, sizes
+
+    @staticmethod
+    def _download(packed, sizes, sums=None):
+        """-> ([stream bytes], [checksum] or None): the byte counts (and the int32 checksums with them, in the same small
+        transfer), then the streams' bytes alone"""
+        count = sizes.numel()
+        head = sizes.view(torch.uint8) if sums is None else torch.cat([sizes.view(torch.uint8), sums.view(torch.uint8)])
+        head = head.cpu().numpy()
+        n = head[:8 * count].view(np.int64).tolist()
+        values = None if sums is None else [int(v) for v in head[8 * count:].view(np.uint32)]
+        host = packed[:sum(n)].cpu().numpy()
+        ends = np.cumsum(n).tolist()
+        return [host[e - k:e].tobytes() for e, k in zip(ends, n)], values
+
+    def _gather_payloads(self, payloads):
+        tensors = [_as_u8(p) for p in payloads]
+        work = [i for i, t in enumerate(tensors) if t.numel()]
+        lengths = [int(tensors[i].numel()) for i in work]
+        data = None
+        if work:
+            data = (torch.cat([tensors[i].to(self.device) for i in work]) if len(work) > 1
+                    else tensors[work[0]].to(self.device).contiguous())
+        return tensors, work, lengths, data
+
+    def compress_many(self, payloads):
+        """payloads (bytes-like or uint8 tensors, on the host or the device) -> their raw streams as bytes, in order"""
+        tensors, work, lengths, data = self._gather_payloads(payloads)
+        out = [EMPTY_STREAM if t.numel() == 0 else None for t in tensors]
+        if not work:
+            return out
+        streams, _ = self._download(*self._launch(data, lengths))
+        for i, s in zip(work, streams):
+            out[i] = s
         return out
+
+    def _containers(self, payloads, kind, host_sum, wrap):
+        from . import checksum
+        tensors, work, lengths, data = self._gather_payloads(payloads)
+        on_device = [isinstance(p, torch.Tensor) and p.device.type != "cpu" for p in payloads]
+        sums = [None if dev else host_sum(t.numpy()) & 0xFFFFFFFF for t, dev in zip(tensors, on_device)]
+        streams = [EMPTY_STREAM] * len(tensors)
+        device_sums = None
+        if work:
+            if any(on_device[i] for i in work):      # same stream, before the deflate launches: the payload stays where it is
+                device_sums = checksum.DeviceChecksum(self.device).packed(data, lengths, kind)
+            got, values = self._download(*self._launch(data, lengths), sums=device_sums)
+            for k, i in enumerate(work):
+                streams[i] = got[k]
+                if on_device[i]:
+                    sums[i] = values[k]
+        return [wrap(s, checksum.EMPTY[kind] if v is None else v, int(t.numel())) for s, v, t in zip(streams, sums, tensors)]
+
+    def gzip_many(self, payloads):
+        """payloads -> complete gzip members, in order.  A payload that is a device tensor never reaches the host: its
+        CRC-32 comes from `acimg_checksum` in the stream of `acimg_deflate`, and the download carries byte counts and
+        checksums together, then the streams.  Host bytes keep `zlib.crc32`; the result is the same either way."""
+        return self._containers(payloads, 0, zlib.crc32, lambda s, v, n: GZIP_HEADER + s + struct.pack("<II", v, n & 0xFFFFFFFF))
+
+    def zlib_many(self, payloads):
+        """payloads -> complete zlib streams, in order; the Adler-32 of a device tensor comes from the device"""
+        return self._containers(payloads, 3, zlib.adler32, lambda s, v, n: ZLIB_HEADER + s + struct.pack(">I", v))
 
     def deflate(self, data):
         """-> the raw RFC 1951 stream of `data`"""

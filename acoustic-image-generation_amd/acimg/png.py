@@ -26,6 +26,24 @@ def encode_png(rgb_uint8, level=6, deflater=None):
     return SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", idat) + _chunk(b"IEND", b"")
 
 
+def encode_png_many(frames, deflater):
+    """uint8 [n,H,W,3] (a device tensor, or an array) -> the bytes of n PNG files, each what
+    `encode_png(frame, deflater=deflater)` gives.  The filter-0 scanlines are formed on the device, every frame is
+    deflated in ONE call and its Adler-32 comes from the device (`DeviceDeflater.zlib_many`); the chunk CRCs over the
+    small compressed streams are the host's."""
+    import torch
+    f = torch.as_tensor(frames)
+    if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3 or f.shape[1] < 1 or f.shape[2] < 1:
+        raise ValueError("encode_png_many wants a [n,H,W,3] uint8 tensor, got %s %s" % (f.dtype, tuple(f.shape)))
+    n, h, w = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+    if n == 0:
+        return []
+    rows = torch.zeros(n, h, 1 + 3 * w, dtype=torch.uint8, device=deflater.device)     # filter byte 0, then the scanline
+    rows[:, :, 1:] = f.to(deflater.device).reshape(n, h, 3 * w)
+    ihdr = _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+    return [SIGNATURE + ihdr + _chunk(b"IDAT", idat) + _chunk(b"IEND", b"") for idat in deflater.zlib_many(list(rows))]
+
+
 def write_png(path, rgb_uint8, level=6, deflater=None):
     data = encode_png(rgb_uint8, level, deflater)
     with open(path, "wb") as f:

@@ -166,7 +166,7 @@ def run(args, trainer=None, keep_energy=False, log=print):
 
     from .data import BoxRecordLoader, TFRecordDataLoader
     from .evaluate import OverlayRenderer
-    from .png import write_png
+    from .png import encode_png_many, write_png
     device = torch.device(args.device)
     tr = trainer if trainer is not None else build_trainer(args, device)
     avi = args.command == "video" and bool(args.avi)
@@ -204,11 +204,17 @@ def run(args, trainer=None, keep_energy=False, log=print):
         if avi:
             jpegs.extend(enc.encode(img))
             sound.append(batch[6].numpy())
-        host = img.cpu().numpy()
-        width = host.shape[2]
-        for h in range(host.shape[0]):
-            write_png(frame_file(args, num), host[h], level=args.png_level, deflater=deflater)
-            num += 1
+        width = int(img.shape[2])
+        if deflater is not None:     # scanlines, Adler-32 and DEFLATE of the whole batch on the device: one call
+            for data in encode_png_many(img, deflater):
+                with open(frame_file(args, num), "wb") as f:
+                    f.write(data)
+                num += 1
+        else:
+            host = img.cpu().numpy()
+            for h in range(host.shape[0]):
+                write_png(frame_file(args, num), host[h], level=args.png_level)
+                num += 1
         log("{} frames".format(num))
     if num == 0:
         raise ValueError("no samples in %s" % args.train_file)

@@ -439,6 +439,94 @@ def build_sequence_example(context, feature_lists):
     return _ld(1, ctx) + _ld(2, fls)
 
 
+# ---- the layout form: a framed record whose large bytes values are filled in elsewhere ------------------------------------
+class External(object):
+    """stands for a bytes value of `nbytes` bytes in `build_record_layout`: the value itself lies elsewhere (on the
+    device) and is copied into the record's hole later"""
+
+    def __init__(self, nbytes):
+        self.nbytes = int(nbytes)
+        if self.nbytes < 0:
+            raise ValueError("an external value has %d bytes" % self.nbytes)
+
+
+class RecordLayout(object):
+    """skeleton: the FRAMED record ([u64 len][u32 masked crc32c(len)][data][4 bytes of room for the trailer]) with every
+    protobuf key, varint and inline value in place and zeros in the holes; holes: [(offset, length)] of the external
+    values within the skeleton, in the order of the arguments; data: (offset, length) of the span the trailer's CRC-32C
+    covers; trailer: the offset of the trailer's four bytes"""
+
+    def __init__(self, skeleton, holes, data, trailer):
+        self.skeleton, self.holes, self.data, self.trailer = skeleton, holes, data, trailer
+
+    def pieces(self):
+        """[(offset, length)] of the skeleton's bytes outside the holes and the trailer, in order, none empty"""
+        out, at = [], 0
+        for off, n in self.holes + [(self.trailer, 4)]:
+            if off > at:
+                out.append((at, off - at))
+            at = off + n
+        return out
+
+    def fill(self, values):
+        """host completion (tests, tools): the holes' bytes and the trailer -> the framed record"""
+        buf = bytearray(self.skeleton)
+        if len(values) != len(self.holes):
+            raise ValueError("%d values for %d holes" % (len(values), len(self.holes)))
+        for (off, n), v in zip(self.holes, values):
+            if len(v) != n:
+                raise ValueError("a value of %d bytes for a hole of %d" % (len(v), n))
+            buf[off:off + n] = v
+        off, n = self.data
+        buf[self.trailer:self.trailer + 4] = struct.pack("<I", mask_crc(crc32c(bytes(buf[off:off + n]))))
+        return bytes(buf)
+
+
+def _parts_len(parts):
+    return sum(p.nbytes if isinstance(p, External) else len(p) for p in parts)
+
+
+def _ld_parts(fn, parts):
+    return [_key(fn, 2) + _put_varint(_parts_len(parts))] + parts
+
+
+def _feature_parts(val):
+    if isinstance(val, External):
+        val = [val]
+    if isinstance(val, list) and any(isinstance(x, External) for x in val):
+        inner = []
+        for x in val:
+            inner += _ld_parts(1, [x if isinstance(x, External) else bytes(x)])
+        return _ld_parts(1, inner)
+    return [_build_feature(val)]
+
+
+def build_record_layout(context, feature_lists):
+    """`frame_record(build_sequence_example(context, feature_lists))` where some bytes values are `External(nbytes)`
+    (a value, or members of a bytes list) -> RecordLayout.  Filling the holes and the trailer gives that record byte for
+    byte; without an external value the skeleton lacks only its trailer."""
+    ctx, fls = [], []
+    for k, v in context.items():
+        ctx += _ld_parts(1, [_ld(1, k.encode("utf-8"))] + _ld_parts(2, _feature_parts(v)))
+    for k, steps in feature_lists.items():
+        inner = []
+        for x in steps:
+            inner += _ld_parts(1, _feature_parts(x))
+        fls += _ld_parts(1, [_ld(1, k.encode("utf-8"))] + _ld_parts(2, inner))
+    parts = _ld_parts(1, ctx) + _ld_parts(2, fls)
+    n = _parts_len(parts)
+    head = struct.pack("<Q", n)
+    buf, holes = bytearray(head + struct.pack("<I", mask_crc(crc32c(head)))), []
+    for p in parts:
+        if isinstance(p, External):
+            holes.append((len(buf), p.nbytes))
+            buf += bytes(p.nbytes)
+        else:
+            buf += p
+    buf += bytes(4)
+    return RecordLayout(bytes(buf), holes, (12, n), 12 + n)
+
+
 # ---- native reader (libacimg.so: csrc/records.hip) -----------------------------------------------------------------
 def read_tfrecord_native(path, verify=True):
     """[record payload bytes] of a (GZIP or plain) TFRecord file through the C++ reader behind the C ABI

@@ -1129,6 +1129,51 @@ int acimg_inflate(const uint8_t* src, const long* src_lengths, const long* out_l
                   int32_t* status, long* end_bits, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The containers' checksums on the device, and the gather that assembles framed records there (`--assemble device` of
+ * `python -m acimg.convert`, `png.encode_png_many`; the default stays the host).  csrc/checksum.hip has the algebra and
+ * the plan, tests/checksum_ref.py restates the algebra, DESIGN section 8 has the measurements.  (Added without raising
+ * ACIMG_VERSION.)
+ * The definitions are the standards': CRC-32 reflected 0xEDB88320 and CRC-32C reflected 0x82F63B78, init and final XOR
+ * 0xFFFFFFFF; kind 2 is kind 1 under the TFRecord mask, ((crc >> 15 | crc << 17) + 0xa282ead8); Adler-32 mod 65521 with
+ * A starting at 1.  Every value equals zlib.crc32 / acimg_crc32c(data, n, 0) / zlib.adler32 bit for bit; no atomics, so a
+ * second run gives the same bits.  A payload of 0 bytes yields the standard's value (0, 0, the mask of 0, 1) with no
+ * segment launched for it.
+ * A payload is cut on the grid of ACIMG_CHECKSUM_SEGMENT absolute bytes of `in`'s address range, one workgroup per cut.
+ * acimg_checksum_workspace (host only): bytes of `ws` for `count` payloads of `total_bytes` bytes together: a 24-byte
+ *   record and an 8-byte value for each of total_bytes / SEGMENT + 2 count segments and a 24-byte record per payload,
+ *   each part rounded up to 16 bytes.  0 for total_bytes < 0 or count < 1.
+ * acimg_checksum: in uint8 [sum of lengths] ON THE DEVICE, the payloads one behind the other (so a payload starts at any
+ *   byte address); lengths long [count] ON THE HOST, each 0 .. 2^31 - 1 -> out uint32 [count] (device).  store_at: NULL, or
+ *   long [count] ON THE HOST: where store_at[i] >= 0, payload i's value is also written little-endian into the four bytes
+ *   at store_base + store_at[i] (device memory of the caller, any alignment; it may lie in `in`: every payload of the
+ *   call has been read before the first store, so a value never depends on one); negative: no store.  ws 16-byte
+ *   aligned.  The segment and
+ *   payload tables (with the host-built multipliers x^(8 bytes behind) mod P) are copied to the device and the stream is
+ *   waited for once BEFORE the launches (the tables are memory of the call); then two launches: one workgroup per segment,
+ *   one wave per payload (reduction, init term, final XOR, mask, store).  A null pointer (store_base may be NULL without
+ *   store_at), count < 1, a length < 0 or >= 2^31, an unknown kind or a misaligned ws: ACIMG_EINVAL; ws_bytes too small:
+ *   ACIMG_EWORKSPACE; all before anything is launched.
+ * acimg_record_gather_workspace (host only): 32 bytes per segment, rounded up to 16; 0 for nseg < 1.
+ * acimg_record_gather: segments long [nseg][4] ON THE HOST, rows {dst_off, src_off, len, which}: the len bytes at
+ *   src0 + src_off (which = 0: e.g. an uploaded skeleton) or src1 + src_off (which = 1: e.g. a pool of device frames) are
+ *   copied to dst + dst_off.  A byte-exact copy; no offset or length has an alignment requirement, len may be 0, and
+ *   bytes of dst that no segment covers are not written.  The host refuses (ACIMG_EINVAL) a null segments / dst / ws, a
+ *   null source that a segment names, which outside {0, 1}, a negative offset or length, a segment that leaves
+ *   [0, dst_bytes) and two segments that overlap in dst; a short ws is ACIMG_EWORKSPACE; the sources' extents are the
+ *   caller's to know.  The table is copied and the stream waited for once before the ONE launch. */
+#define ACIMG_CHECKSUM_CRC32         0   /* zlib / gzip / PNG */
+#define ACIMG_CHECKSUM_CRC32C        1   /* Castagnoli: = acimg_crc32c(data, n, 0) */
+#define ACIMG_CHECKSUM_CRC32C_MASKED 2   /* TFRecord: tfio.mask_crc of kind 1 */
+#define ACIMG_CHECKSUM_ADLER32       3   /* zlib container */
+#define ACIMG_CHECKSUM_SEGMENT 16384
+size_t acimg_checksum_workspace(long total_bytes, int count);
+int acimg_checksum(const uint8_t* in, const long* lengths, int count, int kind, uint32_t* out, uint8_t* store_base,
+                   const long* store_at, void* ws, size_t ws_bytes, void* stream);
+size_t acimg_record_gather_workspace(int nseg);
+int acimg_record_gather(const uint8_t* src0, const uint8_t* src1, const long* segments, int nseg, uint8_t* dst, size_t dst_bytes,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
  * ---------------------------------------------------------------------------------------- */

@@ -14,9 +14,16 @@ tools compress, and the two converters end to end with each value of their --def
 * end to end: `acimg.convert.convert` on --seconds records and `acimg.convert_boxes.convert` on --files files, --repeats
   times each with `deflate="device"` and `deflate="zlib"` ALTERNATELY after one warm-up pass of each; records (files)
   per second of wall time and deflate's share of the summed seconds.
+* `--assemble host|device|both` (default host: nothing more is run): ONE `acimg_checksum` over 8 device-resident records per
+  kind (device events over --launches calls; a call waits for its tables once) beside `zlib.crc32`, `acimg_crc32c` and
+  `zlib.adler32` over the same bytes on one host thread; one `acimg_record_gather` of those 8 records; and
+  `acimg.convert.convert` with `deflate="device"` and the chosen value(s) of `assemble`, for `both` ALTERNATELY after one
+  warm-up pass of each: records per second (min - max over --repeats) and the split of `Converter.times`.
+  `--skip_payloads` leaves out the per-payload and per-block parts.
 Prints one JSON line.
 
     python tools/bench_deflate.py --seconds 10 --files 64 --workers 4 --repeats 3
+    python tools/bench_deflate.py --seconds 10 --workers 4 --repeats 3 --assemble both --skip_payloads --no_convert
 """
 import argparse
 import ctypes as C
@@ -89,6 +96,57 @@ class RawCall(object):
         return out
 
 
+def event_seconds(dev, call, launches, repeats):
+    for _ in range(3):
+        call()
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        e0.record()
+        for _ in range(launches):
+            call()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        out.append(e0.elapsed_time(e1) * 1e-3 / launches)
+    return out
+
+
+def checksum_part(dev, record, a):
+    """one acimg_checksum over 8 copies of `record` on the device, per kind, and the host's checksums of the same bytes"""
+    from acimg import _lib, checksum, tfio
+    count = 8
+    data = torch.from_numpy(np.frombuffer(record * count, np.uint8).copy()).to(dev)
+    lengths = [len(record)] * count
+    dc = checksum.DeviceChecksum(dev)
+    L = _lib.load()
+    host = {0: lambda b: zlib.crc32(b), 1: lambda b: L.acimg_crc32c(b, len(b), 0), 2: lambda b: tfio.mask_crc(L.acimg_crc32c(b, len(b), 0)),
+            3: lambda b: zlib.adler32(b)}
+    out = dict(records=count, bytes_each=len(record))
+    for kind, name in ((0, "crc32"), (1, "crc32c"), (2, "crc32c_masked"), (3, "adler32")):
+        got = dc.values(dc.packed(data, lengths, kind))
+        assert got == [host[kind](record) & 0xFFFFFFFF] * count, name
+        dev_s = event_seconds(dev, lambda: dc.packed(data, lengths, kind), a.launches, a.repeats)
+        host_s = host_seconds(lambda: [host[kind](record) for _ in range(count)], a.repeats)
+        out[name] = dict(device_call_us=spread([t * 1e6 for t in dev_s]), host_one_thread_us=spread([t * 1e6 for t in host_s]))
+    # the gather of the same 8 records: 13 skeleton pieces and 12 frames each, frames at the offsets they have in a record
+    from acimg import convert
+    lay = convert.build_record_layout(convert.Recording("", 1, 1, 1, "", ""), np.zeros((12, 1024), np.int32), 224 * 298 * 3,
+                                      (12, 224, 298, 3))
+    assert len(lay.skeleton) == len(record)
+    pool = torch.zeros(count, 12 * 224 * 298 * 3, dtype=torch.uint8, device=dev)
+    skel = torch.from_numpy(np.frombuffer(lay.skeleton * count, np.uint8).copy()).to(dev)
+    rows, base = [], 0
+    for r in range(count):
+        rows += [(base + o, base + o, n, 0) for o, n in lay.pieces()]
+        rows += [(base + o, r * pool.shape[1] + j * n, n, 1) for j, (o, n) in enumerate(lay.holes)]
+        base += len(lay.skeleton)
+    dst = torch.empty(base, dtype=torch.uint8, device=dev)
+    t = event_seconds(dev, lambda: dc.gather(skel, pool.view(-1), rows, dst), a.launches, a.repeats)
+    out["record_gather"] = dict(segments=len(rows), device_call_us=spread([x * 1e6 for x in t]))
+    return out
+
+
 def payloads(rng, dev):
     import bench_convert
     import bench_convert_boxes
@@ -112,6 +170,40 @@ def payloads(rng, dev):
     return (("convert_record_12_frames", record), ("box_record", box), ("png_rows_224x298", rows.tobytes()))
 
 
+def assemble_part(dev, rng, a):
+    """acimg.convert.convert with deflate="device" and each chosen value of `assemble`, alternately"""
+    import bench_convert
+
+    from acimg import convert
+    modes = ("host", "device") if a.assemble == "both" else (a.assemble,)
+    tmp = tempfile.mkdtemp(prefix="bench_assemble_", dir=a.tmp)
+    try:
+        raw, outd = os.path.join(tmp, "raw"), os.path.join(tmp, "out")
+        bench_convert.write_tree(raw, rng, a.seconds)
+        rates, times, digest = {m: [] for m in modes}, {m: [] for m in modes}, {}
+        for rep in range(a.repeats + 1):              # the first pass of each is the warm-up
+            for mode in modes:
+                shutil.rmtree(outd, ignore_errors=True)
+                os.makedirs(outd)
+                t0 = time.perf_counter()
+                paths, conv = convert.convert(raw, outd, device=str(dev), workers=a.workers, deflate="device", assemble=mode)
+                dt = time.perf_counter() - t0
+                digest[mode] = [zlib.crc32(open(p, "rb").read()) for p in paths]
+                if rep:
+                    rates[mode].append(len(paths) / dt)
+                    times[mode].append(dict(conv.times))
+        out = {m: dict(per_s=spread(rates[m]),
+                       times_s={k: statistics.median(t[k] for t in times[m]) for k in ("read", "device", "deflate")},
+                       deflate_share=statistics.median(t["deflate"] / sum(t.values()) for t in times[m])) for m in modes}
+        out.update(workers=a.workers, records=a.seconds)
+        if len(modes) == 2:
+            out["same_files"] = digest["host"] == digest["device"]
+            out["slowest_device_above_fastest_host"] = out["device"]["per_s"]["min"] > out["host"]["per_s"]["max"]
+        return out
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=int, default=10)
@@ -121,6 +213,9 @@ def main():
     ap.add_argument("--launches", type=int, default=10)
     ap.add_argument("--tmp", type=str, default=None)
     ap.add_argument("--no_convert", action="store_true", help="the payloads and the blocks alone (a kernel-trace run)")
+    ap.add_argument("--assemble", default="host", choices=("host", "device", "both"),
+                    help="device / both: time acimg_checksum and the converter with --assemble device (both: against host)")
+    ap.add_argument("--skip_payloads", action="store_true", help="leave out the per-payload and per-block parts")
     a = ap.parse_args()
     import bench_convert
     import bench_convert_boxes
@@ -136,7 +231,8 @@ def main():
     res = dict(block=BLOCK, repeats=a.repeats, launches=a.launches)
 
     # ---- the payloads ---------------------------------------------------------------------------------------------------------
-    for name, p in payloads(rng, dev):
+    named = payloads(rng, dev)
+    for name, p in ([] if a.skip_payloads else named):
         mb = len(p) * 1e-6
         stream = dd.deflate(p)
         assert zlib.decompress(stream, -15) == p, name
@@ -149,6 +245,13 @@ def main():
         one["crc32_ms"] = min(host_seconds(lambda: zlib.crc32(p), a.repeats)) * 1e3
         one["adler32_ms"] = min(host_seconds(lambda: zlib.adler32(p), a.repeats)) * 1e3
         res[name] = one
+
+    if a.assemble != "host":
+        res["checksum_8_records"] = checksum_part(dev, named[0][1], a)
+        res["assemble"] = assemble_part(dev, rng, a)
+    if a.skip_payloads:
+        print(json.dumps(res))
+        return
 
     # ---- one block ------------------------------------------------------------------------------------------------------------
     blocks = dict(zeros=bytes(BLOCK), smooth=deflate_cases.smooth_fixture()[:BLOCK],

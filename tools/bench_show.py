@@ -34,7 +34,7 @@ def main():
     import render_ref
     from acimg import colormaps, ops
     from acimg.evaluate import OverlayRenderer
-    from acimg.png import encode_png
+    from acimg.png import encode_png, encode_png_many
 
     dev = torch.device("cuda:0")
     tr = None
@@ -96,6 +96,12 @@ def main():
             t3 = time.perf_counter()
         nbytes = sum(len(encode_png(host[j], a.png_level, deflater)) for j in range(k))
         t4 = time.perf_counter()
+        if deflater is not None:      # what show.py's device branch calls: the batch from the device tensor, one call
+            encode_png_many(out[:k], deflater)
+            t5 = time.perf_counter()
+            many = encode_png_many(out[:k], deflater)
+            res.update(png_many_ms_per_frame=(time.perf_counter() - t5) * 1e3 / k,
+                       png_many_equals_per_frame=many == [encode_png(host[j], deflater=deflater) for j in range(k)])
         res.update(copy_ms_per_frame=(t1 - t0) * 1e3 / n, numpy_ms_per_frame=(t3 - t2) * 1e3 / k,
                    png_ms_per_frame=(t4 - t3) * 1e3 / k, png_bytes_per_frame=nbytes // k, png_level=a.png_level, png_deflate=a.png_deflate,
                    matches_numpy=bool(same))
