@@ -139,9 +139,14 @@ def extend(v, s):
     return v - (1 << s) + 1 if s and v < (1 << (s - 1)) else v
 
 
-def entropy(info, end=None):
+def entropy(info, end=None, reached=None):
     """walk the scan MCU by MCU -> (coef int16 [mcus][blocks][64] natural order, status, [offset of each interval's first
-    byte from the scan's start]); after a nonzero status the rest of the image is zero"""
+    byte from the scan's start]); after a nonzero status the rest of the image is zero.  reached: a dict that receives the
+    largest DC category, AC size, DC and AC code length and |DC|, |AC| coefficient that the walk decoded"""
+    seen = dict(dc_category=0, ac_size=0, dc_code_bits=0, ac_code_bits=0, dc_abs=0, ac_abs=0)
+
+    def note(key, value):
+        seen[key] = max(seen[key], value)
     data = info.data
     end = len(data) if end is None else end
     coef = np.zeros((info.mcus, info.blocks, 64), np.int16)
@@ -163,6 +168,8 @@ def entropy(info, end=None):
                     return coef, STATUS_BAD_CODE, offsets
                 bits.skip(e >> 8)
                 s = e & 255
+                note("dc_code_bits", e >> 8)
+                note("dc_category", s)
                 pred[c] += extend(bits.take(s), s)
                 if bits.overrun():
                     return coef, STATUS_EARLY_END, offsets
@@ -175,6 +182,8 @@ def entropy(info, end=None):
                         return coef, STATUS_BAD_CODE, offsets
                     bits.skip(e >> 8)
                     r, s = (e >> 4) & 15, e & 15
+                    note("ac_code_bits", e >> 8)
+                    note("ac_size", s)
                     if s:
                         k += r
                         if k > 63:
@@ -190,6 +199,10 @@ def entropy(info, end=None):
                 if bits.overrun():
                     return coef, STATUS_EARLY_END, offsets
                 coef[m, b] = block
+                note("dc_abs", abs(block[0]))
+                note("ac_abs", max(abs(v) for v in block[1:]))
+                if reached is not None:
+                    reached.update(seen)
         pos = bits.align()
     return coef, STATUS_OK, offsets
 
@@ -298,18 +311,24 @@ def decode(data):
 
 
 # ---- the fixture and streams derived from it --------------------------------------------------------------------------------
-def load_golden():
-    """tests/golden/jpeg_decode_golden.npz -> {name: (file bytes, Pillow's pixels as uint8 [H][W][3] B G R)}, in file order"""
+GOLDEN_FILES = ("jpeg_decode_golden.npz", "jpeg_decode_extreme_golden.npz")       # mild inputs; full-swing inputs
+
+
+def load_golden(files=GOLDEN_FILES):
+    """tests/golden/jpeg_decode_golden.npz and jpeg_decode_extreme_golden.npz -> {name: (file bytes, Pillow's pixels as uint8
+    [H][W][3] B G R)}, in file order"""
     import collections
     import os
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_decode_golden.npz"))
     out = collections.OrderedDict()
-    for name in z["names"].tolist():
-        px = z["pixels_" + name]
-        bgr = px[::-1].transpose(1, 2, 0) if px.ndim == 3 else np.repeat(px[..., None], 3, 2)
-        bgr = np.ascontiguousarray(bgr)
-        bgr.setflags(write=False)
-        out[name] = (z["jpeg_" + name].tobytes(), bgr)
+    for f in files:
+        z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f))
+        for name in z["names"].tolist():
+            assert name not in out, name
+            px = z["pixels_" + name]
+            bgr = px[::-1].transpose(1, 2, 0) if px.ndim == 3 else np.repeat(px[..., None], 3, 2)
+            bgr = np.ascontiguousarray(bgr)
+            bgr.setflags(write=False)
+            out[name] = (z["jpeg_" + name].tobytes(), bgr)
     return out
 
 

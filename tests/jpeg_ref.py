@@ -200,6 +200,37 @@ def scan(coef, restart_mcus):
     return bytes(out)
 
 
+def synthetic_coefficients(n, mcus, full):
+    """int16 [n,mcus,6,64] whose blocks walk through every path of the coder; full: the capacity case"""
+    c = np.zeros((n, mcus, 6, 64), np.int16)
+    if full:
+        c[..., 1:] = 1023
+        c[..., 1::2] = -1023                                  # every AC at +-1023: 16-bit codes, ten bits each
+        flat = c.reshape(-1, 64)
+        flat[0::2, 0], flat[1::2, 0] = -1024, 1016            # category-11 differences
+        return c
+    rng = np.random.RandomState(n * 100 + mcus)
+    flat = c.reshape(-1, 64)
+    for b in range(flat.shape[0]):
+        kind = b % 7
+        if kind == 1:
+            flat[b, 63] = 1 if b % 2 else -1                  # three ZRL, no EOB
+        elif kind == 2:
+            flat[b, 0], flat[b, 16] = 5, -3                   # a run of exactly 15 zeros
+        elif kind == 3:
+            flat[b, 0], flat[b, 17] = -7, 1023                # 16: one ZRL, then run 0
+        elif kind == 4:
+            flat[b, 1], flat[b, 34] = -1023, 2                # 32: two ZRL
+        elif kind == 5:
+            k = rng.randint(1, 64, size=6)
+            flat[b, k] = rng.randint(-40, 41, size=6)
+            flat[b, 0] = rng.randint(-1024, 1017)
+        elif kind == 6:
+            flat[b] = rng.randint(-3, 4, size=64)
+        # kind 0: all zeros, EOB only
+    return c
+
+
 def _segment(marker, payload):
     return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
 
@@ -221,6 +252,24 @@ def header(H, W, qtables, restart_mcus):
 
 def default_restart(W):
     return -(-W // 16)                   # one MCU row
+
+
+ENCODER_SCANS = [(H, W, full) for (H, W) in ((16, 16), (72, 40)) for full in (False, True)]
+
+
+def encoder_files(H, W, full):
+    """complete 4:2:0 files around the scans that this restatement of the ENCODER (`scan`) writes of synthetic coefficient
+    arrays, at restart intervals 0 (none), 1 and the default of one MCU row -> (files, int16 [3][mcus][6][64] in NATURAL
+    order: what a decoder must give back).  full: every AC at +-1023, DC differences of category 11 - outside what a forward
+    DCT gives, so only the entropy stage is asked about them."""
+    mh, mw = mcu_grid(H, W)
+    coef = synthetic_coefficients(3, mh * mw, full)
+    qt = quant_tables(90)
+    files = [header(H, W, qt, r) + scan(coef[i], r if r else mh * mw) + b"\xFF\xD9"
+             for i, r in enumerate((0, 1, default_restart(W)))]
+    natural = np.zeros_like(coef)
+    natural[..., ZIGZAG] = coef
+    return files, natural
 
 
 def encode(rgb, quality=90, restart_mcus=None):

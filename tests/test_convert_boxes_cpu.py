@@ -13,6 +13,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import jpeg_decode_ref as jref  # noqa: E402
+import jpeg_ref  # noqa: E402
 import convert_boxes_support as support  # noqa: E402
 import resample_ref as rref  # noqa: E402
 from data_support import box_record  # noqa: E402
@@ -26,8 +27,13 @@ def golden():
 
 
 # ---- JPEG -------------------------------------------------------------------------------------------------------------------
+EXTREME = ("blocks_444", "blocks_420", "checker_444", "checker_grey", "colour_blocks_444", "harsh_420_optimize",
+           "restart1_blocks_420")
+
+
 def test_fixture_holds_the_cases(golden):
-    assert len(golden) == 30
+    assert len(golden) == 30 + len(EXTREME) and list(golden)[30:] == list(EXTREME)
+    assert list(jref.load_golden(jref.GOLDEN_FILES[:1])) == list(golden)[:30]
     infos = {n: jref.parse_stream(d) for n, (d, _) in golden.items()}
     assert {(i.comps, i.hs, i.vs) for i in infos.values()} == {(1, 1, 1), (3, 1, 1), (3, 2, 1), (3, 2, 2)}
     assert {(p.shape[1], p.shape[0]) for _, p in golden.values()} >= {(1, 1), (17, 9), (16, 16), (37, 53), (40, 72), (256, 256)}
@@ -41,6 +47,52 @@ def test_restatement_equals_pillow_bit_for_bit(golden):
         got = jref.decode(data)
         assert got.shape == want.shape and np.array_equal(got, want), "%s: %d of %d bytes differ" % (
             name, int((got != want).sum()), want.size)
+
+
+def test_fixture_streams_reach_the_ends_of_the_format(golden):
+    """what the streams make the entropy decoder, the predictor and the IDCT see, counted by the restatement's walk: DC
+    differences of category 11 and AC magnitudes of size 10 (the most that 8-bit input gives), a DC coefficient of 1024,
+    16-bit AC codes, DC codes beyond the 8-bit look-up, a restart after every MCU while the DC swings from end to end.  The
+    floors are what full-swing images reach at quality 100 (|DC| 1024, |AC| 838); each condition names its stream."""
+    reached = {}
+    for name, (data, _) in golden.items():
+        reached[name] = {}
+        assert jref.entropy(jref.parse_stream(data), reached=reached[name])[1] == 0
+    keys = ("dc_category", "ac_size", "dc_abs", "ac_abs", "dc_code_bits", "ac_code_bits")
+    print()
+    for title, names in (("before", list(golden)[:30]), ("after", list(golden))):
+        print("%-7s" % title + "  ".join("%s %d" % (k, max(reached[n][k] for n in names)) for k in keys))
+    top = {k: max(r[k] for r in reached.values()) for k in keys}
+    assert top["dc_category"] == 11 and top["ac_size"] == 10 and top["dc_abs"] >= 1023 and top["ac_abs"] >= 800
+    assert top["ac_code_bits"] == 16 and top["dc_code_bits"] >= 9
+    for name in ("blocks_444", "blocks_420", "restart1_blocks_420"):
+        assert reached[name]["dc_category"] == 11 and reached[name]["dc_abs"] == 1024 and reached[name]["dc_code_bits"] >= 9, name
+    for name in ("checker_444", "checker_grey"):
+        assert reached[name]["ac_size"] == 10 and reached[name]["ac_abs"] >= 800 and reached[name]["ac_code_bits"] == 16, name
+    r = reached["colour_blocks_444"]
+    assert (r["dc_category"], r["dc_code_bits"], r["ac_code_bits"]) == (11, 11, 16) and r["ac_size"] >= 9
+    info = jref.parse_stream(golden["restart1_blocks_420"][0])
+    assert info.restart == 1 and info.mcus == 24 and len(jref.entropy(info)[2]) == 24          # 23 markers: two wraps past RST7
+    own, standard = (jref.parse_stream(golden[n][0]) for n in ("harsh_420_optimize", "blocks_420"))
+    assert not np.array_equal(own.ac[0], standard.ac[0])                                        # its own Huffman tables
+    for name in EXTREME:
+        assert golden[name][1].min() == 0 and golden[name][1].max() == 255, name
+
+
+@pytest.mark.parametrize("H,W,full", jpeg_ref.ENCODER_SCANS)
+def test_restatement_decodes_the_encoders_scans_to_their_coefficients(H, W, full):
+    files, want = jpeg_ref.encoder_files(H, W, full)
+    if full:
+        assert np.abs(want[..., 1:]).min() == 1023 and want[..., 0].min() == -1024
+    for k, data in enumerate(files):
+        info = jref.parse_stream(data)
+        assert (info.height, info.width, info.hs, info.vs, info.mcus, info.blocks) == (H, W, 2, 2, want.shape[1], 6)
+        reached = {}
+        coef, status, offsets = jref.entropy(info, reached=reached)
+        assert status == 0 and coef.shape == want[k].shape and np.array_equal(coef, want[k]), (H, W, full, k)
+        assert len(offsets) == (1 if k == 0 else -(-info.mcus // info.restart))
+        if full:
+            assert (reached["dc_category"], reached["ac_size"], reached["ac_abs"], reached["ac_code_bits"]) == (11, 10, 1023, 16)
 
 
 def test_parser_agrees_with_the_restatement(golden):

@@ -16,6 +16,7 @@ if HERE not in sys.path:
 
 import convert_ref  # noqa: E402
 import jpeg_decode_ref as jref  # noqa: E402
+import jpeg_ref  # noqa: E402
 import convert_boxes_support as support  # noqa: E402
 import resample_ref as rref  # noqa: E402
 from guard_arena import GuardArena  # noqa: E402
@@ -49,9 +50,10 @@ def restated(golden):
     return out
 
 
-def device_decode(device, files, what=""):
+def device_decode(device, files, what="", entropy_only=False):
     """one launch of each stage on `files` (one geometry) -> (coef, planes, bgr, status) as host arrays.  Inputs and outputs
-    lie in one guard arena; the outputs are pre-filled with a sentinel and the bands are checked after every stage."""
+    lie in one guard arena; the outputs are pre-filled with a sentinel and the bands are checked after every stage.
+    entropy_only: the first stage alone -> (coef, status)"""
     from acimg import _lib, jpeg, ops
     L = _lib.load()
     infos = [jpeg.parse_jpeg(f, "%s[%d]" % (what, i)) for i, f in enumerate(files)]
@@ -76,6 +78,12 @@ def device_decode(device, files, what=""):
     assert rc == 0, _lib.last_error()
     torch.cuda.synchronize(device)
     arena.check(what + " entropy")
+    if entropy_only:
+        for r, a in zip(ins, host):
+            assert np.array_equal(r.u8.cpu().numpy(), a.reshape(-1).view(np.uint8)), "%s: input %s was written" % (what, r.name)
+        assert (outs["planes"].u8 == SENT).all() and (outs["bgr"].u8 == SENT).all(), what
+        return (outs["coef"].u8.cpu().numpy().view(np.int16).reshape(n, g.mcus, g.blocks, 64),
+                outs["status"].u8.cpu().numpy().view(np.int32))
     rc = L.acimg_jpeg_decode_idct(outs["coef"].ptr, quant.ptr, n, *geo, outs["planes"].ptr, sizes["planes"], st)
     assert rc == 0, _lib.last_error()
     torch.cuda.synchronize(device)
@@ -104,6 +112,23 @@ def assert_stages(got, k, want, pillow, name):
 def test_every_fixture_stream_stage_by_stage(device, golden, restated):
     for name, (data, pillow) in golden.items():
         assert_stages(device_decode(device, [data], name), 0, restated[name], pillow, name)
+
+
+@pytest.mark.parametrize("H,W,full", jpeg_ref.ENCODER_SCANS)
+def test_entropy_stage_returns_the_coefficients_the_encoder_was_given(device, H, W, full):
+    """the oracle is the INPUT of the encoder's restatement, independent of the decoder's restatement: +-1023 in every AC
+    position, DC differences of category 11, ZRL runs and blocks without an end-of-block code, three restart intervals in one
+    launch.  The entropy stage alone: the IDCT of such arrays is nobody's specification."""
+    files, want = jpeg_ref.encoder_files(H, W, full)
+    what = "encoder scans %dx%d%s" % (W, H, ", full" if full else "")
+    coef, status = device_decode(device, files, what, entropy_only=True)
+    assert status.tolist() == [0, 0, 0], (what, status)
+    assert coef.shape == want.shape
+    bad = np.argwhere(coef != want)
+    assert bad.size == 0, "%s: %d of %d coefficients differ, first at %s: %d against %d" % (
+        what, len(bad), want.size, bad[0].tolist(), coef[tuple(bad[0])], want[tuple(bad[0])])
+    again, status2 = device_decode(device, files, what + " (second run)", entropy_only=True)
+    assert np.array_equal(again, coef) and status2.tolist() == [0, 0, 0]
 
 
 def test_two_runs_of_a_batch_give_the_same_bytes(device, golden, restated):

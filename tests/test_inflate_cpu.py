@@ -1,6 +1,7 @@
 """The device inflater without a GPU: the restatement (tests/inflate_ref.py - the finder's rule, the count pass and its stop
 rule, the chain, the markers and both resolve steps) against zlib on every stream of tests/inflate_cases.py at every chunk
-size; what the finder finds; that the chunks really decode side by side (the coverage condition); corrupt and truncated
+size; what the finder finds; that the chunks really decode side by side (the coverage condition); that the streams reach
+every rare path of RFC 1951 the decoder has code for, in chunks that start live (tests/inflate_census.py); corrupt and truncated
 input with the right status; `parse_gzip`; the refusals of the C entry point with fake pointers (a call that fails to
 refuse reaches a launch and comes back as ACIMG_ELAUNCH here); and the loader's argument check."""
 import ctypes as C
@@ -16,6 +17,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import inflate_cases as cases  # noqa: E402
+import inflate_census as census  # noqa: E402
 import inflate_ref as ref  # noqa: E402
 
 EINVAL, EWORKSPACE = -1, -2
@@ -49,7 +51,8 @@ def test_restatement_equals_zlib(name):
 
 # ---- 2 the finder -------------------------------------------------------------------------------------------------------------
 FINDER_CASES = ("smooth-mem1", "smooth64k-mem1", "tone_int32-mem1_level9", "smooth_noise-sync_flush", "window_spanning",
-                "zeros_then_smooth-device_encoder", "random-level0", "smooth-fixed")
+                "zeros_then_smooth-device_encoder", "random-level0", "smooth-fixed", "deep_codes", "run_crosses_alphabets",
+                "stored_edges")
 
 
 @pytest.mark.parametrize("name", FINDER_CASES)
@@ -102,6 +105,118 @@ def test_markers_reach_back_over_several_short_chunks():
     assert len(live) >= 4 and max(live[1:]) < ref.WINDOW
     assert r.marker_reach >= 3, r.marker_reach
     assert r.out == payload
+
+
+# ---- 2a what the streams reach of the format ------------------------------------------------------------------------------------
+CENSUS_ROWS = (("longest literal/length code decoded", "ll_bits", max), ("longest distance code decoded", "d_bits", max),
+               ("HCLEN", "hclen", max), ("blocks with all 19 code-length lengths, the last one non-zero", "cl_symbol_15", sum),
+               ("longest code of a code-length code", "cl_bits", max), ("length 258 as symbol 284 + extra 31", "len258_as_284", sum),
+               ("length 258 as symbol 285", "len258_as_285", sum), ("largest distance", "dist_max", max),
+               ("copies at distance 32768", "dist_32768", sum), ("largest LEN of a stored block", "stored_len_max", max),
+               ("blocks with HLIT = HDIST = 29", "hlit29_hdist29", sum))
+
+
+def _placed(name, chunk):
+    stream, payload = BY_NAME[name]
+    return census.place_in_chunks(census.walk(stream), ref.inflate(stream, len(payload), chunk))
+
+
+def _copies(blocks):
+    return [(b, t) for b in blocks for t in b.tokens if t.literal is None]
+
+
+def test_the_cases_reach_every_listed_feature():
+    """every rare path of RFC 1951 that the device decoder has code for is reached by a stream of CASES, and reached where it
+    matters: in chunks that start live, not only in the serial decode of chunk 0.  Each condition names its stream, so
+    taking a stream away fails here."""
+    token = {name for name, _ in cases.TOKEN_CASES}
+    counted = {name: census.census(stream) for name, stream, _ in cases.CASES}
+    print()
+    total = {}
+    for title, key, fold in CENSUS_ROWS:
+        before = fold(c[key] for name, c in counted.items() if name not in token)
+        total[key] = fold(c[key] for c in counted.values())
+        print("%-66s %6d -> %6d" % (title, before, total[key]))
+    crossing = sorted(set(x for c in counted.values() for x in c["crossing"]))
+    print("%-66s %s -> %s" % ("repeat runs (symbol, value) over the boundary of the two alphabets",
+                              sorted(set(x for n, c in counted.items() if n not in token for x in c["crossing"])), crossing))
+    assert (total["ll_bits"], total["d_bits"], total["hclen"], total["cl_bits"]) == (15, 15, 15, 7) and total["cl_symbol_15"] > 0
+    assert total["len258_as_284"] > 0 and total["len258_as_285"] > 0
+    assert total["dist_max"] == 32768 and total["dist_32768"] >= 3 and total["stored_len_max"] == 65535
+
+    # deep_codes
+    blocks = _placed("deep_codes", 256)
+    deep = [b for b in blocks if b.btype == 2]
+    assert len([b for b in deep if not b.final]) >= 4 and deep[-1].final and deep[-1] is blocks[-1]
+    assert blocks[blocks.index(deep[0]):] == deep                                    # consecutive
+    for b, nxt in zip(deep, deep[1:] + [None]):
+        assert (nxt.bit if nxt else b.end) - b.bit > 8 * 256, b.bit
+        assert {14, 15} <= {t.ll_bits for t in b.tokens}
+        assert {10, 11, 12, 13, 14, 15} <= {t.d_bits for t in b.tokens if t.literal is None}
+        assert b.hclen == 15 and b.cl[15] and max(b.cl) == 7
+    r = ref.inflate(BY_NAME["deep_codes"][0], len(BY_NAME["deep_codes"][1]), 256)
+    assert {r.starts[j] for j, l in enumerate(r.live) if l} <= {b.bit for b in blocks}      # true block boundaries
+    started = [b for b in deep if b.chunk >= 1 and b.starts_chunk]
+    assert len(started) >= 4 and len({b.chunk for b in started}) == len(started)
+    for b in started:
+        assert any(t.ll_bits == 15 for t in b.tokens) and any(t.d_bits >= 14 for t in b.tokens if t.literal is None)
+    markers = [t for b, t in _copies(started) if t.d_bits == 15 and t.dist > t.produced]
+    print("deep_codes: %d blocks, %d of them start a live chunk at chunk_bytes 256; %d copies through a 15-bit distance code "
+          "write markers" % (len(deep), len(started), len(markers)))
+    assert markers
+
+    # run_crosses_alphabets
+    runs = [b.crossing for b in census.walk(BY_NAME["run_crosses_alphabets"][0]) if b.btype == 2]
+    assert sorted(x[0] for run in runs for x in run) == [16, 17, 18] and all(len(run) == 1 for run in runs)
+    assert [x for run in runs for x in run if x[0] == 16][0][1] > 0                   # a non-zero length is carried across
+    assert counted["run_crosses_alphabets"]["hlit29_hdist29"] >= 1
+    blocks = _placed("run_crosses_alphabets", 256)
+    assert all(b.chunk >= 1 and b.starts_chunk for b in blocks if b.btype == 2)      # so the finder reads these headers too
+
+    # far_and_long
+    blocks = _placed("far_and_long", 256)
+    far = [(b, t) for b, t in _copies(blocks) if t.dist == 32768]
+    stored = [b for b in blocks if b.btype == 0]
+    assert any(b.chunk == 0 and t.out == 32768 for b, t in far)                       # dist == produced in chunk 0
+    assert any(b.chunk >= 1 and b.starts_chunk for b, t in far)
+    assert any(s.out <= t.out - 32768 and t.out - 32768 + t.length <= s.out + s.ln for b, t in far for s in stored)
+    long = [t for b, t in _copies(blocks) if t.length == 258]
+    assert {284, 285} == {t.symbol for t in long}
+    assert {1, 2, 63, 64, 65, 257} <= {t.dist for t in long if t.symbol == 285}
+    assert {1, 2, 63, 64, 65, 257} <= {t.dist for t in long if t.symbol == 284}
+    assert {1, 2, 63, 64, 65, 257} <= {t.dist for b, t in _copies(blocks) if t.length == 258 and b.chunk >= 1}
+
+    # copy_straddles_chunk_start
+    for chunk in (256, 1024):
+        blocks = _placed("copy_straddles_chunk_start", chunk)
+        straddle = [t for b, t in _copies(blocks) if b.chunk >= 1 and b.starts_chunk and t.produced < t.dist < t.produced + t.length]
+        assert any(t.dist >= t.length for t in straddle) and any(t.dist < t.length for t in straddle), chunk
+
+    # literal_runs
+    runs = set(census.runs_of_literals(census.walk(BY_NAME["literal_runs"][0])))
+    print("literal_runs:", sorted(runs))
+    assert {(n, end) for n in cases.LITERAL_RUNS for end in ("copy", "eob", "stored")} <= runs and (63, "end") in runs
+
+    # stored_edges
+    blocks = _placed("stored_edges", 256)
+    big = census.walk(BY_NAME["stored_edges-len_65535"][0])
+    assert any(b.btype == 0 and b.ln == 65535 for b in big)
+    assert any(b.btype == 0 and b.ln == 0 and a.btype == 2 and c.btype == 2 for a, b, c in zip(blocks, blocks[1:], blocks[2:]))
+    assert {b.bit % 8 for b in blocks if b.btype == 0} == set(range(8))
+    assert any(a.btype == 0 and a.end % (8 * 256) == 0 and b.btype == 2 and not b.final and b.starts_chunk
+               and b.bit == 8 * 256 * b.chunk for a, b in zip(blocks, blocks[1:]))
+    ends = [bl[-1] for bl in (blocks, big)]
+    assert all(b.final and b.btype == 1 for b in ends) and sorted(b.end % 8 for b in ends) == [0, 1]      # no pad bit; 7
+
+
+def test_zlib_refuses_the_token_level_corrupt_streams():
+    listed = {c[0]: c for c in cases.corrupt_streams()}
+    for name, stream, size in cases.token_corrupt_streams():
+        _zlib_refuses(stream)
+        for chunk in (256, 1 << 22):
+            assert ref.inflate(stream, size, chunk).status == listed[name][3] != ref.OK, name
+    assert listed["cut_inside_a_15_bit_code"][3] == ref.TRUNCATED
+    assert all(listed[n][3] == ref.CORRUPT for n, _, _ in cases.token_corrupt_streams()[:-1])
 
 
 # ---- 3 corrupt input ------------------------------------------------------------------------------------------------------------

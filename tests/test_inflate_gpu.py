@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 SENT = 0x7B
 BY_NAME = {name: (stream, payload) for name, stream, payload in cases.CASES}
 # the cases that are also decoded at the other chunk sizes: many short chunks, markers over several of them, a dead chunk
-SMALL_CHUNK_CASES = ("smooth64k-mem1", "window_spanning", "false_start", "zeros_then_smooth-device_encoder")
+SMALL_CHUNK_CASES = ("smooth64k-mem1", "window_spanning", "false_start", "zeros_then_smooth-device_encoder") + cases.TOKEN_SMALL_CHUNK_CASES
 
 
 @pytest.fixture(scope="module")

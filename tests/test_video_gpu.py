@@ -76,37 +76,6 @@ def test_blocks_equal_restatement(device, overlay, n, H, W):
 
 
 # ---- scan -------------------------------------------------------------------------------------------------------------
-def synthetic_coefficients(n, mcus, full):
-    """int16 [n,mcus,6,64] whose blocks walk through every path of the coder; full: the capacity case"""
-    c = np.zeros((n, mcus, 6, 64), np.int16)
-    if full:
-        c[..., 1:] = 1023
-        c[..., 1::2] = -1023                                  # every AC at +-1023: 16-bit codes, ten bits each
-        flat = c.reshape(-1, 64)
-        flat[0::2, 0], flat[1::2, 0] = -1024, 1016            # category-11 differences
-        return c
-    rng = np.random.RandomState(n * 100 + mcus)
-    flat = c.reshape(-1, 64)
-    for b in range(flat.shape[0]):
-        kind = b % 7
-        if kind == 1:
-            flat[b, 63] = 1 if b % 2 else -1                  # three ZRL, no EOB
-        elif kind == 2:
-            flat[b, 0], flat[b, 16] = 5, -3                   # a run of exactly 15 zeros
-        elif kind == 3:
-            flat[b, 0], flat[b, 17] = -7, 1023                # 16: one ZRL, then run 0
-        elif kind == 4:
-            flat[b, 1], flat[b, 34] = -1023, 2                # 32: two ZRL
-        elif kind == 5:
-            k = rng.randint(1, 64, size=6)
-            flat[b, k] = rng.randint(-40, 41, size=6)
-            flat[b, 0] = rng.randint(-1024, 1017)
-        elif kind == 6:
-            flat[b] = rng.randint(-3, 4, size=64)
-        # kind 0: all zeros, EOB only
-    return c
-
-
 def device_scan(device, coef, H, W, restart, slack=5):
     """-> (scan bytes per frame, the whole output region as a host array, stride); guard bands checked"""
     from acimg import _lib, ops
@@ -137,7 +106,7 @@ def test_scan_equals_restatement(device, n, H, W, full):
     threads and one for others, the RSTm index wrapping 33 times; restart 266 is one interval of five scan passes"""
     mh, mw = J.mcu_grid(H, W)
     mcus = mh * mw
-    coef = synthetic_coefficients(n, mcus, full)
+    coef = J.synthetic_coefficients(n, mcus, full)
     for restart in (1, mw, 7, mcus) + ((65,) if mcus == 69 else ()):
         counts, region, cap = device_scan(device, coef, H, W, restart)
         for i in range(n):
