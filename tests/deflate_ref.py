@@ -65,22 +65,12 @@ DIST_EXTRA = [dist_code(b)[1] for b in (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49,
                                         2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577)]
 
 
-def huffman_lengths(freq, limit):
-    """Code lengths of one alphabet (the device's `huffman_lengths`): symbols with freq <= 0 get 0; one used symbol gets 1.
-    Otherwise the used symbols are ordered by (freq, symbol); a two-queue Huffman merge (of two equal weights the LEAF
-    is taken first) gives the leaf depths; depths above `limit` are set to `limit`, and while the Kraft sum exceeds 1 by
-    E units of 2^-limit, E times: the deepest level b < limit that holds a leaf gives one up to level b + 1, together with
-    one leaf taken from level `limit` (count[b] -= 1, count[b + 1] += 2, count[limit] -= 1: the sum falls by one unit).
-    Last, the levels' counts are dealt out in the order of the sort, the longest lengths to the least frequent symbols."""
-    freq = [int(f) for f in freq]
-    out = [0] * len(freq)
+def leaf_depths(freq):
+    """(order, depth) of the two-queue Huffman merge, before any limit: the used symbols ordered by (freq, symbol) and the
+    depth of each one's leaf (of two equal weights the LEAF is taken first); two or more used symbols"""
     order = sorted((i for i in range(len(freq)) if freq[i] > 0), key=lambda i: (freq[i], i))
     used = len(order)
-    if used == 0:
-        return out
-    if used == 1:
-        out[order[0]] = 1
-        return out
+    assert used >= 2
     w = [freq[i] for i in order] + [0] * (used - 1)
     parent = [0] * (2 * used - 1)
     i, j = 0, used
@@ -98,6 +88,33 @@ def huffman_lengths(freq, limit):
     depth = [0] * (2 * used - 1)
     for k in range(2 * used - 3, -1, -1):
         depth[k] = depth[parent[k]] + 1
+    return order, depth[:used]
+
+
+def unlimited_depth(freq):
+    """the deepest leaf of `leaf_depths` (the number of used symbols when there are fewer than two): above the alphabet's
+    limit exactly when the limiter of `huffman_lengths` acts"""
+    freq = [int(f) for f in freq]
+    used = sum(1 for f in freq if f > 0)
+    return max(leaf_depths(freq)[1]) if used >= 2 else used
+
+
+def huffman_lengths(freq, limit):
+    """Code lengths of one alphabet (the device's `huffman_lengths`): symbols with freq <= 0 get 0; one used symbol gets 1.
+    Otherwise the used symbols are ordered by (freq, symbol); a two-queue Huffman merge (of two equal weights the LEAF
+    is taken first) gives the leaf depths; depths above `limit` are set to `limit`, and while the Kraft sum exceeds 1 by
+    E units of 2^-limit, E times: the deepest level b < limit that holds a leaf gives one up to level b + 1, together with
+    one leaf taken from level `limit` (count[b] -= 1, count[b + 1] += 2, count[limit] -= 1: the sum falls by one unit).
+    Last, the levels' counts are dealt out in the order of the sort, the longest lengths to the least frequent symbols."""
+    freq = [int(f) for f in freq]
+    out = [0] * len(freq)
+    used = sum(1 for f in freq if f > 0)
+    if used == 0:
+        return out
+    if used == 1:
+        out[next(i for i, f in enumerate(freq) if f > 0)] = 1
+        return out
+    order, depth = leaf_depths(freq)
     count = [0] * (limit + 1)
     for k in range(used):
         count[min(depth[k], limit)] += 1
@@ -157,6 +174,13 @@ def canonical_codes(lengths):
     return out
 
 
+def hashes(b):
+    """int64 [n - 2]: hash(p) of every position of the uint8 array `b` that has three bytes (n >= 3)"""
+    b = b.astype(np.uint32)
+    w = b[:-2] | (b[1:-1] << 8) | (b[2:] << 16)
+    return ((w * np.uint32(0x9E3779B1)) >> np.uint32(32 - HASH_BITS)).astype(np.int64)
+
+
 def find_matches(b):
     """(length uint16 [n], distance uint16 [n]) of every position of one block (length 0: no match)"""
     n = len(b)
@@ -164,8 +188,7 @@ def find_matches(b):
     pad[:n] = b
     cand = np.zeros(n, np.int64)                       # q + 1, 0 = none
     if n >= 3:
-        w = pad[:n - 2].astype(np.uint32) | (pad[1:n - 1].astype(np.uint32) << 8) | (pad[2:n].astype(np.uint32) << 16)
-        h = ((w * np.uint32(0x9E3779B1)) >> np.uint32(32 - HASH_BITS)).astype(np.int64)
+        h = hashes(pad[:n])
         head = np.zeros(1 << HASH_BITS, np.int64)
         for s in range(0, n - 2, CHUNK):
             e = min(s + CHUNK, n - 2)
@@ -216,13 +239,23 @@ def _put(out, off, val, nbits):
         np.bitwise_or.at(out, byte[keep] + k, part[keep])
 
 
-def code_block(b, final):
-    """one block's bytes: stored or dynamic, padded to a byte; the sync marker behind it unless `final`"""
-    b = np.frombuffer(bytes(b), np.uint8)
-    n = len(b)
+class Plan(object):
+    """What is decided about one block before a bit is written, the one statement of the rules that `code_block` writes out
+    and tests/deflate_census.py counts.  data (uint8 [n]), n; toks (the greedy parse); hist_ll, hist_d, hist_cl; len_ll,
+    len_d, len_cl and code_ll, code_d, code_cl; hlit, hdist, hclen (the counts sent, not the header fields); seq (the code
+    lengths the header sends, in order); bits (the dynamic form's exact bit count), dyn_bytes, dynamic (the form chosen), pad
+    (the zero bits that fill the dynamic form's last byte); token_at (the bit offset in the block of the first token);
+    vals, widths (every token's bits and their count, the end-of-block symbol last)"""
+
+
+def plan_block(b):
+    """the Plan of one block of 1..BLOCK bytes"""
+    pl = Plan()
+    pl.data = b = np.frombuffer(bytes(b), np.uint8)
+    pl.n = n = len(b)
     assert 1 <= n <= BLOCK
-    toks = greedy_parse(b)
-    hist_ll, hist_d = [0] * 286, [0] * 30
+    pl.toks = toks = greedy_parse(b)
+    pl.hist_ll, pl.hist_d = hist_ll, hist_d = [0] * 286, [0] * 30
     hist_ll[256] = 1
     for p, l, d in toks:
         if l:
@@ -230,41 +263,28 @@ def code_block(b, final):
             hist_d[dist_code(d)[0]] += 1
         else:
             hist_ll[int(b[p])] += 1
-    len_ll = huffman_lengths(hist_ll, 15)
-    len_d = huffman_lengths(hist_d, 15)
+    pl.len_ll = len_ll = huffman_lengths(hist_ll, 15)
+    pl.len_d = len_d = huffman_lengths(hist_d, 15)
     if not any(len_d):
         len_d[0] = 1
-    hlit = max(257, max(i for i in range(286) if len_ll[i]) + 1)
-    hdist = max(1, max(i for i in range(30) if len_d[i]) + 1)
-    seq = len_ll[:hlit] + len_d[:hdist]
-    hist_cl = [0] * 19
+    pl.hlit = hlit = max(257, max(i for i in range(286) if len_ll[i]) + 1)
+    pl.hdist = hdist = max(1, max(i for i in range(30) if len_d[i]) + 1)
+    pl.seq = seq = len_ll[:hlit] + len_d[:hdist]
+    pl.hist_cl = hist_cl = [0] * 19
     for s in seq:
         hist_cl[s] += 1
-    len_cl = huffman_lengths(hist_cl, 7)
-    hclen = max(4, max(i for i in range(19) if len_cl[CL_ORDER[i]]) + 1)
-    bits = 17 + 3 * hclen + sum(hist_cl[s] * len_cl[s] for s in range(19))
-    bits += sum(hist_ll[s] * len_ll[s] for s in range(257))
+    pl.len_cl = len_cl = huffman_lengths(hist_cl, 7)
+    pl.hclen = hclen = max(4, max(i for i in range(19) if len_cl[CL_ORDER[i]]) + 1)
+    pl.token_at = 17 + 3 * hclen + sum(hist_cl[s] * len_cl[s] for s in range(19))
+    bits = pl.token_at + sum(hist_ll[s] * len_ll[s] for s in range(257))
     bits += sum(hist_ll[257 + c] * (len_ll[257 + c] + LEN_EXTRA[c]) for c in range(29))
     bits += sum(hist_d[c] * (len_d[c] + DIST_EXTRA[c]) for c in range(30))
-    dyn_bytes = (bits + 7) >> 3
-    tail = b"" if final else (SYNC[1:] if dyn_bytes * 8 - bits >= 3 else SYNC)
-    if dyn_bytes >= n + 5:
-        tail = b"" if final else SYNC
-        return bytes([1 if final else 0, n & 255, n >> 8, ~n & 255, (~n >> 8) & 255]) + b.tobytes() + tail
-    code_ll, code_d, code_cl = canonical_codes(len_ll), canonical_codes(len_d), canonical_codes(len_cl)
-    out = np.zeros(dyn_bytes + 8, np.uint8)
-    head = (1 if final else 0) | (2 << 1) | ((hlit - 257) << 3) | ((hdist - 1) << 8) | ((hclen - 4) << 13)
-    for i in range(hclen):
-        head |= len_cl[CL_ORDER[i]] << (17 + 3 * i)
-    at = 17 + 3 * hclen
-    _put(out, [0], [head & ((1 << 40) - 1)], 40)
-    _put(out, [40], [head >> 40], 40)
-    vals = [code_cl[s] for s in seq]
-    nb = np.array([len_cl[s] for s in seq], np.int64)
-    offs = at + np.concatenate(([0], np.cumsum(nb)[:-1]))
-    _put(out, offs, vals, nb)
-    at += int(nb.sum())
-    vals, nb = [], []
+    pl.bits = bits
+    pl.dyn_bytes = (bits + 7) >> 3
+    pl.pad = pl.dyn_bytes * 8 - bits
+    pl.dynamic = pl.dyn_bytes < n + 5
+    pl.code_ll, pl.code_d, pl.code_cl = code_ll, code_d, _ = canonical_codes(len_ll), canonical_codes(len_d), canonical_codes(len_cl)
+    pl.vals, pl.widths = vals, nb = [], []
     for p, l, d in toks:
         if l == 0:
             s = int(b[p])
@@ -284,11 +304,31 @@ def code_block(b, final):
             nb.append(k)
     vals.append(code_ll[256])
     nb.append(len_ll[256])
-    nb = np.array(nb, np.int64)
-    offs = at + np.concatenate(([0], np.cumsum(nb)[:-1]))
-    _put(out, offs, vals, nb)
-    assert at + int(nb.sum()) == bits
-    return out[:dyn_bytes].tobytes() + tail
+    assert pl.token_at + sum(nb) == bits
+    return pl
+
+
+def code_block(b, final):
+    """one block's bytes: stored or dynamic, padded to a byte; the sync marker behind it unless `final`"""
+    pl = plan_block(b)
+    n = pl.n
+    if not pl.dynamic:
+        tail = b"" if final else SYNC
+        return bytes([1 if final else 0, n & 255, n >> 8, ~n & 255, (~n >> 8) & 255]) + pl.data.tobytes() + tail
+    tail = b"" if final else (SYNC[1:] if pl.pad >= 3 else SYNC)
+    out = np.zeros(pl.dyn_bytes + 8, np.uint8)
+    head = (1 if final else 0) | (2 << 1) | ((pl.hlit - 257) << 3) | ((pl.hdist - 1) << 8) | ((pl.hclen - 4) << 13)
+    for i in range(pl.hclen):
+        head |= pl.len_cl[CL_ORDER[i]] << (17 + 3 * i)
+    _put(out, [0], [head & ((1 << 40) - 1)], 40)
+    _put(out, [40], [head >> 40], 40)
+    nb = np.array([pl.len_cl[s] for s in pl.seq], np.int64)
+    offs = 17 + 3 * pl.hclen + np.concatenate(([0], np.cumsum(nb)[:-1]))
+    _put(out, offs, [pl.code_cl[s] for s in pl.seq], nb)
+    nb = np.array(pl.widths, np.int64)
+    offs = pl.token_at + np.concatenate(([0], np.cumsum(nb)[:-1]))
+    _put(out, offs, pl.vals, nb)
+    return out[:pl.dyn_bytes].tobytes() + tail
 
 
 def deflate(payload):

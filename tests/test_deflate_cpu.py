@@ -2,7 +2,8 @@
 construction and header choices) against zlib's own decoder on every payload of tests/deflate_cases.py; the containers of
 acimg.deflate against `gzip` / `zlib`; the code construction's properties on synthetic histograms; the refusals of the C
 entry points with fake pointers (a call that fails to refuse reaches a launch and comes back as ACIMG_ELAUNCH here); and the
-default (zlib) paths of `write_tfrecord` / `encode_png`, which must write what they always wrote."""
+default (zlib) paths of `write_tfrecord` / `encode_png`, which must write what they always wrote.  A census of the
+payloads (tests/deflate_census.py) holds them to the paths of `deflate_block_kernel` they are there to reach."""
 import ctypes as C
 import gzip
 import os
@@ -17,6 +18,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import deflate_cases as cases  # noqa: E402
+import deflate_census as census  # noqa: E402
 import deflate_ref as ref  # noqa: E402
 
 EINVAL, EWORKSPACE = -1, -2
@@ -71,6 +73,141 @@ def test_parse_takes_no_match_across_a_block_and_none_below_three():
     toks = ref.greedy_parse(np.zeros(ref.BLOCK, np.uint8))
     assert toks[0] == (0, 0, 0) and toks[1] == (1, 258, 1) and all(d == 1 for _, l, d in toks[1:])
     assert sum(l if l else 1 for _, l, _ in toks) == ref.BLOCK
+
+
+@pytest.mark.parametrize("name,payloads", cases.many_block_calls(), ids=[n for n, _ in cases.many_block_calls()])
+def test_many_block_calls_inflate_and_cross_the_offsets_threads(name, payloads):
+    """the expected streams of the GPU test's two calls, without a GPU; and the calls are what they are meant to be"""
+    nblocks, per_thread, runs = cases.block_runs(payloads)
+    memo = {}
+    for p in payloads:
+        if p not in memo:
+            memo[p] = ref.deflate(p)
+            assert zlib.decompress(memo[p], -15) == p and len(memo[p]) <= ref.bound(len(p))
+    across = [r for r in runs if r[0] // per_thread != r[1] // per_thread]
+    if name == "1025_of_one_byte":
+        assert (nblocks, per_thread, across) == (1025, 2, []) and all(len(p) == 1 for p in payloads)
+        assert all(a != b for a, b in zip(payloads, payloads[1:]))
+    else:
+        assert nblocks >= 2049 and per_thread >= 3
+        assert sorted(len(p) for p in payloads if len(p) > 3) == [cases.B + 1, 2 * cases.B, 3 * cases.B + 17]
+        assert len(across) == 3 and runs[-1] in across                    # the last payload's `first` is another thread's block
+
+
+# ---- 1b what the payloads reach ----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def counted():
+    """name -> [census.Block]; computed once, shared"""
+    return {name: census.census_blocks(p) for name, p in cases.PAYLOADS}
+
+
+ROWS = (("widest token, bits", "widest"), ("tokens wider than 32 bits", "over_32"),
+        ("tokens that reach a third word", "third_word"), ("the largest shift of one of those", "third_word_shift"),
+        ("length codes emitted", "length_codes"), ("match lengths emitted", "lengths"),
+        ("distance codes emitted", "dist_codes"), ("largest distance", "dist_max"),
+        ("longest code: literal/length, distance, code-length", "longest"),
+        ("blocks where the limiter acts: the same three", "limited"), ("HCLEN sent (count of lengths)", "hclen"),
+        ("pad bits before a marker", "pads"), ("bytes off the stored-or-dynamic edge", "off_the_edge"),
+        ("matches cut by the block's end", "clipped"), ("the one used distance code of blocks with one", "one_dist_code"))
+
+
+def _short(v):
+    return "%d of them" % len(v) if isinstance(v, list) and len(v) > 12 else v
+
+
+def test_the_payloads_reach_every_listed_feature(counted):
+    """every path of `deflate_block_kernel` that DESIGN section 8 lists is taken by a payload of PAYLOADS; each condition names
+    the payload that provides it, so taking a payload away, or a change of the parse rule that defuses one, fails here"""
+    B = ref.BLOCK
+    mild = census.table([b for name, _ in cases.MILD for b in counted[name]])
+    total = census.table([b for blocks in counted.values() for b in blocks])
+    print("\n%d blocks (%d dynamic, %d stored) -> %d (%d, %d)" % (mild["blocks"], mild["dynamic"], mild["stored"], total["blocks"],
+                                                                 total["dynamic"], total["stored"]))
+    for title, key in ROWS:
+        print("%-56s %s -> %s" % (title, _short(mild[key]), _short(total[key])))
+
+    # every_length: every match length, so every length code with every value of its extra bits; 257 and 258 in one block
+    blocks = counted["every_length"]
+    assert all(b.dynamic for b in blocks) and len(blocks) == 3
+    assert set().union(*[b.lengths for b in blocks]) == set(range(3, 259))
+    assert set().union(*[b.length_codes for b in blocks]) == set(range(29))
+    assert {257, 258} <= blocks[0].lengths                                 # symbol 284 with extra 30 against symbol 285
+
+    # every_distance_code.  A match has three bytes, so the largest distance a block of B bytes can hold is B - 3 (the copy at
+    # B - 3, the source at 0), not B - 1: that one stands for "the largest" of code 27 and of the block
+    first, last = counted["every_distance_code"]
+    assert cases.LARGEST_DISTANCE == B - 3 and first.dynamic and last.dynamic
+    wanted = cases.edge_distances()
+    assert wanted[:4] == [1, 2, 3, 4] and wanted[-2:] == [12289, B - 3] and len(wanted) == 4 + 2 * 24
+    assert all(ref.dist_code(d)[0] + 1 == ref.dist_code(d + 1)[0] for d in wanted[5:-1:2])      # each the last of its code
+    assert all(ref.dist_code(d)[0] - 1 == ref.dist_code(d - 1)[0] for d in wanted[4::2])        # each the first of its code
+    assert set(wanted) <= first.dists and first.dist_codes == set(range(28)) and first.dist_max == B - 3
+    assert [p % ref.CHUNK for p, l, d in first.plan.toks if l and d == 2] == [0]
+    assert total["dist_codes"] == list(range(28)) and 1 not in mild["dist_codes"]
+    # matches cut by min(258, n - p): the one that ends a block of exactly B bytes, the one that ends a short last block
+    assert first.n == B and not first.final and first.clipped == [(B - 3, 3, B - 3)]
+    assert last.n == 700 and last.final and last.clipped == [(600, 100, 300)]
+    assert counted["period4"][0].clipped == [(B - 132, 132, 128)]         # one of those that were there by chance
+
+    # wide_tokens: 34 bits is the least that can reach a third word, the shift being 31 at most
+    (wide,) = counted["wide_tokens"]
+    assert wide.dynamic and wide.longest[:2] == (13, 10)
+    far = [i for i, t in enumerate(wide.plan.toks) if t[1:] in cases.WIDE_FAR]
+    assert len(far) == 4 and sorted(wide.widths[i] for i in far) == [39, 40, 40, 40]
+    assert total["widest"] == 40 and mild["widest"] < 32
+    assert len(wide.third_word) == 2 and set(wide.third_word) <= set(far)
+    assert all(wide.shifts[i] >= 27 and wide.shifts[i] + wide.widths[i] > 64 for i in wide.third_word)
+    assert mild["over_32"] == mild["third_word"] == 0
+
+    # pad bits: all of 0..7, and 2 and 3, the two sides of the marker rule, in consecutive blocks of one payload
+    assert total["pads"] == list(range(8)) and 2 not in mild["pads"]
+    blocks = counted["pad_bits_2_then_3"]
+    assert [(b.pad, b.dynamic, b.final) for b in blocks[:2]] == [(2, True, False), (3, True, False)]
+    payload = dict(cases.PAYLOADS)["pad_bits_2_then_3"]
+    coded = [ref.code_block(payload[s:s + B], False) for s in (0, B)]
+    assert coded[0].endswith(ref.SYNC) and len(coded[0]) == blocks[0].plan.dyn_bytes + 5
+    assert coded[1].endswith(ref.SYNC[1:]) and len(coded[1]) == blocks[1].plan.dyn_bytes + 4
+
+    # the stored-or-dynamic decision at its edge, both blocks non-final so that their markers are checked too
+    blocks = counted["stored_or_dynamic_edge"]
+    assert [(b.margin, b.dynamic, b.final, b.n) for b in blocks[:2]] == [(0, False, False, B), (-1, True, False, B)]
+    assert mild["off_the_edge"] > 20 and total["off_the_edge"] == 0
+
+    # HCLEN.  Every code length is sent as its own symbol and 16, 17, 18 never are, so HCLEN is one more than the last place
+    # in CL_ORDER of a length in use.  A distance code with two or more lengths is complete, and over the 28 distance
+    # symbols a block can use a complete code has a length of 4 or less (28 * 2^-5 < 1); one used distance gets length 1.
+    # Of 1..4 it is 4 that stands first in CL_ORDER, at place 11, behind 0 and 5..11: HCLEN 12 is the smallest there is.
+    assert min(ref.CL_ORDER.index(l) for l in (1, 2, 3, 4)) + 1 == 12 and set(ref.CL_ORDER[3:12]) == {0} | set(range(4, 12))
+    (small,) = counted["smallest_hclen"]
+    assert small.dynamic and small.hclen == 12 == total["hclen"][0] and mild["hclen"][0] == 14
+    assert counted["zeros_%d" % B][0].hclen == 18                          # the largest below 19: a code of 1 bit in use
+
+    # a block with one used distance code that is not symbol 0: the code of length 1 with HDIST > 1
+    (one,) = counted["one_distance_code"]
+    assert one.dynamic and one.used_dist_codes == [16] and one.hdist == 17 and one.plan.len_d[16] == 1
+    assert set(mild["one_dist_code"]) == {0} and counted["zeros_%d" % B][0].used_dist_codes == [0]
+
+    # a literal/length code of 15 bits inside the block kernel: once from a depth of exactly 15, once from the limiter
+    (deep,) = counted["literal_code_depth_15"]
+    assert deep.dynamic and deep.depth[0] == 15 == deep.longest[0] and not deep.limited[0] and deep.hclen == 19
+    (limited,) = counted["literal_code_limited"]
+    assert limited.dynamic and limited.depth[0] == 16 and limited.longest[0] == 15 and limited.limited[0] and limited.hclen == 19
+    assert cases.check_lengths(limited.plan.hist_ll, limited.plan.len_ll, 15, "literal_code_limited") == 16
+    assert mild["longest"] == (13, 12, 7) and mild["limited"][:2] == (0, 0) and 19 not in mild["hclen"]
+    # the 17 710-byte Fibonacci payload is two blocks full of matches: its codes stay short and no limiter acts on it
+    fib = counted["fibonacci_counts"]
+    assert [b.longest[0] for b in fib] == [12, 9] and not any(any(b.limited) for b in fib)
+    # the 7-bit limiter of the code-length alphabet is what the mild payloads do reach at 1024 threads
+    assert mild["limited"][2] == 6 and any(b.limited[2] for b in counted["smooth_fixture"])
+
+
+def test_planted_copies_are_taken_as_planted():
+    """the Planter's claim: what it lists as placed is in the parse, token for token"""
+    pl = cases.Planter(np.random.RandomState(31), 6000)
+    for at, length, dist in ((300, 3, 1), (512, 3, 2), (800, 40, 300), (1500, 258, 1000), (5000, 7, 4097), (5997, 3, 5000)):
+        pl.place(at, length, dist=dist, step=ref.CHUNK if dist < ref.CHUNK else 1)
+    assert [d for _, _, d in pl.planted] == [1, 2, 300, 1000, 4097, 5000]
+    assert set(pl.planted) <= set(ref.greedy_parse(np.frombuffer(pl.bytes(), np.uint8)))
 
 
 # ---- 2 code construction ---------------------------------------------------------------------------------------------------

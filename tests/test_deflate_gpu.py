@@ -1,7 +1,8 @@
 """The device DEFLATE encoder (csrc/deflate.hip) on the GPU.  Every payload of tests/deflate_cases.py through the raw C ABI,
 input, output, sizes and workspace inside guard bands: the stream inflates to the payload with zlib, equals the
 restatement (tests/deflate_ref.py) byte for byte, is the same on a second run and stays within acimg_deflate_bound.
-`acimg_huffman_lengths` on the CPU test's histograms; `compress_many`; and the three tools' smallest inputs end to end:
+Two calls with more blocks than the offsets kernel has threads.  `acimg_huffman_lengths` on the CPU test's histograms;
+`compress_many`; and the three tools' smallest inputs end to end:
 records written with `--deflate device` read by the project's loaders, a PNG written with the device deflater."""
 import ctypes as C
 import gzip
@@ -68,6 +69,27 @@ def test_stream_inflates_equals_the_restatement_and_repeats(device, restated, na
     assert got == restated[name], "%s: %d bytes, the restatement has %d" % (name, len(got), len(restated[name]))
     (again,) = guarded_deflate(device, [payload], name + " (second run)")
     assert again == got
+
+
+def test_more_blocks_than_the_offsets_kernel_has_threads(device):
+    """deflate_offsets_kernel gives each of its 1024 threads ceil(nblocks / 1024) consecutive blocks: 1025 blocks are the
+    first call in which a thread holds two, and in the call of 2053 three payloads lie across two threads' blocks, the
+    last one among them, so that a payload's first block is summed by another thread than its last.  Every stream and
+    every entry of out_sizes against the restatement, inside guard bands."""
+    for name, payloads in cases.many_block_calls():
+        nblocks, per_thread, runs = cases.block_runs(payloads)
+        across = [r for r in runs if r[0] // per_thread != r[1] // per_thread]
+        if name == "1025_of_one_byte":
+            assert (nblocks, per_thread) == (1025, 2)
+        else:
+            assert nblocks >= 2049 and per_thread >= 3 and len(across) >= 2 and runs[-1] in across
+        got = guarded_deflate(device, payloads, name)
+        assert len(got) == len(payloads)
+        memo = {}
+        for i, (p, g) in enumerate(zip(payloads, got)):
+            if p not in memo:
+                memo[p] = ref.deflate(p)
+            assert g == memo[p], "%s: payload %d of %d bytes (blocks %d..%d)" % (name, i, len(p), runs[i][0], runs[i][1])
 
 
 def test_matching_is_alive(device):
