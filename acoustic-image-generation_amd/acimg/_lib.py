@@ -188,6 +188,7 @@ PROTOTYPES = {
     "acimg_jpeg_decode_plane_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "acimg_jpeg_decode_pixel_bytes": (_SZ, [_I, _I, _I]),
     "acimg_jpeg_decode_entropy": (_I, [_P, _SZ, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
+    "acimg_jpeg_decode_progressive": (_I, [_P, _SZ, _P, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "acimg_jpeg_decode_idct": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "acimg_jpeg_decode_colour": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "acimg_resample_length": (_L, [_L, _I, _I, C.POINTER(_L)]),

@@ -18,9 +18,9 @@ TFRecords of one box-annotated `SequenceExample` each that `acimg.data.BoxRecord
   are refused by name.
 * video (:157-170): `cv2.imread` -> `cv2.resize(..., (298, 224), INTER_CUBIC)`, no crop, bytes in BGR order.  Neither
   OpenCV nor any imaging library is involved: the files of a batch are parsed on the host (`jpeg.parse_jpeg`), decoded
-  on the device by the three kernels of csrc/jpeg_decode.hip, and the pixels stay there for `acimg_resize_cubic_u8`.
-  Baseline JPEG only; everything else is refused by name before a launch, a corrupt scan after the decode - in both
-  cases before a byte of the batch is written.
+  on the device by the kernels of csrc/jpeg_decode.hip, and the pixels stay there for `acimg_resize_cubic_u8`.
+  Sequential (baseline, extended) and complete progressive Huffman files of 8 bits; everything else is refused by name
+  before a launch, a corrupt scan after the decode - in both cases before a byte of the batch is written.
 * audio (:32-49): `np.int32(librosa.core.resample(data * 1.0, fs, 12288))` of the whole file - `Resampler`, the
   windowed-sinc kernel of csrc/resample.hip with resampy's `kaiser_best` filter built here; 12288 Hz passes through.
   Mono PCM of 16 or 32 bits (`convert.read_wav`); stereo is refused by name (`data * 1.0` of a two-column array resamples
@@ -281,7 +281,7 @@ class BoxConverter(object):
             files, infos = [l.jpeg for l in loaded], [l.info for l in loaded]
             groups = collections.OrderedDict()
             for i, g in enumerate(infos):
-                groups.setdefault((g.height, g.width, g.comps, g.hs, g.vs), []).append(i)
+                groups.setdefault(jpeg.group_key(g), []).append(i)
             out = torch.empty(len(items), CROP_H, CROP_W, 3, dtype=torch.uint8, device=self._decoder.device)
             status = []
             for key, members in groups.items():

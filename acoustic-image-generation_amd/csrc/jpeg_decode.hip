@@ -1,4 +1,4 @@
-// Baseline JPEG (ITU-T T.81, sequential DCT, Huffman, 8 bit; SOF0) to B, G, R pixels on the GPU: the decoder behind
+// Baseline and progressive JPEG (ITU-T T.81, DCT, Huffman, 8 bit; SOF0, SOF1, SOF2) to B, G, R pixels on the GPU: the decoder behind
 // `python -m acimg.convert_boxes` (the `cv2.imread` of convert_data2.py:157), the mirror of jpeg.hip.  Integer arithmetic
 // throughout, so that tests/jpeg_decode_ref.py restates every stage bit for bit on any machine and the pixels equal
 // libjpeg's (`jpeg_idct_islow`, fancy upsampling, 16-bit fixed-point colour) - DESIGN section 8.
@@ -17,6 +17,20 @@
 //   the loop over the interval's own MCUs, a coefficient index is checked against 63 before the store, and every loop
 //   runs a number of times fixed by the geometry.  A lane that meets an error writes zeros for the rest of its interval;
 //   the image's status is the error of its first bad interval.  Other images never see it.
+// acimg_jpeg_decode_progressive: the same coefficient slot from a progressive file (SOF2; T.81 Annex G: spectral selection
+//   and successive approximation over several scans).  One workgroup (one wave) per image again; the unit of work is one
+//   (scan, restart interval) pair, ONE LANE each.  Scans are separate byte-aligned bit streams and depend on each other only
+//   where they touch the same coefficients of the same component, so the host gives every scan a LEVEL (0, or 1 + the
+//   highest level of an earlier scan that shares a component and overlaps its band); the kernel zeroes the slot, then runs
+//   the levels in order with a fence and a workgroup barrier between them, all items of a level side by side.  A scan of
+//   one component walks that component's OWN block grid, not the MCU-padded one.  The scan records are checked field by
+//   field into LDS before anything of them is used; a record that fails is one item that reports DESCRIPTOR and writes
+//   nothing.  An item that meets an error stops writing there; the status is that of the first bad item in (scan,
+//   interval) order, and later levels still run on what is there.
+//   The Huffman tables are read from GLOBAL memory, not staged in LDS: a legal level may hold one scan per coefficient and
+//   component (189 scans with a table each, 171 KB) which no LDS holds, so staging would need a second path for the levels
+//   that do not fit; the tables of a level are a few KB that every lane reads again and again, so they stay in the CU's
+//   vector cache, and the wave is bound by its serial bit walk, not by these loads.
 // acimg_jpeg_decode_idct: dequantise + libjpeg's jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2) in wrapping 32-bit
 //   integers, eight threads per block: a column each, then a row each; +128, clamp, eight bytes per thread into the
 //   component's plane (padded to the MCU grid).
@@ -228,6 +242,289 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* data, l
     }
 }
 
+// ---- progressive entropy decoding (T.81 Annex G) ----------------------------------------------------------------------
+// One validated scan record in LDS.  `code` is ST_OK or ST_DESCRIPTOR; a record that fails a check has ONE item, which
+// reports the error and touches nothing.
+struct ProgScan {
+    int code, level, mask, ncomp;   // components of the scan as a bit mask, and how many
+    int ss, se, refine, al;
+    int tab[3];                     // per component: index into the table pool (DC first: DC table; AC scans: AC table)
+    int comp;                       // the component of a one-component scan
+    int units, restart, count;      // MCUs (interleaved) or blocks of the component's own grid; per interval; intervals
+    int bw;                         // blocks per row of the component's own grid (one-component scans)
+    int seg_a, seg_e;               // the scan's bytes relative to the image's data, clamped
+    int first;                      // index of its first interval in `intervals`
+};
+constexpr int PROG_MAX_SCANS = ACIMG_JPEG_PROG_MAX_SCANS;
+constexpr int PROG_FIELDS = ACIMG_JPEG_PROG_SCAN_FIELDS;
+
+struct ProgGeometry {
+    int comps, hs, vs, luma_blocks, blocks;
+    int mcu_w, mcus;
+    int bw[3], bh[3];   // each component's own block grid: ceil(ceil(W h / hmax) / 8) x ceil(ceil(H v / vmax) / 8)
+};
+
+__device__ __forceinline__ int take_bit(BitSource& s) {
+    s.fill();
+    const int v = (int)s.peek(1);
+    s.skip(1);
+    return v;
+}
+
+// the correction bit of one coefficient that is already nonzero (G.1.2.3): 16-bit arithmetic that wraps, as a JCOEF does
+__device__ __forceinline__ void refine_nonzero(BitSource& s, int16_t* at, int p1) {
+    const int bit = take_bit(s);
+    if (s.real < 0) return;   // the caller reports it; nothing is written from bits the data does not hold
+    const int v = *at;
+    if (bit && (v & p1) == 0) *at = (int16_t)(v >= 0 ? v + p1 : v - p1);
+}
+
+// One (scan, restart interval) pair: the blocks [u0, u1) of the scan, in the image's coefficient slot.  Returns its status.
+__device__ int prog_item(const ProgScan& sc, const ProgGeometry& g, long j, const uint8_t* data, long img_a,
+                         const int32_t* intervals, const HuffDec* pool, int16_t* slot) {
+    if (sc.code != ST_OK) return sc.code;
+    long a = intervals[((long)sc.first + j) * 2 + 0], e = intervals[((long)sc.first + j) * 2 + 1];
+    const long seg_len = (long)sc.seg_e - sc.seg_a;
+    a = a < 0 ? 0 : (a > seg_len ? seg_len : a);
+    e = e < a ? a : (e > seg_len ? seg_len : e);
+    BitSource s = {data + img_a + sc.seg_a + a, data + img_a + sc.seg_a + e, 0, 0, 0};
+    const long u0 = j * (long)sc.restart;
+    const long u1 = u0 + sc.restart < sc.units ? u0 + sc.restart : sc.units;
+    const int p1 = 1 << sc.al;
+    int pred[3] = {0, 0, 0};
+    int eobrun = 0;
+    for (long u = u0; u < u1; ++u) {
+        if (sc.ss == 0) {   // DC: every block of the scan's components in this MCU, or the one block of a one-component scan
+            const int b_hi = sc.ncomp > 1 ? g.blocks : 1;
+            for (int bi = 0; bi < b_hi; ++bi) {
+                int c, b;
+                long m;
+                if (sc.ncomp > 1) {
+                    b = bi;
+                    m = u;
+                    c = b < g.luma_blocks ? 0 : b - g.luma_blocks + 1;
+                    if (!((sc.mask >> c) & 1)) continue;
+                } else {
+                    c = sc.comp;
+                    const int br = (int)(u / sc.bw), bc = (int)(u - (long)br * sc.bw);
+                    const int h = c == 0 ? g.hs : 1, v = c == 0 ? g.vs : 1;
+                    m = (long)(br / v) * g.mcu_w + bc / h;
+                    b = c == 0 ? (br % v) * h + bc % h : g.luma_blocks + c - 1;
+                }
+                if (m < 0 || m >= g.mcus || b < 0 || b >= g.blocks) return ST_DESCRIPTOR;   // cannot happen for a checked record
+                int16_t* const blk = slot + (m * g.blocks + b) * 64;
+                if (!sc.refine) {
+                    s.fill();
+                    const int sym = huff_symbol(s, pool[sc.tab[c]]);
+                    if (sym < 0 || sym > 15) return ST_BAD_CODE;
+                    const int diff = s.receive_extend(sym);
+                    if (s.real < 0) return ST_EARLY_END;
+                    pred[c] += diff;
+                    blk[0] = (int16_t)((uint32_t)pred[c] << sc.al);
+                } else {
+                    const int bit = take_bit(s);
+                    if (s.real < 0) return ST_EARLY_END;
+                    if (bit) blk[0] = (int16_t)(blk[0] | p1);
+                }
+            }
+            continue;
+        }
+        // AC: one component, its own block grid
+        const int c = sc.comp;
+        const int br = (int)(u / sc.bw), bc = (int)(u - (long)br * sc.bw);
+        const int h = c == 0 ? g.hs : 1, v = c == 0 ? g.vs : 1;
+        const long m = (long)(br / v) * g.mcu_w + bc / h;
+        const int b = c == 0 ? (br % v) * h + bc % h : g.luma_blocks + c - 1;
+        if (m < 0 || m >= g.mcus || b < 0 || b >= g.blocks) return ST_DESCRIPTOR;
+        int16_t* const blk = slot + (m * g.blocks + b) * 64;
+        const HuffDec& ac = pool[sc.tab[c]];
+        if (!sc.refine) {
+            if (eobrun > 0) {
+                --eobrun;
+                continue;
+            }
+            for (int k = sc.ss; k <= sc.se; ++k) {   // a symbol advances k by at least one
+                s.fill();
+                const int sym = huff_symbol(s, ac);
+                if (sym < 0) return ST_BAD_CODE;
+                const int r = sym >> 4, size = sym & 15;
+                if (size) {
+                    k += r;
+                    const int val = s.receive_extend(size);
+                    if (s.real < 0) return ST_EARLY_END;
+                    if (k > sc.se || k > 63) return ST_RUN;
+                    blk[c_dezigzag[k]] = (int16_t)((uint32_t)val << sc.al);
+                } else if (r == 15) {
+                    k += 15;
+                } else {
+                    eobrun = 1 << r;
+                    if (r) {
+                        eobrun += (int)s.peek(r);
+                        s.skip(r);
+                    }
+                    if (s.real < 0) return ST_EARLY_END;
+                    --eobrun;
+                    break;
+                }
+                if (s.real < 0) return ST_EARLY_END;
+            }
+        } else {
+            int k = sc.ss;
+            if (eobrun == 0) {
+                for (; k <= sc.se; ++k) {
+                    s.fill();
+                    const int sym = huff_symbol(s, ac);
+                    if (sym < 0) return ST_BAD_CODE;
+                    int r = sym >> 4;
+                    const int size = sym & 15;
+                    int val = 0;
+                    if (size) {
+                        if (size != 1) return ST_BAD_CODE;
+                        val = take_bit(s) ? p1 : -p1;
+                    } else if (r != 15) {
+                        eobrun = 1 << r;
+                        if (r) {
+                            eobrun += (int)s.peek(r);
+                            s.skip(r);
+                        }
+                        if (s.real < 0) return ST_EARLY_END;
+                        break;   // the rest of the band is handled as the first block of the run
+                    }
+                    if (s.real < 0) return ST_EARLY_END;
+                    // over the coefficients with a history (a correction bit each) and r that have none
+                    for (; k <= sc.se; ++k) {
+                        int16_t* const at = blk + c_dezigzag[k];
+                        if (*at != 0) {
+                            refine_nonzero(s, at, p1);
+                            if (s.real < 0) return ST_EARLY_END;
+                        } else if (--r < 0) {
+                            break;
+                        }
+                    }
+                    if (val) {
+                        if (k > sc.se || k > 63) return ST_RUN;
+                        blk[c_dezigzag[k]] = (int16_t)val;
+                    }
+                }
+            }
+            if (eobrun > 0) {
+                for (; k <= sc.se; ++k) {
+                    int16_t* const at = blk + c_dezigzag[k];
+                    if (*at != 0) {
+                        refine_nonzero(s, at, p1);
+                        if (s.real < 0) return ST_EARLY_END;
+                    }
+                }
+                --eobrun;
+            }
+        }
+    }
+    return ST_OK;
+}
+
+// img int64 [n][4], scans int32 [total_scans][PROG_FIELDS], intervals int32 [total_intervals][2], pool of total_tables
+// tables: include/acimg.h has the layout.  Levels run in order; between two levels every lane's stores are made visible to
+// the workgroup (one wave: the fence is what matters) before the barrier lets anyone read them.
+__global__ __launch_bounds__(64) void jpeg_progressive_kernel(const uint8_t* data, long data_bytes, const int64_t* img,
+                                                              const int32_t* scans, long total_scans, const int32_t* intervals,
+                                                              long total_intervals, const uint8_t* huff, long total_tables,
+                                                              ProgGeometry g, int16_t* coef, int32_t* status) {
+    __shared__ ProgScan rec[PROG_MAX_SCANS];
+    __shared__ long long first_error[64];
+    const int lane = threadIdx.x;
+    const long i = blockIdx.x;
+    const long per_image = (long)g.mcus * g.blocks * 64;
+    int16_t* const slot = coef + (size_t)i * per_image;
+    {   // the slot starts as zeros: 128 bytes a block, so 16-byte stores cover it exactly
+        uint4* const z = reinterpret_cast<uint4*>(slot);
+        for (long q = lane; q < per_image / 8; q += 64) z[q] = make_uint4(0, 0, 0, 0);
+    }
+    long img_a = img[i * 4 + 0], img_e = img[i * 4 + 1];
+    const long first_scan = img[i * 4 + 2], nscan_l = img[i * 4 + 3];
+    img_a = img_a < 0 ? 0 : (img_a > data_bytes ? data_bytes : img_a);
+    img_e = img_e < img_a ? img_a : (img_e > data_bytes ? data_bytes : img_e);
+    if (img_e - img_a > 0x7FFFFFFFl) img_e = img_a + 0x7FFFFFFFl;
+    const long img_len = img_e - img_a;
+    const bool img_ok = first_scan >= 0 && nscan_l >= 1 && nscan_l <= PROG_MAX_SCANS && first_scan <= total_scans &&
+                        nscan_l <= total_scans - first_scan;
+    const int nscan = img_ok ? (int)nscan_l : 0;
+    for (int k = lane; k < nscan; k += 64) {   // validate: nothing of a record is used before its check
+        const int32_t* f = scans + (first_scan + k) * PROG_FIELDS;
+        ProgScan sc;
+        sc.mask = f[0];
+        sc.ss = f[1];
+        sc.se = f[2];
+        const int ah = f[3];
+        sc.al = f[4];
+        sc.tab[0] = f[5];
+        sc.tab[1] = f[6];
+        sc.tab[2] = f[7];
+        long restart = f[8];
+        long sa = f[9], se = f[10];
+        const long first = f[11];
+        sc.level = f[12];
+        bool ok = sc.mask >= 1 && sc.mask < (1 << g.comps) && sc.ss >= 0 && sc.ss <= sc.se && sc.se <= 63 &&
+                  (sc.ss != 0 || sc.se == 0) && ah >= 0 && ah <= 13 && sc.al >= 0 && sc.al <= 13 && restart >= 0 &&
+                  sc.level >= 0 && sc.level < nscan && f[13] == 0 && f[14] == 0 && f[15] == 0;
+        sc.ncomp = ok ? __popc((unsigned)sc.mask) : 1;
+        sc.comp = ok ? __ffs(sc.mask) - 1 : 0;
+        ok = ok && (sc.ss == 0 || sc.ncomp == 1);
+        sc.refine = ah != 0;
+        if (ok && !(sc.ss == 0 && sc.refine))   // DC refinement reads no table
+            for (int c = 0; c < g.comps; ++c)
+                if (((sc.mask >> c) & 1) && (sc.tab[c] < 0 || sc.tab[c] >= total_tables)) ok = false;
+        sc.bw = g.bw[sc.comp];
+        const long units = sc.ncomp > 1 ? (long)g.mcus : (long)g.bw[sc.comp] * g.bh[sc.comp];
+        if (restart < 1 || restart > units) restart = units;
+        const long count = (units + restart - 1) / restart;
+        ok = ok && first >= 0 && first <= total_intervals && count <= total_intervals - first;
+        sa = sa < 0 ? 0 : (sa > img_len ? img_len : sa);
+        se = se < sa ? sa : (se > img_len ? img_len : se);
+        sc.units = (int)units;
+        sc.restart = (int)restart;
+        sc.count = ok ? (int)count : 1;
+        sc.seg_a = (int)sa;
+        sc.seg_e = (int)se;
+        sc.first = (int)first;
+        sc.code = ok ? ST_OK : ST_DESCRIPTOR;
+        if (!ok) sc.level = 0;
+        rec[k] = sc;
+    }
+    __threadfence_block();
+    __syncthreads();
+    int top = 0;
+    for (int k = 0; k < nscan; ++k) top = rec[k].level > top ? rec[k].level : top;
+    long long err = 0x7FFFFFFFFFFFFFFFll;   // (scan << 40) | (interval << 3) | code of this lane's first error in that order
+    const HuffDec* const pool = reinterpret_cast<const HuffDec*>(huff);
+    for (int level = 0; level <= top; ++level) {
+        long t = lane, base = 0;   // item t of this level; items of the level's scans before scan k
+        int k = 0;
+        while (true) {
+            while (k < nscan && (rec[k].level != level || t >= base + rec[k].count)) {
+                if (rec[k].level == level) base += rec[k].count;
+                ++k;
+            }
+            if (k >= nscan) break;
+            const long j = t - base;
+            const int code = prog_item(rec[k], g, j, data, img_a, intervals, pool, slot);
+            if (code != ST_OK) {
+                const long long key = ((long long)k << 40) | ((long long)j << 3) | code;
+                err = key < err ? key : err;
+            }
+            t += 64;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+    first_error[lane] = err;
+    __syncthreads();
+    if (lane == 0) {
+        long long least = first_error[0];
+        for (int q = 1; q < 64; ++q) least = first_error[q] < least ? first_error[q] : least;
+        status[i] = !img_ok ? ST_DESCRIPTOR : (least == 0x7FFFFFFFFFFFFFFFll ? ST_OK : (int)(least & 7));
+    }
+}
+
 // ---- dequantise + jpeg_idct_islow -----------------------------------------------------------------------------------
 // 13-bit fixed point; unsigned arithmetic wraps like the 32-bit integers of the definition, the descale is arithmetic
 constexpr uint32_t FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
@@ -393,6 +690,42 @@ int acimg_jpeg_decode_entropy(const uint8_t* data, size_t data_bytes, const int6
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, data, (long)data_bytes, desc,
                        intervals, total_intervals, huff, comps, comps == 1 ? 1 : hs * vs, g.blocks, g.mcus, coef, status);
     return check_launch("jpeg_decode_entropy");
+}
+
+int acimg_jpeg_decode_progressive(const uint8_t* data, size_t data_bytes, const int64_t* img, const int32_t* scans,
+                                  long total_scans, const int32_t* intervals, long total_intervals, const uint8_t* huff,
+                                  long total_tables, int n, int H, int W, int comps, int hs, int vs, int16_t* coef,
+                                  size_t coef_bytes, int32_t* status, void* stream) {
+    if (!data || !img || !scans || !intervals || !huff || !coef || !status)
+        return fail(ACIMG_EINVAL, "jpeg_decode_progressive: null argument");
+    if (n < 1) return fail(ACIMG_EINVAL, "jpeg_decode_progressive: n = %d must be positive", n);
+    if (!jpeg_dec_args_ok(H, W, comps, hs, vs))
+        return fail(ACIMG_EINVAL, "jpeg_decode_progressive: %d x %d, %d component(s), sampling %d x %d is not decoded", H, W,
+                    comps, hs, vs);
+    if (total_scans < 1 || total_intervals < 1 || total_tables < 1 || data_bytes > (size_t)INT64_MAX)
+        return fail(ACIMG_EINVAL, "jpeg_decode_progressive: %ld scans, %ld intervals, %ld tables in %zu bytes", total_scans,
+                    total_intervals, total_tables, data_bytes);
+    if (!aligned16(coef) || !aligned16(huff) || !aligned16(img) || !aligned16(scans) || !aligned16(intervals))
+        return fail(ACIMG_EINVAL, "jpeg_decode_progressive: coef, huff, img, scans and intervals must be 16-byte aligned");
+    const size_t need = acimg_jpeg_decode_coef_bytes(n, H, W, comps, hs, vs);
+    if (coef_bytes < need) return fail(ACIMG_EWORKSPACE, "jpeg_decode_progressive: coef of %zu < %zu bytes", coef_bytes, need);
+    const DecGeometry d = jpeg_dec_geometry(H, W, comps, hs, vs);
+    ProgGeometry g;
+    g.comps = comps;
+    g.hs = hs;
+    g.vs = vs;
+    g.luma_blocks = comps == 1 ? 1 : hs * vs;
+    g.blocks = d.blocks;
+    g.mcu_w = (int)d.mcu_w;
+    g.mcus = (int)d.mcus;
+    for (int c = 0; c < 3; ++c) {   // component 0 has the largest factors, so its samples are the picture's
+        const int cw = c == 0 ? W : (W + hs - 1) / hs, ch = c == 0 ? H : (H + vs - 1) / vs;
+        g.bw[c] = (cw + 7) / 8;
+        g.bh[c] = (ch + 7) / 8;
+    }
+    hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, data, (long)data_bytes, img,
+                       scans, total_scans, intervals, total_intervals, huff, total_tables, g, coef, status);
+    return check_launch("jpeg_decode_progressive");
 }
 
 int acimg_jpeg_decode_idct(const int16_t* coef, const uint8_t* quant, int n, int H, int W, int comps, int hs, int vs,

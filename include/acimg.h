@@ -1018,6 +1018,59 @@ int acimg_jpeg_decode_entropy(const uint8_t* data, size_t data_bytes, const int6
                               int16_t* coef, size_t coef_bytes, int32_t* status, void* stream);
 int acimg_jpeg_decode_idct(const int16_t* coef, const uint8_t* quant, int n, int H, int W, int comps, int hs, int vs,
                            uint8_t* planes, size_t plane_bytes, void* stream);
+
+/* Progressive JPEG files (SOF2: spectral selection and successive approximation, Huffman, 8 bit; T.81 Annex G): the second
+ * entropy stage.  It fills the coefficient slot of acimg_jpeg_decode_entropy - same layout, same geometry rules, same status
+ * array - and acimg_jpeg_decode_idct / _colour follow unchanged: a complete progressive file holds exactly the coefficients
+ * of its baseline twin, so the pixels equal libjpeg-turbo's bit for bit.  tests/jpeg_progressive_ref.py restates it; the
+ * fixture is tests/golden/jpeg_progressive_golden.npz; DESIGN section 8 has the definition.  (Added without raising
+ * ACIMG_VERSION: nothing existing changed, and the number is pinned by the host tests.)
+ *   data uint8 [data_bytes]: the files' bytes from the first scan to the end of the last, anywhere in it.
+ *   img int64 [n][4]: per image the first and the end byte of its bytes in data, the index of its first record in `scans`
+ *     and the number of its scans (1..ACIMG_JPEG_PROG_MAX_SCANS), in file order.
+ *   scans int32 [total_scans][ACIMG_JPEG_PROG_SCAN_FIELDS], one record per scan:
+ *     [0] the scan's components as a bit mask (bit c: component c of the frame)      [1] Ss  [2] Se  [3] Ah  [4] Al
+ *     [5..7] per component c the index in `huff` of the table the scan reads for it: its DC table in a first DC scan, its
+ *            AC table in an AC scan; not read for a component outside the mask or in a DC refinement scan (-1 there)
+ *     [8] the restart interval in the scan's own units - MCUs for a scan of several components, blocks of the component's
+ *         own grid for a scan of one - 0: the scan is one interval
+ *     [9] [10] first and end byte of the scan's entropy-coded segment RELATIVE to the image's first byte
+ *     [11] index of its first interval in `intervals`; it has ceil(units / restart) of them, in order
+ *     [12] its level: 0, or 1 + the highest level of an earlier scan of the image that shares a component with it and
+ *          whose [Ss, Se] overlaps its own.  Scans of one level touch disjoint coefficients.    [13..15] zero
+ *   intervals int32 [total_intervals][2]: first and end byte of a restart interval RELATIVE to its scan's segment.
+ *   huff uint8 [total_tables][ACIMG_JPEG_HUFF_BYTES]: the pool of every table some scan names, in the layout above.
+ *   -> coef, status as acimg_jpeg_decode_entropy.  The kernel zeroes the slot itself, then runs level after level; the
+ *   unit of work is one (scan, interval) pair.  A scan of ONE component walks that component's own grid of
+ *   ceil(ceil(W h / hmax) / 8) x ceil(ceil(H v / vmax) / 8) blocks in raster order (not the MCU-padded grid: luma blocks in
+ *   the padding are reached by interleaved scans only); a scan of several walks the MCUs and in each the blocks of its
+ *   components.  Per interval the DC predictors and EOBRUN start at 0.  DC first (Ss = 0, Ah = 0): as the baseline DC, the
+ *   value shifted left by Al.  DC refinement: one bit per block, OR-ed in at bit Al.  AC first: symbol (r, s): s > 0 skips
+ *   r coefficients and stores the next as value << Al; (15, 0) skips 16; (r < 15, 0) starts an end-of-band run of 2^r + r
+ *   further bits blocks, this one included.  AC refinement: s must be 1, a sign bit follows (1: +2^Al, 0: -2^Al); the run
+ *   r counts coefficients that are still zero only, and every nonzero coefficient passed on the way - also in the blocks
+ *   of an end-of-band run - takes one correction bit, which adds 2^Al away from zero where bit Al is still clear; 16-bit
+ *   arithmetic that wraps, as libjpeg's.
+ *   Status: ACIMG_JPEG_STATUS_BAD_CODE (no code matches; a DC category above 15; an AC refinement size other than 1), _RUN
+ *   (a coefficient would land past Se), _EARLY_END (more bits used than the interval holds), _DESCRIPTOR (an img or scan
+ *   record outside the ranges above: mask 1..2^comps - 1, 0 <= Ss <= Se <= 63, Ss = 0 only with Se = 0, one component
+ *   where Ss > 0, Ah and Al 0..13, a table index inside the pool, intervals inside the table, a level below the image's
+ *   number of scans, zero padding).  An item that meets an error stops writing there; the image's status is the code of
+ *   its first bad item in (scan, interval) order; later levels still run on what is there.  NOTHING IS TRUSTED, as above:
+ *   byte ranges are clamped, every loop count comes from the geometry, no write leaves the image's slot.
+ *   Caps: ACIMG_JPEG_PROG_MAX_SCANS scans a file (the records of one image are staged in LDS; one band per coefficient and
+ *   component is 3 + 189 scans), ACIMG_JPEG_PROG_MAX_TABLES tables a file, ACIMG_JPEG_PROG_MAX_INTERVALS intervals a file;
+ *   the host refuses a file beyond them by name.  Refusals as acimg_jpeg_decode_entropy (img, scans take desc's place).
+ *   ONE launch: one workgroup (one wave) per image, one lane per (scan, interval) of the current level; tables are read
+ *   from global memory.  No atomics: bit-identical from run to run. */
+#define ACIMG_JPEG_PROG_MAX_SCANS 256
+#define ACIMG_JPEG_PROG_MAX_TABLES 512
+#define ACIMG_JPEG_PROG_MAX_INTERVALS (1 << 24)
+#define ACIMG_JPEG_PROG_SCAN_FIELDS 16
+int acimg_jpeg_decode_progressive(const uint8_t* data, size_t data_bytes, const int64_t* img, const int32_t* scans,
+                                  long total_scans, const int32_t* intervals, long total_intervals, const uint8_t* huff,
+                                  long total_tables, int n, int H, int W, int comps, int hs, int vs, int16_t* coef,
+                                  size_t coef_bytes, int32_t* status, void* stream);
 int acimg_jpeg_decode_colour(const uint8_t* planes, int n, int H, int W, int comps, int hs, int vs, uint8_t* bgr,
                              size_t bgr_bytes, void* stream);
 
