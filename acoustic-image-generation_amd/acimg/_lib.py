@@ -203,6 +203,13 @@ PROTOTYPES = {
     "acimg_checksum": (_I, [_P, C.POINTER(_L), _I, _I, _P, _P, C.POINTER(_L), _P, _SZ, _P]),
     "acimg_record_gather_workspace": (_SZ, [_I]),
     "acimg_record_gather": (_I, [_P, _P, C.POINTER(_L), _I, _P, _SZ, _P, _SZ, _P]),
+    "acimg_png_inflated_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "acimg_png_sample_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "acimg_png_pixel_bytes": (_SZ, [_I, _I]),
+    "acimg_png_unfilter_workspace": (_SZ, [_I]),
+    "acimg_png_unfilter": (_I, [_P, _SZ, C.POINTER(_L), _I, _I, _P, _SZ, _P, _P, _SZ, _P]),
+    "acimg_png_pixels_workspace": (_SZ, [_I]),
+    "acimg_png_pixels": (_I, [_P, _SZ, C.POINTER(_L), _I, _P, _SZ, _P, _SZ, _P, _P, _SZ, _P]),
     "acimg_gzip_inflate": (_I, [_P, _SZ, _P, _SZ, C.POINTER(_SZ)]),
     "acimg_tfrecord_index": (_L, [_P, _SZ, _P, _P, _L, _I]),
     "acimg_sequence_example_decode": (_I, [_P, _SZ, C.POINTER(SequenceDims), _P, _SZ, _P, _SZ, _P, _SZ]),

@@ -23,7 +23,10 @@ audio [n,12])), `.num_samples`, `.total_batches` (:117,214,973-976).
   embedding=1, nr_frames=1, sample_length=1, shuffle=False)`, written by convert_data2.py:200-307): 8-tuples (acoustic
   zeros [n,36,48,12], mfcc [n,12], video [n,224,298,3], xmin, xmax, ymin, ymax, typescene [n,3] int32) that
   showimages_bb.py:86-93 indexes.  Records through `acimg_box_sequence_example_decode`; the MFCC of the whole clip is
-  `box_mfcc` on the host (the [1, L] reading of `_build_spectrograms_function`)."""
+  `box_mfcc` on the host (the [1, L] reading of `_build_spectrograms_function`).
+* `ClassRecordLoader`: the two-object test set of dataloader/framesclass.py (records written by convert_data4.py, here
+  `python -m acimg.convert_collected`): 4-tuples (acoustic zeros, mfcc [n,12], video [n,224,298,3], classnumber [n,1]
+  int32), parsed with `tfio.parse_sequence_example`; the same `box_mfcc`."""
 import collections
 import concurrent.futures
 import ctypes
@@ -1115,3 +1118,81 @@ class BoxRecordLoader(object):
                     pend = [rest] if have else []
         if have:
             yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(8))
+
+
+class ClassRecordLoader(object):
+    """`ActionsDataLoader(txt_file, 'testing', batch_size, ..., embedding=1, nr_frames=1, sample_length=1, shuffle=False,
+    modalities=[1, 2])` of dataloader/framesclass.py on the records `python -m acimg.convert_collected` writes (the
+    two-object test set): a sibling of `BoxRecordLoader`, sharing `box_mfcc`.  Batches are (acoustic zeros [n,36,48,12]
+    as :284 builds them, mfcc float32 [n,12], video float32 R G B / 255 [n,224,298,3], classnumber int32 [n,1]).  Records
+    are parsed with `tfio.parse_sequence_example`; a frame that is not 224 x 298 x 3 is refused by name, because the
+    reference's reshape (:333) fails there.  The reference's fifth output, the MFCC of the low-passed clip (:392-408), is
+    NOT produced: `showimages_collected.py` never reads it.  `files`: a list of TFRecord paths or the path of a text
+    file listing them.  Everything runs on the host; tensors are returned on the host."""
+
+    FRAME = (224, 298, 3)
+
+    def __init__(self, files, batch_size, compression_verify=True):
+        if isinstance(files, str):
+            with open(files) as f:
+                files = [ln.strip() for ln in f if ln.strip()]
+        self.files = list(files)
+        self.batch_size = int(batch_size)
+        self.verify = bool(compression_verify)
+        self.data = self
+        self._num_samples = None
+
+    @property
+    def num_samples(self):
+        """frames in the data set (one per record in convert_collected's files)"""
+        if self._num_samples is None:
+            from . import tfio
+            self._num_samples = sum(len(tfio.parse_sequence_example(r)[1].get("video/image", ()))
+                                    for p in self.files for r in tfio.read_tfrecord_native(p, verify=False) if len(r))
+        return self._num_samples
+
+    @property
+    def total_batches(self):
+        return -(-self.num_samples // self.batch_size)
+
+    def _record(self, rec, path):
+        from . import tfio
+        ctx, lists = tfio.parse_sequence_example(rec)
+        for key in ("audio_data/mics", "audio_data/samples", "classnumber", "video/height", "video/width", "video/depth"):
+            if key not in ctx:
+                raise ValueError("%s: a record without the context feature %r" % (path, key))
+        for key in ("audio/data", "video/image"):
+            if key not in lists:
+                raise ValueError("%s: a record without the feature list %r" % (path, key))
+        shape = tuple(int(np.asarray(ctx[k]).reshape(-1)[0]) for k in ("video/height", "video/width", "video/depth"))
+        if shape != self.FRAME:
+            raise ValueError("%s: a frame of %d x %d x %d: only 224 x 298 x 3 frames are loaded" % ((path,) + shape))
+        samples = int(np.asarray(ctx["audio_data/samples"]).reshape(-1)[0])
+        sa = np.frombuffer(b"".join(v for step in lists["audio/data"] for v in step), "<i4").reshape(-1, samples)
+        vi = np.frombuffer(b"".join(v for step in lists["video/image"] for v in step), np.uint8).reshape((-1,) + self.FRAME)
+        n = vi.shape[0]
+        if not (sa.shape[0] == n and n > 0):
+            raise ValueError("%s: a record with %d video frames and %d audio rows" % (path, n, sa.shape[0]))
+        # video: float, channel order reversed, 1/255 (`_normalize_images_rescaled`)
+        v = vi[..., ::-1].astype(np.float32) * np.float32(1.0 / 255.0)
+        label = np.full((n, 1), int(np.asarray(ctx["classnumber"]).reshape(-1)[0]), np.int32)
+        out = [np.zeros((n, 36, 48, 12), np.float32), box_mfcc(sa), np.ascontiguousarray(v), label]
+        return tuple(torch.from_numpy(a) for a in out)
+
+    def __iter__(self):
+        from . import tfio
+        pend, have = [], 0
+        for path in self.files:
+            for rec in tfio.read_tfrecord_native(path, verify=self.verify):
+                if len(rec) == 0:
+                    continue
+                pend.append(self._record(rec, path))
+                have += pend[-1][0].shape[0]
+                while have >= self.batch_size:
+                    cat = [torch.cat([p_[k] for p_ in pend], 0) for k in range(4)]
+                    yield tuple(c[:self.batch_size] for c in cat)
+                    rest = tuple(c[self.batch_size:] for c in cat)
+                    have = rest[0].shape[0]
+                    pend = [rest] if have else []
+        if have:
+            yield tuple(torch.cat([p_[k] for p_ in pend], 0) for k in range(4))

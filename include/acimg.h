@@ -1227,6 +1227,58 @@ int acimg_record_gather(const uint8_t* src0, const uint8_t* src1, const long* se
                         void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PNG decoding on the device, the part that is not DEFLATE (`python -m acimg.convert_collected`, `acimg.png.PngDecoder`):
+ * the scanline filters of RFC 2083 section 6 undone for many images in one launch, and the samples of all 15 colour-type /
+ * bit-depth forms, interlaced or not, turned into the uint8 [H, W, 3] B, G, R pixels `cv2.imread(path)` returns with its
+ * default flag.  csrc/png_decode.hip has the plan, tests/png_decode_ref.py restates both stages, DESIGN section 8 has the
+ * definition and the measurements.  (Added without raising ACIMG_VERSION.)
+ * Size queries (host only; 0 for a dimension < 1, an illegal colour-type / depth pair, interlace outside {0, 1} or a result
+ *   above 2^31 - 1): acimg_png_inflated_bytes = the bytes the file's zlib stream inflates to, rows * (1 + row bytes) summed
+ *   over the passes that have a row and a column (one pass without interlace); acimg_png_sample_bytes = the same without
+ *   the filter bytes; acimg_png_pixel_bytes = 3 H W.  Row bytes = ceil(width * channels * depth / 8).
+ * acimg_png_unfilter: src uint8 [src_bytes] ON THE DEVICE, the inflated streams of `nfiles` files back to back; jobs long
+ *   [njobs][ACIMG_PNG_JOB_FIELDS] ON THE HOST, one row per (file, pass that has a row and a column): {offset in src of the
+ *   job's first filter byte, offset in dst, rows, bytes per row without the filter byte, the filter unit bpp = max(1, bits
+ *   per pixel / 8) in {1, 2, 3, 4, 6, 8}, file index} -> dst uint8 [dst_bytes]: the job's rows * row bytes reconstructed
+ *   bytes at its dst offset, and status int32 [nfiles] (device): ACIMG_PNG_OK, or ACIMG_PNG_BAD_FILTER for a file with a
+ *   filter byte above 4 - such a row is copied as filter 0, so the file's bytes are unspecified but every write stays in
+ *   its jobs' extents, and no other file is affected.  Arithmetic mod 256; left and upleft are 0 in a row's first bpp
+ *   bytes, up and upleft in a JOB's first row (filters never cross passes); Average floors the 9-bit sum; Paeth ties go
+ *   to left, then up.  One wave per job: a wavefront over bands of 64 rows, ceil(rows / 64) * (units + 63) steps, not rows * units.
+ *   The host refuses (ACIMG_EINVAL) a null pointer, njobs or nfiles < 1, a misaligned ws, a bpp outside the set, rows or
+ *   row bytes < 1, row bytes no multiple of bpp, a file index outside [0, nfiles) and a job that leaves src or dst; a short
+ *   ws is ACIMG_EWORKSPACE; jobs that overlap in dst are the caller's to avoid.  The table is copied, status zeroed and
+ *   the stream waited for once before the ONE launch.  acimg_png_unfilter_workspace: 48 bytes per job, rounded up to 16.
+ * acimg_png_pixels: samples = acimg_png_unfilter's dst; files long [nfiles][ACIMG_PNG_FILE_FIELDS] ON THE HOST: {offset of
+ *   the file's samples, H, W, colour type, bit depth, interlace, offset of its palette in `palette` (bytes), palette
+ *   entries, offset in out}; palette uint8 [palette_bytes] (device; R, G, B per entry; may be NULL when no file has
+ *   colour type 3) -> out: 3 H W bytes per file at its offset.  libpng's transforms as OpenCV sets them for IMREAD_COLOR:
+ *   indices go through PLTE, grey of 1 / 2 / 4 bits is scaled by 255 / 85 / 17, 16-bit samples keep their high byte, grey
+ *   is replicated, alpha is dropped (not composited), tRNS / gAMA and the other ancillary chunks have no effect, the
+ *   order is B, G, R.  Interlaced files are gathered from their passes by the Adam7 table (x origins 0 4 0 2 0 1 0, steps
+ *   8 8 4 4 2 2 1; y origins 0 0 4 0 2 0 1, steps 8 8 8 4 4 2 2); samples below 8 bits are packed MSB first, rows padded
+ *   to a byte.  status int32 [nfiles] (device) is IN / OUT: the kernel only ever stores ACIMG_PNG_BAD_INDEX, for a file
+ *   with a palette index at or beyond its PLTE length (that pixel becomes 0 0 0; a stated choice: libpng's behaviour
+ *   there depends on its version) - so handing it acimg_png_unfilter's array keeps that stage's verdicts.  The host
+ *   refuses (ACIMG_EINVAL) a null pointer, nfiles outside 1 .. 65535, a geometry the size queries give 0 for, a file that
+ *   leaves samples / out / palette, a colour type 3 file with 0 or more than 256 entries; a short ws is ACIMG_EWORKSPACE.
+ *   acimg_png_pixels_workspace: 72 bytes per file, rounded up to 16. */
+#define ACIMG_PNG_OK         0
+#define ACIMG_PNG_BAD_FILTER 1   /* a filter byte above 4 */
+#define ACIMG_PNG_BAD_INDEX  2   /* a palette index at or beyond the PLTE length */
+#define ACIMG_PNG_JOB_FIELDS  6
+#define ACIMG_PNG_FILE_FIELDS 9
+size_t acimg_png_inflated_bytes(int height, int width, int colour_type, int bit_depth, int interlace);
+size_t acimg_png_sample_bytes(int height, int width, int colour_type, int bit_depth, int interlace);
+size_t acimg_png_pixel_bytes(int height, int width);
+size_t acimg_png_unfilter_workspace(int njobs);
+int acimg_png_unfilter(const uint8_t* src, size_t src_bytes, const long* jobs, int njobs, int nfiles, uint8_t* dst, size_t dst_bytes,
+                       int32_t* status, void* ws, size_t ws_bytes, void* stream);
+size_t acimg_png_pixels_workspace(int nfiles);
+int acimg_png_pixels(const uint8_t* samples, size_t sample_bytes, const long* files, int nfiles, const uint8_t* palette,
+                     size_t palette_bytes, uint8_t* out, size_t out_bytes, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dataset records (host side, no GPU work; caller-owned memory like everything else): the GZIP TFRecord files of
  * tf.train.SequenceExample written by convert_data.py:247-279 and read by dataloader/outdoor_data_mfcc.py:62,263-343.
  * ---------------------------------------------------------------------------------------- */
